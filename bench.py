@@ -3,6 +3,7 @@
 synthetic graph of the ogbn-papers100M shape (BASELINE.json metric), one process per GPU.
 
   python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR   # + the last timed batch as DIR/<name>.npy
   python bench.py --gpus N ...          # spawns N ranks itself (parent never touches the GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -75,7 +76,11 @@ def parse(argv=None):
                     "fragments per clique (0: topology stays replicated)")
     ap.add_argument("--presc-steps", type=int, default=8, help="unified: batches of the pre-sampling (hotness) epoch")
     ap.add_argument("--min-time", type=float, default=3.0,
-                    help="the K-step timed window is repeated until this many seconds are covered; ms_per_step is the median window")
+                    help="legs other than the headline (its alternative schedules, the extra legs' own --extra-min-time): the K-step window is "
+                         "repeated until this many seconds are covered and ms_per_step is the median window.  The headline times exactly --steps steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the headline's timed steps, write what its last step computed (the batch Engine.result() hands a caller) as "
+                         "DIR/<name>.npy, float64 (integers) / float32 (features), a fixed sample of the longer arrays, at most 64 MB (rank 0)")
     ap.add_argument("--max-reps", type=int, default=400)
     ap.add_argument("--skew", type=int, default=205, help="synthetic neighbours: n/256 of them drawn from the Zipf-like skew "
                     "(205 = the spec'd 80 %%; 0 = uniform neighbours, the Infinity-Cache control run)")
@@ -1172,9 +1177,45 @@ def make_seeds(c):
     c.steps_avail = max(1, (c.n_mine - 1) // c.B)  # train_step = (n-1)/B, CUDA_IPC_Service.cu:89
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_ELEMENTS = 1 << 20      # per 1-D output (ids, src_off, dst_off: about 2 M / 3.6 M per papers100M batch)
+DUMP_MAX_ROWS = 1 << 15          # feature rows (16 MB at F = 128)
+
+
+def dump_sample(n, k, seed=0):
+    """Sorted positions of a fixed, seeded sample of k out of n (all n when n <= k): a function of (n, k) alone, so that two runs of the
+    same command sample the same positions."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the arrays of one batch as Engine.result() returns them (nc, ec, ids, labels, src_off, dst_off, features) written as
+    out_dir/<name>.npy -- integers as float64 (exact), features as float32 -- the longer ones as the dump_sample() of their positions /
+    rows.  Returns {name: shape written}; the files together stay within DUMP_LIMIT_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    written, used = {}, 0
+    for name in ("nc", "ec", "labels", "ids", "src_off", "dst_off"):
+        a = np.asarray(res[name]).reshape(-1)
+        a = a[dump_sample(len(a), DUMP_MAX_ELEMENTS)].astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name], used = a.shape, used + a.nbytes
+    f = res.get("features")
+    if f is not None:
+        row_bytes = max(1, f.shape[1] * 4)
+        rows = max(0, min(DUMP_MAX_ROWS, (DUMP_LIMIT_BYTES - used - 4096) // row_bytes))
+        f = np.ascontiguousarray(f[dump_sample(f.shape[0], rows)], dtype=np.float32)
+        np.save(os.path.join(out_dir, "features.npy"), f)
+        written["features"], used = f.shape, used + f.nbytes
+    assert used <= DUMP_LIMIT_BYTES, used
+    return written
+
+
 def run_leg(c, unified, headline, min_time=None, with_alt=False):
-    """W warm-up steps, then R windows of exactly K timed steps (barrier + synchronize on both sides of every
-    window, max over ranks per window, median over windows).  Returns the raw numbers of the leg."""
+    """W warm-up steps, then windows of exactly K timed steps (barrier + synchronize on both sides of every window, max over ranks
+    per window, median over windows): the headline runs ONE window -- exactly --steps timed steps --, the other legs repeat it until
+    min_time is covered.  Returns the raw numbers of the leg."""
     import torch
     args, K, D, L = c.args, c.K, c.D, c.L
     min_time = args.min_time if min_time is None else min_time
@@ -1391,15 +1432,18 @@ def run_leg(c, unified, headline, min_time=None, with_alt=False):
     windows = [window()]
     if not per_level:
         g_ms += [L.d_event_elapsed_ms(a, b) for a, b in ev]
-    # every rank runs the same number of windows: R from the slowest rank's first window
+    # every rank runs the same number of windows: R from the slowest rank's first window (the headline: exactly one)
     first_max, _ = D.aggregate(windows[0], [0.0], world, device=dev)
-    reps = int(min(args.max_reps, max(1, -(-min_time // max(first_max, 1e-6)))))
+    reps = 1 if headline else int(min(args.max_reps, max(1, -(-min_time // max(first_max, 1e-6)))))
     for _ in range(reps - 1):
         windows.append(window())
         if not per_level:
             g_ms += [L.d_event_elapsed_ms(a, b) for a, b in ev]
     K.check()
     xgmi_hw = xc.rate(x0, xc.read(), time.perf_counter() - t_x0, world) if xc else None
+    if headline and rank == 0 and args.dump_outputs:
+        # the batch of the last timed step (W + K - 1), still in its pipe: the schedules below overwrite the pipes
+        dump_outputs(args.dump_outputs, eng.result(me, pipe=(W + K_steps - 1) % depth if overlap else 0))
 
     counters = log.to_numpy(np.int32, (K_steps + W) * 32).reshape(K_steps + W, 2, 16)[W:]
     edges = counters[:, 1, 2 + H].astype(np.int64)          # ec[2+H]: cumulative edges of the batch
@@ -1653,7 +1697,7 @@ def headline_line(c, leg):
         "timing": {"windows": len(leg["windows"]), "steps_per_window": K_steps,
                    "window_ms_min_median_max": [min(leg["windows"]), round(float(np.median(leg["windows"])), 4), max(leg["windows"])],
                    "window_ms_first_32": leg["windows"][:32],
-                   "reported": "median window, max over ranks per window"},
+                   "reported": "one window of exactly --steps timed steps, max over ranks"},
         "feature_GBps": round(leg["job_nodes"] * 4 * F / el / 1e9, 2),
         "batches_per_s": round(K_steps * world / el, 2),
         "edges_per_batch": round(leg["job_edges"] / (K_steps * world), 1),

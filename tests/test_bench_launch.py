@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -367,3 +368,32 @@ def test_a_served_leg_stops_its_children_inside_the_watchdogs_grant():
     assert abs((bench.served_deadline(c) - time.time()) - 40.0) < 1.0
     clock[0] += 70.0                                                              # 10 s left: the floor
     assert abs((bench.served_deadline(c) - time.time()) - 20.0) < 1.0
+
+
+def test_dump_outputs_writes_the_batch_exactly_or_as_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs: every array of Engine.result() as <name>.npy, integers as float64 (exact), features as float32; a papers100M-sized
+    batch (1.9 M rows of 128 floats, 3.6 M edges) becomes a fixed sample within 64 MB, the same positions every time."""
+    rng = np.random.default_rng(1)
+    small = dict(nc=np.arange(16, dtype=np.int32), ec=np.arange(16, dtype=np.int32), labels=np.arange(7, dtype=np.int32),
+                 ids=np.array([2 ** 31 - 1, 5, 7], np.int32), src_off=np.array([0, 1, 2], np.int32), dst_off=np.array([0, 0, 1], np.int32),
+                 features=rng.random((3, 4), dtype=np.float32))
+    got = bench.dump_outputs(str(tmp_path / "s"), small)
+    assert sorted(got) == sorted(small)
+    for k, a in small.items():
+        d = np.load(tmp_path / "s" / (k + ".npy"))
+        assert d.dtype == (np.float32 if k == "features" else np.float64) and np.array_equal(d, a.reshape(d.shape)), k
+    n, e, F = 1936922, 3611965, 128
+    big = dict(small, ids=np.arange(n, dtype=np.int32), src_off=np.arange(e, dtype=np.int32), dst_off=np.arange(e, dtype=np.int32) // 3,
+               features=np.broadcast_to(np.arange(n, dtype=np.float32)[:, None], (n, F)))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    pos = np.load(tmp_path / "a" / "ids.npy").astype(np.int64)              # ids[i] == i: the sample's positions
+    assert len(pos) == bench.DUMP_MAX_ELEMENTS and np.all(np.diff(pos) > 0) and pos[-1] < n
+    feats = np.load(tmp_path / "a" / "features.npy")
+    assert feats.shape[1] == F and 0 < feats.shape[0] <= bench.DUMP_MAX_ROWS and np.all(feats == feats[:, :1])
+    assert np.array_equal(np.load(tmp_path / "a" / "dst_off.npy"), np.load(tmp_path / "a" / "src_off.npy") // 3)

@@ -1,29 +1,39 @@
-"""Boundary B2 against the reference's REAL code: `make -C oracle ref` compiles /root/reference/src/helper_multiprocess.cpp -- the one plain
-C++ file of the reference's path, the shm-slab helper its server and its trainer extension both call -- from where it lies into oracle/_ref/
-(git-ignored; it travels to the GPU box as a built library, the reference tree does not).  tests/ref_shm_compat.py drives it against the
-product's slab in both directions.  Skipped where the library was never built (no reference tree)."""
+"""Boundary B2 against the reference's shm-slab helper -- the one plain C++ file of the reference's path, which its server and its trainer
+extension both call.  tests/ref_shm_compat.py drives it against the product's slab in both directions: the reference's OWN code where
+`make -C oracle ref` could compile it into oracle/_ref/ (git-ignored; only where the reference tree exists), and on every checkout the
+Python stand-in that tests/golden/ref_shm_helper.json holds to what that code did."""
 import os
 import subprocess
 import sys
 
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, load_golden
+from ref_shm_compat import REF_LIB, observe
 
-REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libhelper_multiprocess_ref.so")
+KINDS = ["standin"] + (["ref"] if os.path.exists(REF_LIB) else [])     # the reference's own build as well, where it exists
 
 
-@pytest.mark.skipif(not os.path.exists(REF_LIB), reason="oracle/_ref not built (make -C oracle ref needs /root/reference)")
+def test_the_stand_in_does_what_the_references_helper_did():
+    """The helper's cases (no object yet, one of its size with data in it, a longer one, a shorter one, a write through the mapping):
+    sizes, modes, the bytes kept or cut -- as recorded from the reference's own code."""
+    g = load_golden("ref_shm_helper")
+    for kind in KINDS:
+        assert observe(kind, "refshm_obs%d_" % os.getpid()) == g["cases"], kind
+    assert not [f for f in os.listdir("/dev/shm") if "refshm_obs%d_" % os.getpid() in f]
+
+
 def test_slab_is_the_references_own_struct_in_both_directions():
-    ns = "refshm%d_" % os.getpid()
     env = {k: v for k, v in os.environ.items() if k not in ("LEGION_IPC_NAMESPACE", "LEGION_IPC_DEVICE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ref_shm_compat.py"), ns], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "REF_SHM_COMPAT_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
-    assert not [f for f in os.listdir("/dev/shm") if ns in f]
+    for kind in KINDS:
+        ns = "refshm%d_%s_" % (os.getpid(), kind)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ref_shm_compat.py"), ns, kind], env=env, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0 and "REF_SHM_COMPAT_OK" in r.stdout, kind + ": " + r.stdout[-2000:] + r.stderr[-3000:]
+        assert not [f for f in os.listdir("/dev/shm") if ns in f]
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(REF_LIB), reason="oracle/_ref not built (make -C oracle ref needs /root/reference)")
 def test_reference_helper_reads_a_live_servers_handle_table():
     """The same check with a REAL device behind the slab (the CPU test above runs with $LEGION_IPC_NO_DEVICE=1, where every handle slot is zero):
     the product's server half registers its 7 hand-off buffers x 2 pipes of GPU 0 with hipMalloc + hipIpcGetMemHandle; the reference's own
@@ -33,18 +43,13 @@ def test_reference_helper_reads_a_live_servers_handle_table():
     import ctypes as C
     import numpy as np
     import legion1_amd.capi as K
+    from ref_shm_compat import ShmInfo, helper
     L = K.lib()
     L.legion_set_error_mode(K.ERR_RETURN)
     L.SetGPUDevice(0)
     ns = "refshm_gpu%d_" % os.getpid()
     L.legion_ipc_set_namespace(ns.encode())
-    ref = C.CDLL(REF_LIB)
-
-    class ShmInfo(C.Structure):
-        _fields_ = [("addr", C.c_void_p), ("size", C.c_size_t), ("fd", C.c_int)]
-    create, close = ref._Z18sharedMemoryCreatePKcmP19sharedMemoryInfo_st, ref._Z17sharedMemoryCloseP19sharedMemoryInfo_st
-    create.argtypes, create.restype = [C.c_char_p, C.c_size_t, C.POINTER(ShmInfo)], C.c_int
-    close.argtypes = [C.POINTER(ShmInfo)]
+    create, close = helper(KINDS[-1])        # the reference's own build where it exists, else the stand-in
     slab = 12 + 8 * 2 * 7 * 64
     path = "/dev/shm/" + ns + "simpleIPCshm"
     e = C.c_void_p(L.NewIPCEnv(2))
