@@ -56,9 +56,7 @@ void GPUCache_Initialize(GPUCache* c, int64_t cache_memory, int32_t int_attr_len
         c->ctl[i]->train_step = train_step;
         c->ctl[i]->device_count = device_count;
     }
-    c->float_feature_cache.assign(device_count, nullptr);
-    c->cache_imported.assign(device_count, false);
-    c->shard_chunks.assign(device_count, {});
+    c->shards.assign(device_count, {});
     c->d_shard_tab.assign(device_count, nullptr);
     c->cache_memory = cache_memory;
     c->int_attr_len = int_attr_len;
@@ -95,33 +93,15 @@ void GPUCache_InitializeCacheController(GPUCache* c, int32_t dev_id, int32_t tot
     HIP_CHECK(hipDeviceSynchronize());
 }
 
-static void free_shard(GPUCache* c, int dev)
-{
-    for (float* p : c->shard_chunks[dev]) {
-        if (!p) continue;
-        if (c->cache_imported[dev]) (void)hipIpcCloseMemHandle(p);
-        else (void)hipFree(p);
-    }
-    c->shard_chunks[dev].clear();
-    c->float_feature_cache[dev] = nullptr;
-    c->cache_imported[dev] = false;
-}
-
 // (re)write the device-side chunk-pointer tables of the local members of clique Ki
 static void publish_shard_tables(GPUCache* c, int Ki)
 {
     const int Kg = c->Kg, nch = c->nchunks[Ki];
     std::vector<float*> h((size_t)Kg * nch, nullptr);
     for (int j = 0; j < Kg; j++)
-        for (size_t q = 0; q < c->shard_chunks[Ki * Kg + j].size() && (int)q < nch; q++) h[(size_t)j * nch + q] = c->shard_chunks[Ki * Kg + j][q];
-    for (int j = 0; j < Kg; j++) {
-        const int dev = Ki * Kg + j;
-        if (is_remote_device(dev)) continue;
-        DeviceGuard guard(dev);
-        LEGION_AUDIT_TABLE(dev, h.data(), h.size(), "feature shard chunk table");
-        if (!c->d_shard_tab[dev]) HIP_CHECK(hipMalloc(&c->d_shard_tab[dev], h.size() * sizeof(float*)));
-        HIP_CHECK(hipMemcpy(c->d_shard_tab[dev], h.data(), h.size() * sizeof(float*), hipMemcpyHostToDevice));
-    }
+        for (int q = 0; q < nch; q++) h[(size_t)j * nch + q] = c->shards[Ki * Kg + j].at(q);
+    for (int j = 0; j < Kg; j++)
+        if (!is_remote_device(Ki * Kg + j)) upload_table(Ki * Kg + j, h, c->d_shard_tab[Ki * Kg + j], false, "feature shard chunk table");
 }
 
 static void free_controller_maps(CacheController* k)
@@ -146,7 +126,7 @@ void GPUCache_Finalize(GPUCache* c, int32_t dev_id)
     for (int q = 0; q < 2; q++) if (k->hit_ev[q]) { (void)hipEventDestroy(k->hit_ev[q]); k->hit_ev[q] = nullptr; k->hit_ev_armed[q] = false; }
     k->node_access_time = k->edge_access_time = nullptr;
     k->d_max_ids = k->d_global_count = nullptr;
-    free_shard(c, dev_id);
+    c->shards[dev_id].release();
     if (c->d_shard_tab[dev_id]) { (void)hipFree(c->d_shard_tab[dev_id]); c->d_shard_tab[dev_id] = nullptr; }
 }
 
@@ -480,19 +460,15 @@ void GPUCache_FillUp(GPUCache* c, int cache_agg_mode, GPUNodeStorage* noder, GPU
         pitch = legion_shard_pitch(F, c->node_capacity[i], c->cache_memory > 0 ? (int64_t)((1.0 - a) * (double)c->cache_memory) : 0);
     }
     c->shard_pitch = pitch;
-    c->chunk_shift.assign(c->Kc, 30);
-    c->nchunks.assign(c->Kc, 1);
     // A shard is a list of chunk allocations (2^chunk_shift rows each, <= 1 GiB by default): a large single
     // allocation could not be imported over HIP IPC on the test pool (profiles/r01_unified_ipc_notes.md).
-    const char* env_chunk = getenv("LEGION_SHARD_CHUNK_BYTES");
-    const int64_t chunk_bytes = env_chunk ? atoll(env_chunk) : (1ll << 30);
+    const int shift = chunk_shift((int64_t)pitch * sizeof(float), 0);
+    const int32_t rpc = 1 << shift;
+    c->chunk_shift.assign(c->Kc, shift);
+    c->nchunks.assign(c->Kc, 1);
     for (int i = 0; i < c->Kc; i++) {
         const int32_t ncap = c->node_capacity[i], ecap = c->edge_capacity[i];
-        int shift = 0;
-        while (shift < 30 && (2ll << shift) * pitch * (int64_t)sizeof(float) <= chunk_bytes) shift++;
-        const int32_t rpc = 1 << shift;
-        c->chunk_shift[i] = shift;
-        c->nchunks[i] = ncap > 0 ? (ncap + rpc - 1) / rpc : 1;
+        c->nchunks[i] = chunk_count(ncap, shift);
         for (int j = 0; j < Kg; j++)
             if (c->d_shard_tab[i * Kg + j]) { (void)hipFree(c->d_shard_tab[i * Kg + j]); c->d_shard_tab[i * Kg + j] = nullptr; }
         for (int j = 0; j < Kg; j++) {
@@ -509,7 +485,7 @@ void GPUCache_FillUp(GPUCache* c, int cache_agg_mode, GPUNodeStorage* noder, GPU
             LEGION_AUDIT_OWNER(k->feat_map, dev, "FillUp: id -> slot map");
             launch_build_feat_map(nullptr, k->feat_map, c->QF[i], ncap, Kg, V);
             launch_build_topo_map(nullptr, k->topo_owner, k->topo_row, c->QT[i], ecap, Kg, i, V);
-            free_shard(c, dev);
+            c->shards[dev].release();
             if (F > 0 && ncap > 0) {
                 for (int q = 0; q < c->nchunks[i]; q++) {
                     const int32_t row0 = q * rpc, rows = std::min(rpc, ncap - row0);
@@ -518,9 +494,8 @@ void GPUCache_FillUp(GPUCache* c, int cache_agg_mode, GPUNodeStorage* noder, GPU
                     if (pitch != F) HIP_CHECK(hipMemsetAsync(chunk, 0, (size_t)rows * pitch * sizeof(float), nullptr));
                     launch_feat_fill_up(nullptr, row0, rows, F, pitch, noder->float_attr_pitch, chunk, noder->float_attrs, c->QF[i], Kg, j, V);
                     LEGION_AUDIT_OWNER(chunk, dev, "FillUp: feature shard chunk");
-                    c->shard_chunks[dev].push_back(chunk);
+                    c->shards[dev].chunks.push_back(chunk);
                 }
-                c->float_feature_cache[dev] = c->shard_chunks[dev][0];
             }
             HIP_CHECK(hipDeviceSynchronize());
         }
@@ -532,10 +507,7 @@ void GPUCache_FillUp(GPUCache* c, int cache_agg_mode, GPUNodeStorage* noder, GPU
     log_out() << "Finish load topology cache\n";
 }
 
-float* GPUCache_Float_Feature_Cache(const GPUCache* c, int32_t dev_id)
-{
-    return (dev_id >= 0 && dev_id < c->device_count) ? c->float_feature_cache[dev_id] : nullptr;
-}
+float* GPUCache_Float_Feature_Cache(const GPUCache* c, int32_t dev_id) { return GPUCache_GetShardChunk(c, dev_id, 0); }
 int32_t GPUCache_ShardChunkCount(const GPUCache* c, int32_t dev_id)
 {
     if (!c || dev_id < 0 || dev_id >= c->device_count || c->nchunks.empty()) return 0;
@@ -549,43 +521,23 @@ int32_t GPUCache_ShardChunkRows(const GPUCache* c, int32_t dev_id)
 int32_t GPUCache_ShardPitch(const GPUCache* c) { return c ? (c->shard_pitch > 0 ? c->shard_pitch : c->float_attr_len) : 0; }
 float* GPUCache_GetShardChunk(const GPUCache* c, int32_t dev_id, int32_t chunk)
 {
-    if (!c || dev_id < 0 || dev_id >= c->device_count || chunk < 0 || chunk >= (int)c->shard_chunks[dev_id].size()) return nullptr;
-    return c->shard_chunks[dev_id][chunk];
+    return (c && dev_id >= 0 && dev_id < c->device_count) ? c->shards[dev_id].at(chunk) : nullptr;
 }
 int GPUCache_ExportFeatureShardChunk(GPUCache* c, int32_t dev_id, int32_t chunk, void* handle64)
 {
-    if (!c || !handle64 || dev_id < 0 || dev_id >= c->device_count || c->cache_imported[dev_id] || chunk < 0 ||
-        chunk >= (int)c->shard_chunks[dev_id].size()) { LEGION_ARG_ERROR("ExportFeatureShardChunk: no such local chunk"); return -1; }
-    DeviceGuard guard(dev_id);
-    if (!ipc_export_ok(c->shard_chunks[dev_id][chunk], "ExportFeatureShardChunk")) return -1;
-    HIP_CHECK(hipIpcGetMemHandle((hipIpcMemHandle_t*)handle64, c->shard_chunks[dev_id][chunk]));
-    return error_pending() ? -1 : 0;
+    if (!c || dev_id < 0 || dev_id >= c->device_count) { LEGION_ARG_ERROR("ExportFeatureShardChunk: no such local chunk"); return -1; }
+    return c->shards[dev_id].export_chunk(dev_id, chunk, handle64, "ExportFeatureShardChunk");
 }
 int GPUCache_ImportFeatureShardChunk(GPUCache* c, int32_t dev_id, int32_t chunk, const void* handle64)
 {
     if (!c || !handle64 || dev_id < 0 || dev_id >= c->device_count || !is_remote_device(dev_id) || c->nchunks.empty() || chunk < 0 ||
         chunk >= c->nchunks[dev_id / c->Kg]) { LEGION_ARG_ERROR("ImportFeatureShardChunk: dev_id must be a remote member, chunk in range"); return -1; }
-    {   // what the exporter allocated for this chunk: 2^shift rows (the last chunk may be shorter)
-        const int Ki = dev_id / c->Kg;
-        const int64_t rows = std::min<int64_t>(1ll << c->chunk_shift[Ki], std::max<int64_t>(1, c->node_capacity[Ki]));
-        if (c->shard_pitch <= 0) c->shard_pitch = legion_row_pitch(c->float_attr_len);
-        if (!ipc_size_ok(rows * c->shard_pitch * (int64_t)sizeof(float), "ImportFeatureShardChunk")) return -1;
-    }
-    hipIpcMemHandle_t h;
-    memcpy(&h, handle64, sizeof(h));
-    void* p = nullptr;
-    {
-        const int home = clique_home(dev_id / c->Kg, c->Kg);
-        DeviceGuard guard(home >= 0 ? home : dev_id);
-        HIP_CHECK(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-    }
-    if (!p) return -1;
-    auto& v = c->shard_chunks[dev_id];
-    if ((int)v.size() <= chunk) v.resize(chunk + 1, nullptr);
-    v[chunk] = (float*)p;
-    c->cache_imported[dev_id] = true;
-    if (chunk == 0) c->float_feature_cache[dev_id] = (float*)p;
-    publish_shard_tables(c, dev_id / c->Kg);
+    // what the exporter allocated for this chunk: 2^shift rows (the last chunk may be shorter); the clique's home GPU opens it, again if open
+    const int Ki = dev_id / c->Kg, home = clique_home(Ki, c->Kg);
+    const int64_t rows = std::min<int64_t>(1ll << c->chunk_shift[Ki], std::max<int64_t>(1, c->node_capacity[Ki]));
+    if (c->shard_pitch <= 0) c->shard_pitch = legion_row_pitch(c->float_attr_len);
+    if (c->shards[dev_id].import_chunk(chunk, handle64, rows * c->shard_pitch * (int64_t)sizeof(float), home >= 0 ? home : dev_id, "ImportFeatureShardChunk") != 0) return -1;
+    publish_shard_tables(c, Ki);
     return 0;
 }
 // What an importer has to agree with before it opens a peer's shard: it addresses the peer's rows as

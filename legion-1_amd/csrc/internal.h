@@ -20,6 +20,7 @@ bool error_is_fatal();                                     // LEGION_ERR_EXIT mo
 int64_t ipc_max_bytes();                                   // $LEGION_IPC_MAX_BYTES, see runtime.cpp
 bool ipc_size_ok(int64_t bytes, const char* who);          // sticky error + false above the limit
 bool ipc_export_ok(const void* ptr, const char* who);      // same, for the allocation `ptr` belongs to
+int64_t shard_chunk_bytes();                               // $LEGION_SHARD_CHUNK_BYTES (default 1 GiB), read on every call
 inline void check(hipError_t e, const char* file, int line)
 {
     if (e != hipSuccess) report_error(file, line, hipGetErrorString(e), true);
@@ -41,6 +42,23 @@ struct DeviceGuard {
     explicit DeviceGuard(int logical);
     ~DeviceGuard();
 };
+
+// ---- cache shards and CSR fragments (chunks.cpp): lists of chunk allocations of <= shard_chunk_bytes(), each one HIP-IPC export
+int chunk_shift(int64_t unit_bytes, int min_shift);        // largest s <= 30 (>= min_shift) with (1 << s) * unit_bytes <= chunk bytes
+inline int chunk_count(int64_t n, int shift) { return n > 0 ? (int)(((n - 1) >> shift) + 1) : 1; }   // chunks of 2^shift for n elements
+template <typename T>
+struct ChunkList {
+    std::vector<T*> chunks;
+    bool imported = false;                                 // opened from another process' IPC handles (closed, not freed)
+    T* at(int q) const { return q >= 0 && q < (int)chunks.size() ? chunks[q] : nullptr; }
+    bool complete(size_t n) const { for (T* p : chunks) if (!p) return false; return chunks.size() == n; }
+    void release();                                        // free / close every chunk: an empty local list again
+    int export_chunk(int dev, int q, void* handle64, const char* who) const;   // 0, or -1 with a sticky error naming `who`
+    // open the handle under logical GPU open_dev as chunk q, once the exporter's allocation (>= floor_bytes) passed the IPC limit
+    int import_chunk(int q, const void* handle64, int64_t floor_bytes, int open_dev, const char* who);
+};
+// on `viewer`: audit h, then copy it into `tab` (allocated when null; freed first, after a device sync, when `realloc`; empty h: freed)
+template <typename T> void upload_table(int viewer, const std::vector<T*>& h, T**& tab, bool realloc, const char* what);
 
 // ---- constants --------------------------------------------------------------------------------
 // Position-table entry: (epoch << kPosShift) | value.  epoch = kEpochTop - batch serial: entries of older batches compare GREATER than
@@ -159,8 +177,7 @@ void launch_find_topo(hipStream_t s, const int32_t* input_ids, int8_t* part_inde
 struct GatherArgs {
     const float* table;                       // V x F rows: the "cpu_float_attrs" of the reference
     // clique caches (Global_Float_Feature_Cache, the reference's float** cache_float_attrs): device table of
-    // Kg x nchunks chunk pointers; shard row r lives in chunk r >> chunk_shift (shards are allocated in
-    // chunks so that each piece can be exported over HIP IPC)
+    // Kg x nchunks chunk pointers (a shard is a ChunkList); shard row r lives in chunk r >> chunk_shift
     const float* const* shard_tab;
     int32_t chunk_shift, nchunks;
     const int32_t* feat_map;                  // int32[V] global slot or -1; null = no cache
@@ -277,17 +294,15 @@ struct GPUGraphStorage {
     std::vector<int32_t*> replica_indices;
     int32_t csr_location = LEGION_LOC_HOST_PINNED;
     bool owns_csr = false;
-    // CSR fragment of one logical GPU (device memory on that GPU's physical device).  Both arrays are lists of
-    // chunk allocations (<= $LEGION_SHARD_CHUNK_BYTES, default 1 GiB, like the feature shards) so that every piece
-    // can be opened over HIP IPC.  indptr chunk q: entries [q<<row_shift, min(rows, (q+1)<<row_shift)] (one entry of
+    // CSR fragment of one logical GPU (device memory on that GPU's physical device).  Both arrays are chunk lists
+    // (ChunkList, like the feature shards).  indptr chunk q: entries [q<<row_shift, min(rows, (q+1)<<row_shift)] (one entry of
     // overlap, so ip[r] and ip[r+1] come from the same chunk).  indices chunk q: every row whose first edge offset o
     // satisfies o >> edge_shift == q, whole, at element o & mask (the chunk is as long as its last row needs).
     struct Fragment {
         int32_t rows = 0;
         int64_t edges = 0;
-        std::vector<int64_t*> ip;
-        std::vector<int32_t*> ix;
-        bool imported = false;               // opened from another process' IPC handles
+        legion::ChunkList<int64_t> ip;       // both imported, or neither
+        legion::ChunkList<int32_t> ix;
         bool complete = false;               // every chunk present (built locally, or all chunks imported)
     };
     std::vector<Fragment> frag;
@@ -346,9 +361,7 @@ struct GPUCache {
     std::vector<double> alpha;
     int64_t cache_memory = 0;
     int32_t int_attr_len = 0, float_attr_len = 0, train_step = 0;
-    std::vector<float*> float_feature_cache;         // per logical GPU
-    std::vector<bool> cache_imported;                // shard opened from another process' IPC handle
-    std::vector<std::vector<float*>> shard_chunks;   // per logical GPU: the shard's chunk allocations
+    std::vector<legion::ChunkList<float>> shards;    // per logical GPU: the shard's chunk allocations
     std::vector<float**> d_shard_tab;                // per LOCAL logical GPU: device table [Kg x nchunks]
     std::vector<int32_t> chunk_shift, nchunks;       // per clique
     int32_t shard_pitch = 0;                         // floats between two rows of a shard chunk (legion_row_pitch(F))

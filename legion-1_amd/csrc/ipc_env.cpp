@@ -250,9 +250,7 @@ static VmmRegion* vmm_create(int logical_dev, int pipe, size_t bytes)
         LEGION_ARG_ERROR("hand-off buffer above the HIP-IPC limit: this runtime has no virtual memory management");
         return nullptr;
     }
-    const char* e = getenv("LEGION_SHARD_CHUNK_BYTES");     // one chunk size for everything that crosses a process boundary in pieces
-    size_t chunk = e && atoll(e) > 0 ? (size_t)atoll(e) : ((size_t)1 << 30);
-    chunk = std::max(gran, chunk / gran * gran);
+    const size_t chunk = std::max(gran, (size_t)shard_chunk_bytes() / gran * gran);   // the chunk size of the cache shards too
     VmmRegion* r = new VmmRegion();
     r->device = logical_dev;
     const size_t total = (bytes + gran - 1) / gran * gran;

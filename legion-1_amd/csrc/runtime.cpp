@@ -50,6 +50,12 @@ int64_t ipc_max_bytes()
     const char* e = getenv("LEGION_IPC_MAX_BYTES");
     return e && atoll(e) > 0 ? atoll(e) : LEGION_IPC_MAX_BYTES_DEFAULT;
 }
+// chunk size of everything that crosses a process boundary in pieces (not cached: tests change it inside one process)
+int64_t shard_chunk_bytes()
+{
+    const char* e = getenv("LEGION_SHARD_CHUNK_BYTES");
+    return e && atoll(e) > 0 ? atoll(e) : (1ll << 30);
+}
 bool ipc_size_ok(int64_t bytes, const char* who)
 {
     if (bytes <= ipc_max_bytes()) return true;

@@ -107,31 +107,16 @@ void GPUGraphStorage_Build(GPUGraphStorage* g, const LegionBuildInfo* info)
     g->replica_indices.assign(P, nullptr);
     g->view.assign(P, std::vector<bool>(P, false));
     g->d_frag_tab.assign(P, nullptr);
-    // chunk geometry of the fragments: powers of two that fit $LEGION_SHARD_CHUNK_BYTES (default 1 GiB)
-    const char* env_chunk = getenv("LEGION_SHARD_CHUNK_BYTES");
-    const int64_t chunk_bytes = env_chunk ? atoll(env_chunk) : (1ll << 30);
-    g->row_shift = 4; g->edge_shift = 4;
-    while (g->row_shift < 30 && (2ll << g->row_shift) * (int64_t)sizeof(int64_t) <= chunk_bytes) g->row_shift++;
-    while (g->edge_shift < 30 && (2ll << g->edge_shift) * (int64_t)sizeof(int32_t) <= chunk_bytes) g->edge_shift++;
+    // chunk geometry of the fragments: powers of two that fit shard_chunk_bytes()
+    g->row_shift = chunk_shift(sizeof(int64_t), 4);
+    g->edge_shift = chunk_shift(sizeof(int32_t), 4);
 }
-
-static int frag_ip_chunks(const GPUGraphStorage* g, int32_t rows) { return rows > 0 ? (int)((((int64_t)rows - 1) >> g->row_shift) + 1) : 1; }
-static int frag_ix_chunks(const GPUGraphStorage* g, int64_t edges) { return edges > 0 ? (int)(((edges - 1) >> g->edge_shift) + 1) : 1; }
 
 static void free_fragment(GPUGraphStorage::Fragment& f)
 {
-    for (int64_t* p : f.ip) if (p) { if (f.imported) (void)hipIpcCloseMemHandle(p); else (void)hipFree(p); }
-    for (int32_t* p : f.ix) if (p) { if (f.imported) (void)hipIpcCloseMemHandle(p); else (void)hipFree(p); }
+    f.ip.release();
+    f.ix.release();
     f = GPUGraphStorage::Fragment();
-}
-
-static bool fragment_complete(const GPUGraphStorage* g, int dev)
-{
-    const auto& f = g->frag[dev];
-    if (f.rows <= 0 || (int)f.ip.size() != frag_ip_chunks(g, f.rows) || (int)f.ix.size() != frag_ix_chunks(g, f.edges)) return false;
-    for (auto* p : f.ip) if (!p) return false;
-    for (auto* p : f.ix) if (!p) return false;
-    return true;
 }
 
 // (re)write the device-side chunk-pointer tables of every local viewer
@@ -139,25 +124,20 @@ static void publish_fragment_tables(GPUGraphStorage* g)
 {
     const int P = g->partition_count;
     int ip_nch = 1, ix_nch = 1;
-    for (int p = 0; p < P; p++) { ip_nch = std::max(ip_nch, (int)g->frag[p].ip.size()); ix_nch = std::max(ix_nch, (int)g->frag[p].ix.size()); }
+    for (const auto& f : g->frag) { ip_nch = std::max(ip_nch, (int)f.ip.chunks.size()); ix_nch = std::max(ix_nch, (int)f.ix.chunks.size()); }
     const bool regrow = ip_nch != g->ip_nch || ix_nch != g->ix_nch;
     g->ip_nch = ip_nch; g->ix_nch = ix_nch;
-    std::vector<void*> h((size_t)P * (ip_nch + ix_nch) + 1); // +1: a zero-degree row at offset == edges names chunk ix_nch
     for (int dev = 0; dev < P; dev++) {
         if (is_remote_device(dev)) continue;
         bool any = false;
-        std::fill(h.begin(), h.end(), nullptr);
+        std::vector<void*> h((size_t)P * (ip_nch + ix_nch) + 1, nullptr); // +1: a zero-degree row at offset == edges names chunk ix_nch
         for (int p = 0; p < P; p++) {
             if (!g->view[dev][p]) continue;
-            for (size_t q = 0; q < g->frag[p].ip.size(); q++) { h[(size_t)p * ip_nch + q] = g->frag[p].ip[q]; any = true; }
-            for (size_t q = 0; q < g->frag[p].ix.size(); q++) h[(size_t)P * ip_nch + (size_t)p * ix_nch + q] = g->frag[p].ix[q];
+            for (size_t q = 0; q < g->frag[p].ip.chunks.size(); q++) { h[(size_t)p * ip_nch + q] = g->frag[p].ip.chunks[q]; any = true; }
+            for (size_t q = 0; q < g->frag[p].ix.chunks.size(); q++) h[(size_t)P * ip_nch + (size_t)p * ix_nch + q] = g->frag[p].ix.chunks[q];
         }
-        DeviceGuard guard(dev);
-        LEGION_AUDIT_TABLE(dev, h.data(), h.size(), "fragment chunk table");
-        if (g->d_frag_tab[dev] && (regrow || !any)) { HIP_CHECK(hipDeviceSynchronize()); (void)hipFree(g->d_frag_tab[dev]); g->d_frag_tab[dev] = nullptr; }
-        if (!any) continue;
-        if (!g->d_frag_tab[dev]) HIP_CHECK(hipMalloc(&g->d_frag_tab[dev], h.size() * sizeof(void*)));
-        HIP_CHECK(hipMemcpy(g->d_frag_tab[dev], h.data(), h.size() * sizeof(void*), hipMemcpyHostToDevice));
+        if (!any) h.clear();   // the viewer sees no fragment: its table is freed
+        upload_table(dev, h, g->d_frag_tab[dev], regrow, "fragment chunk table");
     }
 }
 
@@ -186,7 +166,7 @@ void GPUGraphStorage_GraphCache(GPUGraphStorage* g, int32_t* QT, int32_t Ki, int
         f.rows = capacity;
         f.edges = total;
         // indices chunks: chunk q ends where the last row that starts before its upper boundary ends
-        const int nx = frag_ix_chunks(g, total);
+        const int nx = chunk_count(total, g->edge_shift);
         std::vector<int64_t> ends(nx, total);
         if (nx > 1) {
             int64_t* d_ends = nullptr;
@@ -195,34 +175,34 @@ void GPUGraphStorage_GraphCache(GPUGraphStorage* g, int32_t* QT, int32_t Ki, int
             HIP_CHECK(hipMemcpy(ends.data(), d_ends, (size_t)(nx - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
             HIP_CHECK(hipFree(d_ends));
         }
-        f.ix.assign(nx, nullptr);
+        f.ix.chunks.assign(nx, nullptr);
         for (int q = 0; q < nx; q++) {
             const int64_t elems = ends[q] - ((int64_t)q << g->edge_shift); // <= 0: no row starts in this chunk
-            HIP_CHECK(hipMalloc(&f.ix[q], (size_t)(elems > 0 ? elems : 1) * sizeof(int32_t)));
+            HIP_CHECK(hipMalloc(&f.ix.chunks[q], (size_t)(elems > 0 ? elems : 1) * sizeof(int32_t)));
         }
         int32_t** d_chunks = nullptr;
         HIP_CHECK(hipMalloc(&d_chunks, ((size_t)nx + 1) * sizeof(int32_t*))); // +1: see publish_fragment_tables
-        HIP_CHECK(hipMemcpy(d_chunks, f.ix.data(), (size_t)nx * sizeof(int32_t*), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_chunks, f.ix.chunks.data(), (size_t)nx * sizeof(int32_t*), hipMemcpyHostToDevice));
         launch_topo_fill_up(nullptr, QT, Kg, i, capacity, g->node_num, g->csr_node_index_cpu, g->csr_dst_node_ids_cpu, d_index, d_chunks, g->edge_shift);
         // indptr chunks (one entry of overlap); a single chunk adopts the build copy
-        const int np = frag_ip_chunks(g, capacity);
+        const int np = chunk_count(capacity, g->row_shift);
         if (np == 1) {
-            f.ip.assign(1, d_index);
+            f.ip.chunks.assign(1, d_index);
             d_index = nullptr;
         } else {
-            f.ip.assign(np, nullptr);
+            f.ip.chunks.assign(np, nullptr);
             const int64_t rpc = 1ll << g->row_shift;
             for (int q = 0; q < np; q++) {
                 const int64_t r0 = q * rpc, n = std::min<int64_t>(rpc, capacity - r0) + 1;
-                HIP_CHECK(hipMalloc(&f.ip[q], (size_t)n * sizeof(int64_t)));
-                HIP_CHECK(hipMemcpy(f.ip[q], d_index + r0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice));
+                HIP_CHECK(hipMalloc(&f.ip.chunks[q], (size_t)n * sizeof(int64_t)));
+                HIP_CHECK(hipMemcpy(f.ip.chunks[q], d_index + r0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice));
             }
         }
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipFree(d_chunks));
         if (d_index) HIP_CHECK(hipFree(d_index));
-        for (auto* q : f.ip) LEGION_AUDIT_OWNER(q, dev, "GraphCache: indptr chunk of a fragment");
-        for (auto* q : f.ix) LEGION_AUDIT_OWNER(q, dev, "GraphCache: indices chunk of a fragment");
+        for (auto* q : f.ip.chunks) LEGION_AUDIT_OWNER(q, dev, "GraphCache: indptr chunk of a fragment");
+        for (auto* q : f.ix.chunks) LEGION_AUDIT_OWNER(q, dev, "GraphCache: indices chunk of a fragment");
         f.complete = true;
     }
     // every clique member sees every clique fragment (pointer tables copied D2D in the reference, :128-131)
@@ -245,7 +225,7 @@ void GPUGraphStorage_Finalize(GPUGraphStorage* g)
     free_replicas(g->replica_indptr);
     free_replicas(g->replica_indices);
     for (size_t i = 0; i < g->frag.size(); i++) {
-        if (!is_remote_device((int)i) || g->frag[i].imported) { DeviceGuard guard((int)i); free_fragment(g->frag[i]); }
+        if (!is_remote_device((int)i) || g->frag[i].ip.imported) { DeviceGuard guard((int)i); free_fragment(g->frag[i]); }
         if (g->d_frag_tab[i]) { DeviceGuard guard((int)i); (void)hipFree(g->d_frag_tab[i]); g->d_frag_tab[i] = nullptr; }
     }
     if (g->owns_csr) {
@@ -263,20 +243,18 @@ static bool frag_args_ok(const GPUGraphStorage* g, int32_t dev_id, int32_t part_
 }
 int64_t* GPUGraphStorage_GetFragmentIndex(const GPUGraphStorage* g, int32_t dev_id, int32_t part_id)
 {   // first chunk (the whole indptr when the fragment has one chunk)
-    if (!frag_args_ok(g, dev_id, part_id) || !g->view[dev_id][part_id] || g->frag[part_id].ip.empty()) return nullptr;
-    return g->frag[part_id].ip[0];
+    return frag_args_ok(g, dev_id, part_id) && g->view[dev_id][part_id] ? g->frag[part_id].ip.at(0) : nullptr;
 }
 int32_t* GPUGraphStorage_GetFragmentMatrix(const GPUGraphStorage* g, int32_t dev_id, int32_t part_id)
 {
-    if (!frag_args_ok(g, dev_id, part_id) || !g->view[dev_id][part_id] || g->frag[part_id].ix.empty()) return nullptr;
-    return g->frag[part_id].ix[0];
+    return frag_args_ok(g, dev_id, part_id) && g->view[dev_id][part_id] ? g->frag[part_id].ix.at(0) : nullptr;
 }
 int32_t GPUGraphStorage_FragmentRows(const GPUGraphStorage* g, int32_t dev_id) { return frag_args_ok(g, dev_id, 0) ? g->frag[dev_id].rows : 0; }
 int64_t GPUGraphStorage_FragmentEdges(const GPUGraphStorage* g, int32_t dev_id) { return frag_args_ok(g, dev_id, 0) ? g->frag[dev_id].edges : 0; }
 int32_t GPUGraphStorage_FragmentChunkCount(const GPUGraphStorage* g, int32_t dev_id, int32_t which)
 {
     if (!frag_args_ok(g, dev_id, 0)) return 0;
-    return which == 0 ? (int32_t)g->frag[dev_id].ip.size() : (int32_t)g->frag[dev_id].ix.size();
+    return which == 0 ? (int32_t)g->frag[dev_id].ip.chunks.size() : (int32_t)g->frag[dev_id].ix.chunks.size();
 }
 int64_t GPUGraphStorage_FragmentChunkSpan(const GPUGraphStorage* g, int32_t which)
 {
@@ -284,48 +262,34 @@ int64_t GPUGraphStorage_FragmentChunkSpan(const GPUGraphStorage* g, int32_t whic
 }
 void* GPUGraphStorage_GetFragmentChunk(const GPUGraphStorage* g, int32_t dev_id, int32_t which, int32_t chunk)
 {
-    if (!frag_args_ok(g, dev_id, 0) || chunk < 0 || chunk >= GPUGraphStorage_FragmentChunkCount(g, dev_id, which)) return nullptr;
-    return which == 0 ? (void*)g->frag[dev_id].ip[chunk] : (void*)g->frag[dev_id].ix[chunk];
+    if (!frag_args_ok(g, dev_id, 0)) return nullptr;
+    return which == 0 ? (void*)g->frag[dev_id].ip.at(chunk) : (void*)g->frag[dev_id].ix.at(chunk);
 }
 int GPUGraphStorage_ExportFragmentChunk(GPUGraphStorage* g, int32_t dev_id, int32_t which, int32_t chunk, void* handle64)
 {
-    void* p = GPUGraphStorage_GetFragmentChunk(g, dev_id, which, chunk);
-    if (!p || !handle64 || g->frag[dev_id].imported) { LEGION_ARG_ERROR("ExportFragmentChunk: no such local chunk"); return -1; }
-    DeviceGuard guard(dev_id);
-    if (!ipc_export_ok(p, "ExportFragmentChunk")) return -1;
-    HIP_CHECK(hipIpcGetMemHandle((hipIpcMemHandle_t*)handle64, p));
-    return error_pending() ? -1 : 0;
+    if (!frag_args_ok(g, dev_id, 0)) { LEGION_ARG_ERROR("ExportFragmentChunk: no such local chunk"); return -1; }
+    const auto& f = g->frag[dev_id];
+    return which == 0 ? f.ip.export_chunk(dev_id, chunk, handle64, "ExportFragmentChunk") : f.ix.export_chunk(dev_id, chunk, handle64, "ExportFragmentChunk");
 }
 int GPUGraphStorage_ImportFragmentChunk(GPUGraphStorage* g, int32_t owner_dev, int32_t viewer_dev, int32_t which, int32_t chunk,
                                         const void* handle64, int32_t rows, int64_t edges)
 {
     if (!frag_args_ok(g, owner_dev, viewer_dev) || !handle64 || !is_remote_device(owner_dev) || rows <= 0 || edges < 0) { LEGION_ARG_ERROR("ImportFragmentChunk: owner must be a remote member"); return -1; }
     GPUGraphStorage::Fragment& f = g->frag[owner_dev];
-    if (!f.imported) {
-        f.rows = rows; f.edges = edges; f.imported = true;
-        f.ip.assign(frag_ip_chunks(g, rows), nullptr);
-        f.ix.assign(frag_ix_chunks(g, edges), nullptr);
+    if (!f.ip.imported) {
+        f.rows = rows; f.edges = edges; f.ip.imported = f.ix.imported = true;
+        f.ip.chunks.assign(chunk_count(rows, g->row_shift), nullptr);
+        f.ix.chunks.assign(chunk_count(edges, g->edge_shift), nullptr);
     }
     if (f.rows != rows || f.edges != edges) { LEGION_ARG_ERROR("ImportFragmentChunk: rows/edges differ from the first chunk's"); return -1; }
-    const int n = which == 0 ? (int)f.ip.size() : (int)f.ix.size();
+    const int n = which == 0 ? (int)f.ip.chunks.size() : (int)f.ix.chunks.size();
     if (chunk < 0 || chunk >= n) { LEGION_ARG_ERROR("ImportFragmentChunk: chunk out of range"); return -1; }
-    void*& slot = which == 0 ? (void*&)f.ip[chunk] : (void*&)f.ix[chunk];
-    {   // lower bound of what the exporter allocated for this chunk
-        const int64_t bytes = which == 0 ? (std::min<int64_t>(rows, 1ll << g->row_shift) + 1) * (int64_t)sizeof(int64_t)
-                                         : std::min<int64_t>(edges, 1ll << g->edge_shift) * (int64_t)sizeof(int32_t);
-        if (!slot && !ipc_size_ok(bytes, "ImportFragmentChunk")) return -1;
-    }
-    if (!slot) {
-        DeviceGuard guard(viewer_dev);
-        hipIpcMemHandle_t h;
-        memcpy(&h, handle64, sizeof(h));
-        void* p = nullptr;
-        HIP_CHECK(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-        if (!p) return -1;
-        slot = p;
-    }
+    // the viewer opens the chunk, once; floor: a lower bound of what the exporter allocated for it
+    auto open = [&](auto& list, int64_t floor) { return list.chunks[chunk] ? 0 : list.import_chunk(chunk, handle64, floor, viewer_dev, "ImportFragmentChunk"); };
+    if ((which == 0 ? open(f.ip, (std::min<int64_t>(rows, 1ll << g->row_shift) + 1) * (int64_t)sizeof(int64_t))
+                    : open(f.ix, std::min<int64_t>(edges, 1ll << g->edge_shift) * (int64_t)sizeof(int32_t))) != 0) return -1;
     g->view[viewer_dev][owner_dev] = true;
-    f.complete = fragment_complete(g, owner_dev);
+    f.complete = f.ip.complete(chunk_count(rows, g->row_shift)) && f.ix.complete(chunk_count(edges, g->edge_shift));
     if (f.complete) publish_fragment_tables(g);
     return 0;
 }
