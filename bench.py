@@ -4,15 +4,18 @@ synthetic graph of the ogbn-papers100M shape (BASELINE.json metric), one process
 
   python bench.py --gpus 1 --steps 50 --warmup 5
   python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR   # + the last timed batch as DIR/<name>.npy
+  python bench.py --gpus 1 --steps 50 --warmup 5 --full   # + every other schedule, leg and baseline (full_legs)
   python bench.py --gpus N ...          # spawns N ranks itself (parent never touches the GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one mini-batch (B seeds, H-hop sampling, COO construction, gather of every unique
 node's feature row) with CSR and features already resident in HBM.  Each rank owns the seeds
 `tid % N == rank` (GPUGraphStore.cu:332-346) and a full replica of the graph (Kg = 1), so there is
-no data-path collective: scaling is weak.  With N > 1 the same processes then run the reference's
-unified feature cache (Kg = N: rank-t hot row on GPU t % N, peer shards read in-kernel over xGMI;
-GPUCache.cu:88-108,593-607) and report it inside the same line.  Rank 0 prints ONE JSON line.
+no data-path collective: scaling is weak.  A plain run does only what the headline needs: it sets up,
+warms up, times --steps steps, writes --dump-outputs and prints the line.  With --full the same
+processes then run everything else and report it inside the same line; at N > 1 that includes the
+reference's unified feature cache (Kg = N: rank-t hot row on GPU t % N, peer shards read in-kernel
+over xGMI; GPUCache.cu:88-108,593-607).  Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -84,7 +87,12 @@ def parse(argv=None):
     ap.add_argument("--max-reps", type=int, default=400)
     ap.add_argument("--skew", type=int, default=205, help="synthetic neighbours: n/256 of them drawn from the Zipf-like skew "
                     "(205 = the spec'd 80 %%; 0 = uniform neighbours, the Infinity-Cache control run)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the alt_schedule and graph_replay legs (clean kernel profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline, in the same processes and the same line: the headline's other schedules "
+                         "(alt_schedule, alt_schedule_levels, graph_replay), the unified-cache leg (N > 1), roofline.measured_copy_GBps and the "
+                         "in-run traffic passes, cpu_baseline and --extra-legs.  Without it a run sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the headline line")
+    ap.add_argument("--headline-only", action="store_true", help="--full: skip the alt_schedule and graph_replay legs and the auto extra legs (clean kernel profiles)")
     ap.add_argument("--stream-priority", default="none", choices=["none", "sampler", "gather"],
                     help="overlap schedule: which of the two streams gets the high stream priority (the other the low one)")
     ap.add_argument("--cu-split", type=int, default=0, help="experiment (overlap schedule): of every 8 compute units, this many run "
@@ -324,60 +332,18 @@ def worker(args):
     head = run_leg(c, unified=(args.cache == "unified"), headline=True)
     c.head = head
     line = headline_line(c, head) if rank == 0 else {"legs_failed": [], "legs_skipped": [], "extra_legs": {}}
-    c.guard = guard = LegGuard(c, line)
-    # Everything behind the headline is evidence beside it: whatever goes wrong in the glue between the legs (a leg's own failures are
-    # caught and reported by LegGuard), rank 0 still prints the line it has -- with the error named -- before the process ends non-zero.
-    try:
-
-        def budgeted(name, want, fn):
-            return run_budgeted(c, line, guard, name, want, fn)
-
-        if world > 1 and args.cache == "replicated" and not args.no_unified_leg and args.table == "device":
-            line["unified_cache"] = budgeted("unified_cache", args.unified_timeout,
-                                             lambda: unified_summary(c, run_leg(c, unified=True, headline=False, min_time=args.extra_min_time)))
-
-        # measured streaming-copy rate of this box (float4 copy kernel sized like the gather, read + write bytes)
-        if rank == 0 and line.get("roofline") is not None:
-            try:
-                line["roofline"]["measured_copy_GBps"] = measure_copy(c)
-            except Exception as ex:   # noqa: BLE001 -- evidence beside the headline: never lose the line over it (e.g. no 8 GiB left at N > 1 behind the unified leg)
-                line["roofline"]["measured_copy_GBps"] = None
-                line["roofline"]["measured_copy_error"] = repr(ex)[:200]
-            if (world == 1 and args.measure_traffic == "auto" and not args.headline_only and args.table == "device" and args.cache == "replicated"
-                    and args.gather == "all" and args.pipeline == "serial" and c.budget.left() > 240.0):   # two passes of <= 90 s each
-                got = measure_traffic_in_run(args)
-                if got is not None:
-                    line["roofline"].update(got)
-        if rank == 0 and world > 1 and args.cpu_baseline_seconds > 0 and c.budget.left() > 120.0:
-            # N > 1: the same baseline, short -- sampler + COO only (no 57 GB host copy of the table), <= 5 s of CPU time, on rank 0
-            # while the other ranks wait in the next collective
-            import copy
-            a1 = copy.copy(args)
-            a1.no_cpu_features, a1.cpu_baseline_seconds = True, min(5.0, args.cpu_baseline_seconds)
-            try:
-                line["cpu_baseline"] = run_cpu_baseline(a1, c.spec, c.indptr, c.indices, None, c.mine, c.my_labels, c.B, c.fan, c.steps_avail)
-            except Exception as ex:   # noqa: BLE001 -- reported baseline only
-                line["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(ex)[:200]}
-        if rank == 0 and world == 1 and args.cpu_baseline_seconds > 0 and c.budget.left() > 150.0:   # reported baseline
-            feats = c.feats
-            if c.host_table is not None:   # the table already is host memory: view it, no copy
-                import ctypes
-                feats = np.ctypeslib.as_array(ctypes.cast(c.host_table, ctypes.POINTER(ctypes.c_float)), shape=(c.spec.V, c.spec.F))
-            try:
-                line["cpu_baseline"] = run_cpu_baseline(args, c.spec, c.indptr, c.indices, feats, c.mine, c.my_labels, c.B, c.fan, c.steps_avail)
-            except Exception as ex:   # noqa: BLE001 -- reported baseline only: never lose the headline line over it
-                line["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(ex)[:200]}
-
-        for name in extra_leg_names(c):      # BASELINE configs 4 and 5, same processes, same line (after everything that needs the headline graph)
-            line["extra_legs"][name] = budgeted(name, args.extra_timeout, lambda name=name: extra_leg(c, name))
-
-    except Exception as ex:   # noqa: BLE001
-        if rank == 0:
-            import traceback
-            line["worker_error"] = {"error": repr(ex)[:300], "where": traceback.format_exc()[-1200:]}
-            line["time_budget"] = {"budget_s": args.time_budget, "used_s": round(time.time() - c.budget.t0, 1)}
-            emit_line(line)
-        raise
+    if args.full:
+        # Everything behind the headline is evidence beside it: whatever goes wrong in the glue between the legs (a leg's own failures are
+        # caught and reported by LegGuard), rank 0 still prints the line it has -- with the error named -- before the process ends non-zero.
+        try:
+            full_legs(c, line)
+        except Exception as ex:   # noqa: BLE001
+            if rank == 0:
+                import traceback
+                line["worker_error"] = {"error": repr(ex)[:300], "where": traceback.format_exc()[-1200:]}
+                line["time_budget"] = {"budget_s": args.time_budget, "used_s": round(time.time() - c.budget.t0, 1)}
+                emit_line(line)
+            raise
     if rank == 0:
         sv = line["extra_legs"].get("served") or {}
         if isinstance(sv, dict) and sv.get("value"):      # the headline batches as a trainer sees them, next to `value` (serial) and `value_overlap` (two streams, in-process):
@@ -393,6 +359,55 @@ def worker(args):
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def full_legs(c, line):
+    """--full: the legs after the headline, reported in the same line -- the unified-cache leg (N > 1), the measured copy rate and
+    HBM traffic of the roofline, the CPU baselines and the extra legs.  A plain run prints the headline without them."""
+    args, rank, world = c.args, c.rank, c.world
+    c.guard = guard = LegGuard(c, line)
+
+    def budgeted(name, want, fn):
+        return run_budgeted(c, line, guard, name, want, fn)
+
+    if world > 1 and args.cache == "replicated" and not args.no_unified_leg and args.table == "device":
+        line["unified_cache"] = budgeted("unified_cache", args.unified_timeout,
+                                         lambda: unified_summary(c, run_leg(c, unified=True, headline=False, min_time=args.extra_min_time)))
+
+    # measured streaming-copy rate of this box (float4 copy kernel sized like the gather, read + write bytes)
+    if rank == 0 and line.get("roofline") is not None:
+        try:
+            line["roofline"]["measured_copy_GBps"] = measure_copy(c)
+        except Exception as ex:   # noqa: BLE001 -- evidence beside the headline: never lose the line over it (e.g. no 8 GiB left at N > 1 behind the unified leg)
+            line["roofline"]["measured_copy_GBps"] = None
+            line["roofline"]["measured_copy_error"] = repr(ex)[:200]
+        if (world == 1 and args.measure_traffic == "auto" and not args.headline_only and args.table == "device" and args.cache == "replicated"
+                and args.gather == "all" and args.pipeline == "serial" and c.budget.left() > 240.0):   # two passes of <= 90 s each
+            got = measure_traffic_in_run(args)
+            if got is not None:
+                line["roofline"].update(got)
+    if rank == 0 and world > 1 and args.cpu_baseline_seconds > 0 and c.budget.left() > 120.0:
+        # N > 1: the same baseline, short -- sampler + COO only (no 57 GB host copy of the table), <= 5 s of CPU time, on rank 0
+        # while the other ranks wait in the next collective
+        import copy
+        a1 = copy.copy(args)
+        a1.no_cpu_features, a1.cpu_baseline_seconds = True, min(5.0, args.cpu_baseline_seconds)
+        try:
+            line["cpu_baseline"] = run_cpu_baseline(a1, c.spec, c.indptr, c.indices, None, c.mine, c.my_labels, c.B, c.fan, c.steps_avail)
+        except Exception as ex:   # noqa: BLE001 -- reported baseline only
+            line["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(ex)[:200]}
+    if rank == 0 and world == 1 and args.cpu_baseline_seconds > 0 and c.budget.left() > 150.0:   # reported baseline
+        feats = c.feats
+        if c.host_table is not None:   # the table already is host memory: view it, no copy
+            import ctypes
+            feats = np.ctypeslib.as_array(ctypes.cast(c.host_table, ctypes.POINTER(ctypes.c_float)), shape=(c.spec.V, c.spec.F))
+        try:
+            line["cpu_baseline"] = run_cpu_baseline(args, c.spec, c.indptr, c.indices, feats, c.mine, c.my_labels, c.B, c.fan, c.steps_avail)
+        except Exception as ex:   # noqa: BLE001 -- reported baseline only: never lose the headline line over it
+            line["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(ex)[:200]}
+
+    for name in extra_leg_names(c):      # BASELINE configs 4 and 5, same processes, same line (after everything that needs the headline graph)
+        line["extra_legs"][name] = budgeted(name, args.extra_timeout, lambda name=name: extra_leg(c, name))
 
 
 def load_workload(c, workload):
@@ -1470,7 +1485,7 @@ def run_leg(c, unified, headline, min_time=None, with_alt=False):
 
     # the other schedule on the very same K batches, in windows like the headline (median window): with --pipeline serial this
     # is the two-stream schedule the `legion` server runs (gather of batch i on stream 1 while batch i+1 is sampled)
-    if (headline or with_alt) and not per_level and not intra and not args.headline_only:
+    if (headline or with_alt) and not per_level and not intra and args.full and not args.headline_only:
         alt_w = [window(timed=False, overlap=not overlap)]
         a_first, _ = D.aggregate(alt_w[0], [0.0], world, device=dev)
         a_reps = int(min(args.max_reps, max(1, -(-(min_time / 2) // max(a_first, 1e-6)))))
@@ -1495,7 +1510,7 @@ def run_leg(c, unified, headline, min_time=None, with_alt=False):
             used[:] = [False] * depth
 
     # the serial schedule again, recorded once as a hipGraph and replayed with one launch per batch (same K batches)
-    if headline and not per_level and not intra and not args.headline_only and world == 1:   # informational leg: N = 1 only, never fatal
+    if headline and not per_level and not intra and args.full and not args.headline_only and world == 1:   # informational leg: N = 1 only, never fatal
         try:
             L.legion_set_error_mode(K.ERR_RETURN)     # a HIP error in this leg raises (K.check) instead of exit(1)
             L.GPUMemoryPool_SetCurrentPipe(pool, 0)
@@ -1714,7 +1729,8 @@ def headline_line(c, leg):
         "alt_schedule": leg["alt"],
         "alt_schedule_levels": leg.get("alt_levels"),
         "graph_replay": leg["graph"],
-        "legs_failed": [],          # legs after the headline that raised or hung: [] = every leg in this line is valid
+        "full": bool(args.full),    # false: the headline alone; the other schedules, legs, baselines and roofline passes ran only with --full
+        "legs_failed": [],         # legs after the headline that raised or hung: [] = every leg in this line is valid
         "legs_skipped": [],         # legs the time budget did not admit (--time-budget)
         "extra_legs": {},
         "cache": {"mode": "unified" if unified else "replicated", **(leg["cache_info"] or {}), **(leg["xgmi"] or {})},

@@ -36,8 +36,8 @@ profiled = last_json(r.stdout)
 stats = glob.glob(os.path.join(prof_dir, "*", "*kernel_stats.csv"))[0]
 shutil.copy(stats, os.path.join(ROOT, "profiles", tag + "_bench_papers100M_kernel_stats.csv"))
 
-# 2. the default bench line (all legs, CPU baseline)
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")], cwd=ROOT, capture_output=True, text=True)
+# 2. the full bench line (all legs, CPU baseline)
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"], cwd=ROOT, capture_output=True, text=True)
 if r.returncode != 0:
     sys.exit(r.stdout[-2000:] + r.stderr[-2000:])
 line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -49,7 +49,7 @@ out = ["# %s: kernel table + bench line, papers100M shape\n" % tag,
        "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --headline-only --cpu-baseline-seconds 0`",
        "(batch 8000, fan-out 25,10,5; 5 warm-up + 50 census batches + R windows of 50 timed batches of the serial schedule; MI355X)\n",
        "profiled run: %.4f ms/batch, k_gather avg %.2f us by HIP events;" % (profiled["ms_per_step"], profiled["roofline"]["avg_launch_us"]),
-       "un-profiled default run (`%s_bench_line.json`): %.4f ms/batch, k_gather %.1f us = %.0f GB/s = %.3f of 8 TB/s, whole batch %.3f, %.2f G edges/s, %.0f GB/s of rows;" % (
+       "un-profiled `--full` run (`%s_bench_line.json`): %.4f ms/batch, k_gather %.1f us = %.0f GB/s = %.3f of 8 TB/s, whole batch %.3f, %.2f G edges/s, %.0f GB/s of rows;" % (
            tag, d["ms_per_step"], rf["avg_launch_us"], rf["achieved"], rf["frac"], rf["pipeline_frac"], d["value"] / 1e9, d["feature_GBps"]),
        "overlapped schedule %s ms/batch, hipGraph replay %s ms/batch.\n" % ((d.get("alt_schedule") or {}).get("ms_per_step"), (d.get("graph_replay") or {}).get("ms_per_step")),
        "| kernel | calls | avg us | max us | total ms | % |", "|---|---|---|---|---|---|"]

@@ -26,6 +26,15 @@ def test_launch_plan_matrix():
     assert bench.launch_plan(bench.parse(["--gpus", "0"]), {}).startswith("error")
 
 
+def test_a_plain_run_leaves_everything_beside_the_headline_to_full():
+    assert bench.parse([]).full is False and bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    assert bench.parse(["--full"]).full is True
+    # what --full runs is still planned from the other flags: the auto extra legs of the default workload at N = 1
+    c = type("C", (), {})()
+    c.world, c.args = 1, bench.parse(["--full"])
+    assert bench.extra_leg_names(c) == bench.N1_LEGS
+
+
 def test_child_env_is_a_torchrun_style_rank():
     env = bench.child_env({"PATH": "/bin", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}, 3, 8, 29511)
     assert (env["RANK"], env["LOCAL_RANK"], env["WORLD_SIZE"]) == ("3", "3", "8")

@@ -1,4 +1,4 @@
-"""bench.py's legs after the headline with real ranks (two processes on the one GPU of the test box, gloo): the extra legs run
+"""bench.py's legs after the headline (--full) with real ranks (two processes on the one GPU of the test box, gloo): the extra legs run
 and land in the line; a leg that raises on one rank is named in "legs_failed" and the run still exits 0; a leg that hangs on one
 rank ends EVERY rank with exit code 3 after rank 0 printed the headline (no rank may be left in a collective)."""
 import json
@@ -13,18 +13,31 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def _bench(extra_env, *flags, timeout=400, gpus=2):
+def _bench(extra_env, *flags, timeout=400, gpus=2, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     if gpus > 1:
         env.update(LEGION_BENCH_FORCE_DEVICE="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--scale", "0.02", "--steps", "4", "--warmup", "1",
-                        "--min-time", "0.05", "--extra-min-time", "0.05", "--presc-steps", "2"] + list(flags),
+                        "--min-time", "0.05", "--extra-min-time", "0.05", "--presc-steps", "2"] + (["--full"] if full else []) + list(flags),
                        env=env, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     # whatever the ranks, the HIP library and their children print, the command's stdout is the ONE JSON line
     assert r.stdout.count("\n") <= 1 and len(lines) == len(r.stdout.splitlines()), r.stdout[:2000]
     return r, (json.loads(lines[-1]) if lines else None)
+
+
+def test_a_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: warm-up, the timed steps, --dump-outputs and the line -- the headline fields as a full run prints them, nothing behind it."""
+    r, line = _bench({}, "--dump-outputs", str(tmp_path / "out"), gpus=1, full=False)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == 4 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "edges/s" and line["higher_is_better"] is True
+    assert line["timing"]["windows"] == 1 and line["roofline"]["timed_launches"] == 4 and "measured_copy_GBps" not in line["roofline"]
+    assert line["alt_schedule"] is None and line["alt_schedule_levels"] is None and line["graph_replay"] is None and line["value_overlap"] is None
+    assert line["extra_legs"] == {} and line["cpu_baseline"] is None and line["legs_failed"] == [] and line["legs_skipped"] == []
+    assert "unified_cache" not in line and line["value_served"] is None
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(n + ".npy" for n in ("nc", "ec", "ids", "labels", "src_off", "dst_off", "features"))
 
 
 def test_two_rank_line_has_every_leg():
@@ -99,6 +112,7 @@ def test_one_gpu_line_has_every_single_gpu_baseline_path():
     r, line = _bench({}, "--cpu-baseline-seconds", "1.5", "--measure-traffic", "off", gpus=1)
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["n_gpus"] == 1 and line["legs_failed"] == [] and line["value"] > 0 and line["cpu_baseline"]["value"] > 0
+    assert line["full"] is True and line["alt_schedule"]["ms_per_step"] > 0
     legs = line["extra_legs"]
     assert list(legs) == ["served", "lp", "cached_gather", "products_2hop", "products_3hop", "partitioned_csr", "partitioned_csr_host_spill"]
     sv = legs.pop("served")
