@@ -84,6 +84,20 @@ static_assert(kMaxChunks % kBlock == 0 && kMaxChunks >= 256 * 8, "kMaxChunks: a 
 constexpr int ilog2_c(int v) { return v <= 1 ? 0 : 1 + ilog2_c(v >> 1); }
 constexpr int kMaxParts = LEGION_MAX_DEVICE;
 
+// The seed sets are indexed by mode everywhere (LEGION_TRAINMODE, LEGION_VALIDMODE, LEGION_TESTMODE); LegionBuildInfo names their fields
+// one by one, this table gives them the same index.
+constexpr int kModes = 3;
+static_assert(LEGION_TRAINMODE == 0 && LEGION_VALIDMODE == 1 && LEGION_TESTMODE == 2, "seed sets are indexed by mode");
+struct BuildInfoSeedFields {
+    const int32_t* LegionBuildInfo::*num;
+    const int32_t* const* LegionBuildInfo::*ids;
+    const int32_t* const* LegionBuildInfo::*labels;
+};
+constexpr BuildInfoSeedFields kBuildInfoSeeds[kModes] = {
+    {&LegionBuildInfo::training_set_num, &LegionBuildInfo::training_set_ids, &LegionBuildInfo::training_labels},
+    {&LegionBuildInfo::validation_set_num, &LegionBuildInfo::validation_set_ids, &LegionBuildInfo::validation_labels},
+    {&LegionBuildInfo::testing_set_num, &LegionBuildInfo::testing_set_ids, &LegionBuildInfo::testing_labels}};
+
 // minstd_rand arithmetic (thrust::minstd_rand: x <- 48271 x mod 2^31-1), shared by the sampler and the generators
 constexpr uint32_t kP31 = 2147483647u; // minstd modulus 2^31 - 1
 constexpr uint32_t kA = 48271u;        // minstd multiplier
@@ -322,9 +336,14 @@ struct GPUNodeStorage {
     int32_t replica_pitch = 0;        // ... of the replicas (legion_row_pitch)
     int32_t features_location = LEGION_LOC_HOST_PINNED;
     bool owns_features = false;
-    std::vector<int32_t> training_set_num, validation_set_num, testing_set_num;
-    std::vector<int32_t*> training_set_ids, validation_set_ids, testing_set_ids;
-    std::vector<int32_t*> training_labels, validation_labels, testing_labels;
+    struct SeedSet { int32_t num = 0; int32_t* ids = nullptr; int32_t* labels = nullptr; };   // device copies
+    std::vector<SeedSet> seeds[legion::kModes];    // by mode, per partition
+    // the set of `mode` on partition p; an empty one (no lists, size 0) for any other mode or partition
+    const SeedSet& seed_set(int32_t mode, int32_t p) const
+    {
+        static const SeedSet none;
+        return mode >= 0 && mode < legion::kModes && p >= 0 && p < (int32_t)seeds[mode].size() ? seeds[mode][p] : none;
+    }
 };
 
 struct CacheController {              // PreSCCacheController, GPUCache.cu:239-500

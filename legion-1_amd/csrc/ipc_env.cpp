@@ -389,6 +389,19 @@ static void pin_slab(IPCEnv* e)
     e->ext->mirror_magic = kMirrorMagic;    // the mirror is maintained either way (synchronously in IPCPost if need be)
 }
 
+// An evaluation split (validation or test): as many steps as the largest partition needs in batches of 512, every partition's set
+// spread evenly over them (CUDA_IPC_Service.cu:101-118).  Returns the step count.
+static int32_t eval_split(const int32_t* set_num, int32_t P, std::vector<int32_t>& batch_size)
+{
+    const int32_t raw_batch_size = 512;
+    int32_t max_size = 0;
+    for (int32_t i = 0; i < P; i++) max_size = std::max(max_size, set_num[i]);
+    const int32_t step = (max_size - 1) / raw_batch_size + 1;
+    batch_size.resize(P);
+    for (int32_t i = 0; i < P; i++) batch_size[i] = (set_num[i] - 1) / step + 1;
+    return step;
+}
+
 // Coordinate, CUDA_IPC_Service.cu:66-134
 void IPCEnv_Coordinate(IPCEnv* e, const LegionBuildInfo* info)
 {
@@ -406,16 +419,8 @@ void IPCEnv_Coordinate(IPCEnv* e, const LegionBuildInfo* info)
     for (int32_t i = 0; i < P; i++) min_train_size = std::min(min_train_size, info->training_set_num[i]);
     e->train_step = (min_train_size - 1) / e->raw_batch_size;
     e->train_batch_size.assign(P, e->raw_batch_size);
-    int32_t max_valid_size = 0, max_test_size = 0;
-    const int32_t raw_valid_batch_size = 512, raw_test_batch_size = 512;
-    for (int32_t i = 0; i < P; i++) max_valid_size = std::max(max_valid_size, info->validation_set_num[i]);
-    e->valid_step = (max_valid_size - 1) / raw_valid_batch_size + 1;
-    e->valid_batch_size.resize(P);
-    for (int32_t i = 0; i < P; i++) e->valid_batch_size[i] = (info->validation_set_num[i] - 1) / e->valid_step + 1;
-    for (int32_t i = 0; i < P; i++) max_test_size = std::max(max_test_size, info->testing_set_num[i]);
-    e->test_step = (max_test_size - 1) / raw_test_batch_size + 1;
-    e->test_batch_size.resize(P);
-    for (int32_t i = 0; i < P; i++) e->test_batch_size[i] = (info->testing_set_num[i] - 1) / e->test_step + 1;
+    e->valid_step = eval_split(info->validation_set_num, P, e->valid_batch_size);
+    e->test_step = eval_split(info->testing_set_num, P, e->test_batch_size);
     log_out() << "Train Steps: " << e->train_step << "\n";
     log_out() << "Valid Steps: " << e->valid_step << "\n";
     log_out() << "Test Steps: " << e->test_step << "\n";

@@ -39,24 +39,11 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     (void)cache; (void)part_id;
     if (!noder || !pool_ready(memorypool, "batch_generator_kernel")) return;
     hipStream_t s = (hipStream_t)strm_hdl;
-    int32_t* all_ids = nullptr;
-    int32_t* all_labels = nullptr;
-    int32_t total_cap = 0;
-    if (mode == LEGION_TRAINMODE) {
-        all_ids = GPUNodeStorage_GetTrainingSetIds(noder, dev_id);
-        all_labels = GPUNodeStorage_GetTrainingLabels(noder, dev_id);
-        total_cap = GPUNodeStorage_TrainingSetSize(noder, dev_id);
-    } else if (mode == LEGION_VALIDMODE) {
-        all_ids = GPUNodeStorage_GetValidationSetIds(noder, dev_id);
-        all_labels = GPUNodeStorage_GetValidationLabels(noder, dev_id);
-        total_cap = GPUNodeStorage_ValidationSetSize(noder, dev_id);
-    } else if (mode == LEGION_TESTMODE) {
-        all_ids = GPUNodeStorage_GetTestingSetIds(noder, dev_id);
-        all_labels = GPUNodeStorage_GetTestingLabels(noder, dev_id);
-        total_cap = GPUNodeStorage_TestingSetSize(noder, dev_id);
-    } else {
-        log_out() << "invalid mode: " << mode << "\n";
-    }
+    if (mode < 0 || mode >= kModes) log_out() << "invalid mode: " << mode << "\n";
+    const GPUNodeStorage::SeedSet& set = noder->seed_set(mode, dev_id);   // empty for an invalid mode
+    int32_t* all_ids = set.ids;
+    int32_t* all_labels = set.labels;
+    const int32_t total_cap = set.num;
     if (all_ids == nullptr) { log_out() << "invalid src id ptr\n"; return; }
     if (all_labels == nullptr) { log_out() << "invalid label ptr\n"; return; }
 

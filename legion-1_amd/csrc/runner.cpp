@@ -74,6 +74,129 @@ static void hand_over(Runner* r, IPCEnv* env, int pipe)
     IPCEnv_IPCPost(env, r->local_dev_id, pipe);
 }
 
+static void advance_pipe(Runner* r)
+{
+    r->current_pipe = (r->current_pipe + 1) % r->pipeline_depth;
+    GPUMemoryPool_SetCurrentPipe(r->memorypool, r->current_pipe);
+}
+
+// Wait for the trainer to free the current pipe.  Pipelined loop (batch i-1 in flight): hand batch i-1 over the moment it is complete --
+// a trainer that is the bottleneck must not wait for our next enqueue.
+// Poll first (IPCEnv_HandoffSpinUs, 200 us): the trainer usually frees the pipe within tens of microseconds of the post at the
+// end of the previous RunOnce, and a sleep_for(10 us) really sleeps 60+ us (timer slack) -- on the critical chain of every batch
+// (gather i-1 done -> post -> trainer -> pipe free -> sampler i+1 may start).  After the polling budget: sleep between looks, as before.
+static void wait_for_pipe(Runner* r, IPCEnv* env)
+{
+    if (!r->pending) {
+        IPCEnv_IPCWait(env, r->local_dev_id, r->current_pipe);
+        return;
+    }
+    const auto t_wait = std::chrono::steady_clock::now();
+    const auto spin = std::chrono::microseconds(IPCEnv_HandoffSpinUs());
+    while (IPCEnv_IPCTryWait(env, r->local_dev_id, r->current_pipe, 0) != 0) {
+        if (hipEventQuery(r->done_ev[r->pending_pipe]) == hipSuccess) {
+            hand_over(r, env, r->pending_pipe);
+            r->pending = false;
+            IPCEnv_IPCWait(env, r->local_dev_id, r->current_pipe);
+            break;
+        }
+        if (std::chrono::steady_clock::now() - t_wait < spin) { for (int i = 0; i < 64; i++) __builtin_ia32_pause(); }
+        else std::this_thread::sleep_for(std::chrono::microseconds(10));
+    }
+}
+
+// LEGION_ERR_RETURN (embedding / tests) and a failed batch: never leave a trainer blocked on sem_w.  The batch in flight
+// is handed over as usual; the failed pipe is posted with nc[0] = -1 (every counter word 0xFFFFFFFF), which no valid
+// batch produces -- a consumer must treat it as "server failed" (the reference's behaviour, exit(EXIT_FAILURE), is what
+// the default LEGION_ERR_EXIT mode does instead).
+static void post_poisoned(Runner* r, IPCEnv* env)
+{
+    if (r->pending) {
+        (void)hipEventSynchronize(r->done_ev[r->pending_pipe]);
+        hand_over(r, env, r->pending_pipe);
+        r->pending = false;
+    }
+    (void)hipDeviceSynchronize();
+    int32_t* nc = IPCEnv_GetNodeCounter(env, r->local_dev_id, r->current_pipe);
+    if (nc) (void)hipMemset(nc, 0xFF, 16 * sizeof(int32_t));
+    int32_t* ec = IPCEnv_GetEdgeCounter(env, r->local_dev_id, r->current_pipe);   // no stale edge counts of the pipe's previous batch
+    if (ec) (void)hipMemset(ec, 0, 16 * sizeof(int32_t));
+    IPCEnv_SetMirror(env, r->local_dev_id, r->current_pipe, -1, 0);
+    (void)hipGetLastError();
+    IPCEnv_IPCPost(env, r->local_dev_id, r->current_pipe);
+    advance_pipe(r);
+}
+
+static void run_ops(Runner* r)
+{
+    const int last_feat = 2 * r->hops + 1;           // the FeatureExtractor behind the last hop
+    for (int i = 0; i < r->op_num; i++) {
+        if (r->gather_all && (i & 1) && i < last_feat) continue;
+        if (i % 2 == 1) HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[i - 1], 0));
+        r->op_params[i]->is_presc = 0;
+        if (r->gather_all && i == last_feat) {
+            OpParams* fp = r->op_params[i];
+            get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
+        } else {
+            Operator_run(r->op_factory[i], r->op_params[i]);
+        }
+    }
+}
+
+// $LEGION_BATCH_GRAPH=1 (see Runner::use_graph): the recorded sampler side of (pipe, mode) on stream 0 -- recorded on first use --, then
+// all rows gathered on stream 1 behind it.  False when the recording failed.
+static bool run_graph(Runner* r, IPCEnv* env, int32_t batch_id)
+{
+    LegionBatchGraph*& g = r->graphs[r->current_pipe][r->mode];
+    if (!g) { // record this (pipe, mode) once
+        if (GPUMemoryPool_BeginBatchCapture(r->memorypool, r->streams[0]) == 0) {
+            // the sampler side only (BatchGen, samplers, planner: the even ops), on ONE stream; the rows are gathered by one plain
+            // launch on stream 1 behind the graph, so the gather of batch i overlaps the recorded sampler of batch i + 1 (the other pipe)
+            for (int i = 0; i < r->op_num; i += 2) {
+                OpParams op = *r->op_params[i];
+                op.stream = r->streams[0];
+                op.event = nullptr;
+                op.is_presc = 0;
+                Operator_run(r->op_factory[i], &op);
+            }
+            g = GPUMemoryPool_EndBatchCapture(r->memorypool, r->streams[0]);
+        }
+        if (!g) return false;
+    }
+    LegionBatchGraph_Launch(g, r->streams[0], IPCEnv_GetLocalBatchId(env, batch_id));
+    HIP_CHECK(hipEventRecord(r->events[0], r->streams[0]));
+    HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[0], 0));
+    OpParams* fp = r->op_params[1];
+    get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
+    Operator_run(r->op_factory[r->op_num - 1], r->op_params[r->op_num - 1]);   // Updater, stream 1
+    return true;
+}
+
+// $LEGION_RUNNER_GATHER=auto: one-off estimate from the last batch of the pre-sampling epoch (its counters are still in pipe 0): sampler ~ 45 ps
+// per slot (the memory system's random-access rate: 54 ps at papers100M, 43 ps at products {25,10,5}), gather ~ rows x (8F + 8) bytes at 6 TB/s
+// (5.2 TB/s for rows that are not whole 128-byte lines).  A wrong guess costs a few per cent, never correctness.
+static void choose_gather(Runner* r, GPUCache* cache, IPCEnv* env, const int32_t* fanout)
+{
+    int32_t nc[16] = {0}, ec[16] = {0};
+    const int32_t* dnc = IPCEnv_GetNodeCounter(env, r->local_dev_id, 0);
+    const int32_t* dec = IPCEnv_GetEdgeCounter(env, r->local_dev_id, 0);
+    if (!(dnc && dec && hipMemcpy(nc, dnc, sizeof(nc), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(ec, dec, sizeof(ec), hipMemcpyDeviceToHost) == hipSuccess)) {
+        (void)hipGetLastError();
+        return;
+    }
+    double slots = 0.0, n_in = (double)nc[4];
+    for (int h = 1; h <= r->hops; h++) {
+        slots += n_in * (double)fanout[h - 1];
+        n_in = (double)(ec[2 + h] - (h > 1 ? ec[2 + h - 1] : 0));     // edges of hop h = input of hop h + 1
+    }
+    const double rows = (double)GPUCache_MaxIdNum(cache, r->local_dev_id);
+    double gather_us = 0.0, sampler_us = 0.0;
+    (void)legion_runner_gather_estimate(r->float_attr_len, rows, slots, &gather_us, &sampler_us);
+    r->gather_all = gather_us > sampler_us;
+    log_out() << r->local_dev_id << " Runner gather: " << (r->gather_all ? "one launch over all rows behind the last hop" : "per level behind each hop")
+              << " (estimated gather " << (int)gather_us << " us, sampler " << (int)sampler_us << " us per batch)\n";
+}
+
 extern "C" {
 
 // The estimate behind $LEGION_RUNNER_GATHER=auto (see Runner::gather_all): microseconds per batch of the gather (rows x (8F + 8) bytes at
@@ -185,31 +308,7 @@ void Runner_InitializeFeaturesBuffer(Runner* r, RunnerParams* params)
     }
     if (num_ids > r->num_ids) num_ids = r->num_ids;
     if (num_ids < 1) num_ids = r->num_ids;
-    if (r->gather_auto) {
-        // One-off estimate from the last batch of the pre-sampling epoch (its counters are still in pipe 0): sampler ~ 45 ps per slot (the
-        // memory system's random-access rate: 54 ps at papers100M, 43 ps at products {25,10,5}), gather ~ rows x (8F + 8) bytes at 6 TB/s
-        // (5.2 TB/s for rows that are not whole 128-byte lines).  A wrong guess costs a few per cent, never correctness.
-        int32_t nc[16] = {0}, ec[16] = {0};
-        const int32_t* dnc = IPCEnv_GetNodeCounter(env, r->local_dev_id, 0);
-        const int32_t* dec = IPCEnv_GetEdgeCounter(env, r->local_dev_id, 0);
-        if (dnc && dec && hipMemcpy(nc, dnc, sizeof(nc), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(ec, dec, sizeof(ec), hipMemcpyDeviceToHost) == hipSuccess) {
-            const int H = r->hops;
-            double slots = 0.0, n_in = (double)nc[4];
-            for (int h = 1; h <= H; h++) {
-                slots += n_in * (double)params->fanout[h - 1];
-                n_in = (double)(ec[2 + h] - (h > 1 ? ec[2 + h - 1] : 0));     // edges of hop h = input of hop h + 1
-            }
-            const double rows = (double)GPUCache_MaxIdNum(cache, r->local_dev_id);
-            const int F = r->float_attr_len;
-            double gather_us = 0.0, sampler_us = 0.0;
-            (void)legion_runner_gather_estimate(F, rows, slots, &gather_us, &sampler_us);
-            r->gather_all = gather_us > sampler_us;
-            log_out() << r->local_dev_id << " Runner gather: " << (r->gather_all ? "one launch over all rows behind the last hop" : "per level behind each hop")
-                      << " (estimated gather " << (int)gather_us << " us, sampler " << (int)sampler_us << " us per batch)\n";
-        } else {
-            (void)hipGetLastError();
-        }
-    }
+    if (r->gather_auto) choose_gather(r, cache, env, params->fanout);
     r->feature_rows = (int32_t)num_ids;
     IPCEnv_InitializeFeaturesBuffer(env, 0, (int32_t)num_ids, r->float_attr_len, r->local_dev_id, r->pipeline_depth);
     for (int i = 0; i < r->pipeline_depth; i++)
@@ -240,92 +339,16 @@ void Runner_RunOnce(Runner* r, RunnerParams* params)
     r->mode = IPCEnv_GetCurrentMode(env, batch_id);
     GPUMemoryPool_SetCurrentMode(r->memorypool, r->mode);
     GPUMemoryPool_SetIter(r->memorypool, IPCEnv_GetLocalBatchId(env, batch_id));
-    if (r->pending) {
-        // Pipelined loop: batch i-1 is in flight.  Wait for the trainer to free this pipe, but hand batch i-1 over
-        // the moment it is complete -- a trainer that is the bottleneck must not wait for our next enqueue.
-        // Poll first (IPCEnv_HandoffSpinUs, 200 us): the trainer usually frees the pipe within tens of microseconds of the post at the
-        // end of the previous RunOnce, and a sleep_for(10 us) really sleeps 60+ us (timer slack) -- on the critical chain of every batch
-        // (gather i-1 done -> post -> trainer -> pipe free -> sampler i+1 may start).  After the polling budget: sleep between looks, as before.
-        const auto t_wait = std::chrono::steady_clock::now();
-        const auto spin = std::chrono::microseconds(IPCEnv_HandoffSpinUs());
-        while (IPCEnv_IPCTryWait(env, r->local_dev_id, r->current_pipe, 0) != 0) {
-            if (hipEventQuery(r->done_ev[r->pending_pipe]) == hipSuccess) {
-                hand_over(r, env, r->pending_pipe);
-                r->pending = false;
-                IPCEnv_IPCWait(env, r->local_dev_id, r->current_pipe);
-                break;
-            }
-            if (std::chrono::steady_clock::now() - t_wait < spin) { for (int i = 0; i < 64; i++) __builtin_ia32_pause(); }
-            else std::this_thread::sleep_for(std::chrono::microseconds(10));
-        }
-    } else {
-        IPCEnv_IPCWait(env, r->local_dev_id, r->current_pipe);
-    }
-    // LEGION_ERR_RETURN (embedding / tests) and a failed batch: never leave a trainer blocked on sem_w.  The batch in flight
-    // is handed over as usual; the failed pipe is posted with nc[0] = -1 (every counter word 0xFFFFFFFF), which no valid
-    // batch produces -- a consumer must treat it as "server failed" (the reference's behaviour, exit(EXIT_FAILURE), is what
-    // the default LEGION_ERR_EXIT mode does instead).
-    auto post_poisoned = [&]() {
-        if (r->pending) {
-            (void)hipEventSynchronize(r->done_ev[r->pending_pipe]);
-            hand_over(r, env, r->pending_pipe);
-            r->pending = false;
-        }
-        (void)hipDeviceSynchronize();
-        int32_t* nc = IPCEnv_GetNodeCounter(env, r->local_dev_id, r->current_pipe);
-        if (nc) (void)hipMemset(nc, 0xFF, 16 * sizeof(int32_t));
-        int32_t* ec = IPCEnv_GetEdgeCounter(env, r->local_dev_id, r->current_pipe);   // no stale edge counts of the pipe's previous batch
-        if (ec) (void)hipMemset(ec, 0, 16 * sizeof(int32_t));
-        IPCEnv_SetMirror(env, r->local_dev_id, r->current_pipe, -1, 0);
-        (void)hipGetLastError();
-        IPCEnv_IPCPost(env, r->local_dev_id, r->current_pipe);
-        r->current_pipe = (r->current_pipe + 1) % r->pipeline_depth;
-        GPUMemoryPool_SetCurrentPipe(r->memorypool, r->current_pipe);
-    };
-    auto run_ops = [&]() {
-        const int last_feat = 2 * r->hops + 1;           // the FeatureExtractor behind the last hop
-        for (int i = 0; i < r->op_num; i++) {
-            if (r->gather_all && (i & 1) && i < last_feat) continue;
-            if (i % 2 == 1) HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[i - 1], 0));
-            r->op_params[i]->is_presc = 0;
-            if (r->gather_all && i == last_feat) {
-                OpParams* fp = r->op_params[i];
-                get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
-            } else {
-                Operator_run(r->op_factory[i], r->op_params[i]);
-            }
-        }
-    };
+    wait_for_pipe(r, env);
     if (r->use_graph && r->mode >= 0 && r->mode < 3) {
-        LegionBatchGraph*& g = r->graphs[r->current_pipe][r->mode];
-        if (!g) { // record this (pipe, mode) once
-            if (GPUMemoryPool_BeginBatchCapture(r->memorypool, r->streams[0]) == 0) {
-                // the sampler side only (BatchGen, samplers, planner: the even ops), on ONE stream; the rows are gathered by one plain
-                // launch on stream 1 behind the graph, so the gather of batch i overlaps the recorded sampler of batch i + 1 (the other pipe)
-                for (int i = 0; i < r->op_num; i += 2) {
-                    OpParams op = *r->op_params[i];
-                    op.stream = r->streams[0];
-                    op.event = nullptr;
-                    op.is_presc = 0;
-                    Operator_run(r->op_factory[i], &op);
-                }
-                g = GPUMemoryPool_EndBatchCapture(r->memorypool, r->streams[0]);
-            }
-            if (!g) {
-                LEGION_ARG_ERROR("Runner_RunOnce: recording the batch graph failed");
-                if (error_is_fatal()) exit(EXIT_FAILURE);   // never leave the trainer waiting for a batch that will not come
-                post_poisoned();
-                return;
-            }
+        if (!run_graph(r, env, batch_id)) {
+            LEGION_ARG_ERROR("Runner_RunOnce: recording the batch graph failed");
+            if (error_is_fatal()) exit(EXIT_FAILURE);   // never leave the trainer waiting for a batch that will not come
+            post_poisoned(r, env);
+            return;
         }
-        LegionBatchGraph_Launch(g, r->streams[0], IPCEnv_GetLocalBatchId(env, batch_id));
-        HIP_CHECK(hipEventRecord(r->events[0], r->streams[0]));
-        HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[0], 0));
-        OpParams* fp = r->op_params[1];
-        get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
-        Operator_run(r->op_factory[r->op_num - 1], r->op_params[r->op_num - 1]);   // Updater, stream 1
     } else {
-        run_ops();
+        run_ops(r);
     }
     // the last op of the batch (updater / gather, stream 1) is ordered behind every other op through the op events; the reference spins on
     // cudaEventQuery of the updater's event here (Server.cu:318-324) -- this loop hands the batch over one RunOnce later (see `pending`)
@@ -336,7 +359,7 @@ void Runner_RunOnce(Runner* r, RunnerParams* params)
         // them to a trainer -- the reference's error behaviour is exit(EXIT_FAILURE) (Kernels.cuh:14-22).
         log_out() << "Runner_RunOnce: batch " << batch_id << " on GPU " << r->local_dev_id << " failed; server stops\n" << std::flush;
         if (error_is_fatal()) exit(EXIT_FAILURE);
-        post_poisoned();
+        post_poisoned(r, env);
         return;
     }
     if (r->pending) { // batch i is queued: now hand batch i-1 to its trainer
@@ -345,8 +368,7 @@ void Runner_RunOnce(Runner* r, RunnerParams* params)
     }
     r->pending = true;
     r->pending_pipe = r->current_pipe;
-    r->current_pipe = (r->current_pipe + 1) % r->pipeline_depth;
-    GPUMemoryPool_SetCurrentPipe(r->memorypool, r->current_pipe);
+    advance_pipe(r);
 }
 
 // Finalize, Server.cu:330-335
@@ -409,9 +431,19 @@ bool read_file(const std::string& path, void* dst, int64_t max_bytes, int64_t* g
 
 struct Meta { // ReadMetaFIle, GPUGraphStore.cu:190-223
     std::string dataset_path;
-    int32_t raw_batch_size = 0, node_num = 0, float_attr_len = 0, training_set_num = 0, validation_set_num = 0,
-            testing_set_num = 0, epoch = 0, partition = 0;
+    int32_t raw_batch_size = 0, node_num = 0, float_attr_len = 0, epoch = 0, partition = 0;
+    int32_t set_num[kModes] = {0, 0, 0};   // seed-set sizes by mode: training, validation, testing
     int64_t edge_num = 0, cache_memory = 0;
+};
+
+// Dataset source `synth:<workload>[:<scale>[:<skew>]]` (extension): the tables of the named synthetic shape are generated on the device by
+// the legion_synth_* calls bench.py uses -- 64 GB of files per start is not an option for the papers100M shape.  V, E, F of the meta line
+// must be the generator's (E = 0: not checked); the seed-set sizes of the meta line take the first n ids of the generator's train / valid /
+// test ranges.
+struct SynthSource {
+    std::string name;
+    double scale = 1.0;
+    int32_t skew = 205;
 };
 
 } // namespace
@@ -422,14 +454,13 @@ struct Server {
     std::string meta_path = "./meta_config";
     std::vector<int32_t> fanout{25, 10}; // Server.cu:68-69
     Meta meta;
+    SynthSource synth_src;     // meta.dataset_path, when it names a synth: source
     GPUGraphStorage* graph = nullptr;
     GPUNodeStorage* noder = nullptr;
     GPUCache* cache = nullptr;
     IPCEnv* env = nullptr;
     std::vector<Runner*> runners;
     std::vector<RunnerParams*> params;
-    // host copies kept alive for Build()
-    std::vector<std::vector<int32_t>> tr_ids, va_ids, te_ids, tr_lab, va_lab, te_lab;
     int64_t* indptr = nullptr;
     int32_t* indices = nullptr;
     float* feats = nullptr;
@@ -438,6 +469,70 @@ struct Server {
 };
 
 namespace {
+
+// The seed lists the dataset source gives the split, by mode; from files also every node's label and, when the file exists,
+// partition_<G>_bn
+struct SeedLists {
+    std::vector<int32_t> ids[kModes];
+    std::vector<int32_t> labels, partition;
+    bool have_part = false;
+};
+
+// One mode's seeds after the split: ids and labels per partition, and the per-partition views LegionBuildInfo takes of them
+struct SeedSplit {
+    std::vector<std::vector<int32_t>> ids, labels;
+    std::vector<int32_t> num;
+    std::vector<const int32_t*> id_ptr, label_ptr;
+};
+
+// The meta line, logged as the reference does.  Returns the refusal text (empty: accepted).  Host code only.
+std::string read_meta(const std::string& path, Meta& m)
+{
+    std::ifstream f(path);
+    if (!f.is_open()) { log_out() << "unable to open meta config file\n"; return "Server_Initialize: meta_config missing"; }
+    std::string line;
+    getline(f, line);
+    std::istringstream iss(line);
+    iss >> m.dataset_path >> m.raw_batch_size >> m.node_num >> m.edge_num >> m.float_attr_len >> m.set_num[LEGION_TRAINMODE] >>
+        m.set_num[LEGION_VALIDMODE] >> m.set_num[LEGION_TESTMODE] >> m.cache_memory >> m.epoch >> m.partition;
+    log_out() << "Dataset path:       " << m.dataset_path << "\nRaw Batchsize:      " << m.raw_batch_size
+              << "\nGraph nodes num:    " << m.node_num << "\nGraph edges num:    " << m.edge_num
+              << "\nFeature dim:        " << m.float_attr_len << "\nTraining set num:   " << m.set_num[LEGION_TRAINMODE]
+              << "\nValidation set num: " << m.set_num[LEGION_VALIDMODE] << "\nTesting set num:    " << m.set_num[LEGION_TESTMODE]
+              << "\nCache memory:       " << m.cache_memory << "\nTrain epoch:        " << m.epoch
+              << "\nPartition?:         " << m.partition << "\n";
+    // The reference reads the eleven fields unchecked (GPUGraphStore.cu:190-223): a short or mistyped line leaves zeros behind and the
+    // first division by the batch size or the first zero-byte table ends the server without a message.  Refuse it here, by name.
+    const int32_t min_set = *std::min_element(m.set_num, m.set_num + kModes), max_set = *std::max_element(m.set_num, m.set_num + kModes);
+    const char* bad = nullptr;
+    if (iss.fail()) bad = "fewer than eleven fields (path batch V E F n_train n_valid n_test cache_bytes epochs partition_flag)";
+    else if (m.raw_batch_size < 1) bad = "batch size < 1";
+    else if (m.node_num < 1) bad = "node count < 1";
+    else if (m.edge_num < 0) bad = "negative edge count";
+    else if (m.float_attr_len < 1) bad = "feature dim < 1";
+    else if (min_set < 0) bad = "negative seed-set size";
+    else if (max_set > m.node_num) bad = "a seed set larger than the node count";
+    else if (m.cache_memory < 0) bad = "negative cache budget";
+    else if (m.epoch < 0) bad = "negative epoch count";
+    else if (m.partition < 0 || m.partition > 2) bad = "partition flag outside 0..2";
+    return bad ? std::string("Server_Initialize: meta_config refused: ") + bad : std::string();
+}
+
+// `synth:<workload>[:<scale>[:<skew>]]` -> src; false for a dataset path that names files
+bool parse_synth(const std::string& path, SynthSource& src)
+{
+    if (path.rfind("synth:", 0) != 0) return false;
+    const std::string rest = path.substr(6);
+    const size_t c1 = rest.find(':');
+    src.name = rest.substr(0, c1);
+    if (c1 != std::string::npos) {
+        const std::string tail = rest.substr(c1 + 1);
+        const size_t c2 = tail.find(':');
+        src.scale = atof(tail.substr(0, c2).c_str());
+        if (c2 != std::string::npos) src.skew = atoi(tail.substr(c2 + 1).c_str());
+    }
+    return true;
+}
 
 // One copy of the synthetic tables on the CURRENT device: degrees -> in-place scan -> indptr, neighbours, features.
 bool synth_tables_here(const LegionSynthSpec& sp, int32_t skew, int32_t pitch, int64_t** indptr, int32_t** indices, float** feats, int64_t* E)
@@ -460,55 +555,281 @@ bool synth_tables_here(const LegionSynthSpec& sp, int32_t skew, int32_t pitch, i
     return !error_pending();
 }
 
-int32_t synth_skew(const std::string& path)
-{
-    const size_t c1 = path.find(':', 6);
-    const size_t c2 = c1 == std::string::npos ? c1 : path.find(':', c1 + 1);
-    return c2 == std::string::npos ? 205 : atoi(path.substr(c2 + 1).c_str());
-}
-
-// `synth:<workload>[:<scale>[:<skew>]]`: parse, check the meta line against the generator, generate on logical GPU 0.
-bool load_synth(Server* s, int G, LegionSynthSpec& spec)
+// synth: source: check the meta line against the generator, generate the tables on logical GPU 0, list the seeds.
+bool load_synth(Server* s, LegionSynthSpec& spec, SeedLists& lists)
 {
     Meta& m = s->meta;
-    std::string rest = m.dataset_path.substr(6), name = rest;
-    double scale = 1.0;
-    int32_t skew = 205;
-    const size_t c1 = rest.find(':');
-    if (c1 != std::string::npos) {
-        name = rest.substr(0, c1);
-        const std::string tail = rest.substr(c1 + 1);
-        const size_t c2 = tail.find(':');
-        scale = atof(tail.substr(0, c2).c_str());
-        if (c2 != std::string::npos) skew = atoi(tail.substr(c2 + 1).c_str());
-    }
-    if (legion_synth_spec(name.c_str(), scale, &spec) != 0) { LEGION_ARG_ERROR("Server_Initialize: the synth: dataset path names no known workload / scale"); return false; }
-    if (spec.V != m.node_num || spec.F != m.float_attr_len || skew < 0 || skew > 256) {
+    const SynthSource& src = s->synth_src;
+    if (legion_synth_spec(src.name.c_str(), src.scale, &spec) != 0) { LEGION_ARG_ERROR("Server_Initialize: the synth: dataset path names no known workload / scale"); return false; }
+    if (spec.V != m.node_num || spec.F != m.float_attr_len || src.skew < 0 || src.skew > 256) {
         LEGION_ARG_ERROR("Server_Initialize: node count / feature dim of the meta line differ from the synth: generator's");
         return false;
     }
-    if (m.training_set_num > spec.n_train || m.validation_set_num > spec.n_valid || m.testing_set_num > spec.n_test ||
-        m.training_set_num < 0 || m.validation_set_num < 0 || m.testing_set_num < 0) {
-        LEGION_ARG_ERROR("Server_Initialize: a seed set of the meta line is larger than the synth: generator's");
-        return false;
-    }
-    log_out() << "Start generate graph (" << name << ", scale " << scale << ", skew " << skew << "/256)\n";
+    const int32_t have[kModes] = {spec.n_train, spec.n_valid, spec.n_test};
+    for (int mode = 0; mode < kModes; mode++)
+        if (m.set_num[mode] > have[mode] || m.set_num[mode] < 0) {
+            LEGION_ARG_ERROR("Server_Initialize: a seed set of the meta line is larger than the synth: generator's");
+            return false;
+        }
+    log_out() << "Start generate graph (" << src.name << ", scale " << src.scale << ", skew " << src.skew << "/256)\n";
     s->synth = true;
     s->synth_pitch = legion_row_pitch(spec.F);
-    (void)G;
-    DeviceGuard guard(0);
-    int64_t E = 0;
-    if (!synth_tables_here(spec, skew, s->synth_pitch, &s->indptr, &s->indices, &s->feats, &E)) {
-        LEGION_ARG_ERROR("Server_Initialize: generating the synth: tables failed");
-        return false;
+    {
+        DeviceGuard guard(0);
+        int64_t E = 0;
+        if (!synth_tables_here(spec, src.skew, s->synth_pitch, &s->indptr, &s->indices, &s->feats, &E)) {
+            LEGION_ARG_ERROR("Server_Initialize: generating the synth: tables failed");
+            return false;
+        }
+        if (m.edge_num != 0 && m.edge_num != E) {
+            LEGION_ARG_ERROR("Server_Initialize: edge count of the meta line differs from the synth: generator's");
+            return false;
+        }
+        m.edge_num = E;
+        log_out() << "Graph generated in HBM: " << E << " edges\n";
     }
-    if (m.edge_num != 0 && m.edge_num != E) {
-        LEGION_ARG_ERROR("Server_Initialize: edge count of the meta line differs from the synth: generator's");
-        return false;
+    const int64_t first[kModes] = {0, spec.n_train, (int64_t)spec.n_train + spec.n_valid};   // the generator's train / valid / test ranges
+    for (int mode = 0; mode < kModes; mode++) {
+        lists.ids[mode].resize(m.set_num[mode]);
+        for (int32_t i = 0; i < m.set_num[mode]; i++) lists.ids[mode][i] = legion_synth_seed_id_host(first[mode] + i, m.node_num, spec.M2, spec.C2);
     }
-    m.edge_num = E;
-    log_out() << "Graph generated in HBM: " << E << " edges\n";
     return true;
+}
+
+// Load_Graph / Load_Feature (GPUGraphStore.cu:254-325): the tables into pinned, device-mapped host memory, then the seed lists, the labels
+// and the optional partition_<G>_bn
+bool load_files(Server* s, SeedLists& lists)
+{
+    static const char* const kSetFile[kModes] = {"trainingset", "validationset", "testingset"};
+    const Meta& m = s->meta;
+    const int32_t V = m.node_num, F = m.float_attr_len;
+    log_out() << "Start load graph\n";
+    s->indptr = (int64_t*)host_alloc_space64(((int64_t)V + 1) * 8);
+    s->indices = (int32_t*)host_alloc_space64(m.edge_num * 4);
+    bool ok = read_file(m.dataset_path + "edge_src", s->indptr, ((int64_t)V + 1) * 8);
+    ok = read_file(m.dataset_path + "edge_dst", s->indices, m.edge_num * 4) && ok;
+    log_out() << "start load node\n";
+    s->feats = (float*)host_alloc_space64((int64_t)V * F * 4);
+    ok = read_file(m.dataset_path + "features", s->feats, (int64_t)V * F * 4) && ok;
+    lists.labels.resize(V); lists.partition.resize(V);
+    for (int mode = 0; mode < kModes; mode++) {
+        lists.ids[mode].resize(m.set_num[mode]);
+        ok = read_file(m.dataset_path + kSetFile[mode], lists.ids[mode].data(), (int64_t)m.set_num[mode] * 4) && ok;
+    }
+    ok = read_file(m.dataset_path + "labels", lists.labels.data(), (int64_t)V * 4) && ok;
+    // the reference only prints "cannout open file" and carries on with garbage (GPUGraphStore.cu:33-35); fail instead
+    if (!ok) { LEGION_ARG_ERROR("Server_Initialize: dataset file(s) missing"); return false; }
+    lists.have_part = read_file(m.dataset_path + "partition_" + std::to_string(s->shard_count) + "_bn", lists.partition.data(), (int64_t)V * 4, nullptr, true);
+    return true;
+}
+
+// synth: source + flag 2: the per-GPU link-prediction lists are GENERATED (legion_synth_lp_seeds, the rule of synth.lp_trainingset): one
+// triple per training id in list order, dealt by src % G with its GLOBAL number, every batch laid out as [src | pos | neg] thirds.
+bool generate_lp_lists(const Server* s, const std::vector<int32_t>& training_ids, std::vector<std::vector<int32_t>>& out)
+{
+    const Meta& m = s->meta;
+    const int G = s->shard_count;
+    DeviceGuard guard(0);
+    for (int g = 0; g < G; g++) {
+        std::vector<int32_t> srcs;
+        std::vector<int64_t> tno;
+        for (int64_t t = 0; t < (int64_t)training_ids.size(); t++)
+            if (training_ids[t] % G == g) { srcs.push_back(training_ids[t]); tno.push_back(t); }
+        const int64_t n = (int64_t)srcs.size(), k = m.raw_batch_size / 3;
+        const int64_t n_out = (n + k - 1) / k * m.raw_batch_size;
+        out[g].assign((size_t)n_out, 0);
+        if (n == 0) continue;
+        int32_t *d_src = nullptr, *d_out = nullptr;
+        int64_t* d_tno = nullptr;
+        HIP_CHECK(hipMalloc(&d_src, (size_t)n * 4)); HIP_CHECK(hipMalloc(&d_tno, (size_t)n * 8)); HIP_CHECK(hipMalloc(&d_out, (size_t)n_out * 4));
+        if (!d_src || !d_tno || !d_out) return false;
+        HIP_CHECK(hipMemcpy(d_src, srcs.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_tno, tno.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+        legion_synth_lp_seeds(nullptr, d_out, d_src, d_tno, n, m.raw_batch_size, s->indptr, s->indices, m.node_num, 1);
+        HIP_CHECK(hipMemcpy(out[g].data(), d_out, (size_t)n_out * 4, hipMemcpyDeviceToHost));
+        (void)hipFree(d_src); (void)hipFree(d_tno); (void)hipFree(d_out);
+    }
+    if (error_pending()) return false;
+    log_out() << "Link-prediction seed lists generated: " << out[0].size() << " seeds on GPU 0\n";
+    return true;
+}
+
+// Pre-partitioned training lists (extension, not in the reference): meta flag 2 = GPU g serves the file
+// trainingset_<G>_<g> verbatim.  Needed for link prediction on G > 1 GPUs: lp_sage.py:87-90 expects every
+// batch as [src | pos | neg] thirds, which neither split rule below preserves (synth.lp_trainingset writes them).
+bool read_lp_lists(const Meta& m, int G, std::vector<std::vector<int32_t>>& out)
+{
+    bool ok = true;
+    for (int g = 0; g < G && ok; g++) {
+        const std::string path = m.dataset_path + "trainingset_" + std::to_string(G) + "_" + std::to_string(g);
+        struct stat st;
+        if (stat(path.c_str(), &st) != 0) { log_out() << "cannout open file: " << path << "\n"; ok = false; break; }
+        out[g].resize((size_t)st.st_size / 4);
+        ok = read_file(path, out[g].data(), (int64_t)out[g].size() * 4);
+        for (int32_t tid : out[g]) if (tid < 0 || tid >= m.node_num) ok = false;
+    }
+    if (!ok) LEGION_ARG_ERROR("Server_Initialize: pre-partitioned training lists (meta flag 2) missing or out of range");
+    return ok;
+}
+
+// flags 0 / 1: training id t to partition t % G, or (flag 1) to partition_<G>_bn[t] when that file exists
+bool split_training(const Meta& m, const SeedLists& lists, int G, std::vector<std::vector<int32_t>>& out)
+{
+    for (int32_t tid : lists.ids[LEGION_TRAINMODE]) {
+        if (tid < 0 || tid >= m.node_num) { LEGION_ARG_ERROR("Server_Initialize: training id outside [0, V)"); return false; }
+        int32_t part = (lists.have_part && m.partition == 1) ? lists.partition[tid] : tid % G;
+        if (part >= 0 && part < G) out[part].push_back(tid); // the reference indexes unchecked (GPUGraphStore.cu:338-341)
+    }
+    return true;
+}
+
+// seed split, GPUGraphStore.cu:332-414: the training ids by the rule of the meta line's partition flag, the validation and test ids by
+// id % G; then every id's label
+bool split_seeds(const Server* s, const SeedLists& lists, const LegionSynthSpec& spec, SeedSplit* split)
+{
+    const Meta& m = s->meta;
+    const int G = s->shard_count;
+    for (int mode = 0; mode < kModes; mode++) split[mode].ids.assign(G, {});
+    std::vector<std::vector<int32_t>>& train = split[LEGION_TRAINMODE].ids;
+    const bool ok = m.partition != 2 ? split_training(m, lists, G, train)
+                  : s->synth ? generate_lp_lists(s, lists.ids[LEGION_TRAINMODE], train)
+                  : read_lp_lists(m, G, train);
+    if (!ok) return false;
+    for (int mode = LEGION_VALIDMODE; mode <= LEGION_TESTMODE; mode++)
+        for (int32_t tid : lists.ids[mode]) { int32_t part = tid % G; if (part < G) split[mode].ids[part].push_back(tid); }
+    for (int mode = 0; mode < kModes; mode++) {
+        split[mode].labels.assign(G, {});
+        for (int p = 0; p < G; p++)
+            for (int32_t id : split[mode].ids[p])
+                split[mode].labels[p].push_back(s->synth ? legion_synth_label_host(id, spec.classes) : lists.labels[id]);
+    }
+    return true;
+}
+
+// LegionBuildInfo of the boot (the split seeds, the tables where the dataset source left them) and what is built from it: the IPC
+// environment's schedule and the two storages
+void build_storages(Server* s, SeedSplit* split)
+{
+    const Meta& m = s->meta;
+    const int G = s->shard_count;
+    LegionBuildInfo info;
+    memset(&info, 0, sizeof(info));
+    info.partition_count = G;
+    for (int mode = 0; mode < kModes; mode++) {
+        SeedSplit& set = split[mode];
+        for (int p = 0; p < G; p++) {
+            set.num.push_back((int32_t)set.ids[p].size());
+            set.id_ptr.push_back(set.ids[p].data());
+            set.label_ptr.push_back(set.labels[p].data());
+        }
+        info.*kBuildInfoSeeds[mode].num = set.num.data();
+        info.*kBuildInfoSeeds[mode].ids = set.id_ptr.data();
+        info.*kBuildInfoSeeds[mode].labels = set.label_ptr.data();
+    }
+    info.total_num_nodes = m.node_num; info.float_attr_len = m.float_attr_len;
+    const int32_t table_loc = s->synth ? LEGION_LOC_DEVICE : LEGION_LOC_HOST_PINNED;
+    info.host_float_attrs = s->feats; info.features_location = table_loc;
+    info.float_attr_pitch = s->synth ? s->synth_pitch : 0;
+    info.csr_node_index = s->indptr; info.csr_dst_node_ids = s->indices; info.csr_location = table_loc;
+    info.total_edge_num = m.edge_num; info.cache_edge_num = 0;
+    info.epoch = m.epoch; info.raw_batch_size = m.raw_batch_size;
+
+    s->env = NewIPCEnv(G);
+    IPCEnv_Coordinate(s->env, &info);
+    s->noder = NewGPUMemoryNodeStorage();
+    GPUNodeStorage_Build(s->noder, &info);
+    s->graph = NewGPUMemoryGraphStorage();
+    GPUGraphStorage_Build(s->graph, &info);
+}
+
+// MI355X-first: 288 GB of HBM usually hold the whole dataset, so replicate the tables into every GPU's HBM
+// instead of reading them over PCIe (the reference's UVA zero-copy).  $LEGION_TABLES = device | host | auto
+// (default auto: replicate when CSR + features + 20 % fit into the free HBM of every GPU).
+bool place_tables(Server* s, const LegionSynthSpec& spec)
+{
+    const Meta& m = s->meta;
+    const int G = s->shard_count;
+    const int32_t V = m.node_num, F = m.float_attr_len;
+    const char* mode = getenv("LEGION_TABLES");
+    const std::string tables = s->synth ? "synth" : (mode ? mode : "auto");
+    const int64_t need = (((int64_t)V + 1) * 8 + m.edge_num * 4 + (int64_t)V * F * 4);
+    bool replicate = tables == "device";
+    if (tables == "auto") {
+        replicate = true;
+        for (int i = 0; i < G; i++) {
+            DeviceGuard guard(i);
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            if ((double)need * 1.2 > (double)free_b) replicate = false;
+        }
+    }
+    if (s->synth) {
+        // generated in HBM on logical GPU 0; every other physical device of the job gets a copy of its own, generated in place
+        // (the storages free them as replicas)
+        std::vector<int> have{physical_device(0)};
+        for (int i = 1; i < G; i++) {
+            const int phys = physical_device(i);
+            int src = -1;
+            for (int j = 1; j < i; j++) if (physical_device(j) == phys && s->graph->replica_indptr[j]) src = j;
+            if (phys == have[0]) {                                 // shares GPU 0's tables
+                LEGION_AUDIT_SHARE(s->indptr, i); LEGION_AUDIT_SHARE(s->indices, i); LEGION_AUDIT_SHARE(s->feats, i);
+                continue;
+            }
+            if (src >= 0) {
+                s->graph->replica_indptr[i] = s->graph->replica_indptr[src]; s->graph->replica_indices[i] = s->graph->replica_indices[src];
+                s->noder->replica_attrs[i] = s->noder->replica_attrs[src];
+                LEGION_AUDIT_SHARE(s->graph->replica_indptr[i], i); LEGION_AUDIT_SHARE(s->graph->replica_indices[i], i); LEGION_AUDIT_SHARE(s->noder->replica_attrs[i], i);
+                continue;
+            }
+            DeviceGuard guard(i);
+            int64_t E2 = 0;
+            if (!synth_tables_here(spec, s->synth_src.skew, s->synth_pitch, &s->graph->replica_indptr[i], &s->graph->replica_indices[i],
+                                   &s->noder->replica_attrs[i], &E2) || E2 != m.edge_num) {
+                LEGION_ARG_ERROR("Server_Initialize: generating the synth: tables on a further GPU failed");
+                return false;
+            }
+        }
+        s->noder->replica_pitch = s->synth_pitch;
+        // $LEGION_SYNTH_CACHE=1: build the hotness cache anyway (budget = the meta line's cache_memory), as if the generated tables were the
+        // reference's host tables -- the cost model, FillUp and the cached gather / partitioned sampler through the server binary on a
+        // synth: source (bench.py's `cached_gather.served`, tests).  Default: everything is already HBM resident, a cache has nothing to add.
+        { const char* e = getenv("LEGION_SYNTH_CACHE"); s->replicated = !(e && e[0] == '1'); }
+        log_out() << "Tables generated in HBM: " << need / 1e9 << " GB per GPU" << (s->replicated ? "" : " (cache built on top: LEGION_SYNTH_CACHE=1)") << "\n";
+    } else if (replicate) {
+        GPUGraphStorage_ReplicateToDevices(s->graph);
+        GPUNodeStorage_ReplicateToDevices(s->noder);
+        s->replicated = true;
+        log_out() << "Tables replicated into HBM: " << need / 1e9 << " GB per GPU\n";
+    } else {
+        log_out() << "Tables stay in pinned host memory (" << need / 1e9 << " GB)\n";
+    }
+    return true;
+}
+
+// the cache, then one runner per GPU (GPUServer::Initialize, Server.cu:70-81)
+void start_runners(Server* s)
+{
+    const int G = s->shard_count;
+    s->cache = NewGPUCache();
+    const int32_t train_step = IPCEnv_GetTrainStep(s->env);
+    GPUCache_Initialize(s->cache, s->meta.cache_memory, 0, s->meta.float_attr_len, train_step, G);
+    log_out() << "Storage Initialized\n";
+    s->train_step = train_step;
+    s->max_step = IPCEnv_GetMaxStep(s->env);
+    s->runners.resize(G);
+    s->params.resize(G);
+    for (int i = 0; i < G; i++) {
+        RunnerParams* p = new RunnerParams();
+        p->device_id = i;
+        p->fanout = s->fanout.data();
+        p->hops = (int32_t)s->fanout.size();
+        p->cache = s->cache; p->graph = s->graph; p->noder = s->noder; p->env = s->env;
+        p->global_batch_id = 0;
+        p->in_memory = 1;
+        s->params[i] = p;
+        s->runners[i] = NewGPURunner();
+        Runner_Initialize(s->runners[i], p);
+    }
 }
 
 } // namespace
@@ -527,250 +848,34 @@ void Server_SetMetaConfigPath(Server* s, const char* path) { if (s && path) s->m
 void Server_Initialize(Server* s, int global_shard_count)
 {
     if (!s || global_shard_count < 1 || global_shard_count > kMaxParts) { LEGION_ARG_ERROR("Server_Initialize: shard count must be 1..8"); return; }
-    const int G = global_shard_count;
-    s->shard_count = G;
-    log_out() << "HIP Device Count: " << G << "\n";
-    Meta& m = s->meta;
-    {
-        std::ifstream f(s->meta_path);
-        if (!f.is_open()) { log_out() << "unable to open meta config file\n"; LEGION_ARG_ERROR("Server_Initialize: meta_config missing"); return; }
-        std::string line;
-        getline(f, line);
-        std::istringstream iss(line);
-        iss >> m.dataset_path >> m.raw_batch_size >> m.node_num >> m.edge_num >> m.float_attr_len >> m.training_set_num >>
-            m.validation_set_num >> m.testing_set_num >> m.cache_memory >> m.epoch >> m.partition;
-        log_out() << "Dataset path:       " << m.dataset_path << "\nRaw Batchsize:      " << m.raw_batch_size
-                  << "\nGraph nodes num:    " << m.node_num << "\nGraph edges num:    " << m.edge_num
-                  << "\nFeature dim:        " << m.float_attr_len << "\nTraining set num:   " << m.training_set_num
-                  << "\nValidation set num: " << m.validation_set_num << "\nTesting set num:    " << m.testing_set_num
-                  << "\nCache memory:       " << m.cache_memory << "\nTrain epoch:        " << m.epoch
-                  << "\nPartition?:         " << m.partition << "\n";
-        // The reference reads the eleven fields unchecked (GPUGraphStore.cu:190-223): a short or mistyped line leaves zeros behind and the
-        // first division by the batch size or the first zero-byte table ends the server without a message.  Refuse it here, by name.
-        const char* bad = nullptr;
-        if (iss.fail()) bad = "fewer than eleven fields (path batch V E F n_train n_valid n_test cache_bytes epochs partition_flag)";
-        else if (m.raw_batch_size < 1) bad = "batch size < 1";
-        else if (m.node_num < 1) bad = "node count < 1";
-        else if (m.edge_num < 0) bad = "negative edge count";
-        else if (m.float_attr_len < 1) bad = "feature dim < 1";
-        else if (m.training_set_num < 0 || m.validation_set_num < 0 || m.testing_set_num < 0) bad = "negative seed-set size";
-        else if (m.training_set_num > m.node_num || m.validation_set_num > m.node_num || m.testing_set_num > m.node_num) bad = "a seed set larger than the node count";
-        else if (m.cache_memory < 0) bad = "negative cache budget";
-        else if (m.epoch < 0) bad = "negative epoch count";
-        else if (m.partition < 0 || m.partition > 2) bad = "partition flag outside 0..2";
-        if (bad) {
-            const std::string msg = std::string("Server_Initialize: meta_config refused: ") + bad;
-            LEGION_ARG_ERROR(msg.c_str());
-            return;
-        }
-    }
+    s->shard_count = global_shard_count;
+    log_out() << "HIP Device Count: " << global_shard_count << "\n";
+    const std::string refused = read_meta(s->meta_path, s->meta);
+    if (!refused.empty()) { LEGION_ARG_ERROR(refused.c_str()); return; }
+    const Meta& m = s->meta;
     // from the first device call on the main thread works on GPU 0 unless a scope below says otherwise (the reference's main thread never
     // leaves device 0); not before the meta line and the synth: source are validated -- a refused configuration touches no device
     std::optional<DeviceGuard> boot;
-    const int32_t V = m.node_num;
-    const int32_t F = m.float_attr_len;
-    std::vector<int32_t> training_ids, validation_ids, testing_ids, all_labels, partition_index;
-    bool have_part = false;
-    const bool synth = m.dataset_path.rfind("synth:", 0) == 0;
-    LegionSynthSpec spec;
-    if (synth) {
-        // Dataset source `synth:<workload>[:<scale>[:<skew>]]` (extension): the tables of the named synthetic shape are generated
-        // on the device by the legion_synth_* calls bench.py uses -- 64 GB of files per start is not an option for the papers100M
-        // shape.  V, E, F of the meta line must be the generator's (E = 0: not checked); the seed-set sizes of the meta line take
-        // the first n ids of the generator's train / valid / test ranges.
-        if (!load_synth(s, G, spec)) return;
+    LegionSynthSpec spec{};
+    SeedLists lists;
+    if (parse_synth(m.dataset_path, s->synth_src)) {
+        if (!load_synth(s, spec, lists)) return;
         boot.emplace(0);
-        training_ids.resize(m.training_set_num); validation_ids.resize(m.validation_set_num); testing_ids.resize(m.testing_set_num);
-        for (int32_t i = 0; i < m.training_set_num; i++) training_ids[i] = legion_synth_seed_id_host(i, V, spec.M2, spec.C2);
-        for (int32_t i = 0; i < m.validation_set_num; i++) validation_ids[i] = legion_synth_seed_id_host((int64_t)spec.n_train + i, V, spec.M2, spec.C2);
-        for (int32_t i = 0; i < m.testing_set_num; i++) testing_ids[i] = legion_synth_seed_id_host((int64_t)spec.n_train + spec.n_valid + i, V, spec.M2, spec.C2);
         if (m.partition == 2 && m.raw_batch_size % 3 != 0) {
             LEGION_ARG_ERROR("Server_Initialize: synth: link-prediction lists (meta flag 2) need a batch size divisible by 3 ([src | pos | neg] thirds, lp_sage.py:87-90)");
             return;
         }
     } else {
-    // Load_Graph / Load_Feature (GPUGraphStore.cu:254-325): pinned, device-mapped host memory
-    boot.emplace(0);
-    log_out() << "Start load graph\n";
-    s->indptr = (int64_t*)host_alloc_space64(((int64_t)V + 1) * 8);
-    s->indices = (int32_t*)host_alloc_space64(m.edge_num * 4);
-    bool ok = read_file(m.dataset_path + "edge_src", s->indptr, ((int64_t)V + 1) * 8);
-    ok = read_file(m.dataset_path + "edge_dst", s->indices, m.edge_num * 4) && ok;
-    log_out() << "start load node\n";
-    s->feats = (float*)host_alloc_space64((int64_t)V * F * 4);
-    ok = read_file(m.dataset_path + "features", s->feats, (int64_t)V * F * 4) && ok;
-    training_ids.resize(m.training_set_num); validation_ids.resize(m.validation_set_num); testing_ids.resize(m.testing_set_num);
-    all_labels.resize(V); partition_index.resize(V);
-    ok = read_file(m.dataset_path + "trainingset", training_ids.data(), (int64_t)m.training_set_num * 4) && ok;
-    ok = read_file(m.dataset_path + "validationset", validation_ids.data(), (int64_t)m.validation_set_num * 4) && ok;
-    ok = read_file(m.dataset_path + "testingset", testing_ids.data(), (int64_t)m.testing_set_num * 4) && ok;
-    ok = read_file(m.dataset_path + "labels", all_labels.data(), (int64_t)V * 4) && ok;
-    // the reference only prints "cannout open file" and carries on with garbage (GPUGraphStore.cu:33-35); fail instead
-    if (!ok) { LEGION_ARG_ERROR("Server_Initialize: dataset file(s) missing"); return; }
-    have_part = read_file(m.dataset_path + "partition_" + std::to_string(G) + "_bn", partition_index.data(), (int64_t)V * 4, nullptr, true);
+        boot.emplace(0);
+        if (!load_files(s, lists)) return;
     }
-    auto label_of = [&](int32_t id) { return synth ? legion_synth_label_host(id, spec.classes) : all_labels[id]; };
     log_out() << "Finish Reading All Files\n";
-    // seed split, GPUGraphStore.cu:332-414
-    s->tr_ids.assign(G, {}); s->va_ids.assign(G, {}); s->te_ids.assign(G, {});
-    s->tr_lab.assign(G, {}); s->va_lab.assign(G, {}); s->te_lab.assign(G, {});
-    if (m.partition == 2 && synth) {
-        // synth: source + flag 2: the per-GPU link-prediction lists are GENERATED (legion_synth_lp_seeds, the rule of synth.lp_trainingset): one
-        // triple per training id in list order, dealt by src % G with its GLOBAL number, every batch laid out as [src | pos | neg] thirds.
-        DeviceGuard guard(0);
-        for (int g = 0; g < G; g++) {
-            std::vector<int32_t> srcs;
-            std::vector<int64_t> tno;
-            for (int64_t t = 0; t < (int64_t)training_ids.size(); t++)
-                if (training_ids[t] % G == g) { srcs.push_back(training_ids[t]); tno.push_back(t); }
-            const int64_t n = (int64_t)srcs.size(), k = m.raw_batch_size / 3;
-            const int64_t n_out = (n + k - 1) / k * m.raw_batch_size;
-            s->tr_ids[g].assign((size_t)n_out, 0);
-            if (n == 0) continue;
-            int32_t *d_src = nullptr, *d_out = nullptr;
-            int64_t* d_tno = nullptr;
-            HIP_CHECK(hipMalloc(&d_src, (size_t)n * 4)); HIP_CHECK(hipMalloc(&d_tno, (size_t)n * 8)); HIP_CHECK(hipMalloc(&d_out, (size_t)n_out * 4));
-            if (!d_src || !d_tno || !d_out) return;
-            HIP_CHECK(hipMemcpy(d_src, srcs.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(d_tno, tno.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-            legion_synth_lp_seeds(nullptr, d_out, d_src, d_tno, n, m.raw_batch_size, s->indptr, s->indices, V, 1);
-            HIP_CHECK(hipMemcpy(s->tr_ids[g].data(), d_out, (size_t)n_out * 4, hipMemcpyDeviceToHost));
-            (void)hipFree(d_src); (void)hipFree(d_tno); (void)hipFree(d_out);
-        }
-        if (error_pending()) return;
-        log_out() << "Link-prediction seed lists generated: " << s->tr_ids[0].size() << " seeds on GPU 0\n";
-    } else if (m.partition == 2) {
-        // Pre-partitioned training lists (extension, not in the reference): meta flag 2 = GPU g serves the file
-        // trainingset_<G>_<g> verbatim.  Needed for link prediction on G > 1 GPUs: lp_sage.py:87-90 expects every
-        // batch as [src | pos | neg] thirds, which neither split rule below preserves (synth.lp_trainingset writes them).
-        bool ok = true;
-        for (int g = 0; g < G && ok; g++) {
-            const std::string path = m.dataset_path + "trainingset_" + std::to_string(G) + "_" + std::to_string(g);
-            struct stat st;
-            if (stat(path.c_str(), &st) != 0) { log_out() << "cannout open file: " << path << "\n"; ok = false; break; }
-            s->tr_ids[g].resize((size_t)st.st_size / 4);
-            ok = read_file(path, s->tr_ids[g].data(), (int64_t)s->tr_ids[g].size() * 4);
-            for (int32_t tid : s->tr_ids[g]) if (tid < 0 || tid >= V) ok = false;
-        }
-        if (!ok) { LEGION_ARG_ERROR("Server_Initialize: pre-partitioned training lists (meta flag 2) missing or out of range"); return; }
-    } else {
-        for (int32_t tid : training_ids) {
-            if (tid < 0 || tid >= V) { LEGION_ARG_ERROR("Server_Initialize: training id outside [0, V)"); return; }
-            int32_t part = (have_part && m.partition == 1) ? partition_index[tid] : tid % G;
-            if (part >= 0 && part < G) s->tr_ids[part].push_back(tid); // the reference indexes unchecked (GPUGraphStore.cu:338-341)
-        }
-    }
-    for (int32_t tid : validation_ids) { int32_t part = tid % G; if (part < G) s->va_ids[part].push_back(tid); }
-    for (int32_t tid : testing_ids) { int32_t part = tid % G; if (part < G) s->te_ids[part].push_back(tid); }
-    std::vector<int32_t> tn(G), vn(G), en(G);
-    std::vector<const int32_t*> tp(G), vp(G), ep(G), tlp(G), vlp(G), elp(G);
-    for (int p = 0; p < G; p++) {
-        for (int32_t id : s->tr_ids[p]) s->tr_lab[p].push_back(label_of(id));
-        for (int32_t id : s->va_ids[p]) s->va_lab[p].push_back(label_of(id));
-        for (int32_t id : s->te_ids[p]) s->te_lab[p].push_back(label_of(id));
-        tn[p] = (int32_t)s->tr_ids[p].size(); vn[p] = (int32_t)s->va_ids[p].size(); en[p] = (int32_t)s->te_ids[p].size();
-        tp[p] = s->tr_ids[p].data(); vp[p] = s->va_ids[p].data(); ep[p] = s->te_ids[p].data();
-        tlp[p] = s->tr_lab[p].data(); vlp[p] = s->va_lab[p].data(); elp[p] = s->te_lab[p].data();
-    }
+    SeedSplit split[kModes];
+    if (!split_seeds(s, lists, spec, split)) return;
     log_out() << "Finish Partition\n";
-    LegionBuildInfo info;
-    memset(&info, 0, sizeof(info));
-    info.partition_count = G;
-    info.training_set_num = tn.data(); info.training_set_ids = tp.data(); info.training_labels = tlp.data();
-    info.validation_set_num = vn.data(); info.validation_set_ids = vp.data(); info.validation_labels = vlp.data();
-    info.testing_set_num = en.data(); info.testing_set_ids = ep.data(); info.testing_labels = elp.data();
-    info.total_num_nodes = V; info.float_attr_len = F;
-    const int32_t table_loc = synth ? LEGION_LOC_DEVICE : LEGION_LOC_HOST_PINNED;
-    info.host_float_attrs = s->feats; info.features_location = table_loc;
-    info.float_attr_pitch = synth ? s->synth_pitch : 0;
-    info.csr_node_index = s->indptr; info.csr_dst_node_ids = s->indices; info.csr_location = table_loc;
-    info.total_edge_num = m.edge_num; info.cache_edge_num = 0;
-    info.epoch = m.epoch; info.raw_batch_size = m.raw_batch_size;
-
-    s->env = NewIPCEnv(G);
-    IPCEnv_Coordinate(s->env, &info);
-    s->noder = NewGPUMemoryNodeStorage();
-    GPUNodeStorage_Build(s->noder, &info);
-    s->graph = NewGPUMemoryGraphStorage();
-    GPUGraphStorage_Build(s->graph, &info);
-    // MI355X-first: 288 GB of HBM usually hold the whole dataset, so replicate the tables into every GPU's HBM
-    // instead of reading them over PCIe (the reference's UVA zero-copy).  $LEGION_TABLES = device | host | auto
-    // (default auto: replicate when CSR + features + 20 % fit into the free HBM of every GPU).
-    {
-        const char* mode = getenv("LEGION_TABLES");
-        const std::string tables = synth ? "synth" : (mode ? mode : "auto");
-        const int64_t need = (((int64_t)V + 1) * 8 + m.edge_num * 4 + (int64_t)V * F * 4);
-        bool replicate = tables == "device";
-        if (tables == "auto") {
-            replicate = true;
-            for (int i = 0; i < G; i++) {
-                DeviceGuard guard(i);
-                size_t free_b = 0, total_b = 0;
-                HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-                if ((double)need * 1.2 > (double)free_b) replicate = false;
-            }
-        }
-        if (synth) {
-            // generated in HBM on logical GPU 0; every other physical device of the job gets a copy of its own, generated in place
-            // (the storages free them as replicas)
-            std::vector<int> have{physical_device(0)};
-            for (int i = 1; i < G; i++) {
-                const int phys = physical_device(i);
-                int src = -1;
-                for (int j = 1; j < i; j++) if (physical_device(j) == phys && s->graph->replica_indptr[j]) src = j;
-                if (phys == have[0]) {                                 // shares GPU 0's tables
-                    LEGION_AUDIT_SHARE(s->indptr, i); LEGION_AUDIT_SHARE(s->indices, i); LEGION_AUDIT_SHARE(s->feats, i);
-                    continue;
-                }
-                if (src >= 0) {
-                    s->graph->replica_indptr[i] = s->graph->replica_indptr[src]; s->graph->replica_indices[i] = s->graph->replica_indices[src];
-                    s->noder->replica_attrs[i] = s->noder->replica_attrs[src];
-                    LEGION_AUDIT_SHARE(s->graph->replica_indptr[i], i); LEGION_AUDIT_SHARE(s->graph->replica_indices[i], i); LEGION_AUDIT_SHARE(s->noder->replica_attrs[i], i);
-                    continue;
-                }
-                DeviceGuard guard(i);
-                int64_t E2 = 0;
-                if (!synth_tables_here(spec, synth_skew(m.dataset_path), s->synth_pitch, &s->graph->replica_indptr[i], &s->graph->replica_indices[i],
-                                       &s->noder->replica_attrs[i], &E2) || E2 != m.edge_num) {
-                    LEGION_ARG_ERROR("Server_Initialize: generating the synth: tables on a further GPU failed");
-                    return;
-                }
-            }
-            s->noder->replica_pitch = s->synth_pitch;
-            // $LEGION_SYNTH_CACHE=1: build the hotness cache anyway (budget = the meta line's cache_memory), as if the generated tables were the
-            // reference's host tables -- the cost model, FillUp and the cached gather / partitioned sampler through the server binary on a
-            // synth: source (bench.py's `cached_gather.served`, tests).  Default: everything is already HBM resident, a cache has nothing to add.
-            { const char* e = getenv("LEGION_SYNTH_CACHE"); s->replicated = !(e && e[0] == '1'); }
-            log_out() << "Tables generated in HBM: " << need / 1e9 << " GB per GPU" << (s->replicated ? "" : " (cache built on top: LEGION_SYNTH_CACHE=1)") << "\n";
-        } else if (replicate) {
-            GPUGraphStorage_ReplicateToDevices(s->graph);
-            GPUNodeStorage_ReplicateToDevices(s->noder);
-            s->replicated = true;
-            log_out() << "Tables replicated into HBM: " << need / 1e9 << " GB per GPU\n";
-        } else {
-            log_out() << "Tables stay in pinned host memory (" << need / 1e9 << " GB)\n";
-        }
-    }
-    s->cache = NewGPUCache();
-    const int32_t train_step = IPCEnv_GetTrainStep(s->env);
-    GPUCache_Initialize(s->cache, m.cache_memory, 0, F, train_step, G);
-    log_out() << "Storage Initialized\n";
-    s->train_step = train_step;
-    s->max_step = IPCEnv_GetMaxStep(s->env);
-    s->runners.resize(G);
-    s->params.resize(G);
-    for (int i = 0; i < G; i++) {
-        RunnerParams* p = new RunnerParams();
-        p->device_id = i;
-        p->fanout = s->fanout.data();
-        p->hops = (int32_t)s->fanout.size();
-        p->cache = s->cache; p->graph = s->graph; p->noder = s->noder; p->env = s->env;
-        p->global_batch_id = 0;
-        p->in_memory = 1;
-        s->params[i] = p;
-        s->runners[i] = NewGPURunner();
-        Runner_Initialize(s->runners[i], p);
-    }
+    build_storages(s, split);
+    if (!place_tables(s, spec)) return;
+    start_runners(s);
 }
 
 // PreSc, Server.cu:83-114

@@ -349,28 +349,19 @@ void GPUNodeStorage_Build(GPUNodeStorage* n, const LegionBuildInfo* info)
         : nullptr;
     n->owns_features = owns;
     n->replica_attrs.assign(P, nullptr);
-    n->training_set_num.assign(P, 0); n->validation_set_num.assign(P, 0); n->testing_set_num.assign(P, 0);
-    n->training_set_ids.assign(P, nullptr); n->validation_set_ids.assign(P, nullptr); n->testing_set_ids.assign(P, nullptr);
-    n->training_labels.assign(P, nullptr); n->validation_labels.assign(P, nullptr); n->testing_labels.assign(P, nullptr);
+    for (auto& sets : n->seeds) sets.assign(P, GPUNodeStorage::SeedSet());
     for (int p = 0; p < P; p++) { // GPU_Memory_Node_Storage.cu:41-96
         if (is_remote_device(p)) continue; // that partition's seed sets live in its own process
         DeviceGuard guard(p);
-        if (info->training_set_num) {
-            n->training_set_num[p] = info->training_set_num[p];
-            n->training_set_ids[p] = upload_i32(info->training_set_ids[p], info->training_set_num[p]);
-            n->training_labels[p] = upload_i32(info->training_labels[p], info->training_set_num[p]);
+        for (int mode = 0; mode < kModes; mode++) {
+            const BuildInfoSeedFields& f = kBuildInfoSeeds[mode];
+            if (!(info->*f.num)) continue;
+            GPUNodeStorage::SeedSet& set = n->seeds[mode][p];
+            set.num = (info->*f.num)[p];
+            set.ids = upload_i32((info->*f.ids)[p], set.num);
+            set.labels = upload_i32((info->*f.labels)[p], set.num);
         }
-        if (info->validation_set_num) {
-            n->validation_set_num[p] = info->validation_set_num[p];
-            n->validation_set_ids[p] = upload_i32(info->validation_set_ids[p], info->validation_set_num[p]);
-            n->validation_labels[p] = upload_i32(info->validation_labels[p], info->validation_set_num[p]);
-        }
-        if (info->testing_set_num) {
-            n->testing_set_num[p] = info->testing_set_num[p];
-            n->testing_set_ids[p] = upload_i32(info->testing_set_ids[p], info->testing_set_num[p]);
-            n->testing_labels[p] = upload_i32(info->testing_labels[p], info->testing_set_num[p]);
-        }
-        LEGION_AUDIT_OWNER(n->training_set_ids[p], p, "GPUNodeStorage_Build: seed list");
+        LEGION_AUDIT_OWNER(n->seeds[LEGION_TRAINMODE][p].ids, p, "GPUNodeStorage_Build: seed list");
     }
 }
 
@@ -411,24 +402,23 @@ void GPUNodeStorage_Finalize(GPUNodeStorage* n)
 {
     if (!n) return;
     free_replicas(n->replica_attrs);
-    auto drop = [](std::vector<int32_t*>& v) { for (auto& p : v) { if (p) (void)hipFree(p); p = nullptr; } };
-    drop(n->training_set_ids); drop(n->validation_set_ids); drop(n->testing_set_ids);
-    drop(n->training_labels); drop(n->validation_labels); drop(n->testing_labels);
+    for (auto& sets : n->seeds)
+        for (auto& set : sets) {
+            if (set.ids) (void)hipFree(set.ids);
+            if (set.labels) (void)hipFree(set.labels);
+            set.ids = set.labels = nullptr;
+        }
     if (n->owns_features) { host_free_space(n->float_attrs); n->owns_features = false; }
 }
-#define NS_GETTER(name, field) \
-    int32_t* GPUNodeStorage_##name(const GPUNodeStorage* n, int32_t part_id) { \
-        return (part_id >= 0 && part_id < n->partition_count) ? n->field[part_id] : nullptr; }
-NS_GETTER(GetTrainingSetIds, training_set_ids)
-NS_GETTER(GetValidationSetIds, validation_set_ids)
-NS_GETTER(GetTestingSetIds, testing_set_ids)
-NS_GETTER(GetTrainingLabels, training_labels)
-NS_GETTER(GetValidationLabels, validation_labels)
-NS_GETTER(GetTestingLabels, testing_labels)
-#undef NS_GETTER
-int32_t GPUNodeStorage_TrainingSetSize(const GPUNodeStorage* n, int32_t p) { return (p >= 0 && p < n->partition_count) ? n->training_set_num[p] : 0; }
-int32_t GPUNodeStorage_ValidationSetSize(const GPUNodeStorage* n, int32_t p) { return (p >= 0 && p < n->partition_count) ? n->validation_set_num[p] : 0; }
-int32_t GPUNodeStorage_TestingSetSize(const GPUNodeStorage* n, int32_t p) { return (p >= 0 && p < n->partition_count) ? n->testing_set_num[p] : 0; }
+int32_t* GPUNodeStorage_GetTrainingSetIds(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_TRAINMODE, p).ids; }
+int32_t* GPUNodeStorage_GetValidationSetIds(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_VALIDMODE, p).ids; }
+int32_t* GPUNodeStorage_GetTestingSetIds(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_TESTMODE, p).ids; }
+int32_t* GPUNodeStorage_GetTrainingLabels(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_TRAINMODE, p).labels; }
+int32_t* GPUNodeStorage_GetValidationLabels(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_VALIDMODE, p).labels; }
+int32_t* GPUNodeStorage_GetTestingLabels(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_TESTMODE, p).labels; }
+int32_t GPUNodeStorage_TrainingSetSize(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_TRAINMODE, p).num; }
+int32_t GPUNodeStorage_ValidationSetSize(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_VALIDMODE, p).num; }
+int32_t GPUNodeStorage_TestingSetSize(const GPUNodeStorage* n, int32_t p) { return n->seed_set(LEGION_TESTMODE, p).num; }
 int32_t GPUNodeStorage_TotalNodeNum(const GPUNodeStorage* n) { return n->total_num_nodes; }
 float* GPUNodeStorage_GetAllFloatAttr(const GPUNodeStorage* n) { return n->float_attrs; }
 int32_t GPUNodeStorage_GetFloatAttrLen(const GPUNodeStorage* n) { return n->float_attr_len; }
