@@ -73,9 +73,28 @@ __host__ __device__ inline pos_t pos_entry(uint32_t epoch, uint32_t value) { ret
 #ifndef LEGION_KTILE
 #define LEGION_KTILE 1024
 #endif
-constexpr int kTile = LEGION_KTILE;            // sampler slots per workgroup tile
+constexpr int kTile = LEGION_KTILE;            // sampler slots per workgroup tile (hops that fill the chip)
 constexpr int kBlock = 256;                    // threads per workgroup
 static_assert(kTile >= kBlock && kTile <= 2048 && (kTile & (kTile - 1)) == 0, "LEGION_KTILE: a power of two in [256, 2048] (k_sample stages 16 bytes of row descriptor per slot in static LDS)");
+// A hop whose static slot bound (seeds x fan-outs so far) is at most kNarrowSlots does not fill the chip with kTile-slot tiles (hop 1 of the
+// headline: 196 tiles on 256 CUs, each thread walking kTile / kBlock slots one after the other): its three passes run the kTileNarrow
+// instantiation, one slot per thread.  The tile is a template parameter of k_sample / k_mark / k_write and the same in all three passes of a
+// hop (launch_sample_hop picks it once); the RNG stream and every rank are indexed by slot, so results do not depend on it.  The per-tile
+// scratch (tile_edge / tile_node / tile_pre) is sized for the larger of the two tile counts (sampler_max_tiles).
+#ifndef LEGION_NARROW_SLOTS
+#define LEGION_NARROW_SLOTS (256 * 1024)
+#endif
+constexpr int kTileNarrow = kBlock;
+constexpr int64_t kNarrowSlots = LEGION_NARROW_SLOTS;
+static_assert(kTileNarrow <= kTile, "one pow_tab of kTile entries serves both tile sizes");
+constexpr int64_t sampler_tile_of(int64_t slots_bound) { return slots_bound <= kNarrowSlots ? kTileNarrow : kTile; }
+// tiles of the largest hop a pool sized for `max_slots` slots can run, whichever tile size each of its hops selects
+constexpr int64_t sampler_max_tiles(int64_t max_slots)
+{
+    const int64_t wide = (max_slots + kTile - 1) / kTile, narrow_slots = max_slots < kNarrowSlots ? max_slots : kNarrowSlots;
+    const int64_t narrow = (narrow_slots + kTileNarrow - 1) / kTileNarrow;
+    return wide > narrow ? wide : narrow;
+}
 // k_mark runs one CONTIGUOUS chunk of tiles per workgroup and leaves the chunk totals in GPUMemoryPool::chunk_tot; k_write scans them in
 // LDS, kMaxChunks / kBlock per thread.  One constant for the allocation (storage.cpp), the grid clamp (launch_sample_hop) and the LDS
 // array (k_write): changing one of them alone would let k_mark write past the allocation.

@@ -28,7 +28,8 @@
 //                 that lost its claim follows loser -> winner through the slot states and computes the
 //                 winner's position from that tile's prefix + rank; it also sets the next hop's states
 //                 to -1; the workgroup of the last tile applies update_counter (S2).
-//    Three launches per hop (round 1: four), 11 per 3-hop batch with k_seed and the gather.
+//    Three launches per hop (round 1: four), 11 per 3-hop batch with k_seed and the gather.  The three passes of a hop share one
+//    tile size (template parameter TILE): kTile slots, or kTileNarrow on hops too small to fill the chip (internal.h).
 //  * One u64[V] "position table" replaces accessed_map (bitmap) + position_map.  Entry =
 //    (epoch << 32) | value, epoch = 0xFFFFFFFF - batch serial, so entries of older batches compare
 //    GREATER than anything of the running batch: they are stale without ever being cleared (no
@@ -161,9 +162,9 @@ struct SampleArgs {
     int32_t* tile_edge;
     unsigned long long* edge_access_time;
     const BatchCtl* ctl;       // table epoch of the running batch
-    const uint32_t* pow_tab;   // pow_tab[m] = 48271^(m+1), m < kTile
-    uint32_t a_tile;           // 48271^kTile
-    uint32_t a_step;           // 48271^(kTile * gridDim.x)
+    const uint32_t* pow_tab;   // pow_tab[m] = 48271^(m+1), m < kTile (a launch with a smaller tile reads its first TILE entries)
+    uint32_t a_tile;           // 48271^TILE
+    uint32_t a_step;           // 48271^(TILE * gridDim.x)
     FastDiv fdiv;              // / count
     int32_t count;
     int32_t op_id;
@@ -205,35 +206,35 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
     return -1;
 }
 
-template <bool PRESC, bool PARTITIONED>
+template <int TILE, bool PRESC, bool PARTITIONED>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
-    __shared__ const int32_t* s_row[kTile + 2]; // pointer to the first neighbour of the staged row
-    __shared__ int32_t s_deg[kTile + 2];
-    __shared__ int32_t s_src[kTile + 2];
+    __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
+    __shared__ int32_t s_deg[TILE + 2];
+    __shared__ int32_t s_src[TILE + 2];
     __shared__ int32_t s_cnt[kBlock / 64];
 
     const int32_t N = a.nc[2];
     const int32_t f = a.count;
     const int32_t total = N * f; // int32 like the reference (Kernels.cu:375)
     const int32_t* __restrict__ input = (a.op_id == 2) ? a.sampled_ids : a.agg_src_ids + a.ec[2];
-    const int32_t n_tiles = (total + kTile - 1) / kTile;
+    const int32_t n_tiles = (total + TILE - 1) / TILE;
     const int tid = threadIdx.x;
     const uint32_t epoch = a.ctl->epoch;
 
     if ((int32_t)blockIdx.x >= n_tiles) return;
 
-    // per-thread RNG state: x[s] = 48271^(tile*kTile + tid + 256*s + 1)
-    uint32_t x[kTile / kBlock];
+    // per-thread RNG state: x[s] = 48271^(tile*TILE + tid + 256*s + 1)
+    uint32_t x[TILE / kBlock];
     {
         uint32_t base = powmod31(a.a_tile, (uint64_t)blockIdx.x); // uniform per workgroup
 #pragma unroll
-        for (int s = 0; s < kTile / kBlock; s++) x[s] = mulmod31(base, a.pow_tab[tid + kBlock * s]);
+        for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(base, a.pow_tab[tid + kBlock * s]);
     }
 
     for (int32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int32_t tile_start = tile * kTile;
-        const int32_t tile_end = min(tile_start + kTile, total);
+        const int32_t tile_start = tile * TILE;
+        const int32_t tile_end = min(tile_start + TILE, total);
         const int32_t i0 = (int32_t)fdiv((uint32_t)tile_start, a.fdiv);
         const int32_t i_last = (int32_t)fdiv((uint32_t)(tile_end - 1), a.fdiv);
         const int32_t nrows = i_last - i0 + 1;
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 
         int32_t cnt = 0;
 #pragma unroll
-        for (int s = 0; s < kTile / kBlock; s++) {
+        for (int s = 0; s < TILE / kBlock; s++) {
             const int32_t idx = tile_start + tid + kBlock * s;
             int32_t dst = -1, known = -1, j = 0, r = 0;
             if (idx < tile_end) {
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             a.tile_edge[tile] = t;
         }
 #pragma unroll
-        for (int s = 0; s < kTile / kBlock; s++) x[s] = mulmod31(x[s], a.a_step);
+        for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(x[s], a.a_step);
         __syncthreads();
     }
 }
@@ -354,15 +355,16 @@ __host__ __device__ inline FastDiv make_fastdiv(uint32_t div)
     return f;
 }
 
+template <int TILE>
 __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc, const int32_t* __restrict__ ec,
                                                  int32_t count, int32_t* __restrict__ aux, const int32_t* __restrict__ tile_edge,
                                                  int32_t* __restrict__ tile_node, int2* __restrict__ tile_pre,
                                                  int2* __restrict__ chunk_tot, HopState* __restrict__ hs)
 {
-    constexpr int S = kTile / kBlock, W = kBlock / 64;
+    constexpr int S = TILE / kBlock, W = kBlock / 64;
     __shared__ int32_t s_c[S * W];
     const int32_t total = nc[2] * count;
-    const int32_t n_tiles = (total + kTile - 1) / kTile;
+    const int32_t n_tiles = (total + TILE - 1) / TILE;
     const int lane = lane_id(), wave = wave_id();
     const unsigned long long lt = (1ull << lane) - 1ull;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -381,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc,
     int32_t nxt[S];
 #pragma unroll
     for (int s = 0; s < S; s++) {
-        const int64_t idx = (int64_t)t0 * kTile + threadIdx.x + kBlock * s;
+        const int64_t idx = (int64_t)t0 * TILE + threadIdx.x + kBlock * s;
         nxt[s] = idx < total ? aux[idx] : 0;
     }
     int32_t te_next = threadIdx.x == 0 ? tile_edge[t0] : 0, run_e = 0, run_n = 0;   // thread 0 keeps the chunk's running sums
@@ -391,14 +393,14 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc,
         const int32_t te = te_next;
 #pragma unroll
         for (int s = 0; s < S; s++) {
-            const int32_t idx = tile * kTile + threadIdx.x + kBlock * s;
+            const int32_t idx = tile * TILE + threadIdx.x + kBlock * s;
             win[s] = idx < total && nxt[s] == -1;
         }
         {
             const int64_t nt = (int64_t)tile + 1;
 #pragma unroll
             for (int s = 0; s < S; s++) {
-                const int64_t idx = nt * kTile + threadIdx.x + kBlock * s;
+                const int64_t idx = nt * TILE + threadIdx.x + kBlock * s;
                 nxt[s] = (nt < t1 && idx < total) ? aux[idx] : 0;
             }
             if (threadIdx.x == 0 && nt < t1) te_next = tile_edge[nt];
@@ -420,7 +422,7 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc,
         }
 #pragma unroll
         for (int s = 0; s < S; s++)
-            if (win[s]) aux[tile * kTile + threadIdx.x + kBlock * s] = enc_win(before[s] + rk[s]);
+            if (win[s]) aux[tile * TILE + threadIdx.x + kBlock * s] = enc_win(before[s] + rk[s]);
         if (threadIdx.x == 0) {
             tile_node[tile] = run;
             tile_pre[tile] = make_int2(run_e, run_n);      // in front of this tile inside its chunk
@@ -488,9 +490,10 @@ struct WriteArgs {
 // per store in a kernel that waits for memory (+0.3-0.6 us per launch: profiles/r05_sampler.md, r05_ab_bounded_stores.log).
 #define LEGION_STORE_OK(i, cap) ((uint32_t)(i) < (uint32_t)(cap))
 
+template <int TILE>
 __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
 {
-    constexpr int S = kTile / kBlock, W = kBlock / 64;
+    constexpr int S = TILE / kBlock, W = kBlock / 64;
     // (edges, new nodes) counted in front of a tile = exclusive prefix over the chunk totals of k_mark, built once per workgroup in
     // LDS (<= kMaxChunks entries: one coalesced round of loads), + tile_pre[t] (one 8-byte read, issued next to the other loads of
     // the tile or of the losing edge that needs it).  No scan launch, no inter-workgroup hand-off (device-scope fences cost an L2
@@ -499,10 +502,30 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
     __shared__ int32_t s_e[S * W];
     __shared__ int2 s_scan[W];
     __shared__ uint32_t s_div_t[3];
+    constexpr int PER = kMaxChunks / kBlock;                        // consecutive chunks per thread
+    const int32_t q0 = (int32_t)threadIdx.x * PER;
+    // The hop's size (hs->slots) is one round trip away and everything below is addressed through it.  What the workgroup's FIRST tile and
+    // the chunk scan read does not need it: the addresses are inside their allocations whatever the hop's size (chunk_tot has kMaxChunks
+    // entries; blockIdx.x < the tiles the per-tile scratch is sized for; slots are checked against aux_cap), so these loads go out beside
+    // the one of hs and are masked once it is known: two dependent round trips less in front of the stores, -1.1 / -0.7 / -2.0 us at the
+    // headline's hops.  (Hop 1's seed ids fetched here as well, in front of their pos_map probe: +-0 / +0.3 / +0.5 us, not kept --
+    // profiles/narrow_hops.md.)
+    int2 v[PER];
+#pragma unroll
+    for (int u = 0; u < PER; u++) v[u] = a.chunk_tot[q0 + u];
+    int32_t c[S], so[S];
+#pragma unroll
+    for (int s = 0; s < S; s++) {
+        const int64_t idx = (int64_t)blockIdx.x * TILE + threadIdx.x + kBlock * s;
+        c[s] = idx < a.aux_cap ? a.cand[idx] : -1;
+        so[s] = idx < a.aux_cap ? a.aux[idx] : 0;
+    }
+    int2 own = a.tile_pre[blockIdx.x];
+    int32_t tile_e = a.tile_edge[blockIdx.x];
     const HopState h = *a.hs;
     const uint32_t epoch = a.ctl->epoch;
     const int32_t total = h.slots;
-    const int32_t n_tiles = (total + kTile - 1) / kTile;
+    const int32_t n_tiles = (total + TILE - 1) / TILE;
     const int lane = lane_id(), wave = wave_id();
     const unsigned long long lt = (1ull << lane) - 1ull;
     if (n_tiles == 0) { // empty hop: only the counters move
@@ -517,11 +540,6 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
     }
     const int32_t n_chunks = (n_tiles + T - 1) / T;                // <= mark_grid <= kMaxChunks
     {
-        constexpr int PER = kMaxChunks / kBlock;                    // consecutive chunks per thread
-        const int32_t q0 = (int32_t)threadIdx.x * PER;
-        int2 v[PER];
-#pragma unroll
-        for (int u = 0; u < PER; u++) v[u] = a.chunk_tot[min(q0 + u, n_chunks - 1)];   // unconditional: all in flight together
         int32_t se = 0, sn = 0;
 #pragma unroll
         for (int u = 0; u < PER; u++) {
@@ -552,25 +570,28 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
     auto nodes_before = [&](int32_t t, int32_t pre_n_in_chunk) { return s_chunk[fdiv((uint32_t)t, div_t)].y + pre_n_in_chunk; };
 
     for (int32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int2 own = a.tile_pre[tile], own_chunk = s_chunk[fdiv((uint32_t)tile, div_t)];
+        const bool first = tile == (int32_t)blockIdx.x;   // its loads were issued at the top
+        if (!first) { own = a.tile_pre[tile]; tile_e = a.tile_edge[tile]; }
+        const int2 own_chunk = s_chunk[fdiv((uint32_t)tile, div_t)];
         const int32_t pre_e = own_chunk.x + own.x, pre_n = own_chunk.y + own.y;
-        const int32_t tile_e = a.tile_edge[tile];
         const int32_t ebase = h.edge_base + pre_e;
         const int32_t nbase = h.node_base + pre_n;
         // ---- loads first, all S slots of the thread in flight together (nothing below this block reads global memory) ----
-        int32_t c[S], so[S], dpos[S], w[S], re[S], wpre[S];
+        int32_t dpos[S], w[S], re[S], wpre[S];
         const int32_t* __restrict__ pre_n_of = reinterpret_cast<const int32_t*>(a.tile_pre) + 1;   // tile_pre[t].y at [2 * t]
 #pragma unroll
         for (int s = 0; s < S; s++) {
-            const int32_t idx = tile * kTile + threadIdx.x + kBlock * s;
-            c[s] = (idx < total) ? a.cand[idx] : -1;
-            so[s] = (idx < total) ? a.aux[idx] : 0;
+            const int32_t idx = tile * TILE + threadIdx.x + kBlock * s;
+            if (!first) {
+                c[s] = (idx < total) ? a.cand[idx] : -1;
+                so[s] = (idx < total) ? a.aux[idx] : 0;
+            } else if (idx >= total) { c[s] = -1; so[s] = 0; }
         }
 #pragma unroll
         for (int s = 0; s < S; s++) {
             dpos[s] = 0; w[s] = -1;
             if (c[s] == -1) continue;
-            const int32_t idx = tile * kTile + threadIdx.x + kBlock * s;
+            const int32_t idx = tile * TILE + threadIdx.x + kBlock * s;
             // dst-side offset = position of the slot's source node; for hops > 1 the sources are the
             // previous hop's edge endpoints, whose positions are that hop's src-side offsets: same value
             // as position_map[src] (construct_graph, Kernels.cu:457-461) without the random read.
@@ -581,11 +602,11 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
             // lost the claim: first link of loser -> (earlier loser ->)* winner or known node
             // (with the in-chunk node prefix of that slot's tile, should it turn out to be the winner: same round trip)
             wpre[s] = 0;
-            if (so[s] < -1 && !is_win(so[s])) { w[s] = -2 - so[s]; so[s] = a.aux[w[s]]; wpre[s] = pre_n_of[2 * (w[s] / kTile)]; }
+            if (so[s] < -1 && !is_win(so[s])) { w[s] = -2 - so[s]; so[s] = a.aux[w[s]]; wpre[s] = pre_n_of[2 * (w[s] / TILE)]; }
         }
 #pragma unroll
         for (int s = 0; s < S; s++) // longer chains are rare: follow them one slot at a time
-            while (w[s] >= 0 && so[s] < -1 && !is_win(so[s])) { w[s] = -2 - so[s]; so[s] = a.aux[w[s]]; wpre[s] = pre_n_of[2 * (w[s] / kTile)]; }
+            while (w[s] >= 0 && so[s] < -1 && !is_win(so[s])) { w[s] = -2 - so[s]; so[s] = a.aux[w[s]]; wpre[s] = pre_n_of[2 * (w[s] / TILE)]; }
 #pragma unroll
         for (int s = 0; s < S; s++) {
             const unsigned long long be = __ballot(c[s] != -1);
@@ -614,7 +635,7 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
             int32_t p = so[s];
             if (w[s] >= 0) {         // an edge that lost its claim
                 if (p < -1)         // ... to a new node: the winner's position from ITS tile's prefix and its rank
-                    p = h.node_base + nodes_before(w[s] / kTile, wpre[s]) + win_rank(p);
+                    p = h.node_base + nodes_before(w[s] / TILE, wpre[s]) + win_rank(p);
             } else if (is_win(p)) {  // this slot discovered the node: k_mark ranked it inside the tile
                 p = nbase + win_rank(p);
                 if (LEGION_STORE_OK(p, a.ids_cap)) a.sampled_ids[p] = dst;
@@ -1165,15 +1186,17 @@ void launch_advance(hipStream_t s, BatchCtl* ctl)
 }
 void warm_static_tables() { (void)pow_table(); (void)cu_count(); }
 
-void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
+template <int TILE>
+static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
                        int32_t hops, int32_t slots_bound, bool is_presc)
 {
-    if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
-    const int max_tiles = (slots_bound + kTile - 1) / kTile;
+    const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
     // are full: 4 workgroups (16 waves) per CU beat 8 by 2-4 % on hop 3 at every shape and tie on the small hops; 3 lose on hop 2
     // (same-box sweep, profiles/r04_sampler.md).
-    constexpr int wg_per_cu = 4;
+    // The narrow hops are the opposite case, chains of dependent round trips walked by too few waves: one tile per workgroup as far as
+    // the k_mark chunk table allows (8 per CU; running hop 2 of the headline narrow at 4 or 8 per CU lost: profiles/narrow_hops.md).
+    constexpr int wg_per_cu = TILE == kTile ? 4 : 8;
     const int grid = std::min(grid_for(max_tiles, 1, wg_per_cu), kMaxChunks);   // one chunk of tiles per k_mark workgroup (see k_mark)
     if (!b.aux_prepared) { // the previous launch prepared the slot states for another fan-out (or there was none)
         LEGION_AUDIT_LAUNCH(s, "k_fill_aux", LEGION_AW(b.aux), LEGION_AL(b.nc));
@@ -1187,8 +1210,8 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
     a.edge_access_time = b.edge_access_time;
     a.ctl = b.ctl;
     a.pow_tab = pow_table();
-    a.a_tile = powmod31(kA, kTile);
-    a.a_step = powmod31(kA, (uint64_t)kTile * (uint64_t)grid);
+    a.a_tile = powmod31(kA, TILE);
+    a.a_step = powmod31(kA, (uint64_t)TILE * (uint64_t)grid);
     a.fdiv = FastDiv((uint32_t)count);
     a.count = count; a.op_id = op_id;
     a.window = std::min(count - 1, 8);
@@ -1196,12 +1219,12 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
     const bool part = csr.topo_owner != nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices));
-    if (is_presc) k_sample<true, false><<<grid, kBlock, 0, s>>>(a);
-    else if (part) k_sample<false, true><<<grid, kBlock, 0, s>>>(a);
-    else k_sample<false, false><<<grid, kBlock, 0, s>>>(a);
+    if (is_presc) k_sample<TILE, true, false><<<grid, kBlock, 0, s>>>(a);
+    else if (part) k_sample<TILE, false, true><<<grid, kBlock, 0, s>>>(a);
+    else k_sample<TILE, false, false><<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
-    k_mark<<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
+    k_mark<TILE><<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
     HIP_CHECK_LAST();
     WriteArgs w;
     w.hs = b.hop_state; w.nc = b.nc; w.ec = b.ec; w.hops = hops; w.cand = b.cand; w.aux = b.aux; w.ctl = b.ctl; w.tile_edge = b.tile_edge; w.tile_node = b.tile_node;
@@ -1212,8 +1235,17 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
     // 17 KB of static LDS (the chunk prefix): 8 workgroups per CU
     const int wgrid = grid_for(max_tiles, 1, 8);
     LEGION_AUDIT_LAUNCH(s, "k_write", LEGION_AW(w.hs), LEGION_AW(w.nc), LEGION_AW(w.ec), LEGION_AW(w.sampled_ids), LEGION_AW(w.agg_src_ids), LEGION_AW(w.agg_src_off), LEGION_AW(w.agg_dst_off), LEGION_AW(w.pos_map), LEGION_AW(w.aux_next), LEGION_AL(w.cand), LEGION_AL(w.aux), LEGION_AL(w.tile_edge), LEGION_AL(w.tile_node), LEGION_AL(w.tile_pre), LEGION_AL(w.chunk_tot), LEGION_AL(w.ctl));
-    k_write<<<wgrid, kBlock, 0, s>>>(w);
+    k_write<TILE><<<wgrid, kBlock, 0, s>>>(w);
     HIP_CHECK_LAST();
+}
+
+void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
+                       int32_t hops, int32_t slots_bound, bool is_presc)
+{
+    if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
+    // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc);
 }
 
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,

@@ -468,7 +468,7 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
     }
     p->num_ids = (int32_t)ids;
     p->max_slots = (int32_t)max_slots;
-    p->max_tiles = (int32_t)((max_slots + kTile - 1) / kTile);
+    p->max_tiles = (int32_t)sampler_max_tiles(max_slots);   // the narrow hops run smaller tiles (internal.h)
     p->owns_scratch = true;
     HIP_CHECK(hipMalloc(&p->pos_map, (size_t)total_num_nodes * sizeof(pos_t)));
     HIP_CHECK(hipMemset(p->pos_map, 0xFF, (size_t)total_num_nodes * sizeof(pos_t)));
