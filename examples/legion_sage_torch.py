@@ -46,6 +46,32 @@ class SageMean(nn.Module):
         return self.fc_self(h[:num_dst]) + self.fc_neigh(agg) + self.bias
 
 
+class SageMeanFused(SageMean):
+    """First layer behind a server that hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1, ipc_service.get_next_aggregated;
+    INTEGRATION.md "Aggregated last hop").  h = x_in[n_in, F]: only the nodes found before the last hop have feature rows.  The edges of
+    the hops < H (the first e_in of block 1: all their sources < n_in) are aggregated as SageMean does; the last hop arrives as one row
+    of sums per input slot, S[N, F], to be added into node run_dst[i].  Same parameters as SageMean, same result up to fp32 summation order."""
+
+    def forward(self, block, h):
+        src, dst, num_src, num_dst, e_in, run_dst, nbr_sum = block
+        assert h.shape[0] == num_dst
+        agg = torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, dst[:e_in], h.index_select(0, src[:e_in]))
+        agg += torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, run_dst, nbr_sum)
+        deg = torch.zeros(num_dst, dtype=h.dtype, device=h.device).index_add_(0, dst, torch.ones_like(dst, dtype=h.dtype))
+        agg = agg / deg.clamp(min=1).unsqueeze(1)
+        return self.fc_self(h) + self.fc_neigh(agg) + self.bias
+
+
+def fused_first_block(src, dst, num_src, num_dst, edges_per_block, nbr_sum):
+    """Block 1 of an aggregated batch for SageMeanFused.  edges_per_block[k] = edges of block k + 1 (hops 1..H-k): block 2 holds the edges
+    of the hops < H, and the destination node of input slot i of the last hop is the source of hop-(H-1) edge i (slot i itself at H = 1)."""
+    H = len(edges_per_block)
+    e_in = edges_per_block[1] if H >= 2 else 0
+    e_prev = edges_per_block[2] if H >= 3 else 0
+    run_dst = src[e_prev:e_in] if H >= 2 else torch.arange(nbr_sum.shape[0], device=src.device)
+    return (src, dst, num_src, num_dst, e_in, run_dst, nbr_sum)
+
+
 class GraphConvBoth(nn.Module):
     """DGL GraphConv(norm='both', allow_zero_in_degree=True) as legion_gcn.py:80-87 uses it:
     h_dst = sum_{(s,d)} h_s / sqrt(outdeg_s * indeg_d) W + b, degrees counted inside the block and clamped to >= 1."""
@@ -65,10 +91,10 @@ class GraphConvBoth(nn.Module):
 
 
 class SAGE(nn.Module):
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, conv=SageMean):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, conv=SageMean, first=None):
         super().__init__()
         dims = [in_feats] + [n_hidden] * (n_layers - 1) + [n_classes]
-        self.layers = nn.ModuleList(conv(dims[i], dims[i + 1]) for i in range(n_layers))
+        self.layers = nn.ModuleList((first if first is not None and i == 0 else conv)(dims[i], dims[i + 1]) for i in range(n_layers))
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, blocks, x):
@@ -80,11 +106,13 @@ class SAGE(nn.Module):
         return h
 
 
-def next_batch(ipc_service, feat_len, hops):
-    out = ipc_service.get_next(feat_len)            # zero-copy views of server-owned device memory
+def next_batch(ipc_service, feat_len, hops, aggregated=False):
+    out = (ipc_service.get_next_aggregated if aggregated else ipc_service.get_next)(feat_len)   # zero-copy views of server-owned device memory
     sizes = ipc_service.get_block_size()
     features, labels = out[1], out[2]
     blocks = [(out[3 + 2 * k].long(), out[4 + 2 * k].long(), sizes[2 * k], sizes[2 * k + 1]) for k in range(hops)]
+    if aggregated:                                  # features = x_in[n_in, F]; out[-1] = the last hop's neighbour sums per input slot
+        blocks[0] = fused_first_block(*blocks[0], [len(b[0]) for b in blocks], out[3 + 2 * hops])
     return features, labels.long(), blocks
 
 
@@ -101,8 +129,11 @@ def worker(rank, world, args):
     ipc_service.initialize()
     train_steps, valid_steps, test_steps = ipc_service.get_steps()
     hops = ipc_service.get_hops() if hasattr(ipc_service, "get_hops") else 2
+    served_agg = bool(ipc_service.aggregated()) if hasattr(ipc_service, "aggregated") else False
+    if served_agg != bool(args.aggregated):
+        raise SystemExit("--aggregated must match the server: it %s the last hop (LEGION_AGG_LAST_HOP)" % ("aggregates" if served_agg else "does not aggregate"))
     model = SAGE(args.features_num, args.hidden_dim, args.class_num, hops, args.drop_rate,
-                 conv=GraphConvBoth if args.model == "gcn" else SageMean).to(device)
+                 conv=GraphConvBoth if args.model == "gcn" else SageMean, first=SageMeanFused if served_agg else None).to(device)
     if world > 1:
         model = DDP(model, device_ids=[rank])
     opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
@@ -113,7 +144,7 @@ def worker(rank, world, args):
         model.eval()
         with torch.no_grad():
             for _ in range(steps):
-                x, y, blocks = next_batch(ipc_service, args.features_num, hops)
+                x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg)
                 ok = y >= 0                                  # -1 padded seeds of a short batch
                 pred = model(blocks, x).argmax(1)
                 hit += int((pred[ok] == y[ok]).sum())
@@ -128,7 +159,7 @@ def worker(rank, world, args):
 
     def drain(steps):
         for _ in range(steps):
-            ipc_service.get_next(args.features_num)
+            (ipc_service.get_next_aggregated if served_agg else ipc_service.get_next)(args.features_num)
             ipc_service.synchronize()
         return float("nan")
 
@@ -142,7 +173,7 @@ def worker(rank, world, args):
         model.train()
         t0, last = time.time(), float("nan")
         for _ in range(train_steps):
-            x, y, blocks = next_batch(ipc_service, args.features_num, hops)
+            x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg)
             loss = lp_loss(model(blocks, x)) if args.task == "lp" else loss_fn(model(blocks, x), y)
             opt.zero_grad()
             loss.backward()
@@ -174,7 +205,10 @@ if __name__ == "__main__":
     ap.add_argument("--epoch", type=int, default=100, help="must equal the epoch count in the server's meta_config")
     ap.add_argument("--gpu_num", type=int, default=1)
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed (weights, dropout)")
+    ap.add_argument("--aggregated", action="store_true", help="the server runs with LEGION_AGG_LAST_HOP=1: first layer = SageMeanFused over get_next_aggregated")
     a = ap.parse_args()
+    if a.aggregated and a.model == "gcn":
+        ap.error("--aggregated serves sum / mean aggregators; GraphConvBoth weights each source row by its out-degree and needs the rows themselves")
     if a.gpu_num == 1:
         worker(0, 1, a)
     else:

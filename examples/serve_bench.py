@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Throughput of the `legion` server process as a trainer sees it: a null consumer (wait -> read counters -> post)
+"""Throughput of the `legion` server process as a trainer sees it: a null consumer (wait -> read counters -> post), or with
+--consumer aggregate a PyTorch consumer that computes the first layer's mean aggregate in both hand-off modes (rows / neighbour sums),
 drains every batch of the schedule through the C-ABI IPC client, for the two RunOnce variants of the runner:
 
     (default)                  enqueue batch i, then wait for batch i-1 and post it (sampler i || gathers i-1)
@@ -41,6 +42,44 @@ def consume(epochs, hops):
     print(total, dt, edges)
 
 
+def consume_aggregating(epochs, feat_dim):
+    """A consumer that computes what the first GNN layer of a mean aggregator computes from a served batch -- the mean aggregate [n_in, F] --
+    in whichever mode the server hands over: by index_select / index_add_ over every edge of block 1 (default), or from the rows of the
+    hops < H plus the last hop's neighbour sums (LEGION_AGG_LAST_HOP=1).  Both modes are timed producing the same tensor."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "legion-1_amd", "ipc_service"))
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    import ipc_service
+    from legion_sage_torch import fused_first_block
+    torch.cuda.set_device(0)
+    ipc_service.initialize()
+    steps = ipc_service.get_steps()
+    hops, agg_mode = ipc_service.get_hops(), ipc_service.aggregated()
+    total = (steps[0] + steps[1]) * epochs + steps[2]
+    edges, check = 0, 0.0
+    t0 = time.perf_counter()
+    for _ in range(total):
+        out = (ipc_service.get_next_aggregated if agg_mode else ipc_service.get_next)(feat_dim)
+        sizes = ipc_service.get_block_size()
+        x, src, dst, n_in = out[1], out[3].long(), out[4].long(), sizes[1]
+        if agg_mode:
+            _, _, _, _, e_in, run_dst, nbr_sum = fused_first_block(src, dst, sizes[0], n_in, [out[3 + 2 * k].numel() for k in range(hops)], out[3 + 2 * hops])
+            agg = torch.zeros(n_in, feat_dim, device=x.device).index_add_(0, dst[:e_in], x.index_select(0, src[:e_in]))
+            agg += torch.zeros(n_in, feat_dim, device=x.device).index_add_(0, run_dst.long(), nbr_sum)
+        else:
+            agg = torch.zeros(n_in, feat_dim, device=x.device).index_add_(0, dst, x.index_select(0, src))
+        deg = torch.bincount(dst, minlength=n_in).clamp(min=1).unsqueeze(1)
+        agg = agg / deg
+        edges += int(src.numel())
+        torch.cuda.synchronize()
+        ipc_service.synchronize()
+    dt = time.perf_counter() - t0
+    check = float(agg.double().sum())            # the last batch's aggregate: the two modes agree to fp32 summation order
+    ipc_service.finalize()
+    print("last-batch aggregate sum %.6f (%s)" % (check, "aggregated" if agg_mode else "default"))
+    print(total, dt, edges)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--consume", type=int, default=0, help="internal: run the null consumer for this many epochs")
@@ -50,13 +89,17 @@ def main():
     ap.add_argument("--fanout", default="25,10")
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--variants", default="all", help="comma list of: pipelined,graph + gather")
+    ap.add_argument("--consumer", default="null", choices=["null", "aggregate"],
+                    help="null: wait -> read counters -> post.  aggregate: a PyTorch consumer that computes the first layer's mean aggregate [n_in, F] "
+                         "of every batch; each variant is then served twice, default hand-off and LEGION_AGG_LAST_HOP=1")
+    ap.add_argument("--features", type=int, default=0, help="internal: feature width for --consume with --consumer aggregate")
     ap.add_argument("--full-eval", action="store_true", help="keep the full validation / test sets (512-seed batches)")
     ap.add_argument("--source", default="files", choices=["files", "synth"],
                     help="files: write the dataset in Legion's raw layout and let the server read it (GPUGraphStore.cu:254-325).  synth: the server generates "
                          "the same tables in its own HBM (meta_config dataset path `synth:<workload>:<scale>`) -- the only way to serve the papers100M / uk-union shapes")
     a = ap.parse_args()
     if a.consume:
-        return consume(a.consume, len(a.fanout.split(",")))
+        return consume_aggregating(a.consume, a.features) if a.consumer == "aggregate" else consume(a.consume, len(a.fanout.split(",")))
     import legion1_amd.synth as S
     if a.source == "synth":
         spec = S.spec_for(a.workload, scale=a.scale)
@@ -66,7 +109,7 @@ def main():
         with open(meta, "w") as f:
             f.write("synth:%s:%r %d %d 0 %d %d %d %d 0 %d 0" % (a.workload, a.scale, a.batch, spec.V, spec.F, spec.n_train,
                                                              n_eval or spec.n_valid, n_eval or spec.n_test, a.epochs))
-        return serve_variants(a, tmp, meta)
+        return serve_variants(a, tmp, meta, spec.F)
     ds = S.generate(S.spec_for(a.workload, scale=a.scale))
     if not a.full_eval:   # keep the schedule dominated by full training batches: one validation / test batch each
         import dataclasses
@@ -78,16 +121,18 @@ def main():
     meta = os.path.join(tmp, "meta_config")
     with open(meta, "w") as f:
         f.write(S.meta_config_line(ds, data, a.batch, 1 << 40, a.epochs, 0))
-    return serve_variants(a, tmp, meta)
+    return serve_variants(a, tmp, meta, ds.spec.F)
 
 
-def serve_variants(a, tmp, meta):
+def serve_variants(a, tmp, meta, F):
     server = os.path.join(ROOT, "legion-1_amd", "csrc", "legion")
     variants = [("pipelined", {}), ("graph + gather", {"LEGION_BATCH_GRAPH": "1"}), ("pipelined", {}), ("graph + gather", {"LEGION_BATCH_GRAPH": "1"})]
     if a.variants != "all":
         variants = [v for v in variants[:2] if v[0] in a.variants.split(",")]
+    if a.consumer == "aggregate":    # every variant in both hand-off modes, alternating
+        variants = [(n + m, dict(e, **x)) for n, e in variants for m, x in ((", rows", {}), (", neighbour sums", {"LEGION_AGG_LAST_HOP": "1"}))]
     for name, extra in variants:
-        ns = "sb%d_%s%s_" % (os.getpid(), name[:3], extra.get("LEGION_BATCH_GRAPH", ""))
+        ns = "sb%d_%s%s%s_" % (os.getpid(), name[:3], extra.get("LEGION_BATCH_GRAPH", ""), extra.get("LEGION_AGG_LAST_HOP", ""))
         env = dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra)
         log = open(os.path.join(tmp, "server_%s.log" % name[:3]), "w")
         proc = subprocess.Popen([server, "1", "0", a.fanout, meta], stdout=log, stderr=subprocess.STDOUT, env=env, cwd=tmp)
@@ -95,14 +140,16 @@ def serve_variants(a, tmp, meta):
             if proc.poll() is not None:
                 raise SystemExit("server died:\n" + open(log.name).read()[-2000:])
             time.sleep(0.2)
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--consume", str(a.epochs), "--fanout", a.fanout],
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--consume", str(a.epochs), "--fanout", a.fanout, "--consumer", a.consumer, "--features", str(F)],
                              env=env, capture_output=True, text=True, timeout=600)   # one consumer process per server
         if out.returncode != 0:
             raise SystemExit(out.stdout[-2000:] + out.stderr[-2000:])
         total, dt, edges = out.stdout.strip().splitlines()[-1].split()
         total, dt, edges = int(total), float(dt), int(edges)
         proc.wait(timeout=60)
-        print("%-15s %5d batches  %.3f ms/batch  %.2f G edges/s" % (name, total, dt / total * 1e3, edges / dt / 1e9), flush=True)
+        if a.consumer == "aggregate":
+            print("    " + out.stdout.strip().splitlines()[-2], flush=True)
+        print("%-32s %5d batches  %.3f ms/batch  %.2f G edges/s" % (name, total, dt / total * 1e3, edges / dt / 1e9), flush=True)
 
 
 if __name__ == "__main__":

@@ -364,6 +364,22 @@ void update_cache(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMem
  * get_feature_kernel for op 1,3,..,2H+1; used when the per-level overlap is not wanted. */
 void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                             int32_t dev_id, int in_memory);
+/* Aggregated last hop (extension; INTEGRATION.md has the contract).  A GraphSAGE trainer uses the rows found in the LAST hop for one
+ * thing: summing them into their hop-(H-1) neighbours.  With GPUMemoryPool_SetAggLastHop(pool, 1) the last hop keeps its draws in a
+ * buffer of the batch's pipe, and get_feature_kernel_agg -- called behind the last hop's GPU_Random_Sampling instead of the last
+ * level's get_feature_kernel -- hands over, in the pipe's feature buffer:
+ *   rows [0, n_in)        the feature rows of the levels < H, n_in = nc[3 + 2H] (gathered here unless get_feature_kernel gathered
+ *                         every one of these levels for this batch)
+ *   rows [n_in, n_in + N) S[i, :] = ((0.0f + x[c(i, j0)]) + x[c(i, j1)]) + ... : the fp32 sum, in ascending slot order, of the rows
+ *                         input slot i of the last hop drew (N = nc[4] at H = 1, ec[3] at H = 2, ec[1 + H] - ec[H] above; slot i is
+ *                         seed i at H = 1, else edge i of hop H - 1); a slot without draws gets a stored row of +0.0f.
+ * nc, ec, ids, labels and both COO arrays are those of the default mode.  Sticky argument errors: mode off, called before the last
+ * hop, a pre-sampling batch, rows * F >= 2^31, $LEGION_PEER_GATHER=exchange (the exchange moves rows, not sums).
+ * SetAggLastHop allocates the per-pipe draw buffers (4 bytes per slot of the largest hop and pipe) on the current device. */
+void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on);
+int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p);
+void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
+                            int32_t dev_id, int in_memory);
 /* Owner-computes exchange variant of the feature gather (SURVEY 5 option b; the reference reads peer caches in-kernel over
  * NVLink, Kernels.cu:662-702 -- this is the collective formulation for one process per GPU, the all-to-all itself is RCCL /
  * hipMemcpyPeer in the caller: legion-1_amd/exchange.py).  plan (requester): rows of the batch cached on another clique member are
@@ -435,12 +451,17 @@ int32_t* IPCEnv_GetEdgeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
  * IPCEnv_SetMirror fills the mirror from the host (poisoned pipe). */
 void IPCEnv_MirrorCounters(IPCEnv* e, int32_t dev_id, int32_t current_pipe, void* stream);
 void IPCEnv_SetMirror(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t nc_fill, int32_t ec_fill);
-/* nc[word] of the batch about to be posted, from the mirror IPCEnv_MirrorCounters queued (wait for that copy first); -1: not queued.
+/* nc[word] (word < 16) or ec[word - 16] (16 <= word < 32) of the batch about to be posted, from the mirror IPCEnv_MirrorCounters queued (wait for that copy first); -1: not queued.
  * The runner compares nc[5 + 2H] with the rows of its feature buffer: a batch that reached more nodes had rows dropped by the bounded
  * gather (kernels.hip k_gather: "never write past the buffer") and its trainer will refuse it -- the server says so, once, and counts. */
 int32_t IPCEnv_MirroredNodeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t word);
 /* the row capacity of a device's feature buffers as published to its trainer (set by IPCEnv_InitializeFeaturesBuffer) */
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows);
+/* The hand-off mode the server publishes to its trainers (a word appended behind the older fields of the "<name>_ext" object): 1 = the
+ * last hop is handed over as neighbour sums (get_feature_kernel_agg; the runner sets it under LEGION_AGG_LAST_HOP=1).  A client of a
+ * server without the word reads 0. */
+void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on);
+int32_t IPCEnv_GetAggLastHop(const IPCEnv* e);
 int IPCEnv_SlabPinned(IPCEnv* e);   /* 1: the slab is page-locked (hipHostRegister), IPCEnv_MirrorCounters queues real asynchronous copies */
 void IPCEnv_IPCPost(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
 void IPCEnv_IPCWait(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
@@ -478,6 +499,7 @@ int32_t legion_ipc_client_hops(LegionIPCClient* c);
  * exceeds it must not be viewed as [n, F]: the reference sizes the buffer from the pre-sampling epoch's training batches (Server.cu:275)
  * and views it unchecked (ipc_cuda_kernel.cu:200). */
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c);
+int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c);
 /* both 16-int counters of the current pipe (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
  * a blocking device copy like the reference */
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16]);

@@ -195,6 +195,9 @@ _SIGS = {
     "GPU_Random_Sampling": (None, [vp, vp, vp, vp, i32, i32, C.c_int]),
     "get_feature_kernel": (None, [vp, vp, vp, vp, i32, i32, C.c_int]),
     "get_feature_kernel_all": (None, [vp, vp, vp, vp, i32, C.c_int]),
+    "get_feature_kernel_agg": (None, [vp, vp, vp, vp, i32, C.c_int]),
+    "GPUMemoryPool_SetAggLastHop": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetAggLastHop": (C.c_int, [vp]),
     "legion_exchange_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "legion_exchange_local": (C.c_int, [vp, vp, vp, vp, i32]),
     "legion_exchange_serve": (None, [vp, vp, i32, vp, i32, vp]),
@@ -231,6 +234,7 @@ _SIGS = {
     "legion_ipc_unlink_namespace": (None, [C.c_char_p, i32]),
     "IPCEnv_MirroredNodeCounter": (i32, [vp, i32, i32, i32]),
     "IPCEnv_SetFeatureRows": (None, [vp, i32, i32]),
+    "IPCEnv_SetAggLastHop": (None, [vp, i32]), "IPCEnv_GetAggLastHop": (i32, [vp]), "legion_ipc_client_agg_last_hop": (i32, [vp]),
     "legion_ipc_client_open": (vp, [i32]), "legion_ipc_client_wait": (None, [vp]),
     "legion_ipc_client_post": (None, [vp]), "legion_ipc_client_post_nosync": (None, [vp]), "legion_ipc_client_buffer": (vp, [vp, i32]),
     "legion_ipc_client_steps": (None, [vp, vp]), "legion_ipc_client_hops": (i32, [vp]), "legion_ipc_client_feature_rows": (i32, [vp]),
@@ -443,6 +447,7 @@ class Engine:
             self.out[g] = pipes
         self.streams = [None] * self.G
         self._graphs = []
+        self._agg = {}      # (dev, pipe) -> the pipe's last batch was handed over aggregated (run_batch(agg_last_hop=True))
         check()
 
     # ---- feature buffers ------------------------------------------------------------------------------
@@ -460,10 +465,17 @@ class Engine:
 
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
-                  batch_size=None, per_level=True, stream=None, sync=True):
+                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False):
+        """agg_last_hop: the aggregated hand-off (get_feature_kernel_agg) -- feature rows of the levels < H (per level behind each hop,
+        or all of them inside that call with per_level=False) and the last hop as neighbour sums; result() then returns
+        `features` [n_in, F] and `nbr_sum` [N, F]."""
         L = self.L
         L.SetGPUDevice(dev)
         pool = self.pools[dev]
+        agg = bool(agg_last_hop) and not is_presc     # gather=False: the sampler side of such a batch (the last hop's draws kept per pipe)
+        if bool(L.GPUMemoryPool_GetAggLastHop(pool)) != agg:
+            L.GPUMemoryPool_SetAggLastHop(pool, int(agg))
+        self._agg[(dev, pipe)] = agg and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
         L.GPUMemoryPool_SetCurrentMode(pool, mode)
         L.GPUMemoryPool_SetIter(pool, counter)
@@ -473,9 +485,11 @@ class Engine:
             L.get_feature_kernel(stream, self.cache, self.noder, pool, dev, 1, 1)
         for h in range(self.hops):
             L.GPU_Random_Sampling(stream, self.graph, self.cache, pool, int(self.fanout[h]), 2 * h + 2, int(is_presc))
-            if gather and not is_presc and per_level:
+            if gather and not is_presc and per_level and not (agg and h == self.hops - 1):
                 L.get_feature_kernel(stream, self.cache, self.noder, pool, dev, 2 * h + 3, 1)
-        if gather and not is_presc and not per_level:
+        if agg and gather:
+            L.get_feature_kernel_agg(stream, self.cache, self.noder, pool, dev, 1)
+        elif gather and not is_presc and not per_level:
             L.get_feature_kernel_all(stream, self.cache, self.noder, pool, dev, 1)
         if plan:
             L.make_update_plan(stream, self.graph, self.cache, pool, dev, mode)
@@ -486,10 +500,11 @@ class Engine:
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None):
+                      stream=None, agg_last_hop=False):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph()."""
         L = self.L
         L.SetGPUDevice(dev)
+        L.GPUMemoryPool_SetAggLastHop(self.pools[dev], int(bool(agg_last_hop)))   # allocates: not between Begin and End
         if stream is None:
             if self.streams[dev] is None:
                 self.streams[dev] = L.d_stream_create()
@@ -498,7 +513,7 @@ class Engine:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
-                       stream=stream, sync=False)
+                       stream=stream, sync=False, agg_last_hop=agg_last_hop)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -516,7 +531,11 @@ class Engine:
             self.L.d_stream_sync(stream)
             check()
 
-    def result(self, dev=0, pipe=0, with_features=True):
+    def result(self, dev=0, pipe=0, with_features=True, aggregated=None):
+        """aggregated: how to read the pipe's feature buffer -- None: as run_batch / capture_batch on this engine left it; True / False
+        for a caller that drove the launchers itself."""
+        if aggregated is None:
+            aggregated = self._agg.get((dev, pipe), False)
         o = self.out[dev][pipe]
         self.L.SetGPUDevice(dev)
         nc = o["nc"].to_numpy(np.int32, 16)
@@ -525,7 +544,16 @@ class Engine:
         n_nodes, n_edges = int(nc[5 + 2 * H]), int(ec[2 + H])
         res = dict(nc=nc, ec=ec, ids=o["ids"].to_numpy(np.int32, n_nodes), labels=o["labels"].to_numpy(np.int32, int(nc[4])),
                    src_off=o["src"].to_numpy(np.int32, n_edges), dst_off=o["dst"].to_numpy(np.int32, n_edges))
-        if with_features and o["feat"] is not None:
+        if with_features and o["feat"] is not None and aggregated:
+            # aggregated hand-off: rows [0, n_in) are features, rows [n_in, n_in + N) the last hop's neighbour sums per input slot
+            n_in = int(nc[3 + 2 * H])
+            runs = int(nc[4]) if H == 1 else int(ec[3]) if H == 2 else int(ec[1 + H] - ec[H])
+            cap = getattr(self, "feature_rows", n_in + runs)
+            r_in = min(n_in, cap)
+            r_sum = max(0, min(n_in + runs, cap) - n_in)
+            buf = o["feat"].to_numpy(np.float32, (r_in + r_sum) * self.F).reshape(r_in + r_sum, self.F)
+            res["features"], res["nbr_sum"] = buf[:r_in], buf[r_in:]
+        elif with_features and o["feat"] is not None:
             rows = min(n_nodes, getattr(self, "feature_rows", n_nodes))
             res["features"] = o["feat"].to_numpy(np.float32, rows * self.F).reshape(rows, self.F)
         return res

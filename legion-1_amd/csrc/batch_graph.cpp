@@ -18,6 +18,10 @@ struct LegionBatchGraph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     GPUMemoryPool* pool = nullptr;
+    // what the recording left in the pool's per-batch host state (launchers called behind a replay decide from it, like behind the plain calls)
+    int32_t sampled_hop = 0;
+    bool sampled_presc = false;
+    uint32_t levels_gathered = 0;
 };
 
 extern "C" {
@@ -41,6 +45,7 @@ LegionBatchGraph* GPUMemoryPool_EndBatchCapture(GPUMemoryPool* p, void* stream)
     p->capturing = false;
     LegionBatchGraph* g = new LegionBatchGraph();
     g->pool = p;
+    g->sampled_hop = p->sampled_hop; g->sampled_presc = p->sampled_presc; g->levels_gathered = p->levels_gathered;
     HIP_CHECK(hipStreamEndCapture((hipStream_t)stream, &g->graph));
     if (g->graph) HIP_CHECK(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
     if (!g->exec || error_pending()) {
@@ -65,6 +70,8 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     }
     if (!p->ctl_synced || p->ctl_counter != counter) launch_set_cursor(s, p->ctl, counter, kEpochTop - p->batch_serial);
     HIP_CHECK(hipGraphLaunch(g->exec, s));
+    // the batch now in flight is the recorded one: what the launchers behind it (get_feature_kernel_agg) decide from
+    p->sampled_hop = g->sampled_hop; p->sampled_presc = g->sampled_presc; p->levels_gathered = g->levels_gathered;
     p->ctl_synced = true;     // k_advance left (counter + 1, next epoch) in ctl
     p->ctl_counter = counter + 1;
     return error_pending() ? -1 : 0;

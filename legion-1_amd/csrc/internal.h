@@ -235,6 +235,15 @@ struct GatherArgs {
     bool row_ptr_ready;                       // row_ptr was filled by the caller (exchange plan): skip the lookup pass
 };
 void launch_gather(hipStream_t s, const GatherArgs& a, int32_t rows_bound);
+// Aggregated last hop (kernels.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
+// slots, from the draws in cand[slot * f + j], into rows [nc[3 + 2 * hops], + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
+void launch_gather_sum(hipStream_t s, const GatherArgs& a, const int32_t* cand, int32_t cand_cap, const int32_t* ec, int32_t hops,
+                       int32_t f, int32_t runs_bound);
+// words of GPUMemoryPool::rows_seen: [l] = level-l gather, then one per launch kind below
+constexpr int kRowsSeenAll = LEGION_MAX_HOPS + 1;      // all rows of the batch (get_feature_kernel_all)
+constexpr int kRowsSeenAggIn = LEGION_MAX_HOPS + 2;    // rows of the levels < H (get_feature_kernel_agg)
+constexpr int kRowsSeenAggRuns = LEGION_MAX_HOPS + 3;  // input slots of the last hop (get_feature_kernel_agg)
+constexpr int kRowsSeenWords = LEGION_MAX_HOPS + 4;
 // owner-computes exchange variant of the gather (kernels.hip "S5, owner-computes"): counts = int32[2 * kMaxParts] scratch
 void launch_exchange_plan(hipStream_t s, const GatherArgs& g, int32_t me, int32_t Kg, int32_t* slot, int32_t* counts,
                           int32_t* req_row, int32_t* req_dst, int32_t rows_bound);
@@ -293,6 +302,14 @@ struct GPUMemoryPool {
     bool ctl_synced = false;          // ctl holds (ctl_counter, epoch of the NEXT batch): a batch graph can run as is
     int32_t ctl_counter = 0;
     int32_t* cand = nullptr;
+    // Aggregated last hop (GPUMemoryPool_SetAggLastHop): the last hop parks its draws in the PIPE's buffer, because k_gather_sum reads
+    // them on the gather stream while hop 1 of the next batch already overwrites `cand` on the sampler stream.  Allocated when the
+    // mode is switched on (max_slots words per pipe); the other hops and the default mode keep the one shared buffer.
+    bool agg_last_hop = false;
+    std::vector<int32_t*> cand_pipe;
+    int32_t sampled_hop = 0;          // hops of the current batch that GPU_Random_Sampling has queued (0 behind batch_generator_kernel)
+    bool sampled_presc = false;       // ... as pre-sampling hops
+    uint32_t levels_gathered = 0;     // bit l: get_feature_kernel gathered level l of the current batch
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
     int32_t aux_ready_hop = 0, aux_ready_count = 0; // the launch before prepared aux2[hop & 1] for this fan-out
     int32_t* tile_edge = nullptr;

@@ -61,6 +61,10 @@ struct shmExt {
     // match the slab it attached to (it then behaves as against a reference server).
     int32_t steps_copy[3];
     uint32_t handle_sum[LEGION_MAX_DEVICE];   // FNV-1a of memHandle[dev][0][0]; 0 = nothing registered for that device yet
+    // Appended behind everything older peers know (the fields above do not move; the object stays inside its one page, so a client of an older
+    // server reads 0 here and an older client never looks): 1 = the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1,
+    // INTEGRATION.md "Aggregated last hop"): feature rows [0, n_in) are features, rows [n_in, n_in + N) the sums.
+    int32_t agg_last_hop;
 };
 static const uint32_t kMirrorMagic = 0x4C474E43u;   // "LGNC"
 static uint32_t handle_checksum(const volatile void* h)
@@ -511,15 +515,17 @@ void IPCEnv_InitializeFeaturesBuffer(IPCEnv* e, int32_t batch_size, int32_t num_
     e->ext->feature_rows[device_id] = num_ids;
 }
 // the row capacity published to the trainers of a device (a server that re-sizes its feature buffers; tests)
+void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on) { if (e && e->ext) e->ext->agg_last_hop = on ? 1 : 0; }
+int32_t IPCEnv_GetAggLastHop(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_last_hop : 0; }
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
     if (e && e->ext && device_id >= 0 && device_id < e->device_count) e->ext->feature_rows[device_id] = rows;
 }
-// nc[word] of the batch about to be posted on (dev, pipe), from the host mirror IPCEnv_MirrorCounters queued (the caller has waited for
+// nc[word] (word < 16) or ec[word - 16] of the batch about to be posted on (dev, pipe), from the host mirror IPCEnv_MirrorCounters queued (the caller has waited for
 // that copy); -1 when the mirror of this batch was not queued
 int32_t IPCEnv_MirroredNodeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t word)
 {
-    if (!e || !e->ext || dev_id < 0 || dev_id >= e->device_count || word < 0 || word >= 16) return -1;
+    if (!e || !e->ext || dev_id < 0 || dev_id >= e->device_count || word < 0 || word >= 32) return -1;
     const int q = current_pipe % e->pipeline_depth;
     if (!e->mirror_fresh[dev_id][q]) return -1;
     if (!e->shm_pinned) return e->mirror_stage[dev_id][q] ? e->mirror_stage[dev_id][q][word] : -1;
@@ -875,6 +881,7 @@ void legion_ipc_client_steps(LegionIPCClient* c, int32_t steps[3])
     for (int i = 0; i < 3; i++) steps[i] = c->steps[i];
 }
 int32_t legion_ipc_client_hops(LegionIPCClient* c) { return c->hops; }
+int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_last_hop : 0; }
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16])
 {

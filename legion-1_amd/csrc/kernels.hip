@@ -695,6 +695,21 @@ struct GatherKArgs {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
+// Source selection of one feature row (GPUCache.cu:387-400, Kernels.cu:672-691): cache slot gidx (FindFeat's answer, < 0 = miss) ->
+// (clique GPU, chunk, row) of the shard tables, else row id % V of the backing table, else no source.  Pitches in floats.
+// The one copy k_row_ptrs, k_gather_lookup and k_gather_sum share.
+__device__ inline const float* row_source(const GatherArgs& g, const FastDiv& div_cap, int32_t id, int32_t gidx, int64_t tpitch, int64_t spitch)
+{
+    if (gidx >= 0) {
+        const uint32_t didx = fdiv((uint32_t)gidx, div_cap);
+        const uint32_t fidx = (uint32_t)gidx - didx * (uint32_t)g.cache_capacity;
+        const float* chunk = g.shard_tab[didx * (uint32_t)g.nchunks + (fidx >> g.chunk_shift)];
+        return chunk + (int64_t)(fidx & ((1u << g.chunk_shift) - 1u)) * spitch;
+    }
+    if (id >= 0 && g.table) return g.table + (int64_t)(id % g.total_num_nodes) * tpitch;
+    return nullptr;
+}
+
 // FindFeat + source selection for the rows of one gather launch (GPUCache.cu:387-400, Kernels.cu:672-691): one thread
 // per ROW resolves id -> cache slot -> (clique GPU, chunk, row) -> address, or the backing-table row on a miss.  The
 // gather then starts every row with one coalesced 8-byte load; done inside the gather, the map probe and the
@@ -719,16 +734,7 @@ __global__ __launch_bounds__(kBlock) void k_row_ptrs(GatherKArgs a)
         for (int u = 0; u < U; u++) {
             const int32_t r = r0 + u * stride;
             if (r >= rows) continue;
-            const float* src = nullptr;
-            if (gidx[u] >= 0) {
-                const uint32_t didx = fdiv((uint32_t)gidx[u], a.div_cap);
-                const uint32_t fidx = (uint32_t)gidx[u] - didx * (uint32_t)g.cache_capacity;
-                const float* chunk = g.shard_tab[didx * (uint32_t)g.nchunks + (fidx >> g.chunk_shift)];
-                src = chunk + (int64_t)(fidx & ((1u << g.chunk_shift) - 1u)) * (g.shard_pitch > 0 ? g.shard_pitch : g.F);
-            } else if (id[u] >= 0 && g.table) {
-                src = g.table + (int64_t)(id[u] % g.total_num_nodes) * (g.table_pitch > 0 ? g.table_pitch : g.F);
-            }
-            g.row_ptr[r] = src;
+            g.row_ptr[r] = row_source(g, a.div_cap, id[u], gidx[u], g.table_pitch > 0 ? g.table_pitch : g.F, g.shard_pitch > 0 ? g.shard_pitch : g.F);
         }
         if (g.hit_stats) { // feature_cache_hit (GPUCache.cu:130-147): one atomic per wave and step
             int32_t h = 0;
@@ -831,17 +837,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_lookup(GatherKArgs a)
         const VT* src[U];
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            const float* p = nullptr;
-            if (lead[u]) {
-                if (gidx[u] >= 0) {
-                    const uint32_t didx = fdiv((uint32_t)gidx[u], a.div_cap);
-                    const uint32_t fidx = (uint32_t)gidx[u] - didx * (uint32_t)g.cache_capacity;
-                    const float* chunk = g.shard_tab[didx * (uint32_t)g.nchunks + (fidx >> g.chunk_shift)];
-                    p = chunk + (int64_t)(fidx & ((1u << g.chunk_shift) - 1u)) * spitch;
-                } else if (id[u] >= 0 && g.table) {
-                    p = g.table + (int64_t)(id[u] % g.total_num_nodes) * tpitch;
-                }
-            }
+            const float* p = lead[u] ? row_source(g, a.div_cap, id[u], gidx[u], tpitch, spitch) : nullptr;
             const unsigned long long bits = (unsigned long long)(uintptr_t)p;
             const uint32_t lo = __shfl((uint32_t)bits, src_lane[u]), hi = __shfl((uint32_t)(bits >> 32), src_lane[u]);
             const float* rp = (const float*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
@@ -857,6 +853,82 @@ __global__ __launch_bounds__(kBlock) void k_gather_lookup(GatherKArgs a)
     }
     // (feature_cache_hit, GPUCache.cu:130-147, is counted by the lookup PASS: the launcher sends every batch whose hit rate is
     // sampled through k_row_ptrs, which sees each row exactly once -- here a row that straddles two waves is probed by both)
+}
+
+// ------------------------------------------------------------------------------------------------
+// S5, aggregated last hop (no counterpart in the reference): neighbour sums per input slot of the last hop
+// ------------------------------------------------------------------------------------------------
+// The rows found in the last hop are read by a GraphSAGE trainer for one thing: being summed into their hop-(H-1) neighbours.  This
+// kernel hands over those sums instead of the rows.  Run i = input slot i of the last hop (a seed at H = 1, else edge i of hop H - 1);
+// its draws are what k_sample parked in cand[i * f .. i * f + f), < 0 = no draw.
+//   S[i, :] = ((0.0f + x[c(i, j0)]) + x[c(i, j1)]) + ...   over the j with a draw, ascending j, fp32, no reassociation
+// written dense behind the n_in rows of the levels < H: dst row n_in + i.  A run without draws stores +0.0 (the buffer is reused).
+// Work space like k_gather: flat (run, 16-byte chunk), one chunk per lane; per lane U slot ids of its run, their sources and their
+// row loads go out together, then the adds in slot order.  Every run has at most f terms: even work, no atomics, and the order of
+// the adds is fixed by construction, so the sums are bitwise reproducible.
+// A hub row is read once per draw here (13-18 % of the papers100M last-hop draws repeat inside a 1-2 Ki-slot tile,
+// profiles/r06_dedup_census.md), unlike k_gather's read-once rows: NT picks non-temporal row loads (profiles/agg_last_hop.md).
+#ifndef LEGION_AGG_NT_LOADS
+#define LEGION_AGG_NT_LOADS 0
+#endif
+struct GatherSumArgs {
+    GatherArgs g;            // table / shards / map / pitches / F / dst / dst_rows / nc of the pipe (sampled_ids, row_ptr: unused)
+    FastDiv div_c;           // / chunks-per-row
+    FastDiv div_cap;         // / cache_capacity
+    const int32_t* cand;     // the last hop's draws (the pipe's own buffer)
+    const int32_t* ec;
+    int32_t hops, f;
+    int32_t cand_cap;        // elements of cand
+};
+// input slots of the last hop, from the counters as apply_update_counter leaves them behind that hop (nc[2] is overwritten by then)
+__device__ inline int32_t last_hop_inputs(const int32_t* nc, const int32_t* ec, int32_t hops)
+{
+    return hops == 1 ? nc[4] : hops == 2 ? ec[3] : ec[1 + hops] - ec[hops];
+}
+
+template <typename VT, int U, bool NT>
+__global__ __launch_bounds__(kBlock) void k_gather_sum(GatherSumArgs a)
+{
+    constexpr int VEC = sizeof(VT) / 4;
+    const GatherArgs& g = a.g;
+    const int32_t n_in = g.nc[3 + 2 * a.hops];
+    const int32_t runs = last_hop_inputs(g.nc, a.ec, a.hops);
+    const int32_t C = g.F / VEC;
+    const int64_t total = (int64_t)runs * C;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tpitch = g.table_pitch > 0 ? g.table_pitch : g.F, spitch = g.shard_pitch > 0 ? g.shard_pitch : g.F;
+    if (g.rows_seen && blockIdx.x == 0 && threadIdx.x == 0) *g.rows_seen = runs; // launch-size feedback for later batches
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
+        const uint32_t i = fdiv((uint32_t)q, a.div_c); // runs * C < 2^31 is checked by the launcher
+        const uint32_t ch = (uint32_t)q - i * (uint32_t)C;
+        if (g.dst_rows > 0 && (int64_t)n_in + i >= g.dst_rows) continue; // never write past the buffer
+        const int64_t slot0 = (int64_t)i * a.f;
+        VT acc = VT(0.0f);
+        for (int32_t j0 = 0; j0 < a.f; j0 += U) {
+            int32_t id[U], gidx[U];
+            const VT* src[U];
+            VT val[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int64_t idx = slot0 + j0 + u;
+                id[u] = (j0 + u < a.f && idx < a.cand_cap) ? a.cand[idx] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) gidx[u] = (id[u] >= 0 && g.feat_map) ? g.feat_map[id[u]] : -1;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const float* p = row_source(g, a.div_cap, id[u], gidx[u], tpitch, spitch);
+                src[u] = p ? reinterpret_cast<const VT*>(p) + ch : nullptr;
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++)
+                if (src[u]) val[u] = NT ? __builtin_nontemporal_load(src[u]) : *src[u];
+#pragma unroll
+            for (int u = 0; u < U; u++)
+                if (src[u]) acc = acc + val[u];
+        }
+        __builtin_nontemporal_store(acc, reinterpret_cast<VT*>(g.dst) + ((int64_t)(n_in + (int32_t)i) * g.F) / VEC + ch);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1310,6 +1382,31 @@ void launch_gather(hipStream_t s, const GatherArgs& g, int32_t rows_bound)
     if (fused) { if (vec4) k_gather_lookup<v4f, 2><<<grid, kBlock, 0, s>>>(a); else k_gather_lookup<float, 2><<<grid, kBlock, 0, s>>>(a); }
     else if (vec4) k_gather<v4f, 1, 2><<<grid, kBlock, 0, s>>>(a);
     else k_gather<float, 1, 2><<<grid, kBlock, 0, s>>>(a);
+    HIP_CHECK_LAST();
+}
+
+void launch_gather_sum(hipStream_t s, const GatherArgs& g, const int32_t* cand, int32_t cand_cap, const int32_t* ec, int32_t hops,
+                       int32_t f, int32_t runs_bound)
+{
+    if (g.F <= 0 || runs_bound <= 0 || f <= 0) return;
+    GatherSumArgs a;
+    a.g = g;
+    a.g.row_ptr = nullptr;
+    a.div_cap = FastDiv((uint32_t)(g.cache_capacity > 0 ? g.cache_capacity : 1));
+    a.cand = cand; a.cand_cap = cand_cap; a.ec = ec; a.hops = hops; a.f = f;
+    // the draws are scratch of this GPU and the sums are written into its feature buffer; the backing table may be the host's or a peer's
+    LEGION_AUDIT_LAUNCH(s, "k_gather_sum", LEGION_AW(g.dst), LEGION_AW(g.rows_seen), LEGION_AL(cand), LEGION_AL(g.nc), LEGION_AL(ec), LEGION_AL(g.feat_map), LEGION_AL(g.shard_tab), LEGION_AR(g.table));
+    const bool vec4 = (g.F % 4 == 0) && (((uintptr_t)g.table | (uintptr_t)g.dst) % 16 == 0);   // same element paths as launch_gather
+    const int C = vec4 ? g.F / 4 : g.F;
+    if ((int64_t)runs_bound * C >= (1ll << 31)) { LEGION_ARG_ERROR("get_feature_kernel_agg: rows*F exceeds 2^31 work items"); return; }
+    a.div_c = FastDiv((uint32_t)C);
+    // one (run, chunk) item per lane; the grid comes from the run count an earlier launch reported (+ 25 %), else from the static
+    // bound of the hop's input list -- no host round trip either way, and the grid-stride loop covers a batch that outgrows the estimate
+    const int64_t est = g.rows_hint > 0 ? std::min<int64_t>(runs_bound, (int64_t)g.rows_hint + g.rows_hint / 4 + 1024) : runs_bound;
+    const int grid = grid_for(est * C, kBlock, 8192);
+    constexpr bool NT = LEGION_AGG_NT_LOADS != 0;
+    if (vec4) k_gather_sum<v4f, 8, NT><<<grid, kBlock, 0, s>>>(a);
+    else k_gather_sum<float, 8, NT><<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
 }
 

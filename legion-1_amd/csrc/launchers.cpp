@@ -52,6 +52,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     if (p->device_id != dev_id && audit::on()) {   // the pool starts serving this GPU: its scratch and its output buffers must live there
         LEGION_AUDIT_OWNER(p->pos_map, dev_id, "batch_generator_kernel: scratch of the memory pool");
         LEGION_AUDIT_OWNER(p->cand, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (int32_t* c : p->cand_pipe) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (int i = 0; i < p->pipeline_depth; i++) {
             LEGION_AUDIT_OWNER(p->sampled_ids[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
             LEGION_AUDIT_OWNER(p->node_counter[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
@@ -59,6 +60,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         LEGION_AUDIT_OWNER(all_ids, dev_id, "batch_generator_kernel: seed list");
     }
     p->device_id = dev_id;
+    p->sampled_hop = 0; p->sampled_presc = false; p->levels_gathered = 0;
     if (p->capturing) {
         // Recording a batch graph: cursor, epoch and the clamped size (Kernels.cu:224) are read / computed on the
         // device, `counter` is ignored, bounds are those of a full batch.
@@ -117,7 +119,12 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     const int q = p->current_pipe;
     b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];
     b.agg_dst_off = p->agg_dst_off[q]; b.nc = p->node_counter[q]; b.ec = p->edge_counter[q];
-    b.pos_map = p->pos_map; b.ctl = p->ctl; b.cand = p->cand; b.aux = p->aux2[hop & 1]; b.aux_next = p->aux2[(hop + 1) & 1]; b.tile_edge = p->tile_edge; b.tile_node = p->tile_node; b.tile_pre = p->tile_pre; b.chunk_tot = p->chunk_tot;
+    b.pos_map = p->pos_map; b.ctl = p->ctl; b.cand = p->cand;
+    if (p->agg_last_hop && hop == p->hops) {   // k_gather_sum reads the last hop's draws while the next batch samples: the pipe's own buffer
+        if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("GPU_Random_Sampling: aggregated last hop without the per-pipe draw buffers (GPUMemoryPool_SetAggLastHop before AllocateScratch failed?)"); return; }
+        b.cand = p->cand_pipe[q];
+    }
+    b.aux = p->aux2[hop & 1]; b.aux_next = p->aux2[(hop + 1) & 1]; b.tile_edge = p->tile_edge; b.tile_node = p->tile_node; b.tile_pre = p->tile_pre; b.chunk_tot = p->chunk_tot;
     b.hop_state = p->hop_state; b.edge_access_time = nullptr;
     if (is_presc) {
         // kernel_pre_sampler_optimized: host CSR only + topology hotness (Kernels.cu:636-649)
@@ -142,6 +149,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.next_count = hop < p->hops ? p->fanout[hop] : 0;
     launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
+    p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint
     p->bound_nodes += (int32_t)slots;
 }
@@ -174,7 +182,7 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
     g.rows_seen = nullptr; g.rows_hint = 0;
     g.hit_stats = nullptr;
     if (p->rows_seen && p->rows_seen_dev) { // slot: level of a per-level gather, or the last one for "all rows of the batch"
-        const int slot = off_idx < 0 ? LEGION_MAX_HOPS + 1 : (off_idx - 3) / 2;
+        const int slot = off_idx < 0 ? kRowsSeenAll : (off_idx - 3) / 2;
         g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
         g.rows_seen = p->rows_seen_dev + slot;
     }
@@ -195,14 +203,17 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
     return true;
 }
 
-static void gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, int32_t dev_id,
+// false: refused, nothing launched
+static bool gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, int32_t dev_id,
                           int off_idx, int size_idx, int32_t rows_bound)
 {
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, off_idx, size_idx)) return;
+    // an aggregated batch never reaches the last level's gather, which closes a hit-rate sample: its level gathers do not open one
+    if (!gather_args(g, cache, noder, p, dev_id, off_idx, size_idx, !p->agg_last_hop)) return false;
     launch_gather((hipStream_t)strm_hdl, g, rows_bound);
     // last counting launch of a sampled batch: the host may read the pinned {hits, rows} words once this event completes
     if (g.hit_stats && (off_idx < 0 || off_idx == 3 + 2 * p->hops)) GPUCache_HitSamplingDone(cache, dev_id, strm_hdl);
+    return true;
 }
 
 // $LEGION_PEER_GATHER=exchange and a filled clique cache (Kg > 1, every member in this process): the peers' rows travel as bulk
@@ -229,7 +240,41 @@ void get_feature_kernel(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, 
         if (l == memorypool->hops) legion_peer_exchange_gather(strm_hdl, cache, noder, memorypool, dev_id);
         return;
     }
-    gather_common(strm_hdl, cache, noder, memorypool, dev_id, 3 + 2 * l, 4 + 2 * l, memorypool->level_bound[l]);
+    if (gather_common(strm_hdl, cache, noder, memorypool, dev_id, 3 + 2 * l, 4 + 2 * l, memorypool->level_bound[l]))
+        memorypool->levels_gathered |= 1u << l;
+}
+
+// Aggregated last hop (no counterpart in the reference): behind the last hop's GPU_Random_Sampling of a pool in that mode
+// (GPUMemoryPool_SetAggLastHop).  Feature rows [0, n_in) -- the levels < H -- are gathered here unless get_feature_kernel already
+// gathered each of them, and the neighbour sums of the last hop's N input slots are written behind them, rows [n_in, n_in + N).
+void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
+                            int32_t dev_id, int in_memory)
+{
+    if (!noder || !pool_ready(memorypool, "get_feature_kernel_agg")) return;
+    GPUMemoryPool* p = memorypool;
+    const int H = p->hops, q = p->current_pipe;
+    if (!p->agg_last_hop) { LEGION_ARG_ERROR("get_feature_kernel_agg: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop)"); return; }
+    {   // the exchange moves rows between clique members, not sums
+        const char* e = getenv("LEGION_PEER_GATHER");
+        if (e && strcmp(e, "exchange") == 0) { LEGION_ARG_ERROR("get_feature_kernel_agg: LEGION_PEER_GATHER=exchange cannot serve the aggregated last hop (GPUMemoryPool_SetAggLastHop): the exchange moves rows, not sums"); return; }
+    }
+    if (p->sampled_hop != H) { LEGION_ARG_ERROR("get_feature_kernel_agg: called before the last hop's GPU_Random_Sampling"); return; }
+    if (p->sampled_presc) { LEGION_ARG_ERROR("get_feature_kernel_agg: a pre-sampling batch gathers nothing"); return; }
+    if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe draw buffers are missing"); return; }
+    if (!in_memory) return;
+    GatherArgs g;
+    if (!gather_args(g, cache, noder, p, dev_id, -1, 3 + 2 * H, false)) return;   // rows [0, nc[3 + 2H]); the hit counter belongs to the default mode's batches
+    auto feedback = [&](int slot) {
+        if (!p->rows_seen || !p->rows_seen_dev) return;
+        g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
+        g.rows_seen = p->rows_seen_dev + slot;
+    };
+    if ((p->levels_gathered & ((1u << H) - 1u)) != (1u << H) - 1u) {
+        feedback(kRowsSeenAggIn);
+        launch_gather((hipStream_t)strm_hdl, g, p->num_ids - p->level_bound[H]);
+    }
+    feedback(kRowsSeenAggRuns);
+    launch_gather_sum((hipStream_t)strm_hdl, g, p->cand_pipe[q], p->max_slots, p->edge_counter[q], H, p->fanout[H - 1], p->level_bound[H - 1]);
 }
 
 void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,

@@ -49,6 +49,10 @@ struct Runner {
     // long hops (products {25,10,5}: `all` +5.7 %).  auto decides once, after the pre-sampling epoch, from the last pre-sampled batch's counters.
     bool gather_all = false;
     bool gather_auto = true;
+    // $LEGION_AGG_LAST_HOP=1: the last hop is handed over as neighbour sums (get_feature_kernel_agg on stream 1 behind the last hop instead of
+    // the last level's gather; INTEGRATION.md "Aggregated last hop").  The feature buffers then hold n_in + N rows per batch, not n.
+    bool agg_last_hop = false;
+    int32_t presc_max_rows = 0;     // largest n_in + N of the pre-sampling epoch (read back per batch: that epoch is not pipelined anyway)
     bool pending = false;
     int pending_pipe = 0;
     int64_t short_batches = 0;      // batches with more nodes than the feature buffers hold rows (see hand_over)
@@ -61,13 +65,24 @@ struct Runner {
 // with its last rows missing and ipc_service.get_next refuses it (the reference's trainer reads past the allocation instead,
 // ipc_cuda_kernel.cu:200).  That is a trainer-side failure with no server-side trace -- so the server leaves one: the first such batch
 // is logged, all are counted (Runner_Finalize prints the total).
+// rows of the feature buffer an aggregated batch fills: n_in + N (the last hop's input slots), from its two counter arrays
+static int32_t agg_rows(const int32_t* nc, const int32_t* ec, int H)
+{
+    return nc[3 + 2 * H] + (H == 1 ? nc[4] : H == 2 ? ec[3] : ec[1 + H] - ec[H]);
+}
+
 static void hand_over(Runner* r, IPCEnv* env, int pipe)
 {
     const int32_t rows = r->memorypool ? r->memorypool->feature_rows : 0;
-    const int32_t nodes = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, 5 + 2 * r->hops);
+    int32_t nodes = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, 5 + 2 * r->hops);
+    if (r->agg_last_hop && nodes >= 0) {     // the mirror is there: n_in + N rows (features, then one row of sums per input slot of the last hop)
+        int32_t nc[16], ec[16];
+        for (int i = 0; i < 16; i++) { nc[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, i); ec[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, 16 + i); }
+        nodes = agg_rows(nc, ec, r->hops);
+    }
     if (rows > 0 && nodes > rows) {
         if (r->short_batches++ == 0)
-            log_out() << r->local_dev_id << " Feature buffer too small: a batch has " << nodes << " nodes, the buffer holds " << rows
+            log_out() << r->local_dev_id << " Feature buffer too small: a batch has " << nodes << (r->agg_last_hop ? " rows (features + neighbour sums)" : " nodes") << ", the buffer holds " << rows
                       << " rows -- the rows beyond it are not gathered and the trainer will refuse the batch (evaluation batches larger than "
                          "the training batches of the pre-sampling epoch?)\n" << std::flush;
     }
@@ -134,7 +149,10 @@ static void run_ops(Runner* r)
         if (r->gather_all && (i & 1) && i < last_feat) continue;
         if (i % 2 == 1) HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[i - 1], 0));
         r->op_params[i]->is_presc = 0;
-        if (r->gather_all && i == last_feat) {
+        if (r->agg_last_hop && i == last_feat) {     // the levels < H that were not gathered per level, and the sums
+            OpParams* fp = r->op_params[i];
+            get_feature_kernel_agg(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
+        } else if (r->gather_all && i == last_feat) {
             OpParams* fp = r->op_params[i];
             get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
         } else {
@@ -167,7 +185,8 @@ static bool run_graph(Runner* r, IPCEnv* env, int32_t batch_id)
     HIP_CHECK(hipEventRecord(r->events[0], r->streams[0]));
     HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[0], 0));
     OpParams* fp = r->op_params[1];
-    get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
+    if (r->agg_last_hop) get_feature_kernel_agg(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
+    else get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
     Operator_run(r->op_factory[r->op_num - 1], r->op_params[r->op_num - 1]);   // Updater, stream 1
     return true;
 }
@@ -245,11 +264,17 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     r->pipeline_depth = LEGION_PIPELINE_DEPTH;
     { const char* e = getenv("LEGION_BATCH_GRAPH"); r->use_graph = e && atoi(e) != 0; }
     { const char* e = getenv("LEGION_RUNNER_GATHER"); r->gather_all = e && strcmp(e, "all") == 0; r->gather_auto = !e || strcmp(e, "auto") == 0; }
+    { const char* e = getenv("LEGION_AGG_LAST_HOP"); r->agg_last_hop = e && atoi(e) != 0; }
     for (auto& ev : r->done_ev) HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     const int total_num_nodes = GPUNodeStorage_TotalNodeNum(noder);
     GPUCache_InitializeCacheController(cache, r->local_dev_id, total_num_nodes);
     r->memorypool = NewGPUMemoryPool(r->pipeline_depth);
     GPUMemoryPool_AllocateScratch(r->memorypool, total_num_nodes, batch_size, params->fanout, hop_num);
+    if (r->agg_last_hop) {
+        GPUMemoryPool_SetAggLastHop(r->memorypool, 1);      // one draw buffer per pipe, here on this runner's GPU
+        IPCEnv_SetAggLastHop(env, 1);                        // what a trainer reads: ipc_service.aggregated()
+        log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
+    }
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");
     LEGION_AUDIT_STREAM(r->streams[1], r->local_dev_id, "Runner_Initialize: gather stream");
@@ -296,7 +321,8 @@ void Runner_InitializeFeaturesBuffer(Runner* r, RunnerParams* params)
     IPCEnv* env = (IPCEnv*)params->env;
     DeviceGuard guard(r->local_dev_id);
     HIP_CHECK(hipStreamSynchronize(r->streams[0]));
-    int64_t num_ids = (int64_t)(GPUCache_MaxIdNum(cache, r->local_dev_id) * 1.2);
+    // aggregated hand-off: the buffer holds n_in + N rows per batch (largest of the pre-sampling epoch), same 1.2 x and seed-ratio rules
+    int64_t num_ids = (int64_t)((r->agg_last_hop ? r->presc_max_rows : GPUCache_MaxIdNum(cache, r->local_dev_id)) * 1.2);
     // The pre-sampling epoch only sees TRAINING batches.  A validation / test batch (up to 512 seeds per GPU, CUDA_IPC_Service.cu:101-118)
     // that is larger than the training batch reaches more nodes: scale the estimate by the seed ratio (unique nodes grow at most linearly
     // with the seeds).  The reference sizes by the training batches alone (Server.cu:275) -- with its 8000-seed training batches the case
@@ -328,6 +354,13 @@ void Runner_RunPreSc(Runner* r, RunnerParams* params)
     }
     // the reference polls the (never recorded) updater event here, i.e. does not wait: batches of
     // the pre-sampling epoch are simply queued in order on stream 0.
+    if (r->agg_last_hop) {   // ... except that sizing the buffer for max(n_in + N) needs both counter arrays of every batch
+        int32_t nc[16] = {0}, ec[16] = {0};
+        HIP_CHECK(hipStreamSynchronize(r->streams[0]));
+        HIP_CHECK(hipMemcpy(nc, r->memorypool->node_counter[r->memorypool->current_pipe], sizeof(nc), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ec, r->memorypool->edge_counter[r->memorypool->current_pipe], sizeof(ec), hipMemcpyDeviceToHost));
+        r->presc_max_rows = std::max(r->presc_max_rows, agg_rows(nc, ec, r->hops));
+    }
 }
 
 // RunOnce, Server.cu:301-328

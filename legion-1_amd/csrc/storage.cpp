@@ -444,6 +444,14 @@ GPUMemoryPool::GPUMemoryPool(int32_t depth)
     agg_dst_off.assign(pipeline_depth, nullptr);
 }
 
+// the per-pipe draw buffers of the aggregated last hop (GPUMemoryPool::cand_pipe), on the current device
+static void alloc_agg_cand(GPUMemoryPool* p)
+{
+    p->cand_pipe.resize(p->pipeline_depth, nullptr);
+    for (auto& c : p->cand_pipe)
+        if (!c) HIP_CHECK(hipMalloc(&c, (size_t)p->max_slots * sizeof(int32_t)));
+}
+
 extern "C" {
 
 GPUMemoryPool* NewGPUMemoryPool(int32_t pipeline_depth) { return new GPUMemoryPool(pipeline_depth); }
@@ -476,8 +484,8 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
     HIP_CHECK(hipMalloc(&p->ctl, sizeof(BatchCtl)));
     { const BatchCtl c{0, kEpochTop}; HIP_CHECK(hipMemcpy(p->ctl, &c, sizeof(c), hipMemcpyHostToDevice)); }
     p->ctl_synced = false;
-    HIP_CHECK(hipHostMalloc((void**)&p->rows_seen, (LEGION_MAX_HOPS + 2) * sizeof(int32_t), hipHostMallocMapped));
-    memset(p->rows_seen, 0, (LEGION_MAX_HOPS + 2) * sizeof(int32_t));
+    HIP_CHECK(hipHostMalloc((void**)&p->rows_seen, kRowsSeenWords * sizeof(int32_t), hipHostMallocMapped));
+    memset(p->rows_seen, 0, kRowsSeenWords * sizeof(int32_t));
     HIP_CHECK(hipHostGetDevicePointer((void**)&p->rows_seen_dev, p->rows_seen, 0));
     HIP_CHECK(hipMalloc(&p->cand, (size_t)p->max_slots * sizeof(int32_t)));
     for (auto& a : p->aux2) HIP_CHECK(hipMalloc(&a, (size_t)p->max_slots * sizeof(int32_t)));
@@ -491,9 +499,21 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
     HIP_CHECK(hipMalloc(&p->agg_src_ids, (size_t)p->num_ids * sizeof(int32_t)));
     HIP_CHECK(hipMalloc(&p->tmp_part_ind, (size_t)p->num_ids));
     HIP_CHECK(hipMalloc(&p->tmp_part_off, (size_t)p->num_ids * sizeof(int32_t)));
+    if (p->agg_last_hop) alloc_agg_cand(p);
     HIP_CHECK(hipDeviceSynchronize());
 }
 int32_t GPUMemoryPool_NumIds(const GPUMemoryPool* p) { return p->num_ids; }
+
+// Aggregated last hop: on = the last hop of every batch keeps its draws in a buffer of the batch's pipe and get_feature_kernel_agg hands
+// over neighbour sums; off (default) = nothing changes.  Call it under the device the pool's scratch lives on.
+void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggLastHop: null pool"); return; }
+    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggLastHop: the pool is being captured"); return; }
+    p->agg_last_hop = on != 0;
+    if (p->agg_last_hop && p->owns_scratch) alloc_agg_cand(p);
+}
+int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->agg_last_hop ? 1 : 0; }
 
 #define POOL_PIPE_SETTER(name, field, type) \
     void GPUMemoryPool_Set##name(GPUMemoryPool* p, type* ptr, int32_t pipe) { \
@@ -530,6 +550,7 @@ void GPUMemoryPool_Finalize(GPUMemoryPool* p)
     (void)hipFree(p->pos_map); (void)hipFree(p->cand); for (auto& a : p->aux2) { (void)hipFree(a); a = nullptr; } (void)hipFree(p->tile_edge); (void)hipFree(p->tile_node); (void)hipFree(p->tile_pre); (void)hipFree(p->chunk_tot); p->tile_pre = p->chunk_tot = nullptr;
     (void)hipFree(p->hop_state); (void)hipFree(p->cache_search_buffer); (void)hipFree((void*)p->row_ptr); p->row_ptr = nullptr; (void)hipFree(p->agg_src_ids);
     (void)hipFree(p->tmp_part_ind); (void)hipFree(p->tmp_part_off); (void)hipFree(p->ctl); p->ctl = nullptr; if (p->rows_seen) { (void)hipHostFree(p->rows_seen); p->rows_seen = nullptr; p->rows_seen_dev = nullptr; }
+    for (auto& c : p->cand_pipe) { (void)hipFree(c); c = nullptr; }
     p->pos_map = nullptr; p->cand = nullptr; p->tile_edge = p->tile_node = nullptr; p->hop_state = nullptr;
     p->cache_search_buffer = p->agg_src_ids = p->tmp_part_off = nullptr; p->tmp_part_ind = nullptr;
     p->owns_scratch = false;

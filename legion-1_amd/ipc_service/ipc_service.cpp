@@ -19,6 +19,7 @@ static LegionIPCClient* env = nullptr;
 static int32_t h_node_counter[16];
 static int32_t h_edge_counter[16];
 static int32_t g_hops = 2;
+static bool g_aggregated = false;   // the server hands the last hop over as neighbour sums (read once, in initialize)
 // ONE consumer thread per process is the contract (the reference's trainer loop, legion_graphsage.py:72-89):
 // get_next / synchronize run without the GIL and share `env`, the two counter arrays and the client's current pipe, so the entry points
 // are serialised by this lock -- uncontended in the reference's loop, and a second Python thread gets whole counters instead of torn ones.
@@ -34,6 +35,7 @@ void InitializeIPC()
     env = legion_ipc_client_open(-1); // current device == torch.cuda.set_device(rank) (ipc_cuda_kernel.cu:41)
     TORCH_CHECK(env != nullptr, "ipc_service: cannot attach to the sampling server: ", legion_last_error());
     g_hops = legion_ipc_client_hops(env);
+    g_aggregated = legion_ipc_client_agg_last_hop(env) != 0;
 }
 
 void FinalizeIPC()
@@ -42,10 +44,16 @@ void FinalizeIPC()
     env = nullptr;
 }
 
-std::vector<torch::Tensor> get_next(int feature_dim)
+// One batch of either hand-off mode.  Default: [ids, features[n, F], labels, (src, dst) x H].  Aggregated (the server runs with
+// LEGION_AGG_LAST_HOP=1): [ids, x_in[n_in, F], labels, (src, dst) x H, S[N, F]] -- feature rows of the nodes found before the last hop, and
+// one row of neighbour sums per input slot of the last hop, both views of the same server buffer (INTEGRATION.md "Aggregated last hop").
+static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated)
 {
     std::lock_guard<std::mutex> lock(g_mu);
     require_env();
+    TORCH_CHECK(aggregated || !g_aggregated, "ipc_service.get_next: the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1): rows >= n_in of "
+                "its feature buffer are sums, not features -- call get_next_aggregated");
+    TORCH_CHECK(!aggregated || g_aggregated, "ipc_service.get_next_aggregated: the server does not aggregate the last hop (start it with LEGION_AGG_LAST_HOP=1) -- call get_next");
     legion_ipc_client_wait(env); // env->Wait(), ipc_service.cpp:42
     legion_ipc_client_read_counters(env, h_node_counter, h_edge_counter);
     // a server that failed mid-batch posts the pipe with every node-counter word at -1 (runner.cpp, post_poisoned)
@@ -56,24 +64,33 @@ std::vector<torch::Tensor> get_next(int feature_dim)
     const auto f32 = torch::TensorOptions().dtype(torch::kF32).device(device);
     const int H = g_hops;
     const int64_t n_nodes = h_node_counter[5 + 2 * H];
+    const int64_t n_in = h_node_counter[3 + 2 * H];
+    const int64_t n_runs = H == 1 ? h_node_counter[4] : H == 2 ? h_edge_counter[3] : h_edge_counter[1 + H] - h_edge_counter[H];
+    const int64_t n_rows = aggregated ? n_in + n_runs : n_nodes;       // rows of the feature buffer this batch fills
     // the feature buffer holds a bounded number of rows (1.2 x the largest pre-sampled batch, Server.cu:275): a batch that reaches more
     // nodes must not be viewed as [n, F] (the reference does, unchecked: ipc_cuda_kernel.cu:200 -- a read past the allocation)
     const int64_t rows = legion_ipc_client_feature_rows(env);
-    TORCH_CHECK(rows <= 0 || n_nodes <= rows, "ipc_service: the batch has ", n_nodes, " nodes but the server's feature buffer holds ", rows,
+    TORCH_CHECK(rows <= 0 || n_rows <= rows, "ipc_service: the batch has ", n_rows, aggregated ? " rows (features + neighbour sums)" : " nodes", " but the server's feature buffer holds ", rows,
                 " rows (sized from the pre-sampling epoch; use a training batch size >= the validation / test batch size)");
     for (int w = 0; w <= 4; w++)    // legion_ipc_client_open refuses a server that has not registered its buffers; never build a tensor on a null one
         TORCH_CHECK(legion_ipc_client_buffer(env, w) != nullptr, "ipc_service: hand-off buffer ", w, " of this GPU was never registered by the server");
     std::vector<torch::Tensor> out;
     out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 0), {n_nodes}, i32));
-    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 1), {n_nodes, (int64_t)feature_dim}, f32));
+    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 1), {aggregated ? n_in : n_nodes, (int64_t)feature_dim}, f32));
     out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 2), {(int64_t)h_node_counter[5]}, i32));
     for (int k = 1; k <= H; k++) {
         const int64_t n_edges = h_edge_counter[2 + (H - k + 1)]; // ec[4], ec[3] at H = 2 (ipc_cuda_kernel.cu:198-213)
         out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 3), {n_edges}, i32));
         out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 4), {n_edges}, i32));
     }
+    if (aggregated)
+        out.push_back(torch::from_blob((float*)legion_ipc_client_buffer(env, 1) + n_in * (int64_t)feature_dim, {n_runs, (int64_t)feature_dim}, f32));
     return out;
 }
+
+std::vector<torch::Tensor> get_next(int feature_dim) { return next_batch(feature_dim, false); }
+std::vector<torch::Tensor> get_next_aggregated(int feature_dim) { return next_batch(feature_dim, true); }
+bool aggregated() { require_env(); return g_aggregated; }
 
 // [b1_src_nodes, b1_dst_nodes, b2_src_nodes, b2_dst_nodes, ...] = [nc9, nc7, nc7, nc5] at H = 2
 // (ipc_service.cpp:60-72)
@@ -113,6 +130,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     // get_next blocks on the pipe's semaphore and synchronize on the trainer's device: neither touches Python state, so both run without the GIL
     // (the reference holds it: a trainer's other Python threads stall for as long as the server takes to produce a batch)
     m.def("get_next", &get_next, "dataset get next (HIP)", pybind11::call_guard<pybind11::gil_scoped_release>());
+    m.def("get_next_aggregated", &get_next_aggregated, "next batch of a server that hands the last hop over as neighbour sums (extension)", pybind11::call_guard<pybind11::gil_scoped_release>());
+    m.def("aggregated", &aggregated, "whether the server hands the last hop over as neighbour sums (extension)");
     m.def("get_block_size", &get_block_size, "get dgl block size");
     m.def("get_steps", &get_steps, "get steps");
     m.def("initialize", &InitializeIPC, "InitializeIPC");
