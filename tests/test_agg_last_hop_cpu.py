@@ -1,6 +1,6 @@
 """Aggregated last hop (INTEGRATION.md "Aggregated last hop"), the parts that need no GPU.
 
-The EXPECTED VALUE of the mode is the NumPy statement below (`expected_nbr_sum`), computed from a DEFAULT-mode batch of a reference
+The EXPECTED VALUE of the mode is the NumPy statement of tests/aggref.py (`expected_nbr_sum`), computed from a DEFAULT-mode batch of a reference
 implementation (tests/pyref.py here, the C oracle in tests/test_gpu_agg_last_hop.py) and the input graph -- never from the code under
 test.  This file checks the statement's own premises on toy batches, the trainer-side formula that folds the sums into nodes against the
 default first-layer aggregate, and that the public surface carries the new names."""
@@ -13,67 +13,8 @@ import numpy as np
 import pytest
 
 import pyref
+from aggref import cum_edges, expected_nbr_sum, last_hop_runs
 from conftest import ROOT
-
-
-# ---------------------------------------------------------------------------------------------------
-# the expected value
-# ---------------------------------------------------------------------------------------------------
-def cum_edges(ec, h):
-    """edges of hops 1..h of a batch (apply_update_counter's layout: ec[2 + h] is cumulative; ec[2] is not a total)"""
-    return 0 if h == 0 else int(ec[2 + h])
-
-
-def last_hop_runs(ref, indptr, indices, fanout):
-    """(n_in, N, run_dst, cnt) of a default-mode batch: rows before the last hop, the last hop's input slots ("runs"), the batch
-    position of every run's input node, and the draws of every run recomputed from the graph -- min(deg, f) for a valid input
-    node, 0 for a -1; where the graph has holes (-1 neighbours) every draw is recomputed and the holes are left out."""
-    nc, ec = np.asarray(ref["nc"]), np.asarray(ref["ec"])
-    H, f = len(fanout), int(fanout[-1])
-    ids = np.asarray(ref["ids"])
-    n_in = int(nc[3 + 2 * H])
-    if H == 1:
-        N = int(nc[4])
-        run_dst = np.arange(N, dtype=np.int64)
-    else:
-        e0, e1 = cum_edges(ec, H - 2), cum_edges(ec, H - 1)
-        run_dst = np.asarray(ref["src_off"][e0:e1], dtype=np.int64)
-        N = e1 - e0
-    # the formula the device and the trainer use for N
-    assert N == (int(nc[4]) if H == 1 else int(ec[3]) if H == 2 else int(ec[1 + H] - ec[H]))
-    L = ids[run_dst] if N else np.zeros(0, np.int32)
-    valid = L >= 0
-    Ls = np.where(valid, L, 0).astype(np.int64)
-    row0 = np.asarray(indptr)[Ls]
-    deg = np.asarray(indptr)[Ls + 1] - row0
-    cnt = np.where(valid, np.minimum(deg, f), 0).astype(np.int64)
-    if (np.asarray(indices) < 0).any():
-        for i in np.flatnonzero(cnt):
-            d = int(deg[i])
-            cnt[i] = sum(int(indices[int(row0[i]) + pyref.sample_index(int(i) * f + j, d)]) >= 0 for j in range(min(d, f)))
-    return n_in, N, run_dst, cnt
-
-
-def expected_nbr_sum(ref, indptr, indices, fanout, x=None):
-    """S[i, :] = ((0.0f + x[c(i, j0)]) + x[c(i, j1)]) + ... in np.float32, edge order.  x: the reference's feature rows by batch
-    position (default: ref["features"]).  Vectorised over the runs without changing the order of any run's adds: step j adds the
-    j-th draw of every run that has one."""
-    x = np.asarray(ref["features"] if x is None else x, dtype=np.float32)
-    ec = np.asarray(ref["ec"])
-    H, f = len(fanout), int(fanout[-1])
-    n_in, N, run_dst, cnt = last_hop_runs(ref, indptr, indices, fanout)
-    e0, e1 = cum_edges(ec, H - 1), cum_edges(ec, H)
-    src, dst = np.asarray(ref["src_off"][e0:e1], dtype=np.int64), np.asarray(ref["dst_off"][e0:e1], dtype=np.int64)
-    # self-checks of the statement: the last hop's COO slice is exactly the runs, in order
-    assert int(cnt.sum()) == e1 - e0, (int(cnt.sum()), e1 - e0)
-    assert np.array_equal(dst, np.repeat(run_dst, cnt))
-    start = np.cumsum(cnt) - cnt
-    S = np.zeros((N, x.shape[1]), dtype=np.float32)
-    for j in range(f):
-        m = cnt > j
-        if m.any():
-            S[m] = S[m] + x[src[start[m] + j]]
-    return n_in, N, run_dst, S
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -1,21 +1,19 @@
 """Aggregated last hop on the GPU (get_feature_kernel_agg / k_gather_sum), through the C ABI, against the CPU oracle's DEFAULT-mode
-batch and the NumPy statement of tests/test_agg_last_hop_cpu.py: nc, ec, ids, labels and both COO arrays word for word, feature rows
+batch and the NumPy statement of tests/aggref.py: nc, ec, ids, labels and both COO arrays word for word, feature rows
 [0, n_in) bit-equal, the neighbour sums bit-equal (array_equal on the uint32 view).  Run with `pytest -m gpu`.
 
 The served path: the `legion` binary with LEGION_AGG_LAST_HOP=1 and a fresh trainer process on ipc_service.get_next_aggregated."""
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 import pytest
 
+from aggref import expected_nbr_sum, last_hop_runs
 from conftest import KEYS_NO_FEATURES, ROOT, assert_batch_equal, sha
-from test_agg_last_hop_cpu import expected_nbr_sum, last_hop_runs
-from test_gpu_parity import K, make_engine  # noqa: F401  (K: the module-scoped library fixture)
+from harness import K, OUT, Children, attached_client, child_env, in_process_runner, make_engine, replay_served, serve_sets, served, wait_for_text  # noqa: F401  (K: the module-scoped library fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -367,58 +365,31 @@ def test_rows_times_chunks_beyond_int32_is_refused(K):
 # ---------------------------------------------------------------------------------------------------
 # served: the `legion` binary -> ipc_service.get_next_aggregated
 # ---------------------------------------------------------------------------------------------------
-SERVER = os.path.join(ROOT, "legion-1_amd", "csrc", "legion")
-
-
 @pytest.mark.parametrize("fan,graph", [([10, 5], "0"), ([5, 4, 3], "0"), ([10, 5], "1"), ([6], "0")])
 def test_server_binary_serves_aggregated_batches(tmp_path, synth, oracle, fan, graph):
     """LEGION_AGG_LAST_HOP=1: a fresh trainer process sees aggregated() == True, get_next raises there, and every batch of the schedule
     (train + valid + test steps, two epochs) through get_next_aggregated equals the oracle's default batch + the NumPy statement.
     graph = 1: the runner's LEGION_BATCH_GRAPH=1 path (sampler graph on stream 0, the sums by a plain call on stream 1 while the next
     batch's graph overwrites the shared draw buffer)."""
-    from test_gpu_ipc import _audit_clean, _wait_ready
     spec = synth.spec_for("products", scale=0.004)
     ds = synth.generate(spec)
     data = str(tmp_path / "ds") + "/"
     synth.write_legion_files(ds, data)
     B, epochs = 512, 2
-    meta = str(tmp_path / "meta_config")
-    with open(meta, "w") as f:
-        f.write(synth.meta_config_line(ds, data, B, 1 << 40, epochs, 0))
-    ns = "ta%d_%d%s_" % (os.getpid(), len(fan), graph)
-    env = dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0", LEGION_BATCH_GRAPH=graph, LEGION_AGG_LAST_HOP="1")
-    log = str(tmp_path / "server.log")
-    with open(log, "w") as lf:
-        server = subprocess.Popen([SERVER, "1", "0", ",".join(map(str, fan)), meta], stdout=lf, stderr=subprocess.STDOUT, env=env, cwd=str(tmp_path))
-    try:
-        _wait_ready(server, log)
-        out = str(tmp_path / "client.json")
-        client = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ipc_client_agg.py"), str(spec.F), str(epochs), out],
-                                env=env, capture_output=True, text=True, timeout=300)
-        assert client.returncode == 0, client.stdout[-2000:] + client.stderr[-3000:]
-        server.wait(timeout=60)
-        assert server.returncode == 0, open(log).read()[-3000:]
-        _audit_clean(open(log).read())
-    finally:
-        if server.poll() is None:
-            server.kill()
-    got = json.load(open(out))
+    with served(tmp_path, synth.meta_config_line(ds, data, B, 1 << 40, epochs, 0), fan, env=dict(LEGION_BATCH_GRAPH=graph, LEGION_AGG_LAST_HOP="1")) as srv:
+        got, = srv.run_clients("ipc_client_agg.py", [spec.F, epochs, OUT])
+        srv.finish()
     H = len(fan)
-    sets = {0: ds.train, 1: ds.valid, 2: ds.test}
-    steps, tb, vb, sb = oracle.coordinate([len(ds.train)], [len(ds.valid)], [len(ds.test)], B)
-    bs = {0: int(tb[0]), 1: int(vb[0]), 2: int(sb[0])}
+    (sets,), steps, (bs,) = serve_sets(oracle, ds, B)
     orc = oracle.OracleRunner(ds.indptr, ds.indices, ds.features, spec.V, spec.F, B, fan)
-    assert got["hops"] == H and len(got["batches"]) == oracle.max_step(steps, epochs) and steps[1] > 0 and steps[2] > 0
-    for rec in got["batches"]:
-        mode, local = oracle.schedule(steps, epochs, rec["b"])
-        ids = sets[mode]
-        ref = orc.run_batch(ids, ds.labels[ids], local, mode=mode, batch_size=bs[mode])
+    assert got["hops"] == H and steps[1] > 0 and steps[2] > 0
+    for rec, ref, mode, local in replay_served(got, orc, sets, ds.labels, steps, epochs, bs):
         n_in, N, run_dst, S = expected_nbr_sum(ref, ds.indptr, ds.indices, fan)
         assert (rec["n"], rec["n_in"], rec["runs"]) == (int(ref["nc"][5 + 2 * H]), n_in, N)
         assert rec["edges"] == [int(ref["ec"][2 + (H - k + 1)]) for k in range(1, H + 1)]
         assert rec["ids"] == sha(ref["ids"]) and rec["labels"] == sha(ref["labels"]) and rec["src"] == sha(ref["src_off"]) and rec["dst"] == sha(ref["dst_off"])
         assert rec["features"] == sha(ref["features"][:n_in]) and rec["nbr_sum"] == sha(S), rec["b"]
-    assert "Hand-off: the last hop as neighbour sums" in open(log).read()
+    assert "Hand-off: the last hop as neighbour sums" in srv.log_text()
 
 
 def test_plain_server_refuses_get_next_aggregated_and_a_short_buffer_is_named(K, small_ds, tmp_path, capfd, monkeypatch):
@@ -427,75 +398,44 @@ def test_plain_server_refuses_get_next_aggregated_and_a_short_buffer_is_named(K,
     the trainer refuses the batch and the server names it as rows of features + neighbour sums and counts it."""
     ds = small_ds
     B, fan = 300, [10, 5]
-    L = K.lib()
-    client_py = os.path.join(ROOT, "tests", "ipc_client_agg.py")
     for agg in (False, True):
         if agg:
             monkeypatch.setenv("LEGION_AGG_LAST_HOP", "1")
         else:
             monkeypatch.delenv("LEGION_AGG_LAST_HOP", raising=False)
-        ns = "lgn_t_agg%d_%d_" % (int(agg), os.getpid())
-        L.legion_ipc_set_namespace(ns.encode())
-        eng = make_engine(K, ds, B, fan)
-        env = L.NewIPCEnv(1)
-        L.IPCEnv_Coordinate(env, C.byref(eng.info))
-        fan_arr = np.asarray(fan, dtype=np.int32)
-        rp = K.RunnerParams()
-        rp.device_id, rp.fanout, rp.hops = 0, fan_arr.ctypes.data, len(fan)
-        rp.cache, rp.graph, rp.noder, rp.env, rp.global_batch_id, rp.in_memory = eng.cache, eng.graph, eng.noder, env, 0, 1
-        runner = L.NewGPURunner()
-        L.Runner_Initialize(runner, C.byref(rp))
-        for b in range(2):                       # a pre-sampling epoch: the buffer is sized for max(n_in + N)
-            rp.global_batch_id = b
-            L.Runner_RunPreSc(runner, C.byref(rp))
-        L.Runner_InitializeFeaturesBuffer(runner, C.byref(rp))
-        L.GPUCache_SetPreSc(eng.cache, 0)
-        K.check()
-        assert L.IPCEnv_GetAggLastHop(env) == int(agg)
-        cenv = dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0")
-        if not agg:
-            code = ("import sys, torch; sys.path.insert(0, %r); import ipc_service; torch.cuda.set_device(0); ipc_service.initialize()\n"
-                    "assert ipc_service.aggregated() is False\n"
-                    "try:\n    ipc_service.get_next_aggregated(%d); sys.exit(7)\n"
-                    "except RuntimeError as e:\n    sys.exit(0 if 'LEGION_AGG_LAST_HOP=1' in str(e) and 'does not aggregate' in str(e) else 5)\n"
-                    % (os.path.join(ROOT, "legion-1_amd", "ipc_service"), ds.spec.F))
-            r = subprocess.run([sys.executable, "-c", code], env=cenv, capture_output=True, text=True, timeout=240)
-            assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
-        else:
+        # two pre-sampling batches: the buffer is sized for max(n_in + N)
+        with in_process_runner(K, ds, B, fan, "agg%d" % agg, presc_batches=2) as r, Children() as children:
+            L, env, runner, rp = r.L, r.env, r.runner, r.rp
+            assert L.IPCEnv_GetAggLastHop(env) == int(agg)
+            cenv = child_env(r.ns)
+            if not agg:
+                code = ("import sys, torch; sys.path.insert(0, %r); import ipc_service; torch.cuda.set_device(0); ipc_service.initialize()\n"
+                        "assert ipc_service.aggregated() is False\n"
+                        "try:\n    ipc_service.get_next_aggregated(%d); sys.exit(7)\n"
+                        "except RuntimeError as e:\n    sys.exit(0 if 'LEGION_AGG_LAST_HOP=1' in str(e) and 'does not aggregate' in str(e) else 5)\n"
+                        % (os.path.join(ROOT, "legion-1_amd", "ipc_service"), ds.spec.F))
+                res = subprocess.run([sys.executable, "-c", code], env=cenv, capture_output=True, text=True, timeout=240)
+                assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
+                continue
             pool = L.Runner_GetMemoryPool(runner)
             small_rows = 100
-            log = open(str(tmp_path / "client.log"), "w+")
-            client = subprocess.Popen([sys.executable, client_py, str(ds.spec.F), "refuse", "feature buffer holds %d rows" % small_rows], stdout=log, stderr=subprocess.STDOUT, env=cenv)
-            try:
-                t0 = time.time()
-                while "ATTACHED" not in open(log.name).read():
-                    assert client.poll() is None and time.time() - t0 < 240, open(log.name).read()[-3000:]
-                    time.sleep(0.1)
-                rp.global_batch_id = 0
-                L.Runner_RunOnce(runner, C.byref(rp))
-                rp.global_batch_id = 1
-                L.Runner_RunOnce(runner, C.byref(rp))          # batch 0 handed over: complete
-                K.check()
-                while "BATCH" not in open(log.name).read():
-                    assert client.poll() is None and time.time() - t0 < 240, open(log.name).read()[-3000:]
-                    time.sleep(0.05)
-                assert L.Runner_ShortBatches(runner) == 0
-                L.GPUMemoryPool_SetFeatureRows(pool, small_rows)
-                L.IPCEnv_SetFeatureRows(env, 0, small_rows)
-                rp.global_batch_id = 2
-                L.Runner_RunOnce(runner, C.byref(rp))          # hands batch 1 over: n_in + N rows no longer fit
-                K.check()
-                rc = client.wait(timeout=120)
-            except BaseException:
-                client.kill()
-                raise
-            text = open(log.name).read()
+            log = str(tmp_path / "client.log")
+            client = attached_client(children, "ipc_client_agg.py", [ds.spec.F, "refuse", "feature buffer holds %d rows" % small_rows], cenv, log)
+            rp.global_batch_id = 0
+            L.Runner_RunOnce(runner, C.byref(rp))
+            rp.global_batch_id = 1
+            L.Runner_RunOnce(runner, C.byref(rp))          # batch 0 handed over: complete
+            K.check()
+            wait_for_text(log, "BATCH", client, 240, 0.05)
+            assert L.Runner_ShortBatches(runner) == 0
+            L.GPUMemoryPool_SetFeatureRows(pool, small_rows)
+            L.IPCEnv_SetFeatureRows(env, 0, small_rows)
+            rp.global_batch_id = 2
+            L.Runner_RunOnce(runner, C.byref(rp))          # hands batch 1 over: n_in + N rows no longer fit
+            K.check()
+            rc = client.wait(timeout=120)
+            text = open(log).read()
             assert rc == 0 and "RAISED after 1 good batches" in text and "rows (features + neighbour sums)" in text, text[-3000:]
             assert L.Runner_ShortBatches(runner) == 1
-        L.d_stream_sync(None)
-        L.Runner_Delete(runner)
-        L.IPCEnv_Finalize(env)
-        eng.close()
-        L.legion_ipc_set_namespace(b"")
     said = capfd.readouterr().out
     assert "Feature buffer too small: a batch has" in said and "rows (features + neighbour sums), the buffer holds 100 rows" in said, said[-1500:]

@@ -14,17 +14,15 @@ import numpy as np
 import pytest
 
 from conftest import KEYS_NO_FEATURES, assert_batch_equal
+from harness import load_library
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def K():
-    import legion1_amd.capi as K
-    L = K.lib()
-    L.legion_set_error_mode(K.ERR_RETURN)
-    L.SetGPUDevice(0)
-    if not L.legion_audit_enabled():
+    K = load_library()
+    if not K.lib().legion_audit_enabled():
         pytest.skip("LEGION_DEVICE_AUDIT is off")
     return K
 

@@ -11,19 +11,11 @@ where the row came from, and -- since round 4 -- every batch word for word again
 import numpy as np
 import pytest
 
-from conftest import assert_batch_equal
+from conftest import KEYS_NO_FEATURES, assert_batch_equal
+from harness import K, OUT, served  # noqa: F401  (K: the module-scoped library fixture)
 from props import check_batch, device_graph, device_seeds
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def K():
-    import legion1_amd.capi as K
-    L = K.lib()
-    L.legion_set_error_mode(K.ERR_RETURN)
-    L.SetGPUDevice(0)
-    return K
 
 
 def _clique_engine(K, spec, indptr, indices, feat_ptr, feat_loc, E, parts, B, fan, presc_steps):
@@ -46,9 +38,6 @@ def _host_oracle(oracle, spec, indptr, indices, B, fan):
     peer fragment: same values, Kernels.cu:392-409) and neither do the gathered rows (a cached row is a copy of the table row), so the
     resident batch is the expected result of the partitioned / cached configurations too -- bit for bit."""
     return oracle.OracleRunner(indptr.cpu().numpy(), indices.cpu().numpy(), None, spec.V, spec.F, B, fan, with_features=False)
-
-
-ORACLE_KEYS = ("nc", "ec", "ids", "labels", "src_off", "dst_off")
 
 
 def _row_sources(K, eng, g, ids, cap):
@@ -86,7 +75,7 @@ def test_papers100m_unified_cache_full_shape(K, oracle, synth, G, mode, presc):
             res = eng.result(g)
             check_batch(res, spec, synth, B, fan, indptr, indices, seeds_g[it * B:(it + 1) * B], rs)
             # the cached configuration against the oracle at full shape, word for word
-            assert_batch_equal(orc.run_batch(seeds_g, labs_g, it, gather=False, omp=True), res, keys=ORACLE_KEYS)
+            assert_batch_equal(orc.run_batch(seeds_g, labs_g, it, gather=False, omp=True), res, keys=KEYS_NO_FEATURES)
             own, peer, miss = _row_sources(K, eng, g, res["ids"], cap)
             # every node of a pre-sampled batch has hotness > 0 and the cache holds more rows than were ever seen, so
             # batch 0 is served from the shards alone; a batch the cache has never seen also misses
@@ -163,7 +152,7 @@ def test_uk_union_sharded_csr_full_shape(K, oracle, synth, G, mode, host_spill):
             res = eng.result(g)
             levels = check_batch(res, spec, synth, B, fan, indptr, indices, seeds_g[it * B:(it + 1) * B], rs)
             # the sampler over partitioned CSR fragments (own, peer, whole-CSR rows mixed; E > 2^32) against the oracle, word for word
-            assert_batch_equal(orc.run_batch(seeds_g, labs_g, it, gather=False, omp=True), res, keys=ORACLE_KEYS)
+            assert_batch_equal(orc.run_batch(seeds_g, labs_g, it, gather=False, omp=True), res, keys=KEYS_NO_FEATURES)
             ids = res["ids"]
             # the sampler expanded rows of all three kinds: own fragment, peer fragments, the whole-CSR replica
             srcs = ids[:levels[0] + levels[1]]
@@ -246,7 +235,7 @@ def test_papers100m_link_prediction_full_shape(K, oracle, synth, world, rank):
         batch = h_seeds[it * B:(it + 1) * B]
         dup_batches += int(len(np.unique(batch)) < B)
         check_batch(res, spec, synth, B, fan, indptr, indices, batch, rs, distinct_seeds=False)
-        assert_batch_equal(orc.run_batch(h_seeds, h_lab, it, gather=False, omp=True), res, keys=ORACLE_KEYS)   # the per-rank list of a 2 / 8-GPU job
+        assert_batch_equal(orc.run_batch(h_seeds, h_lab, it, gather=False, omp=True), res, keys=KEYS_NO_FEATURES)   # the per-rank list of a 2 / 8-GPU job
     assert dup_batches > 0          # hot positives repeat inside a batch: the duplicate-seed path really ran
     eng.close()
 
@@ -334,13 +323,8 @@ def test_synth_server_serves_the_headline_shape(K, oracle, synth, tmp_path):
     also with the SERIAL oracle's digests from the build container (tests/golden/full_shape_digests.json); every served feature row of those
     batches with the generator's closed form (SHA-256 over all rows)."""
     import hashlib
-    import json
     import os
-    import subprocess
-    import sys
-    import time
-    from conftest import ROOT, sha
-    server_bin = os.path.join(ROOT, "legion-1_amd", "csrc", "legion")
+    from conftest import sha
     fields, cases = _full_shape_cases("papers100M")
     case = cases["papers100M-25,10,5"]
     B, fan, H = case["batch"], case["fanout"], 3
@@ -348,14 +332,7 @@ def test_synth_server_serves_the_headline_shape(K, oracle, synth, tmp_path):
     n_eval = 512
     # soak (profiles/r05_runs_soak.sh): LEGION_TEST_EPOCHS=3 LEGION_TEST_SERVED_EVERY=97 also checks every 97th served batch of three epochs
     epochs, every = int(os.environ.get("LEGION_TEST_EPOCHS", "1")), int(os.environ.get("LEGION_TEST_SERVED_EVERY", "0"))
-    meta = str(tmp_path / "meta_config")
-    with open(meta, "w") as f:
-        f.write("synth:papers100M %d %d %d %d %d %d %d 0 %d 0" % (B, spec.V, case["E"], spec.F, spec.n_train, n_eval, n_eval, epochs))
-    env = dict(os.environ, LEGION_IPC_NAMESPACE="fs%d_" % os.getpid(), HSA_ENABLE_IPC_MODE_LEGACY="0", LEGION_CLIENT_DUMP_IDS="1")
-    log = str(tmp_path / "server.log")
-    with open(log, "w") as lf:
-        server = subprocess.Popen([server_bin, "1", "0", ",".join(map(str, fan)), meta], stdout=lf, stderr=subprocess.STDOUT, env=env, cwd=str(tmp_path))
-    out = str(tmp_path / "client.json")
+    meta_line = "synth:papers100M %d %d %d %d %d %d %d 0 %d 0" % (B, spec.V, case["E"], spec.F, spec.n_train, n_eval, n_eval, epochs)
     train_step = (spec.n_train - 1) // B
     record = [0, train_step // 2, train_step - 1, train_step, train_step + 1]
     assert record[1] == 694
@@ -364,23 +341,12 @@ def test_synth_server_serves_the_headline_shape(K, oracle, synth, tmp_path):
         record = [0, train_step // 2, train_step - 1, train_step, total - 1]        # the test batch comes behind the last epoch
     soak = sorted(set(range(0, total, every)) - set(record)) if every > 0 else []
     record = sorted(record + soak)
-    try:
-        t0 = time.time()
-        while "System is ready for serving" not in open(log, errors="ignore").read():
-            assert server.poll() is None, open(log).read()[-3000:]
-            assert time.time() - t0 < 300, open(log).read()[-3000:]
-            time.sleep(0.2)
-        client = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ipc_client_plain.py"), str(spec.F), str(epochs), out, ",".join(map(str, record))],
-                                env=env, capture_output=True, text=True, timeout=1000)
-        assert client.returncode == 0, client.stdout[-2000:] + client.stderr[-3000:]
-        server.wait(timeout=120)
-        assert server.returncode == 0, open(log).read()[-3000:]
-    finally:
-        if server.poll() is None:
-            server.kill()
-    text = open(log).read()
+    with served(tmp_path, meta_line, fan, env=dict(LEGION_CLIENT_DUMP_IDS="1"), ready_timeout=300) as srv:
+        got, = srv.run_clients("ipc_client_plain.py", [spec.F, epochs, OUT, ",".join(map(str, record))], timeout=1000)
+        srv.finish(wait=120, audit_gpus=None)
+    out = str(tmp_path / "client0.json")
+    text = srv.log_text()
     assert "Graph generated in HBM: %d edges" % case["E"] in text and "Train Steps: %d" % train_step in text
-    got = json.load(open(out))
     assert got["steps"] == [train_step, 1, 1] and got["hops"] == H and [r["b"] for r in got["batches"]] == record
     per = train_step + 1
     # the oracle side: the CSR from the independent C generator on the host (oracle/synth_gen.c, OpenMP)

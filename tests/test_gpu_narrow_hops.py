@@ -9,19 +9,11 @@ import numpy as np
 import pytest
 
 from conftest import assert_batch_equal
+from harness import K  # noqa: F401  (the module-scoped library fixture)
 
 pytestmark = pytest.mark.gpu
 
 NARROW_SLOTS = 256 * 1024      # kNarrowSlots (csrc/internal.h)
-
-
-@pytest.fixture(scope="module")
-def K():
-    import legion1_amd.capi as K
-    L = K.lib()
-    L.legion_set_error_mode(K.ERR_RETURN)
-    L.SetGPUDevice(0)
-    return K
 
 
 @pytest.fixture(scope="module")

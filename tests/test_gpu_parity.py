@@ -3,39 +3,14 @@ against the CPU oracle on the same seeded inputs -- bit exact for every id / ind
 for the (verbatim copied) f32 feature rows.  Run on the GPU box with `pytest -m gpu`."""
 import ctypes as C
 import os
-import sys
-import time
 
 import numpy as np
 import pytest
 
-from conftest import KEYS_NO_FEATURES, ROOT, assert_batch_equal, load_golden, sha
+from conftest import KEYS_NO_FEATURES, assert_batch_equal, load_golden, sha
+from harness import K, Children, attached_client, child_env, in_process_runner, make_engine, wait_for_text  # noqa: F401  (K: the module-scoped library fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def K():
-    import legion1_amd.capi as K
-    L = K.lib()
-    L.legion_set_error_mode(K.ERR_RETURN)
-    L.SetGPUDevice(0)
-    return K
-
-
-def make_engine(K, ds_or_arrays, B, fan, G=1, seeds=None, **kw):
-    if hasattr(ds_or_arrays, "spec"):
-        ds = ds_or_arrays
-        V, F, indptr, indices, feats = ds.spec.V, ds.spec.F, ds.indptr, ds.indices, ds.features
-        if seeds is None:
-            import oracle as O
-            parts = O.split_seeds(ds.train, G)
-            seeds = dict(train=[(p, ds.labels[p]) for p in parts])
-    else:
-        V, F, indptr, indices, feats = ds_or_arrays
-    eng = K.Engine(indptr, indices, feats, V, F, seeds, B, fan, G=G, **kw)
-    eng.alloc_features()
-    return eng
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -376,43 +351,25 @@ def test_runner_posts_a_poisoned_pipe_when_an_operator_refuses(K, small_ds):
     Runner_RunOnce posts the pipe with every node-counter word = -1 and keeps the error.  Here the
     feature buffers were never registered (Runner_InitializeFeaturesBuffer skipped), so every FeatureExtractor refuses."""
     import ctypes.util
-    ds = small_ds
-    B, fan = 300, [10, 5]
-    L = K.lib()
-    ns = "lgn_t_poison_%d_" % os.getpid()
-    L.legion_ipc_set_namespace(ns.encode())
-    eng = make_engine(K, ds, B, fan)
-    env = L.NewIPCEnv(1)
-    L.IPCEnv_Coordinate(env, C.byref(eng.info))
-    fan_arr = np.asarray(fan, dtype=np.int32)
-    rp = K.RunnerParams()
-    rp.device_id, rp.fanout, rp.hops = 0, fan_arr.ctypes.data, len(fan)
-    rp.cache, rp.graph, rp.noder, rp.env, rp.global_batch_id, rp.in_memory = eng.cache, eng.graph, eng.noder, env, 0, 1
-    runner = L.NewGPURunner()
-    L.Runner_Initialize(runner, C.byref(rp))
-    L.GPUCache_SetPreSc(eng.cache, 0)
-    K.check()
-    libc = C.CDLL(ctypes.util.find_library("c") or "libc.so.6", use_errno=True)
-    libc.sem_open.restype = C.c_void_p
-    libc.sem_open.argtypes = [C.c_char_p, C.c_int]
-    libc.sem_post.argtypes = libc.sem_trywait.argtypes = libc.sem_close.argtypes = [C.c_void_p]
-    sem_r = libc.sem_open(("/%ssem_r_0_0" % ns).encode(), 0)
-    sem_w = libc.sem_open(("/%ssem_w_0_0" % ns).encode(), 0)
-    assert sem_r and sem_w
-    libc.sem_post(sem_r)                       # the trainer's "pipe 0 is free"
-    L.Runner_RunOnce(runner, C.byref(rp))      # must return, not block and not exit
-    msg = L.legion_last_error()
-    assert msg and b"feature buffer of the current pipe is not set" in msg, msg
-    assert libc.sem_trywait(sem_w) == 0, "the failed pipe was not posted: a consumer would block forever"
-    nc = K.read_dev(L.IPCEnv_GetNodeCounter(env, 0, 0), np.int32, 16)
-    assert (nc == -1).all(), nc
-    L.legion_clear_error()
-    libc.sem_close(sem_r)
-    libc.sem_close(sem_w)
-    L.Runner_Delete(runner)
-    L.IPCEnv_Finalize(env)
-    eng.close()
-    L.legion_ipc_set_namespace(b"")
+    with in_process_runner(K, small_ds, 300, [10, 5], "poison", features_buffer=False) as r:
+        L, env, runner, rp, ns = r.L, r.env, r.runner, r.rp, r.ns
+        libc = C.CDLL(ctypes.util.find_library("c") or "libc.so.6", use_errno=True)
+        libc.sem_open.restype = C.c_void_p
+        libc.sem_open.argtypes = [C.c_char_p, C.c_int]
+        libc.sem_post.argtypes = libc.sem_trywait.argtypes = libc.sem_close.argtypes = [C.c_void_p]
+        sem_r = libc.sem_open(("/%ssem_r_0_0" % ns).encode(), 0)
+        sem_w = libc.sem_open(("/%ssem_w_0_0" % ns).encode(), 0)
+        assert sem_r and sem_w
+        libc.sem_post(sem_r)                       # the trainer's "pipe 0 is free"
+        L.Runner_RunOnce(runner, C.byref(rp))      # must return, not block and not exit
+        msg = L.legion_last_error()
+        assert msg and b"feature buffer of the current pipe is not set" in msg, msg
+        assert libc.sem_trywait(sem_w) == 0, "the failed pipe was not posted: a consumer would block forever"
+        nc = K.read_dev(L.IPCEnv_GetNodeCounter(env, 0, 0), np.int32, 16)
+        assert (nc == -1).all(), nc
+        L.legion_clear_error()
+        libc.sem_close(sem_r)
+        libc.sem_close(sem_w)
 
 
 def test_poisoned_pipe_reaches_the_trainer_as_an_error(K, small_ds, tmp_path):
@@ -420,32 +377,11 @@ def test_poisoned_pipe_reaches_the_trainer_as_an_error(K, small_ds, tmp_path):
     an in-process runner; the runner's next batch fails (its feature buffer is taken away after the hand-shake), the pipe is
     posted with nc[*] = -1 and zeroed edge counters, and the trainer's get_next raises "sampling server failed" instead of
     building tensors with a negative dimension or the previous batch's edge counts."""
-    import subprocess
     ds = small_ds
-    B, fan = 300, [10, 5]
-    L = K.lib()
-    ns = "lgn_t_poison2_%d_" % os.getpid()
-    L.legion_ipc_set_namespace(ns.encode())
-    eng = make_engine(K, ds, B, fan)
-    env = L.NewIPCEnv(1)
-    L.IPCEnv_Coordinate(env, C.byref(eng.info))
-    fan_arr = np.asarray(fan, dtype=np.int32)
-    rp = K.RunnerParams()
-    rp.device_id, rp.fanout, rp.hops = 0, fan_arr.ctypes.data, len(fan)
-    rp.cache, rp.graph, rp.noder, rp.env, rp.global_batch_id, rp.in_memory = eng.cache, eng.graph, eng.noder, env, 0, 1
-    runner = L.NewGPURunner()
-    L.Runner_Initialize(runner, C.byref(rp))
-    L.Runner_InitializeFeaturesBuffer(runner, C.byref(rp))
-    L.GPUCache_SetPreSc(eng.cache, 0)
-    K.check()
-    log = open(str(tmp_path / "client.log"), "w+")
-    client = subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "ipc_client_poison.py"), str(ds.spec.F)], stdout=log, stderr=subprocess.STDOUT,
-                              env=dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    try:
-        t0 = time.time()
-        while "ATTACHED" not in open(log.name).read():
-            assert client.poll() is None and time.time() - t0 < 240, open(log.name).read()[-3000:]
-            time.sleep(0.1)
+    log = str(tmp_path / "client.log")
+    with in_process_runner(K, ds, 300, [10, 5], "poison2") as r, Children() as children:
+        L, env, runner, rp = r.L, r.env, r.runner, r.rp
+        client = attached_client(children, "ipc_client_poison.py", [ds.spec.F], child_env(r.ns), log)
         # a good batch first: the pipe's edge counters now hold real counts a poisoned post must not leave behind
         L.Runner_RunOnce(runner, C.byref(rp))
         K.check()
@@ -460,14 +396,7 @@ def test_poisoned_pipe_reaches_the_trainer_as_an_error(K, small_ds, tmp_path):
         assert (ec == 0).all(), ec
         # the trainer consumes batch 0 (good) and raises on the poisoned pipe: exit code 0 only for exactly that
         rc = client.wait(timeout=120)
-    except BaseException:
-        client.kill()
-        raise
-    text = open(log.name).read()
-    L.Runner_Delete(runner)
-    L.IPCEnv_Finalize(env)
-    eng.close()
-    L.legion_ipc_set_namespace(b"")
+    text = open(log).read()
     assert rc == 0 and "RAISED after 1 good batches" in text and "sampling server failed" in text, text[-3000:]
 
 
@@ -477,40 +406,17 @@ def test_a_batch_larger_than_the_feature_buffer_is_refused_by_the_trainer_and_na
     (a) `ipc_service.get_next` must RAISE for a batch with more nodes than rows -- a real trainer process attached to an in-process runner
     whose published row capacity is shrunk after the first batch -- and (b) the server must not drop rows silently: the runner names the
     first short batch in its log and counts them all (Runner_ShortBatches)."""
-    import subprocess
     ds = small_ds
-    B, fan = 300, [10, 5]
-    L = K.lib()
-    ns = "lgn_t_short_%d_" % os.getpid()
-    L.legion_ipc_set_namespace(ns.encode())
-    eng = make_engine(K, ds, B, fan)
-    env = L.NewIPCEnv(1)
-    L.IPCEnv_Coordinate(env, C.byref(eng.info))
-    fan_arr = np.asarray(fan, dtype=np.int32)
-    rp = K.RunnerParams()
-    rp.device_id, rp.fanout, rp.hops = 0, fan_arr.ctypes.data, len(fan)
-    rp.cache, rp.graph, rp.noder, rp.env, rp.global_batch_id, rp.in_memory = eng.cache, eng.graph, eng.noder, env, 0, 1
-    runner = L.NewGPURunner()
-    L.Runner_Initialize(runner, C.byref(rp))
-    L.Runner_InitializeFeaturesBuffer(runner, C.byref(rp))
-    L.GPUCache_SetPreSc(eng.cache, 0)
-    K.check()
     small_rows = 100
-    log = open(str(tmp_path / "client.log"), "w+")
-    client = subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "ipc_client_poison.py"), str(ds.spec.F), "feature buffer holds %d rows" % small_rows],
-                              stdout=log, stderr=subprocess.STDOUT, env=dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    try:
-        t0 = time.time()
-        while "ATTACHED" not in open(log.name).read():
-            assert client.poll() is None and time.time() - t0 < 240, open(log.name).read()[-3000:]
-            time.sleep(0.1)
+    log = str(tmp_path / "client.log")
+    with in_process_runner(K, ds, 300, [10, 5], "short") as r, Children() as children:
+        L, env, runner, rp = r.L, r.env, r.runner, r.rp
+        client = attached_client(children, "ipc_client_poison.py", [ds.spec.F, "feature buffer holds %d rows" % small_rows], child_env(r.ns), log)
         L.Runner_RunOnce(runner, C.byref(rp))          # batch 0 queued
         rp.global_batch_id = 1
         L.Runner_RunOnce(runner, C.byref(rp))          # batch 1 queued, batch 0 handed over: complete, the trainer takes it
         K.check()
-        while "BATCH" not in open(log.name).read():
-            assert client.poll() is None and time.time() - t0 < 240, open(log.name).read()[-3000:]
-            time.sleep(0.05)
+        wait_for_text(log, "BATCH", client, 240, 0.05)
         assert L.Runner_ShortBatches(runner) == 0
         # from here on the buffers "hold" 100 rows: the gather of batch 2 stops there, and batch 1 (thousands of nodes) no longer fits
         pool = L.Runner_GetMemoryPool(runner)
@@ -520,16 +426,8 @@ def test_a_batch_larger_than_the_feature_buffer_is_refused_by_the_trainer_and_na
         L.Runner_RunOnce(runner, C.byref(rp))          # hands batch 1 over
         K.check()
         rc = client.wait(timeout=120)
-    except BaseException:
-        client.kill()
-        raise
-    text = open(log.name).read()
-    short = L.Runner_ShortBatches(runner)
-    L.d_stream_sync(None)
-    L.Runner_Delete(runner)
-    L.IPCEnv_Finalize(env)
-    eng.close()
-    L.legion_ipc_set_namespace(b"")
+        short = L.Runner_ShortBatches(runner)
+    text = open(log).read()
     assert rc == 0 and "RAISED after 1 good batches" in text and "feature buffer holds %d rows" % small_rows in text, text[-3000:]
     assert short == 1, short
     server_said = capfd.readouterr().out
