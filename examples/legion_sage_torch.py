@@ -90,6 +90,26 @@ class GraphConvBoth(nn.Module):
         return self.fc(agg * in_deg.rsqrt().unsqueeze(1))
 
 
+class GraphConvBothFused(GraphConvBoth):
+    """First layer behind a server that hands the last hop over as out-degree-normalised neighbour sums (LEGION_AGG_LAST_HOP=1
+    LEGION_AGG_NORM=both, ipc_service.get_next_aggregated_norm; INTEGRATION.md "Normalised sums").  h = x_in[n_in, F].  Both degrees are
+    counted from the COO the trainer gets anyway (4-byte work per edge); the edges of the hops < H (the first e_in of block 1, all their
+    sources < n_in) are scaled and aggregated as GraphConvBoth does; the last hop arrives as S_w[N, F], its rows already scaled by
+    out_deg^-1/2 and summed per input slot, to be added into node run_dst[i].  Same parameters as GraphConvBoth, same result up to fp32
+    summation order."""
+
+    def forward(self, block, h):
+        src, dst, num_src, num_dst, e_in, run_dst, nbr_sum = block
+        assert h.shape[0] == num_dst
+        one = torch.ones_like(src, dtype=h.dtype)
+        out_deg = torch.zeros(num_src, dtype=h.dtype, device=h.device).index_add_(0, src, one).clamp(min=1)
+        in_deg = torch.zeros(num_dst, dtype=h.dtype, device=h.device).index_add_(0, dst, one).clamp(min=1)
+        m = (h * out_deg[:num_dst].rsqrt().unsqueeze(1)).index_select(0, src[:e_in])
+        agg = torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, dst[:e_in], m)
+        agg += torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, run_dst, nbr_sum)
+        return self.fc(agg * in_deg.rsqrt().unsqueeze(1))
+
+
 class SAGE(nn.Module):
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, conv=SageMean, first=None):
         super().__init__()
@@ -106,8 +126,13 @@ class SAGE(nn.Module):
         return h
 
 
-def next_batch(ipc_service, feat_len, hops, aggregated=False):
-    out = (ipc_service.get_next_aggregated if aggregated else ipc_service.get_next)(feat_len)   # zero-copy views of server-owned device memory
+def getter(ipc_service, aggregated, norm):
+    """the ipc_service call for the server's hand-off mode: rows, neighbour sums, or out-degree-normalised neighbour sums"""
+    return ipc_service.get_next_aggregated_norm if aggregated and norm else ipc_service.get_next_aggregated if aggregated else ipc_service.get_next
+
+
+def next_batch(ipc_service, feat_len, hops, aggregated=False, norm=0):
+    out = getter(ipc_service, aggregated, norm)(feat_len)   # zero-copy views of server-owned device memory
     sizes = ipc_service.get_block_size()
     features, labels = out[1], out[2]
     blocks = [(out[3 + 2 * k].long(), out[4 + 2 * k].long(), sizes[2 * k], sizes[2 * k + 1]) for k in range(hops)]
@@ -132,8 +157,14 @@ def worker(rank, world, args):
     served_agg = bool(ipc_service.aggregated()) if hasattr(ipc_service, "aggregated") else False
     if served_agg != bool(args.aggregated):
         raise SystemExit("--aggregated must match the server: it %s the last hop (LEGION_AGG_LAST_HOP)" % ("aggregates" if served_agg else "does not aggregate"))
+    served_norm = int(ipc_service.aggregate_norm()) if hasattr(ipc_service, "aggregate_norm") else 0
+    if served_agg and (served_norm != 0) != (args.model == "gcn"):      # the sums must be the ones the first layer adds up
+        raise SystemExit("--model %s --aggregated needs a server that %s the neighbour sums (LEGION_AGG_NORM%s): GraphConvBoth adds rows scaled by "
+                         "out-degree^-1/2, SageMean the rows themselves" % (args.model, "normalises" if args.model == "gcn" else "does not normalise",
+                                                                          "=both" if args.model == "gcn" else " unset"))
+    fused = (GraphConvBothFused if args.model == "gcn" else SageMeanFused) if served_agg else None
     model = SAGE(args.features_num, args.hidden_dim, args.class_num, hops, args.drop_rate,
-                 conv=GraphConvBoth if args.model == "gcn" else SageMean, first=SageMeanFused if served_agg else None).to(device)
+                 conv=GraphConvBoth if args.model == "gcn" else SageMean, first=fused).to(device)
     if world > 1:
         model = DDP(model, device_ids=[rank])
     opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
@@ -144,7 +175,7 @@ def worker(rank, world, args):
         model.eval()
         with torch.no_grad():
             for _ in range(steps):
-                x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg)
+                x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg, served_norm)
                 ok = y >= 0                                  # -1 padded seeds of a short batch
                 pred = model(blocks, x).argmax(1)
                 hit += int((pred[ok] == y[ok]).sum())
@@ -159,7 +190,7 @@ def worker(rank, world, args):
 
     def drain(steps):
         for _ in range(steps):
-            (ipc_service.get_next_aggregated if served_agg else ipc_service.get_next)(args.features_num)
+            getter(ipc_service, served_agg, served_norm)(args.features_num)
             ipc_service.synchronize()
         return float("nan")
 
@@ -173,7 +204,7 @@ def worker(rank, world, args):
         model.train()
         t0, last = time.time(), float("nan")
         for _ in range(train_steps):
-            x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg)
+            x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg, served_norm)
             loss = lp_loss(model(blocks, x)) if args.task == "lp" else loss_fn(model(blocks, x), y)
             opt.zero_grad()
             loss.backward()
@@ -205,10 +236,9 @@ if __name__ == "__main__":
     ap.add_argument("--epoch", type=int, default=100, help="must equal the epoch count in the server's meta_config")
     ap.add_argument("--gpu_num", type=int, default=1)
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed (weights, dropout)")
-    ap.add_argument("--aggregated", action="store_true", help="the server runs with LEGION_AGG_LAST_HOP=1: first layer = SageMeanFused over get_next_aggregated")
+    ap.add_argument("--aggregated", action="store_true", help="the server runs with LEGION_AGG_LAST_HOP=1: first layer = SageMeanFused over get_next_aggregated; "
+                                                              "with --model gcn the server also runs with LEGION_AGG_NORM=both: GraphConvBothFused over get_next_aggregated_norm")
     a = ap.parse_args()
-    if a.aggregated and a.model == "gcn":
-        ap.error("--aggregated serves sum / mean aggregators; GraphConvBoth weights each source row by its out-degree and needs the rows themselves")
     if a.gpu_num == 1:
         worker(0, 1, a)
     else:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the `legion` server process as a trainer sees it: a null consumer (wait -> read counters -> post), or with
 --consumer aggregate a PyTorch consumer that computes the first layer's mean aggregate in both hand-off modes (rows / neighbour sums),
+--consumer aggregate-gcn the same for GraphConv(norm='both')'s first-layer aggregate (rows / out-degree-normalised neighbour sums),
 drains every batch of the schedule through the C-ABI IPC client, for the two RunOnce variants of the runner:
 
     (default)                  enqueue batch i, then wait for batch i-1 and post it (sampler i || gathers i-1)
@@ -80,6 +81,48 @@ def consume_aggregating(epochs, feat_dim):
     print(total, dt, edges)
 
 
+def consume_aggregating_gcn(epochs, feat_dim):
+    """consume_aggregating for GraphConv(norm='both'): the first layer's aggregate [n_in, F] in front of its linear map,
+    sum_{(s,d)} x_s / sqrt(outdeg_s) / sqrt(indeg_d), degrees counted inside block 1 -- from every row of the batch (default), or from the
+    rows of the hops < H plus the last hop's normalised sums (LEGION_AGG_LAST_HOP=1 LEGION_AGG_NORM=both).  Both count the degrees from
+    the COO; both are timed producing the same tensor."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "legion-1_amd", "ipc_service"))
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    import ipc_service
+    from legion_sage_torch import fused_first_block
+    torch.cuda.set_device(0)
+    ipc_service.initialize()
+    steps = ipc_service.get_steps()
+    hops, agg_mode = ipc_service.get_hops(), ipc_service.aggregated()
+    if agg_mode and not ipc_service.aggregate_norm():
+        raise SystemExit("--consumer aggregate-gcn: the server aggregates the last hop without LEGION_AGG_NORM=both")
+    total = (steps[0] + steps[1]) * epochs + steps[2]
+    edges = 0
+    t0 = time.perf_counter()
+    for _ in range(total):
+        out = (ipc_service.get_next_aggregated_norm if agg_mode else ipc_service.get_next)(feat_dim)
+        sizes = ipc_service.get_block_size()
+        x, src, dst, n, n_in = out[1], out[3].long(), out[4].long(), sizes[0], sizes[1]
+        out_w = torch.bincount(src, minlength=n).clamp(min=1).to(x.dtype).rsqrt().unsqueeze(1)
+        in_w = torch.bincount(dst, minlength=n_in).clamp(min=1).to(x.dtype).rsqrt().unsqueeze(1)
+        if agg_mode:
+            _, _, _, _, e_in, run_dst, nbr_sum = fused_first_block(src, dst, n, n_in, [out[3 + 2 * k].numel() for k in range(hops)], out[3 + 2 * hops])
+            agg = torch.zeros(n_in, feat_dim, device=x.device).index_add_(0, dst[:e_in], (x * out_w[:n_in]).index_select(0, src[:e_in]))
+            agg += torch.zeros(n_in, feat_dim, device=x.device).index_add_(0, run_dst.long(), nbr_sum)
+        else:
+            agg = torch.zeros(n_in, feat_dim, device=x.device).index_add_(0, dst, (x * out_w).index_select(0, src))
+        agg = agg * in_w
+        edges += int(src.numel())
+        torch.cuda.synchronize()
+        ipc_service.synchronize()
+    dt = time.perf_counter() - t0
+    check = float(agg.double().sum())            # the last batch's aggregate: the two modes agree to fp32 summation order
+    ipc_service.finalize()
+    print("last-batch GraphConv aggregate sum %.6f (%s)" % (check, "normalised sums" if agg_mode else "default"))
+    print(total, dt, edges)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--consume", type=int, default=0, help="internal: run the null consumer for this many epochs")
@@ -89,9 +132,10 @@ def main():
     ap.add_argument("--fanout", default="25,10")
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--variants", default="all", help="comma list of: pipelined,graph + gather")
-    ap.add_argument("--consumer", default="null", choices=["null", "aggregate"],
+    ap.add_argument("--consumer", default="null", choices=["null", "aggregate", "aggregate-gcn"],
                     help="null: wait -> read counters -> post.  aggregate: a PyTorch consumer that computes the first layer's mean aggregate [n_in, F] "
-                         "of every batch; each variant is then served twice, default hand-off and LEGION_AGG_LAST_HOP=1")
+                         "of every batch; each variant is then served twice, default hand-off and LEGION_AGG_LAST_HOP=1.  aggregate-gcn: the same for "
+                         "GraphConv(norm='both')'s aggregate, default hand-off and LEGION_AGG_LAST_HOP=1 LEGION_AGG_NORM=both")
     ap.add_argument("--features", type=int, default=0, help="internal: feature width for --consume with --consumer aggregate")
     ap.add_argument("--full-eval", action="store_true", help="keep the full validation / test sets (512-seed batches)")
     ap.add_argument("--source", default="files", choices=["files", "synth"],
@@ -99,6 +143,8 @@ def main():
                          "the same tables in its own HBM (meta_config dataset path `synth:<workload>:<scale>`) -- the only way to serve the papers100M / uk-union shapes")
     a = ap.parse_args()
     if a.consume:
+        if a.consumer == "aggregate-gcn":
+            return consume_aggregating_gcn(a.consume, a.features)
         return consume_aggregating(a.consume, a.features) if a.consumer == "aggregate" else consume(a.consume, len(a.fanout.split(",")))
     import legion1_amd.synth as S
     if a.source == "synth":
@@ -131,6 +177,8 @@ def serve_variants(a, tmp, meta, F):
         variants = [v for v in variants[:2] if v[0] in a.variants.split(",")]
     if a.consumer == "aggregate":    # every variant in both hand-off modes, alternating
         variants = [(n + m, dict(e, **x)) for n, e in variants for m, x in ((", rows", {}), (", neighbour sums", {"LEGION_AGG_LAST_HOP": "1"}))]
+    if a.consumer == "aggregate-gcn":
+        variants = [(n + m, dict(e, **x)) for n, e in variants for m, x in ((", rows", {}), (", normalised sums", {"LEGION_AGG_LAST_HOP": "1", "LEGION_AGG_NORM": "both"}))]
     for name, extra in variants:
         ns = "sb%d_%s%s%s_" % (os.getpid(), name[:3], extra.get("LEGION_BATCH_GRAPH", ""), extra.get("LEGION_AGG_LAST_HOP", ""))
         env = dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra)
@@ -147,7 +195,7 @@ def serve_variants(a, tmp, meta, F):
         total, dt, edges = out.stdout.strip().splitlines()[-1].split()
         total, dt, edges = int(total), float(dt), int(edges)
         proc.wait(timeout=60)
-        if a.consumer == "aggregate":
+        if a.consumer != "null":
             print("    " + out.stdout.strip().splitlines()[-2], flush=True)
         print("%-32s %5d batches  %.3f ms/batch  %.2f G edges/s" % (name, total, dt / total * 1e3, edges / dt / 1e9), flush=True)
 

@@ -378,6 +378,17 @@ void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
  * SetAggLastHop allocates the per-pipe draw buffers (4 bytes per slot of the largest hop and pipe) on the current device. */
 void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p);
+/* Normalised sums for GraphConv(norm='both') (extension; INTEGRATION.md "Aggregated last hop", "Normalised sums").  Only together with the
+ * aggregated last hop.  With GPUMemoryPool_SetAggNorm(pool, 1) get_feature_kernel_agg writes into rows [n_in, n_in + N)
+ *   S_w[i, :] = ((0.0f + fl(w[p0] * x[c0])) + fl(w[p1] * x[c1])) + ...   (the product and the add rounded separately, no FMA)
+ * where p_j is the batch position of draw j (the src_off of its last-hop edge), w[p] = fl(1 / fl(sqrt((float)max(d[p], 1)))) and
+ * d[p] = #{ e < ec[2 + H] : src_off[e] == p } is the out-degree of position p inside block 1.  Everything else is as in the plain
+ * aggregated mode.  norm: 0 = none, 1 = out-degree rsqrt; any other value, a pool that does not aggregate the last hop and a pool that is
+ * being captured are sticky argument errors.  Setting it allocates per pipe 4 bytes per id of a batch, 4 per slot of the largest hop and
+ * a few KB on the current device.  GetAggOutDeg: d of the current pipe's last normalised batch (device, int32[n]; for tests). */
+void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm);
+int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p);
+int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p);
 void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                             int32_t dev_id, int in_memory);
 /* Owner-computes exchange variant of the feature gather (SURVEY 5 option b; the reference reads peer caches in-kernel over
@@ -462,6 +473,10 @@ void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows);
  * server without the word reads 0. */
 void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on);
 int32_t IPCEnv_GetAggLastHop(const IPCEnv* e);
+/* ... and, in a word appended behind that one, how the sums are normalised: 0 = plain sums, 1 = out-degree rsqrt (GPUMemoryPool_SetAggNorm;
+ * the runner sets it under LEGION_AGG_NORM=both).  A client of a server without the word reads 0. */
+void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm);
+int32_t IPCEnv_GetAggNorm(const IPCEnv* e);
 int IPCEnv_SlabPinned(IPCEnv* e);   /* 1: the slab is page-locked (hipHostRegister), IPCEnv_MirrorCounters queues real asynchronous copies */
 void IPCEnv_IPCPost(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
 void IPCEnv_IPCWait(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
@@ -500,6 +515,7 @@ int32_t legion_ipc_client_hops(LegionIPCClient* c);
  * and views it unchecked (ipc_cuda_kernel.cu:200). */
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c);
+int32_t legion_ipc_client_agg_norm(LegionIPCClient* c);
 /* both 16-int counters of the current pipe (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
  * a blocking device copy like the reference */
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16]);

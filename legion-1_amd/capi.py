@@ -198,6 +198,9 @@ _SIGS = {
     "get_feature_kernel_agg": (None, [vp, vp, vp, vp, i32, C.c_int]),
     "GPUMemoryPool_SetAggLastHop": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetAggLastHop": (C.c_int, [vp]),
+    "GPUMemoryPool_SetAggNorm": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetAggNorm": (C.c_int, [vp]),
+    "GPUMemoryPool_GetAggOutDeg": (vp, [vp]),
     "legion_exchange_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "legion_exchange_local": (C.c_int, [vp, vp, vp, vp, i32]),
     "legion_exchange_serve": (None, [vp, vp, i32, vp, i32, vp]),
@@ -235,6 +238,7 @@ _SIGS = {
     "IPCEnv_MirroredNodeCounter": (i32, [vp, i32, i32, i32]),
     "IPCEnv_SetFeatureRows": (None, [vp, i32, i32]),
     "IPCEnv_SetAggLastHop": (None, [vp, i32]), "IPCEnv_GetAggLastHop": (i32, [vp]), "legion_ipc_client_agg_last_hop": (i32, [vp]),
+    "IPCEnv_SetAggNorm": (None, [vp, i32]), "IPCEnv_GetAggNorm": (i32, [vp]), "legion_ipc_client_agg_norm": (i32, [vp]),
     "legion_ipc_client_open": (vp, [i32]), "legion_ipc_client_wait": (None, [vp]),
     "legion_ipc_client_post": (None, [vp]), "legion_ipc_client_post_nosync": (None, [vp]), "legion_ipc_client_buffer": (vp, [vp, i32]),
     "legion_ipc_client_steps": (None, [vp, vp]), "legion_ipc_client_hops": (i32, [vp]), "legion_ipc_client_feature_rows": (i32, [vp]),
@@ -448,6 +452,7 @@ class Engine:
         self.streams = [None] * self.G
         self._graphs = []
         self._agg = {}      # (dev, pipe) -> the pipe's last batch was handed over aggregated (run_batch(agg_last_hop=True))
+        self._norm = {}     # (dev, pipe) -> ... with normalised sums (run_batch(agg_norm="both"))
         check()
 
     # ---- feature buffers ------------------------------------------------------------------------------
@@ -465,17 +470,26 @@ class Engine:
 
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
-                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False):
+                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None):
         """agg_last_hop: the aggregated hand-off (get_feature_kernel_agg) -- feature rows of the levels < H (per level behind each hop,
         or all of them inside that call with per_level=False) and the last hop as neighbour sums; result() then returns
-        `features` [n_in, F] and `nbr_sum` [N, F]."""
+        `features` [n_in, F] and `nbr_sum` [N, F].  agg_norm="both" (only with agg_last_hop): the sums weighted by out-degree^-1/2 inside
+        block 1 (GPUMemoryPool_SetAggNorm); result() additionally returns `out_deg` int32 [n]."""
+        if agg_norm not in (None, "both"):
+            raise ValueError("agg_norm: None or 'both'")
+        if agg_norm and not agg_last_hop:
+            raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
         L = self.L
         L.SetGPUDevice(dev)
         pool = self.pools[dev]
         agg = bool(agg_last_hop) and not is_presc     # gather=False: the sampler side of such a batch (the last hop's draws kept per pipe)
         if bool(L.GPUMemoryPool_GetAggLastHop(pool)) != agg:
             L.GPUMemoryPool_SetAggLastHop(pool, int(agg))
+        norm = int(agg and agg_norm == "both")
+        if L.GPUMemoryPool_GetAggNorm(pool) != norm:
+            L.GPUMemoryPool_SetAggNorm(pool, norm)
         self._agg[(dev, pipe)] = agg and gather
+        self._norm[(dev, pipe)] = bool(norm) and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
         L.GPUMemoryPool_SetCurrentMode(pool, mode)
         L.GPUMemoryPool_SetIter(pool, counter)
@@ -500,11 +514,12 @@ class Engine:
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False):
+                      stream=None, agg_last_hop=False, agg_norm=None):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph()."""
         L = self.L
         L.SetGPUDevice(dev)
         L.GPUMemoryPool_SetAggLastHop(self.pools[dev], int(bool(agg_last_hop)))   # allocates: not between Begin and End
+        L.GPUMemoryPool_SetAggNorm(self.pools[dev], int(bool(agg_last_hop) and agg_norm == "both"))   # likewise
         if stream is None:
             if self.streams[dev] is None:
                 self.streams[dev] = L.d_stream_create()
@@ -513,7 +528,7 @@ class Engine:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
-                       stream=stream, sync=False, agg_last_hop=agg_last_hop)
+                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -531,11 +546,13 @@ class Engine:
             self.L.d_stream_sync(stream)
             check()
 
-    def result(self, dev=0, pipe=0, with_features=True, aggregated=None):
+    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None):
         """aggregated: how to read the pipe's feature buffer -- None: as run_batch / capture_batch on this engine left it; True / False
-        for a caller that drove the launchers itself."""
+        for a caller that drove the launchers itself.  normalised: likewise, whether the pipe's block out-degrees are read (`out_deg`)."""
         if aggregated is None:
             aggregated = self._agg.get((dev, pipe), False)
+        if normalised is None:
+            normalised = self._norm.get((dev, pipe), False)
         o = self.out[dev][pipe]
         self.L.SetGPUDevice(dev)
         nc = o["nc"].to_numpy(np.int32, 16)
@@ -553,6 +570,9 @@ class Engine:
             r_sum = max(0, min(n_in + runs, cap) - n_in)
             buf = o["feat"].to_numpy(np.float32, (r_in + r_sum) * self.F).reshape(r_in + r_sum, self.F)
             res["features"], res["nbr_sum"] = buf[:r_in], buf[r_in:]
+            if normalised:
+                self.L.GPUMemoryPool_SetCurrentPipe(self.pools[dev], pipe)
+                res["out_deg"] = read_dev(self.L.GPUMemoryPool_GetAggOutDeg(self.pools[dev]), np.int32, n_nodes)
         elif with_features and o["feat"] is not None:
             rows = min(n_nodes, getattr(self, "feature_rows", n_nodes))
             res["features"] = o["feat"].to_numpy(np.float32, rows * self.F).reshape(rows, self.F)

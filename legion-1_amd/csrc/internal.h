@@ -237,8 +237,25 @@ struct GatherArgs {
 void launch_gather(hipStream_t s, const GatherArgs& a, int32_t rows_bound);
 // Aggregated last hop (kernels.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
 // slots, from the draws in cand[slot * f + j], into rows [nc[3 + 2 * hops], + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
+// wdraw (normalised sums): the weight of every draw by slot, as launch_agg_norm_weights left it; null = plain sums.
 void launch_gather_sum(hipStream_t s, const GatherArgs& a, const int32_t* cand, int32_t cand_cap, const int32_t* ec, int32_t hops,
-                       int32_t f, int32_t runs_bound);
+                       int32_t f, int32_t runs_bound, const float* wdraw = nullptr);
+// Normalised last hop (kernels.hip "S5, normalised last hop"): out_deg[p] = out-degree of batch position p inside block 1 (all edges of
+// the batch), and wdraw[slot] = 1 / sqrt(max(out_deg[position of the slot's draw], 1)) for every slot of the last hop with a draw.
+// Everything here belongs to the batch's pipe.
+struct AggNormArgs {
+    const int32_t* nc;
+    const int32_t* ec;
+    int32_t hops, f;
+    const int32_t* cand;     // the last hop's draws
+    int32_t cand_cap;        // elements of cand and of wdraw
+    const int32_t* src_off;  // the pipe's COO sources (agg_src_off)
+    int32_t ids_cap;         // elements of src_off and of out_deg
+    int32_t* out_deg;
+    int32_t* chunk_cnt;      // int32[kMaxChunks]: draws per chunk of slots
+    float* wdraw;
+};
+void launch_agg_norm_weights(hipStream_t s, const AggNormArgs& a, int32_t slots_bound, int32_t edges_bound);
 // words of GPUMemoryPool::rows_seen: [l] = level-l gather, then one per launch kind below
 constexpr int kRowsSeenAll = LEGION_MAX_HOPS + 1;      // all rows of the batch (get_feature_kernel_all)
 constexpr int kRowsSeenAggIn = LEGION_MAX_HOPS + 2;    // rows of the levels < H (get_feature_kernel_agg)
@@ -310,6 +327,12 @@ struct GPUMemoryPool {
     int32_t sampled_hop = 0;          // hops of the current batch that GPU_Random_Sampling has queued (0 behind batch_generator_kernel)
     bool sampled_presc = false;       // ... as pre-sampling hops
     uint32_t levels_gathered = 0;     // bit l: get_feature_kernel gathered level l of the current batch
+    // Normalised sums (GPUMemoryPool_SetAggNorm, only with agg_last_hop): 1 = every row of the last hop is scaled by the out-degree^-1/2
+    // of its batch position inside block 1 before it is summed (GraphConv norm='both').  Per pipe, allocated when the mode is set:
+    // the degrees (num_ids words), the draws' weights (max_slots floats) and the chunk counts of the slot -> edge prefix.
+    int32_t agg_norm = 0;
+    std::vector<int32_t*> agg_out_deg, agg_chunk_cnt;
+    std::vector<float*> agg_wdraw;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
     int32_t aux_ready_hop = 0, aux_ready_count = 0; // the launch before prepared aux2[hop & 1] for this fan-out
     int32_t* tile_edge = nullptr;

@@ -65,6 +65,9 @@ struct shmExt {
     // server reads 0 here and an older client never looks): 1 = the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1,
     // INTEGRATION.md "Aggregated last hop"): feature rows [0, n_in) are features, rows [n_in, n_in + N) the sums.
     int32_t agg_last_hop;
+    // Appended behind agg_last_hop (nothing above moves): how a server in that mode normalises the sums.  0 = plain sums, 1 = every row scaled by
+    // its out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both, INTEGRATION.md "Normalised sums").  A client of an older server reads 0.
+    int32_t agg_norm;
 };
 static const uint32_t kMirrorMagic = 0x4C474E43u;   // "LGNC"
 static uint32_t handle_checksum(const volatile void* h)
@@ -517,6 +520,8 @@ void IPCEnv_InitializeFeaturesBuffer(IPCEnv* e, int32_t batch_size, int32_t num_
 // the row capacity published to the trainers of a device (a server that re-sizes its feature buffers; tests)
 void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on) { if (e && e->ext) e->ext->agg_last_hop = on ? 1 : 0; }
 int32_t IPCEnv_GetAggLastHop(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_last_hop : 0; }
+void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm) { if (e && e->ext) e->ext->agg_norm = norm; }
+int32_t IPCEnv_GetAggNorm(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_norm : 0; }
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
     if (e && e->ext && device_id >= 0 && device_id < e->device_count) e->ext->feature_rows[device_id] = rows;
@@ -882,6 +887,7 @@ void legion_ipc_client_steps(LegionIPCClient* c, int32_t steps[3])
 }
 int32_t legion_ipc_client_hops(LegionIPCClient* c) { return c->hops; }
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_last_hop : 0; }
+int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_norm : 0; }
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16])
 {

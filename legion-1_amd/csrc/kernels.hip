@@ -879,6 +879,7 @@ struct GatherSumArgs {
     const int32_t* ec;
     int32_t hops, f;
     int32_t cand_cap;        // elements of cand
+    const float* wdraw;      // WT: the weight of every draw, by slot (k_draw_weights; the pipe's own buffer, cand_cap elements)
 };
 // input slots of the last hop, from the counters as apply_update_counter leaves them behind that hop (nc[2] is overwritten by then)
 __device__ inline int32_t last_hop_inputs(const int32_t* nc, const int32_t* ec, int32_t hops)
@@ -886,7 +887,10 @@ __device__ inline int32_t last_hop_inputs(const int32_t* nc, const int32_t* ec, 
     return hops == 1 ? nc[4] : hops == 2 ? ec[3] : ec[1 + hops] - ec[hops];
 }
 
-template <typename VT, int U, bool NT>
+// WT (normalised sums, "S5, normalised last hop" below): every row is scaled by its draw's weight before it is added, the product and the
+// add rounded separately -- S_w[i, :] = ((0.0f + fl(w0 * x0)) + fl(w1 * x1)) + ... -- which is what a trainer computes when it scales the
+// rows first (GraphConv norm='both') and what NumPy states; a fused multiply-add would round once.
+template <typename VT, int U, bool NT, bool WT>
 __global__ __launch_bounds__(kBlock) void k_gather_sum(GatherSumArgs a)
 {
     constexpr int VEC = sizeof(VT) / 4;
@@ -908,10 +912,12 @@ __global__ __launch_bounds__(kBlock) void k_gather_sum(GatherSumArgs a)
             int32_t id[U], gidx[U];
             const VT* src[U];
             VT val[U];
+            float wt[WT ? U : 1];
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int64_t idx = slot0 + j0 + u;
                 id[u] = (j0 + u < a.f && idx < a.cand_cap) ? a.cand[idx] : -1;
+                if constexpr (WT) wt[u] = (j0 + u < a.f && idx < a.cand_cap) ? a.wdraw[idx] : 0.0f;   // streamed beside the draw; read only where the slot has one
             }
 #pragma unroll
             for (int u = 0; u < U; u++) gidx[u] = (id[u] >= 0 && g.feat_map) ? g.feat_map[id[u]] : -1;
@@ -923,11 +929,134 @@ __global__ __launch_bounds__(kBlock) void k_gather_sum(GatherSumArgs a)
 #pragma unroll
             for (int u = 0; u < U; u++)
                 if (src[u]) val[u] = NT ? __builtin_nontemporal_load(src[u]) : *src[u];
+            if constexpr (WT) {
+#pragma clang fp contract(off)
 #pragma unroll
-            for (int u = 0; u < U; u++)
-                if (src[u]) acc = acc + val[u];
+                for (int u = 0; u < U; u++)
+                    if (src[u]) acc = acc + val[u] * wt[u];
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    if (src[u]) acc = acc + val[u];
+            }
         }
         __builtin_nontemporal_store(acc, reinterpret_cast<VT*>(g.dst) + ((int64_t)(n_in + (int32_t)i) * g.F) / VEC + ch);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// S5, normalised last hop (no counterpart in the reference): the sums a GraphConv(norm='both') first layer needs
+// ------------------------------------------------------------------------------------------------
+// GraphConv(norm='both') scales every source row of block 1 by outdeg^-1/2, the out-degree counted INSIDE the block:
+//   d[p] = #{ e < E : src_off[e] == p },  w[p] = 1.0f / sqrtf((float)max(d[p], 1))    (both correctly rounded)
+// The block is the server's own output, so the server can weight the last hop's rows before it sums them (k_gather_sum<WT>).  Three
+// small passes in front of the sums, all over data of the batch's PIPE (its draws, its COO, its counters: the pool's shared sampler
+// scratch belongs to the next batch by then):
+//   k_agg_norm_prep     zeroes d[0, n) and counts the draws (slots with cand != -1) of each chunk of slots;
+//   k_block_out_deg     counts d over src_off[0, E) with integer atomics (order-independent: reproducible), one atomic per run of
+//                       equal neighbouring lanes -- hub positions repeat in adjacent lanes;
+//   k_draw_weights      k_write appended the last hop's edges in slot order, one per slot with a draw, so the edge of such a slot is
+//                       (edges of the hops < H) + (draws in front of it): every workgroup adds up the chunk counts in front of its
+//                       chunk (<= kMaxChunks words, no scan launch, no device-scope hand-off: k_write's scheme), ranks its slots by
+//                       ballot, and leaves wdraw[slot] = w[src_off[edge]].
+// A chunk is a contiguous range of slots, the same for the first and the third pass (both derive it from the slot count on the device
+// and their common grid).
+__device__ inline int64_t agg_norm_chunk_len(int64_t total, int32_t chunks)
+{
+    const int64_t per = (total + chunks - 1) / chunks;
+    return (per + kBlock - 1) / kBlock * kBlock;
+}
+__device__ inline int64_t agg_norm_slots(const AggNormArgs& a)
+{
+    return min((int64_t)last_hop_inputs(a.nc, a.ec, a.hops) * a.f, (int64_t)a.cand_cap);
+}
+
+__global__ __launch_bounds__(kBlock) void k_agg_norm_prep(AggNormArgs a)
+{
+    constexpr int W = kBlock / 64;
+    __shared__ int32_t s_w[W];
+    const int32_t n = min(a.nc[5 + 2 * a.hops], a.ids_cap);
+    for (int32_t p = (int32_t)(blockIdx.x * kBlock + threadIdx.x); p < n; p += (int32_t)(gridDim.x * kBlock)) a.out_deg[p] = 0;
+    const int64_t total = agg_norm_slots(a);
+    const int64_t len = agg_norm_chunk_len(total, (int32_t)gridDim.x);
+    const int64_t lo = min((int64_t)blockIdx.x * len, total), hi = min(lo + len, total);
+    int32_t mine = 0;
+    for (int64_t idx = lo + threadIdx.x; idx < hi; idx += kBlock) mine += a.cand[idx] != -1;
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if (lane_id() == 0) s_w[wave_id()] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) t += s_w[w];
+        a.chunk_cnt[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_block_out_deg(AggNormArgs a)
+{
+    const int32_t E = min(a.ec[2 + a.hops], a.ids_cap);
+    const int lane = lane_id();
+    const int32_t stride = (int32_t)(gridDim.x * kBlock);
+    for (int32_t base = (int32_t)(blockIdx.x * kBlock); base < E; base += stride) {   // whole waves: the lanes settle their repeats together
+        const int32_t e = base + (int32_t)threadIdx.x;
+        const bool valid = e < E;
+        const int32_t p = valid ? a.src_off[e] : -1;
+        const int32_t before = __shfl_up(p, 1);
+        const bool head = valid && (lane == 0 || before != p);
+        // a run of equal positions ends in front of the next head or the first lane beyond E: its head adds the run's length
+        const unsigned long long ends = __ballot(head) | ~__ballot(valid);
+        const unsigned long long above = lane == 63 ? 0ull : ends & ~((2ull << lane) - 1ull);
+        const int32_t run = (above ? __ffsll((long long)above) - 1 : 64) - lane;
+        if (head && LEGION_STORE_OK(p, a.ids_cap)) atomicAdd(a.out_deg + p, run);     // no return value: fire and forget
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_draw_weights(AggNormArgs a)
+{
+    constexpr int W = kBlock / 64, PER = kMaxChunks / kBlock;
+    __shared__ int32_t s_w[W];
+    __shared__ int32_t s_c[W];
+    const int lane = lane_id(), wave = wave_id();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    // draws in front of this workgroup's chunk
+    int32_t mine = 0;
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int32_t c = (int32_t)threadIdx.x + kBlock * u;
+        if (c < (int32_t)blockIdx.x) mine += a.chunk_cnt[c];
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if (lane == 0) s_w[wave] = mine;
+    __syncthreads();
+    int32_t rank0 = 0;
+#pragma unroll
+    for (int w = 0; w < W; w++) rank0 += s_w[w];
+    const int32_t e_in = a.hops == 1 ? 0 : a.ec[1 + a.hops];     // edges of the hops < H
+    const int32_t E = min(a.ec[2 + a.hops], a.ids_cap);
+    const int64_t total = agg_norm_slots(a);
+    const int64_t len = agg_norm_chunk_len(total, (int32_t)gridDim.x);
+    const int64_t lo = min((int64_t)blockIdx.x * len, total), hi = min(lo + len, total);
+    for (int64_t s0 = lo; s0 < hi; s0 += kBlock) {
+        const int64_t idx = s0 + threadIdx.x;
+        const bool draw = idx < hi && a.cand[idx] != -1;
+        const unsigned long long b = __ballot(draw);
+        if (lane == 0) s_c[wave] = __popcll(b);
+        __syncthreads();
+        int32_t r = rank0 + __popcll(b & lt), all = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            if (w < wave) r += s_c[w];
+            all += s_c[w];
+        }
+        if (draw) {
+            const int32_t e = e_in + r;
+            const int32_t p = e < E ? a.src_off[e] : -1;
+            const int32_t d = LEGION_STORE_OK(p, a.ids_cap) ? a.out_deg[p] : 1;
+            a.wdraw[idx] = 1.0f / sqrtf((float)max(d, 1));
+        }
+        rank0 += all;
+        __syncthreads();
     }
 }
 
@@ -1386,16 +1515,16 @@ void launch_gather(hipStream_t s, const GatherArgs& g, int32_t rows_bound)
 }
 
 void launch_gather_sum(hipStream_t s, const GatherArgs& g, const int32_t* cand, int32_t cand_cap, const int32_t* ec, int32_t hops,
-                       int32_t f, int32_t runs_bound)
+                       int32_t f, int32_t runs_bound, const float* wdraw)
 {
     if (g.F <= 0 || runs_bound <= 0 || f <= 0) return;
     GatherSumArgs a;
     a.g = g;
     a.g.row_ptr = nullptr;
     a.div_cap = FastDiv((uint32_t)(g.cache_capacity > 0 ? g.cache_capacity : 1));
-    a.cand = cand; a.cand_cap = cand_cap; a.ec = ec; a.hops = hops; a.f = f;
-    // the draws are scratch of this GPU and the sums are written into its feature buffer; the backing table may be the host's or a peer's
-    LEGION_AUDIT_LAUNCH(s, "k_gather_sum", LEGION_AW(g.dst), LEGION_AW(g.rows_seen), LEGION_AL(cand), LEGION_AL(g.nc), LEGION_AL(ec), LEGION_AL(g.feat_map), LEGION_AL(g.shard_tab), LEGION_AR(g.table));
+    a.cand = cand; a.cand_cap = cand_cap; a.ec = ec; a.hops = hops; a.f = f; a.wdraw = wdraw;
+    // the draws (and their weights) are scratch of this GPU and the sums are written into its feature buffer; the backing table may be the host's or a peer's
+    LEGION_AUDIT_LAUNCH(s, "k_gather_sum", LEGION_AW(g.dst), LEGION_AW(g.rows_seen), LEGION_AL(cand), LEGION_AL(wdraw), LEGION_AL(g.nc), LEGION_AL(ec), LEGION_AL(g.feat_map), LEGION_AL(g.shard_tab), LEGION_AR(g.table));
     const bool vec4 = (g.F % 4 == 0) && (((uintptr_t)g.table | (uintptr_t)g.dst) % 16 == 0);   // same element paths as launch_gather
     const int C = vec4 ? g.F / 4 : g.F;
     if ((int64_t)runs_bound * C >= (1ll << 31)) { LEGION_ARG_ERROR("get_feature_kernel_agg: rows*F exceeds 2^31 work items"); return; }
@@ -1405,8 +1534,29 @@ void launch_gather_sum(hipStream_t s, const GatherArgs& g, const int32_t* cand, 
     const int64_t est = g.rows_hint > 0 ? std::min<int64_t>(runs_bound, (int64_t)g.rows_hint + g.rows_hint / 4 + 1024) : runs_bound;
     const int grid = grid_for(est * C, kBlock, 8192);
     constexpr bool NT = LEGION_AGG_NT_LOADS != 0;
-    if (vec4) k_gather_sum<v4f, 8, NT><<<grid, kBlock, 0, s>>>(a);
-    else k_gather_sum<float, 8, NT><<<grid, kBlock, 0, s>>>(a);
+    if (wdraw) {
+        if (vec4) k_gather_sum<v4f, 8, NT, true><<<grid, kBlock, 0, s>>>(a);
+        else k_gather_sum<float, 8, NT, true><<<grid, kBlock, 0, s>>>(a);
+    } else {
+        if (vec4) k_gather_sum<v4f, 8, NT, false><<<grid, kBlock, 0, s>>>(a);
+        else k_gather_sum<float, 8, NT, false><<<grid, kBlock, 0, s>>>(a);
+    }
+    HIP_CHECK_LAST();
+}
+
+void launch_agg_norm_weights(hipStream_t s, const AggNormArgs& a, int32_t slots_bound, int32_t edges_bound)
+{
+    if (slots_bound <= 0 || a.f <= 0) return;
+    // every buffer is the pipe's own, on this GPU; grids from the static bounds of the hop and of the batch, loop bounds from the counters
+    const int chunks = std::min<int64_t>(kMaxChunks, grid_for(slots_bound, kBlock));   // one grid for both chunked passes
+    LEGION_AUDIT_LAUNCH(s, "k_agg_norm_prep", LEGION_AW(a.out_deg), LEGION_AW(a.chunk_cnt), LEGION_AL(a.cand), LEGION_AL(a.nc), LEGION_AL(a.ec));
+    k_agg_norm_prep<<<chunks, kBlock, 0, s>>>(a);
+    HIP_CHECK_LAST();
+    LEGION_AUDIT_LAUNCH(s, "k_block_out_deg", LEGION_AW(a.out_deg), LEGION_AL(a.src_off), LEGION_AL(a.ec));
+    k_block_out_deg<<<grid_for(edges_bound, kBlock), kBlock, 0, s>>>(a);
+    HIP_CHECK_LAST();
+    LEGION_AUDIT_LAUNCH(s, "k_draw_weights", LEGION_AW(a.wdraw), LEGION_AL(a.out_deg), LEGION_AL(a.chunk_cnt), LEGION_AL(a.cand), LEGION_AL(a.src_off), LEGION_AL(a.nc), LEGION_AL(a.ec));
+    k_draw_weights<<<chunks, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
 }
 

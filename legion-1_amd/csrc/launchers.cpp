@@ -53,6 +53,9 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         LEGION_AUDIT_OWNER(p->pos_map, dev_id, "batch_generator_kernel: scratch of the memory pool");
         LEGION_AUDIT_OWNER(p->cand, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (int32_t* c : p->cand_pipe) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (int32_t* c : p->agg_out_deg) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (int32_t* c : p->agg_chunk_cnt) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (float* c : p->agg_wdraw) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (int i = 0; i < p->pipeline_depth; i++) {
             LEGION_AUDIT_OWNER(p->sampled_ids[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
             LEGION_AUDIT_OWNER(p->node_counter[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
@@ -261,6 +264,9 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (p->sampled_hop != H) { LEGION_ARG_ERROR("get_feature_kernel_agg: called before the last hop's GPU_Random_Sampling"); return; }
     if (p->sampled_presc) { LEGION_ARG_ERROR("get_feature_kernel_agg: a pre-sampling batch gathers nothing"); return; }
     if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe draw buffers are missing"); return; }
+    const bool norm = p->agg_norm != 0;
+    if (norm && ((int)p->agg_out_deg.size() <= q || !p->agg_out_deg[q] || !p->agg_wdraw[q] || !p->agg_chunk_cnt[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe buffers of the normalised sums are missing (GPUMemoryPool_SetAggNorm before AllocateScratch failed?)"); return; }
+    if (norm && !p->agg_src_off[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the COO buffers of the current pipe are not set"); return; }
     if (!in_memory) return;
     GatherArgs g;
     if (!gather_args(g, cache, noder, p, dev_id, -1, 3 + 2 * H, false)) return;   // rows [0, nc[3 + 2H]); the hit counter belongs to the default mode's batches
@@ -274,7 +280,16 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
         launch_gather((hipStream_t)strm_hdl, g, p->num_ids - p->level_bound[H]);
     }
     feedback(kRowsSeenAggRuns);
-    launch_gather_sum((hipStream_t)strm_hdl, g, p->cand_pipe[q], p->max_slots, p->edge_counter[q], H, p->fanout[H - 1], p->level_bound[H - 1]);
+    if (norm) {   // the block's out-degrees and every draw's weight, from the pipe's own COO and draws, in front of the weighted sums
+        legion::AggNormArgs w;
+        w.nc = p->node_counter[q]; w.ec = p->edge_counter[q]; w.hops = H; w.f = p->fanout[H - 1];
+        w.cand = p->cand_pipe[q]; w.cand_cap = p->max_slots; w.src_off = p->agg_src_off[q]; w.ids_cap = p->num_ids;
+        w.out_deg = p->agg_out_deg[q]; w.chunk_cnt = p->agg_chunk_cnt[q]; w.wdraw = p->agg_wdraw[q];
+        const int64_t slots = (int64_t)p->level_bound[H - 1] * p->fanout[H - 1];
+        launch_agg_norm_weights((hipStream_t)strm_hdl, w, (int32_t)std::min<int64_t>(slots, p->max_slots), p->num_ids);
+    }
+    launch_gather_sum((hipStream_t)strm_hdl, g, p->cand_pipe[q], p->max_slots, p->edge_counter[q], H, p->fanout[H - 1], p->level_bound[H - 1],
+                      norm ? p->agg_wdraw[q] : nullptr);
 }
 
 void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,

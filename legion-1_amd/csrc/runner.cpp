@@ -52,6 +52,9 @@ struct Runner {
     // $LEGION_AGG_LAST_HOP=1: the last hop is handed over as neighbour sums (get_feature_kernel_agg on stream 1 behind the last hop instead of
     // the last level's gather; INTEGRATION.md "Aggregated last hop").  The feature buffers then hold n_in + N rows per batch, not n.
     bool agg_last_hop = false;
+    // $LEGION_AGG_NORM=both (only with LEGION_AGG_LAST_HOP=1): the sums are weighted for GraphConv(norm='both') -- every row by the
+    // out-degree^-1/2 of its batch position inside block 1 (INTEGRATION.md "Normalised sums").  Same rows, same buffer sizing.
+    int32_t agg_norm = 0;
     int32_t presc_max_rows = 0;     // largest n_in + N of the pre-sampling epoch (read back per batch: that epoch is not pipelined anyway)
     bool pending = false;
     int pending_pipe = 0;
@@ -69,6 +72,18 @@ struct Runner {
 static int32_t agg_rows(const int32_t* nc, const int32_t* ec, int H)
 {
     return nc[3 + 2 * H] + (H == 1 ? nc[4] : H == 2 ? ec[3] : ec[1 + H] - ec[H]);
+}
+
+// $LEGION_AGG_NORM: unset / empty = plain sums (0), "both" = out-degree rsqrt (1) and only on a server that aggregates the last hop.
+// Returns the mode, or -1 with the refusal in `why`.
+static int32_t agg_norm_from_env(std::string& why)
+{
+    const char* n = getenv("LEGION_AGG_NORM");
+    if (!n || !n[0]) return 0;
+    if (strcmp(n, "both") != 0) { why = std::string("LEGION_AGG_NORM=") + n + " is not a known norm: `both` (GraphConv norm='both', out-degree rsqrt inside block 1) or unset"; return -1; }
+    const char* a = getenv("LEGION_AGG_LAST_HOP");
+    if (!a || atoi(a) == 0) { why = "LEGION_AGG_NORM=both needs LEGION_AGG_LAST_HOP=1: only the last hop's neighbour sums are normalised"; return -1; }
+    return 1;
 }
 
 static void hand_over(Runner* r, IPCEnv* env, int pipe)
@@ -235,6 +250,12 @@ Runner* NewGPURunner(void) { return new Runner(); }
 void Runner_Initialize(Runner* r, RunnerParams* params)
 {
     if (!r || !params || !params->fanout || params->hops < 1 || params->hops > LEGION_MAX_HOPS) { LEGION_ARG_ERROR("Runner_Initialize: bad arguments"); return; }
+    {
+        std::string why;
+        const int32_t norm = agg_norm_from_env(why);
+        if (norm < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
+        r->agg_norm = norm;
+    }
     r->local_dev_id = params->device_id;
     DeviceGuard guard(r->local_dev_id);
     GPUCache* cache = (GPUCache*)params->cache;
@@ -274,6 +295,11 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
         GPUMemoryPool_SetAggLastHop(r->memorypool, 1);      // one draw buffer per pipe, here on this runner's GPU
         IPCEnv_SetAggLastHop(env, 1);                        // what a trainer reads: ipc_service.aggregated()
         log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
+    }
+    if (r->agg_norm) {
+        GPUMemoryPool_SetAggNorm(r->memorypool, r->agg_norm);   // degrees, draw weights and chunk counts per pipe, on this runner's GPU
+        IPCEnv_SetAggNorm(env, r->agg_norm);                    // what a trainer reads: ipc_service.aggregate_norm()
+        log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
     }
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");
@@ -885,6 +911,10 @@ void Server_Initialize(Server* s, int global_shard_count)
     log_out() << "HIP Device Count: " << global_shard_count << "\n";
     const std::string refused = read_meta(s->meta_path, s->meta);
     if (!refused.empty()) { LEGION_ARG_ERROR(refused.c_str()); return; }
+    {   // the hand-off switches, before any device is touched
+        std::string why;
+        if (agg_norm_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
+    }
     const Meta& m = s->meta;
     // from the first device call on the main thread works on GPU 0 unless a scope below says otherwise (the reference's main thread never
     // leaves device 0); not before the meta line and the synth: source are validated -- a refused configuration touches no device

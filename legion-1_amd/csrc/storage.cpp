@@ -452,6 +452,20 @@ static void alloc_agg_cand(GPUMemoryPool* p)
         if (!c) HIP_CHECK(hipMalloc(&c, (size_t)p->max_slots * sizeof(int32_t)));
 }
 
+// the per-pipe buffers of the normalised sums (GPUMemoryPool::agg_out_deg / agg_wdraw / agg_chunk_cnt), on the current device
+static void alloc_agg_norm(GPUMemoryPool* p)
+{
+    p->agg_out_deg.resize(p->pipeline_depth, nullptr);
+    p->agg_wdraw.resize(p->pipeline_depth, nullptr);
+    p->agg_chunk_cnt.resize(p->pipeline_depth, nullptr);
+    for (auto& d : p->agg_out_deg)
+        if (!d) HIP_CHECK(hipMalloc(&d, (size_t)p->num_ids * sizeof(int32_t)));
+    for (auto& w : p->agg_wdraw)
+        if (!w) HIP_CHECK(hipMalloc(&w, (size_t)p->max_slots * sizeof(float)));
+    for (auto& c : p->agg_chunk_cnt)
+        if (!c) HIP_CHECK(hipMalloc(&c, (size_t)legion::kMaxChunks * sizeof(int32_t)));
+}
+
 extern "C" {
 
 GPUMemoryPool* NewGPUMemoryPool(int32_t pipeline_depth) { return new GPUMemoryPool(pipeline_depth); }
@@ -500,6 +514,7 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
     HIP_CHECK(hipMalloc(&p->tmp_part_ind, (size_t)p->num_ids));
     HIP_CHECK(hipMalloc(&p->tmp_part_off, (size_t)p->num_ids * sizeof(int32_t)));
     if (p->agg_last_hop) alloc_agg_cand(p);
+    if (p->agg_last_hop && p->agg_norm) alloc_agg_norm(p);
     HIP_CHECK(hipDeviceSynchronize());
 }
 int32_t GPUMemoryPool_NumIds(const GPUMemoryPool* p) { return p->num_ids; }
@@ -514,6 +529,26 @@ void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on)
     if (p->agg_last_hop && p->owns_scratch) alloc_agg_cand(p);
 }
 int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->agg_last_hop ? 1 : 0; }
+
+// Normalised sums: 0 = plain neighbour sums, 1 = every row scaled by the out-degree^-1/2 of its batch position inside block 1 (GraphConv
+// norm='both').  Only a pool that aggregates the last hop can normalise; the mode stays set while the aggregated mode is switched off
+// and on again.  Call it under the device the pool's scratch lives on.
+void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: null pool"); return; }
+    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool is being captured"); return; }
+    if (norm != 0 && norm != 1) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: unknown norm (0 = none, 1 = out-degree rsqrt)"); return; }
+    if (norm && !p->agg_last_hop) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return; }
+    p->agg_norm = norm;
+    if (norm && p->owns_scratch) alloc_agg_norm(p);
+}
+int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->agg_norm : 0; }
+// the current pipe's block out-degrees as the last normalised batch left them (int32[nc[5 + 2H]]); null before the mode was set
+int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p)
+{
+    if (!p || p->current_pipe < 0 || p->current_pipe >= (int)p->agg_out_deg.size()) return nullptr;
+    return p->agg_out_deg[p->current_pipe];
+}
 
 #define POOL_PIPE_SETTER(name, field, type) \
     void GPUMemoryPool_Set##name(GPUMemoryPool* p, type* ptr, int32_t pipe) { \
@@ -551,6 +586,9 @@ void GPUMemoryPool_Finalize(GPUMemoryPool* p)
     (void)hipFree(p->hop_state); (void)hipFree(p->cache_search_buffer); (void)hipFree((void*)p->row_ptr); p->row_ptr = nullptr; (void)hipFree(p->agg_src_ids);
     (void)hipFree(p->tmp_part_ind); (void)hipFree(p->tmp_part_off); (void)hipFree(p->ctl); p->ctl = nullptr; if (p->rows_seen) { (void)hipHostFree(p->rows_seen); p->rows_seen = nullptr; p->rows_seen_dev = nullptr; }
     for (auto& c : p->cand_pipe) { (void)hipFree(c); c = nullptr; }
+    for (auto& c : p->agg_out_deg) { (void)hipFree(c); c = nullptr; }
+    for (auto& c : p->agg_wdraw) { (void)hipFree(c); c = nullptr; }
+    for (auto& c : p->agg_chunk_cnt) { (void)hipFree(c); c = nullptr; }
     p->pos_map = nullptr; p->cand = nullptr; p->tile_edge = p->tile_node = nullptr; p->hop_state = nullptr;
     p->cache_search_buffer = p->agg_src_ids = p->tmp_part_off = nullptr; p->tmp_part_ind = nullptr;
     p->owns_scratch = false;

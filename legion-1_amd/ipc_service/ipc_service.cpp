@@ -20,6 +20,7 @@ static int32_t h_node_counter[16];
 static int32_t h_edge_counter[16];
 static int32_t g_hops = 2;
 static bool g_aggregated = false;   // the server hands the last hop over as neighbour sums (read once, in initialize)
+static int g_agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
 // ONE consumer thread per process is the contract (the reference's trainer loop, legion_graphsage.py:72-89):
 // get_next / synchronize run without the GIL and share `env`, the two counter arrays and the client's current pipe, so the entry points
 // are serialised by this lock -- uncontended in the reference's loop, and a second Python thread gets whole counters instead of torn ones.
@@ -36,6 +37,7 @@ void InitializeIPC()
     TORCH_CHECK(env != nullptr, "ipc_service: cannot attach to the sampling server: ", legion_last_error());
     g_hops = legion_ipc_client_hops(env);
     g_aggregated = legion_ipc_client_agg_last_hop(env) != 0;
+    g_agg_norm = legion_ipc_client_agg_norm(env);
 }
 
 void FinalizeIPC()
@@ -47,10 +49,15 @@ void FinalizeIPC()
 // One batch of either hand-off mode.  Default: [ids, features[n, F], labels, (src, dst) x H].  Aggregated (the server runs with
 // LEGION_AGG_LAST_HOP=1): [ids, x_in[n_in, F], labels, (src, dst) x H, S[N, F]] -- feature rows of the nodes found before the last hop, and
 // one row of neighbour sums per input slot of the last hop, both views of the same server buffer (INTEGRATION.md "Aggregated last hop").
-static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated)
+// norm: what the caller expects of the sums (0 = plain, 1 = out-degree rsqrt, S_w of INTEGRATION.md "Normalised sums"): same tensors, other values.
+static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated, int norm = 0)
 {
     std::lock_guard<std::mutex> lock(g_mu);
     require_env();
+    TORCH_CHECK(!aggregated || !g_aggregated || norm != 0 || g_agg_norm == 0, "ipc_service.get_next_aggregated: the server normalises the neighbour sums (LEGION_AGG_NORM=both): "
+                "every row is scaled by its out-degree^-1/2 inside block 1 -- call get_next_aggregated_norm");
+    TORCH_CHECK(!aggregated || norm == 0 || (g_aggregated && g_agg_norm == norm), "ipc_service.get_next_aggregated_norm: the server does not normalise the neighbour sums (start it with "
+                "LEGION_AGG_LAST_HOP=1 LEGION_AGG_NORM=both) -- call ", g_aggregated ? "get_next_aggregated" : "get_next");
     TORCH_CHECK(aggregated || !g_aggregated, "ipc_service.get_next: the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1): rows >= n_in of "
                 "its feature buffer are sums, not features -- call get_next_aggregated");
     TORCH_CHECK(!aggregated || g_aggregated, "ipc_service.get_next_aggregated: the server does not aggregate the last hop (start it with LEGION_AGG_LAST_HOP=1) -- call get_next");
@@ -90,7 +97,9 @@ static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated)
 
 std::vector<torch::Tensor> get_next(int feature_dim) { return next_batch(feature_dim, false); }
 std::vector<torch::Tensor> get_next_aggregated(int feature_dim) { return next_batch(feature_dim, true); }
+std::vector<torch::Tensor> get_next_aggregated_norm(int feature_dim) { return next_batch(feature_dim, true, 1); }
 bool aggregated() { require_env(); return g_aggregated; }
+int aggregate_norm() { require_env(); return g_agg_norm; }
 
 // [b1_src_nodes, b1_dst_nodes, b2_src_nodes, b2_dst_nodes, ...] = [nc9, nc7, nc7, nc5] at H = 2
 // (ipc_service.cpp:60-72)
@@ -131,7 +140,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     // (the reference holds it: a trainer's other Python threads stall for as long as the server takes to produce a batch)
     m.def("get_next", &get_next, "dataset get next (HIP)", pybind11::call_guard<pybind11::gil_scoped_release>());
     m.def("get_next_aggregated", &get_next_aggregated, "next batch of a server that hands the last hop over as neighbour sums (extension)", pybind11::call_guard<pybind11::gil_scoped_release>());
+    m.def("get_next_aggregated_norm", &get_next_aggregated_norm, "next batch of a server that hands the last hop over as out-degree-normalised neighbour sums (extension)", pybind11::call_guard<pybind11::gil_scoped_release>());
     m.def("aggregated", &aggregated, "whether the server hands the last hop over as neighbour sums (extension)");
+    m.def("aggregate_norm", &aggregate_norm, "how the server normalises the neighbour sums: 0 = not, 1 = out-degree rsqrt inside block 1 (extension)");
     m.def("get_block_size", &get_block_size, "get dgl block size");
     m.def("get_steps", &get_steps, "get steps");
     m.def("initialize", &InitializeIPC, "InitializeIPC");
