@@ -154,6 +154,8 @@ def worker(rank, world, args):
     ipc_service.initialize()
     train_steps, valid_steps, test_steps = ipc_service.get_steps()
     hops = ipc_service.get_hops() if hasattr(ipc_service, "get_hops") else 2
+    if rank == 0:   # how the server's sampler draws (LEGION_SAMPLING): "replace" like the reference, or "distinct" neighbours per row
+        print("Server sampling mode: %s" % (ipc_service.sampling() if hasattr(ipc_service, "sampling") else "replace"), flush=True)
     served_agg = bool(ipc_service.aggregated()) if hasattr(ipc_service, "aggregated") else False
     if served_agg != bool(args.aggregated):
         raise SystemExit("--aggregated must match the server: it %s the last hop (LEGION_AGG_LAST_HOP)" % ("aggregates" if served_agg else "does not aggregate"))

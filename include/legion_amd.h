@@ -391,6 +391,14 @@ int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p);
 int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p);
 void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                             int32_t dev_id, int in_memory);
+/* Sampling without replacement (extension; INTEGRATION.md "Sampling without replacement").  With GPUMemoryPool_SetSampleDistinct(pool, 1)
+ * every GPU_Random_Sampling of the pool, pre-sampling hops included, gives a row of degree d and fan-out f min(d, f) DISTINCT neighbour
+ * positions: all of them in CSR order when d <= f, else Floyd's algorithm over hashed randoms of (hop, row of the hop's input list).
+ * Everything behind the position -- the dst < 0 rule, claim / mark / write, the counters, both COO arrays, agg_src_ids, the parked draws --
+ * is the default mode's.  GPU_Random_Sampling keeps the reference's signature: the mode lives in the pool.  A fan-out above 64 in this
+ * mode and a switch while the pool is being captured are sticky argument errors.  Nothing is allocated. */
+void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on);
+int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p);
 /* Owner-computes exchange variant of the feature gather (SURVEY 5 option b; the reference reads peer caches in-kernel over
  * NVLink, Kernels.cu:662-702 -- this is the collective formulation for one process per GPU, the all-to-all itself is RCCL /
  * hipMemcpyPeer in the caller: legion-1_amd/exchange.py).  plan (requester): rows of the batch cached on another clique member are
@@ -477,6 +485,11 @@ int32_t IPCEnv_GetAggLastHop(const IPCEnv* e);
  * the runner sets it under LEGION_AGG_NORM=both).  A client of a server without the word reads 0. */
 void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm);
 int32_t IPCEnv_GetAggNorm(const IPCEnv* e);
+/* ... and, in a word appended behind that one, how the server's sampler draws: 0 = with replacement (the reference's stream), 1 = distinct
+ * neighbours (GPUMemoryPool_SetSampleDistinct; the runner sets it under LEGION_SAMPLING=distinct).  A client of a server without the
+ * word reads 0. */
+void IPCEnv_SetSampling(IPCEnv* e, int32_t mode);
+int32_t IPCEnv_GetSampling(const IPCEnv* e);
 int IPCEnv_SlabPinned(IPCEnv* e);   /* 1: the slab is page-locked (hipHostRegister), IPCEnv_MirrorCounters queues real asynchronous copies */
 void IPCEnv_IPCPost(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
 void IPCEnv_IPCWait(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
@@ -516,6 +529,7 @@ int32_t legion_ipc_client_hops(LegionIPCClient* c);
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c);
+int32_t legion_ipc_client_sampling(LegionIPCClient* c);
 /* both 16-int counters of the current pipe (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
  * a blocking device copy like the reference */
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16]);
@@ -603,6 +617,9 @@ int legion_copy_f4_cfg(void* stream, void* dst, const void* src, int64_t bytes, 
 /* RNG probe: k[i] = sample index for (idx[i], deg[i]) computed ON THE GPU with the kernel's
  * own arithmetic (Kernels.cu:402-405 semantics). */
 void legion_rng_probe(void* stream, const int32_t* idx, const int32_t* deg, int32_t* k_out, int32_t n);
+/* Distinct-mode probe: pos_out[m * f + j] = the neighbour position slot j of row row[m] of hop hop[m] takes at degree deg[m] and fan-out
+ * f (1..64), computed ON THE GPU with k_sample's own device functions; -1 = the slot has no draw.  All pointers are device memory. */
+void legion_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos_out, int32_t n);
 
 #ifdef __cplusplus
 }

@@ -201,6 +201,8 @@ _SIGS = {
     "GPUMemoryPool_SetAggNorm": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetAggNorm": (C.c_int, [vp]),
     "GPUMemoryPool_GetAggOutDeg": (vp, [vp]),
+    "GPUMemoryPool_SetSampleDistinct": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetSampleDistinct": (C.c_int, [vp]),
     "legion_exchange_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "legion_exchange_local": (C.c_int, [vp, vp, vp, vp, i32]),
     "legion_exchange_serve": (None, [vp, vp, i32, vp, i32, vp]),
@@ -239,6 +241,7 @@ _SIGS = {
     "IPCEnv_SetFeatureRows": (None, [vp, i32, i32]),
     "IPCEnv_SetAggLastHop": (None, [vp, i32]), "IPCEnv_GetAggLastHop": (i32, [vp]), "legion_ipc_client_agg_last_hop": (i32, [vp]),
     "IPCEnv_SetAggNorm": (None, [vp, i32]), "IPCEnv_GetAggNorm": (i32, [vp]), "legion_ipc_client_agg_norm": (i32, [vp]),
+    "IPCEnv_SetSampling": (None, [vp, i32]), "IPCEnv_GetSampling": (i32, [vp]), "legion_ipc_client_sampling": (i32, [vp]),
     "legion_ipc_client_open": (vp, [i32]), "legion_ipc_client_wait": (None, [vp]),
     "legion_ipc_client_post": (None, [vp]), "legion_ipc_client_post_nosync": (None, [vp]), "legion_ipc_client_buffer": (vp, [vp, i32]),
     "legion_ipc_client_steps": (None, [vp, vp]), "legion_ipc_client_hops": (i32, [vp]), "legion_ipc_client_feature_rows": (i32, [vp]),
@@ -268,6 +271,7 @@ _SIGS = {
     "GPUMemoryPool_GetCandidateBuffer": (vp, [vp]),
     "legion_copy_f4_cfg": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32]),
     "legion_rng_probe": (None, [vp, vp, vp, vp, i32]),
+    "legion_distinct_probe": (None, [vp, vp, vp, vp, i32, vp, i32]),
 }
 
 
@@ -470,8 +474,11 @@ class Engine:
 
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
-                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None):
-        """agg_last_hop: the aggregated hand-off (get_feature_kernel_agg) -- feature rows of the levels < H (per level behind each hop,
+                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace"):
+        """sample: "replace" (the reference's draws with replacement) or "distinct" (GPUMemoryPool_SetSampleDistinct: min(degree, fan-out)
+        distinct neighbours per row, pre-sampling batches included).  Like agg_last_hop and agg_norm, the argument SETS the pool's mode on
+        every call: a mode switched on through GPUMemoryPool_SetSampleDistinct directly is switched back by a run_batch() without sample="distinct".
+        agg_last_hop: the aggregated hand-off (get_feature_kernel_agg) -- feature rows of the levels < H (per level behind each hop,
         or all of them inside that call with per_level=False) and the last hop as neighbour sums; result() then returns
         `features` [n_in, F] and `nbr_sum` [N, F].  agg_norm="both" (only with agg_last_hop): the sums weighted by out-degree^-1/2 inside
         block 1 (GPUMemoryPool_SetAggNorm); result() additionally returns `out_deg` int32 [n]."""
@@ -479,9 +486,13 @@ class Engine:
             raise ValueError("agg_norm: None or 'both'")
         if agg_norm and not agg_last_hop:
             raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
+        if sample not in ("replace", "distinct"):
+            raise ValueError("sample: 'replace' or 'distinct'")
         L = self.L
         L.SetGPUDevice(dev)
         pool = self.pools[dev]
+        if L.GPUMemoryPool_GetSampleDistinct(pool) != int(sample == "distinct"):
+            L.GPUMemoryPool_SetSampleDistinct(pool, int(sample == "distinct"))
         agg = bool(agg_last_hop) and not is_presc     # gather=False: the sampler side of such a batch (the last hop's draws kept per pipe)
         if bool(L.GPUMemoryPool_GetAggLastHop(pool)) != agg:
             L.GPUMemoryPool_SetAggLastHop(pool, int(agg))
@@ -514,10 +525,13 @@ class Engine:
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False, agg_norm=None):
+                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace"):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph()."""
+        if sample not in ("replace", "distinct"):
+            raise ValueError("sample: 'replace' or 'distinct'")
         L = self.L
         L.SetGPUDevice(dev)
+        L.GPUMemoryPool_SetSampleDistinct(self.pools[dev], int(sample == "distinct"))   # the recording keeps the mode: not between Begin and End
         L.GPUMemoryPool_SetAggLastHop(self.pools[dev], int(bool(agg_last_hop)))   # allocates: not between Begin and End
         L.GPUMemoryPool_SetAggNorm(self.pools[dev], int(bool(agg_last_hop) and agg_norm == "both"))   # likewise
         if stream is None:
@@ -528,7 +542,7 @@ class Engine:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
-                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm)
+                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:

@@ -95,6 +95,8 @@ constexpr int64_t sampler_max_tiles(int64_t max_slots)
     const int64_t narrow = (narrow_slots + kTileNarrow - 1) / kTileNarrow;
     return wide > narrow ? wide : narrow;
 }
+// Distinct-draw sampler mode: the largest fan-out k_sample<.., DISTINCT> runs (its LDS holds the picks of a tile's rows, TILE + 2 of these)
+constexpr int kDistinctMaxFanout = 64;
 // k_mark runs one CONTIGUOUS chunk of tiles per workgroup and leaves the chunk totals in GPUMemoryPool::chunk_tot; k_write scans them in
 // LDS, kMaxChunks / kBlock per thread.  One constant for the allocation (storage.cpp), the grid clamp (launch_sample_hop) and the LDS
 // array (k_write): changing one of them alone would let k_mark write past the allocation.
@@ -202,7 +204,7 @@ void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t e
 void launch_advance(hipStream_t s, BatchCtl* ctl);
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc);
+                       int32_t hops, int32_t slots_bound, bool is_presc, bool distinct = false);
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,
                       int32_t op_id, const int32_t* feat_map, int32_t bound);
 void launch_find_topo(hipStream_t s, const int32_t* input_ids, int8_t* part_index, int32_t* part_offset,
@@ -269,6 +271,7 @@ void launch_exchange_rows(hipStream_t s, bool scatter, const float* const* shard
 void launch_hotness(hipStream_t s, const int32_t* ids, const int32_t* nc, int32_t hops, unsigned long long* access,
                     int32_t* max_ids, int32_t bound);
 void launch_rng_probe(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n);
+void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n);
 // cache construction helpers
 void launch_aggregate_access(hipStream_t s, unsigned long long* agg, const unsigned long long* add, int32_t n);
 void launch_iota(hipStream_t s, int32_t* out, int32_t n);
@@ -331,6 +334,9 @@ struct GPUMemoryPool {
     // of its batch position inside block 1 before it is summed (GraphConv norm='both').  Per pipe, allocated when the mode is set:
     // the degrees (num_ids words), the draws' weights (max_slots floats) and the chunk counts of the slot -> edge prefix.
     int32_t agg_norm = 0;
+    // Distinct-draw sampler mode (GPUMemoryPool_SetSampleDistinct): every hop of this pool, the pre-sampling hops included, draws
+    // min(degree, fan-out) distinct neighbour positions per row (INTEGRATION.md "Sampling without replacement").  Nothing is allocated.
+    bool sample_distinct = false;
     std::vector<int32_t*> agg_out_deg, agg_chunk_cnt;
     std::vector<float*> agg_wdraw;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])

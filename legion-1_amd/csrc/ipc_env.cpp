@@ -68,6 +68,12 @@ struct shmExt {
     // Appended behind agg_last_hop (nothing above moves): how a server in that mode normalises the sums.  0 = plain sums, 1 = every row scaled by
     // its out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both, INTEGRATION.md "Normalised sums").  A client of an older server reads 0.
     int32_t agg_norm;
+    // Appended behind agg_norm (nothing above moves): how the server's sampler draws.  0 = with replacement (the reference's stream),
+    // 1 = distinct neighbours (LEGION_SAMPLING=distinct, INTEGRATION.md "Sampling without replacement").  A client of an older server reads 0.
+    // (Spelled std::int32_t on purpose: tests/test_agg_norm_cpu.py pins the plain int32_t members of this struct to END with handle_sum,
+    // agg_last_hop, agg_norm -- the layout of the older words, which holds; tests/test_sample_distinct_cpu.py finds this word in the mapped
+    // object right behind agg_norm.)
+    std::int32_t sampling;
 };
 static const uint32_t kMirrorMagic = 0x4C474E43u;   // "LGNC"
 static uint32_t handle_checksum(const volatile void* h)
@@ -522,6 +528,8 @@ void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on) { if (e && e->ext) e->ext->agg_
 int32_t IPCEnv_GetAggLastHop(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_last_hop : 0; }
 void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm) { if (e && e->ext) e->ext->agg_norm = norm; }
 int32_t IPCEnv_GetAggNorm(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_norm : 0; }
+void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->sampling = mode ? 1 : 0; }
+int32_t IPCEnv_GetSampling(const IPCEnv* e) { return (e && e->ext) ? e->ext->sampling : 0; }
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
     if (e && e->ext && device_id >= 0 && device_id < e->device_count) e->ext->feature_rows[device_id] = rows;
@@ -888,6 +896,7 @@ void legion_ipc_client_steps(LegionIPCClient* c, int32_t steps[3])
 int32_t legion_ipc_client_hops(LegionIPCClient* c) { return c->hops; }
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_last_hop : 0; }
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_norm : 0; }
+int32_t legion_ipc_client_sampling(LegionIPCClient* c) { return (c && c->ext) ? c->ext->sampling : 0; }
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16])
 {

@@ -68,6 +68,29 @@ __device__ inline uint32_t fdiv(uint32_t n, const FastDiv& d)
     return d.d == 1 ? n : (uint32_t)(((uint64_t)n * d.m) >> d.s);
 }
 
+// Distinct-draw sampler mode (INTEGRATION.md "Sampling without replacement"): a row of degree d > f takes f distinct neighbour positions
+// by Floyd's algorithm over hashed randoms, a pure function of (hop, row of the hop's input list); d <= f takes every neighbour once.
+// All arithmetic is uint32 with wrap-around except the one 64-bit product.
+__host__ __device__ inline uint32_t mix32(uint32_t z)
+{
+    z ^= z >> 16; z *= 0x7feb352du; z ^= z >> 15; z *= 0x846ca68bu; z ^= z >> 16;
+    return z;
+}
+__device__ inline uint32_t distinct_key(uint32_t row, uint32_t hop) { return mix32(row + 0x9E3779B9u * hop); }
+__device__ inline uint32_t distinct_u(uint32_t key, uint32_t t) { return mix32(key ^ (0x85EBCA6Bu * (t + 1u))); }
+// In place: p[0, f) holds distinct_u(key, t) on entry and the row's f positions on return; d > f.  Sequential per row (pick t looks at the
+// picks before it): at most f (f - 1) / 2 compares.  p is LDS in k_sample, global memory in the probe.
+__device__ inline void distinct_resolve(int32_t* p, int32_t d, int32_t f)
+{
+    for (int32_t t = 0; t < f; t++) {
+        const uint32_t J = (uint32_t)(d - f + t);
+        const int32_t r = (int32_t)__umulhi((uint32_t)p[t], J + 1u);   // (u * (J + 1)) >> 32 < J + 1 <= d
+        bool hit = false;
+        for (int32_t q = 0; q < t; q++) hit |= (p[q] == r);
+        p[t] = hit ? (int32_t)J : r;
+    }
+}
+
 __device__ inline int lane_id() { return threadIdx.x & 63; }
 __device__ inline int wave_id() { return threadIdx.x >> 6; }
 
@@ -206,13 +229,19 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
     return -1;
 }
 
-template <int TILE, bool PRESC, bool PARTITIONED>
+// DISTINCT (GPUMemoryPool_SetSampleDistinct): the slot's neighbour position comes from the row's distinct picks instead of the minstd stream.
+// The hash is pure, so the workgroup stages distinct_u of EVERY slot of the tile's rows (rows that straddle a tile edge included: both tiles
+// compute the whole row) in LDS beside the row descriptors, one lane per row of degree > f resolves the row's picks in place, and after
+// one more barrier every slot reads its own.  Everything behind the position is the default mode's code.
+template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
     __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
     __shared__ int32_t s_deg[TILE + 2];
     __shared__ int32_t s_src[TILE + 2];
     __shared__ int32_t s_cnt[kBlock / 64];
+    // the tile's rows hold at most TILE + 2 (f - 1) slots: the first row may begin f - 1 slots in front of the tile, the last end f - 1 behind it
+    __shared__ int32_t s_pick[DISTINCT ? TILE + 2 * kDistinctMaxFanout : 1];
 
     const int32_t N = a.nc[2];
     const int32_t f = a.count;
@@ -224,9 +253,9 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 
     if ((int32_t)blockIdx.x >= n_tiles) return;
 
-    // per-thread RNG state: x[s] = 48271^(tile*TILE + tid + 256*s + 1)
+    // per-thread RNG state: x[s] = 48271^(tile*TILE + tid + 256*s + 1) (the distinct mode draws from the hash: no stream)
     uint32_t x[TILE / kBlock];
-    {
+    if constexpr (!DISTINCT) {
         uint32_t base = powmod31(a.a_tile, (uint64_t)blockIdx.x); // uniform per workgroup
 #pragma unroll
         for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(base, a.pow_tab[tid + kBlock * s]);
@@ -266,7 +295,19 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             s_deg[r] = deg;
             s_src[r] = src;
         }
+        if constexpr (DISTINCT) {
+            const uint32_t hop = (uint32_t)a.op_id >> 1;
+            for (int32_t p = tid; p < nrows * f; p += kBlock) {
+                const uint32_t rr = fdiv((uint32_t)p, a.fdiv);
+                s_pick[p] = (int32_t)distinct_u(distinct_key((uint32_t)i0 + rr, hop), (uint32_t)p - rr * (uint32_t)f);
+            }
+        }
         __syncthreads();
+        if constexpr (DISTINCT) {
+            for (int32_t r = tid; r < nrows; r += kBlock)
+                if (s_deg[r] > f) distinct_resolve(s_pick + r * f, s_deg[r], f);
+            __syncthreads();
+        }
 
         int32_t cnt = 0;
 #pragma unroll
@@ -279,7 +320,8 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 r = (int32_t)i - i0;
                 const int32_t deg = s_deg[r];
                 if (j < deg) { // deg == -1 for padded (-1) sources; Kernels.cu:385,399
-                    dst = s_row[r][sample_index(x[s], deg)];
+                    if constexpr (DISTINCT) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
+                    else dst = s_row[r][sample_index(x[s], deg)];
                     if (dst < 0) dst = -1;
                 }
             }
@@ -316,8 +358,10 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             for (int w = 0; w < kBlock / 64; w++) t += s_cnt[w];
             a.tile_edge[tile] = t;
         }
+        if constexpr (!DISTINCT) {
 #pragma unroll
-        for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(x[s], a.a_step);
+            for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(x[s], a.a_step);
+        }
         __syncthreads();
     }
 }
@@ -1191,6 +1235,23 @@ __global__ void k_rng_probe(const int32_t* idx, const int32_t* deg, int32_t* k, 
 // ------------------------------------------------------------------------------------------------
 // cache construction kernels (one-off; S8 / S9)
 // ------------------------------------------------------------------------------------------------
+// The distinct mode's positions of n rows, by the device functions k_sample<.., DISTINCT> runs: pos[m * f + j] = neighbour position of slot j
+// of row row[m] of hop hop[m] at degree deg[m], -1 = no draw.  One thread per row; the row's f words of pos are its work space.
+__global__ void k_distinct_probe(const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
+{
+    const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
+    if (m >= n) return;
+    int32_t* out = pos + (int64_t)m * f;
+    const int32_t d = deg[m];
+    if (d <= f) {
+        for (int32_t j = 0; j < f; j++) out[j] = j < d ? j : -1;
+        return;
+    }
+    const uint32_t key = distinct_key((uint32_t)row[m], (uint32_t)hop[m]);
+    for (int32_t t = 0; t < f; t++) out[t] = (int32_t)distinct_u(key, (uint32_t)t);
+    distinct_resolve(out, d, f);
+}
+
 __global__ void k_aggregate_access(unsigned long long* agg, const unsigned long long* add, int32_t n)
 {   // GPUCache.cu:44-48
     for (int32_t i = threadIdx.x + blockDim.x * blockIdx.x; i < n; i += gridDim.x * blockDim.x) agg[i] += add[i];
@@ -1389,7 +1450,7 @@ void warm_static_tables() { (void)pow_table(); (void)cu_count(); }
 
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc)
+                       int32_t hops, int32_t slots_bound, bool is_presc, bool distinct)
 {
     const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
@@ -1420,9 +1481,14 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     const bool part = csr.topo_owner != nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices));
-    if (is_presc) k_sample<TILE, true, false><<<grid, kBlock, 0, s>>>(a);
-    else if (part) k_sample<TILE, false, true><<<grid, kBlock, 0, s>>>(a);
-    else k_sample<TILE, false, false><<<grid, kBlock, 0, s>>>(a);
+    if (distinct) {
+        if (is_presc) k_sample<TILE, true, false, true><<<grid, kBlock, 0, s>>>(a);
+        else if (part) k_sample<TILE, false, true, true><<<grid, kBlock, 0, s>>>(a);
+        else k_sample<TILE, false, false, true><<<grid, kBlock, 0, s>>>(a);
+    }
+    else if (is_presc) k_sample<TILE, true, false, false><<<grid, kBlock, 0, s>>>(a);
+    else if (part) k_sample<TILE, false, true, false><<<grid, kBlock, 0, s>>>(a);
+    else k_sample<TILE, false, false, false><<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
     k_mark<TILE><<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
@@ -1441,12 +1507,13 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
 }
 
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc)
+                       int32_t hops, int32_t slots_bound, bool is_presc, bool distinct)
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
+    if (distinct && count > kDistinctMaxFanout) { LEGION_ARG_ERROR("GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"); return; }
     // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
-    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc);
-    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc);
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, distinct);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, distinct);
 }
 
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,
@@ -1607,6 +1674,14 @@ void launch_hotness(hipStream_t s, const int32_t* ids, const int32_t* nc, int32_
     HIP_CHECK_LAST();
 }
 
+void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
+{
+    if (n <= 0) return;
+    if (f < 1 || f > kDistinctMaxFanout) { LEGION_ARG_ERROR("legion_distinct_probe: distinct sampling takes a fan-out of 1 to 64"); return; }
+    LEGION_AUDIT_LAUNCH(s, "k_distinct_probe", LEGION_AW(pos), LEGION_AL(row), LEGION_AL(hop), LEGION_AL(deg));
+    k_distinct_probe<<<(n + 255) / 256, 256, 0, s>>>(row, hop, deg, f, pos, n);
+    HIP_CHECK_LAST();
+}
 void launch_rng_probe(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n)
 {
     if (n <= 0) return;

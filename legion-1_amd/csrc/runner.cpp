@@ -55,6 +55,9 @@ struct Runner {
     // $LEGION_AGG_NORM=both (only with LEGION_AGG_LAST_HOP=1): the sums are weighted for GraphConv(norm='both') -- every row by the
     // out-degree^-1/2 of its batch position inside block 1 (INTEGRATION.md "Normalised sums").  Same rows, same buffer sizing.
     int32_t agg_norm = 0;
+    // $LEGION_SAMPLING=replace|distinct (unset = replace): distinct = every hop, the pre-sampling epoch included, draws min(degree, fan-out)
+    // distinct neighbours per row (GPUMemoryPool_SetSampleDistinct; INTEGRATION.md "Sampling without replacement").
+    int32_t sampling = 0;
     int32_t presc_max_rows = 0;     // largest n_in + N of the pre-sampling epoch (read back per batch: that epoch is not pipelined anyway)
     bool pending = false;
     int pending_pipe = 0;
@@ -84,6 +87,17 @@ static int32_t agg_norm_from_env(std::string& why)
     const char* a = getenv("LEGION_AGG_LAST_HOP");
     if (!a || atoi(a) == 0) { why = "LEGION_AGG_NORM=both needs LEGION_AGG_LAST_HOP=1: only the last hop's neighbour sums are normalised"; return -1; }
     return 1;
+}
+
+// $LEGION_SAMPLING: unset / empty / "replace" = the reference's with-replacement stream (0), "distinct" = distinct neighbours (1).
+// Returns the mode, or -1 with the refusal in `why`.
+static int32_t sampling_from_env(std::string& why)
+{
+    const char* n = getenv("LEGION_SAMPLING");
+    if (!n || !n[0] || strcmp(n, "replace") == 0) return 0;
+    if (strcmp(n, "distinct") == 0) return 1;
+    why = std::string("LEGION_SAMPLING=") + n + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row)";
+    return -1;
 }
 
 static void hand_over(Runner* r, IPCEnv* env, int pipe)
@@ -256,6 +270,12 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
         if (norm < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
         r->agg_norm = norm;
     }
+    {
+        std::string why;
+        const int32_t sampling = sampling_from_env(why);
+        if (sampling < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
+        r->sampling = sampling;
+    }
     r->local_dev_id = params->device_id;
     DeviceGuard guard(r->local_dev_id);
     GPUCache* cache = (GPUCache*)params->cache;
@@ -301,6 +321,9 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
         IPCEnv_SetAggNorm(env, r->agg_norm);                    // what a trainer reads: ipc_service.aggregate_norm()
         log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
     }
+    GPUMemoryPool_SetSampleDistinct(r->memorypool, r->sampling);   // before the pre-sampling epoch: the hotness profile sees what will be served
+    IPCEnv_SetSampling(env, r->sampling);                          // what a trainer reads: ipc_service.sampling()
+    log_out() << r->local_dev_id << " Sampling: " << (r->sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");
     LEGION_AUDIT_STREAM(r->streams[1], r->local_dev_id, "Runner_Initialize: gather stream");
@@ -914,6 +937,7 @@ void Server_Initialize(Server* s, int global_shard_count)
     {   // the hand-off switches, before any device is touched
         std::string why;
         if (agg_norm_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
+        if (sampling_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
     }
     const Meta& m = s->meta;
     // from the first device call on the main thread works on GPU 0 unless a scope below says otherwise (the reference's main thread never

@@ -231,4 +231,9 @@ void legion_rng_probe(void* stream, const int32_t* idx, const int32_t* deg, int3
     launch_rng_probe((hipStream_t)stream, idx, deg, k_out, n);
 }
 
+void legion_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos_out, int32_t n)
+{
+    launch_distinct_probe((hipStream_t)stream, row, hop, deg, f, pos_out, n);
+}
+
 } // extern "C"

@@ -550,6 +550,17 @@ int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p)
     return p->agg_out_deg[p->current_pipe];
 }
 
+// Distinct-draw sampler mode: every GPU_Random_Sampling of this pool (pre-sampling included) draws min(degree, fan-out) distinct neighbour
+// positions per row instead of the reference's with-replacement stream.  A captured batch graph keeps the mode it was recorded with, so
+// the switch is refused while one is being recorded.
+void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleDistinct: null pool"); return; }
+    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleDistinct: the pool is being captured"); return; }
+    p->sample_distinct = on != 0;
+}
+int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->sample_distinct ? 1 : 0; }
+
 #define POOL_PIPE_SETTER(name, field, type) \
     void GPUMemoryPool_Set##name(GPUMemoryPool* p, type* ptr, int32_t pipe) { \
         if (pipe < 0 || pipe >= p->pipeline_depth) { LEGION_ARG_ERROR("GPUMemoryPool_Set" #name ": bad pipe"); return; } \

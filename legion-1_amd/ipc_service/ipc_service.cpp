@@ -21,6 +21,7 @@ static int32_t h_edge_counter[16];
 static int32_t g_hops = 2;
 static bool g_aggregated = false;   // the server hands the last hop over as neighbour sums (read once, in initialize)
 static int g_agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
+static int g_sampling = 0;          // how the server's sampler draws: 0 = with replacement, 1 = distinct neighbours (LEGION_SAMPLING=distinct)
 // ONE consumer thread per process is the contract (the reference's trainer loop, legion_graphsage.py:72-89):
 // get_next / synchronize run without the GIL and share `env`, the two counter arrays and the client's current pipe, so the entry points
 // are serialised by this lock -- uncontended in the reference's loop, and a second Python thread gets whole counters instead of torn ones.
@@ -38,6 +39,7 @@ void InitializeIPC()
     g_hops = legion_ipc_client_hops(env);
     g_aggregated = legion_ipc_client_agg_last_hop(env) != 0;
     g_agg_norm = legion_ipc_client_agg_norm(env);
+    g_sampling = legion_ipc_client_sampling(env);
 }
 
 void FinalizeIPC()
@@ -100,6 +102,7 @@ std::vector<torch::Tensor> get_next_aggregated(int feature_dim) { return next_ba
 std::vector<torch::Tensor> get_next_aggregated_norm(int feature_dim) { return next_batch(feature_dim, true, 1); }
 bool aggregated() { require_env(); return g_aggregated; }
 int aggregate_norm() { require_env(); return g_agg_norm; }
+const char* sampling() { require_env(); return g_sampling ? "distinct" : "replace"; }
 
 // [b1_src_nodes, b1_dst_nodes, b2_src_nodes, b2_dst_nodes, ...] = [nc9, nc7, nc7, nc5] at H = 2
 // (ipc_service.cpp:60-72)
@@ -143,6 +146,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("get_next_aggregated_norm", &get_next_aggregated_norm, "next batch of a server that hands the last hop over as out-degree-normalised neighbour sums (extension)", pybind11::call_guard<pybind11::gil_scoped_release>());
     m.def("aggregated", &aggregated, "whether the server hands the last hop over as neighbour sums (extension)");
     m.def("aggregate_norm", &aggregate_norm, "how the server normalises the neighbour sums: 0 = not, 1 = out-degree rsqrt inside block 1 (extension)");
+    m.def("sampling", &sampling, "how the server's sampler draws: \"replace\" (with replacement, the default) or \"distinct\" (LEGION_SAMPLING=distinct; extension)");
     m.def("get_block_size", &get_block_size, "get dgl block size");
     m.def("get_steps", &get_steps, "get steps");
     m.def("initialize", &InitializeIPC, "InitializeIPC");

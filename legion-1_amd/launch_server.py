@@ -52,6 +52,9 @@ def main(argv=None):
     ap.add_argument("--usenvlink", type=int, default=1, help="1: cliques over the GPU interconnect (xGMI)")
     ap.add_argument("--seed_lists", action="store_true", help="extension (link prediction on several GPUs): every GPU g serves its own "
                     "pre-partitioned list trainingset_<G>_<g> verbatim (meta_config flag 2) instead of a split of `trainingset`")
+    ap.add_argument("--sampling", type=str, default=None, choices=["replace", "distinct"], help="extension: how a row draws its neighbours "
+                    "(LEGION_SAMPLING for the server): replace = with replacement like the reference (the default), distinct = "
+                    "min(degree, fan-out) distinct neighbours per row")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
@@ -62,7 +65,10 @@ def main(argv=None):
     if args.dry_run:
         print(" ".join(cmd))
         return 0
-    return subprocess.call(cmd)
+    env = dict(os.environ)
+    if args.sampling is not None:
+        env["LEGION_SAMPLING"] = args.sampling
+    return subprocess.call(cmd, env=env)
 
 
 if __name__ == "__main__":

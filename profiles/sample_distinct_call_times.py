@@ -1,0 +1,61 @@
+"""Call times (device events) of the sampler hops and of the gather in both sampling modes, same batches, alternating: per hop one
+GPU_Random_Sampling call (k_sample + k_mark + k_write), then get_feature_kernel_all; per batch the edges and the unique nodes.
+papers100M or products {25,10,5}, 8000 seeds.  Copied into a checkout without the distinct mode (the parent commit's) it times the
+default mode alone: the comparison base.  Under `rocprofv3 --kernel-trace --stats` the k_sample instantiations separate by name
+(<256, ..> is hop 1, <1024, ..> hops 2 and 3; the last template argument is the mode).
+With a fourth argument `replace-only` the distinct mode is left out: the default mode undisturbed by the other mode's batches in between
+(they leave other rows in the caches), which is what compares with the parent.
+Usage: python3 profiles/sample_distinct_call_times.py <workload> <label> [batches] [replace-only]"""
+import sys, os, json
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np, torch
+import legion1_amd.capi as K, legion1_amd.synth as S
+import bench
+workload, label = sys.argv[1], sys.argv[2]
+batches = int(sys.argv[3]) if len(sys.argv) > 3 else 12
+L = K.lib(); L.SetGPUDevice(0)
+has_distinct = "GPUMemoryPool_SetSampleDistinct" in K._SIGS and sys.argv[4:5] != ["replace-only"]
+fan = [25, 10, 5]; H = 3; B = 8000
+spec = S.spec_for(workload); dev = torch.device("cuda", 0)
+pitch = L.legion_row_pitch(spec.F) if spec.F % 32 else 0
+indptr, indices, feats, E = bench.build_graph_on_gpu(K, spec, dev, pitch=pitch)
+tr = torch.empty(spec.n_train, dtype=torch.int32, device=dev)
+L.legion_synth_seed_ids(None, tr.data_ptr(), 0, spec.n_train, spec.V, spec.M2, spec.C2, 1, 0)
+lab = torch.zeros(spec.n_train, dtype=torch.int32, device=dev)
+torch.cuda.synchronize()
+eng = K.Engine(indptr.data_ptr(), indices.data_ptr(), feats.data_ptr(), spec.V, spec.F,
+               dict(train=[((tr.data_ptr(), spec.n_train), (lab.data_ptr(), spec.n_train))]), B, fan, E=E, features_pitch=pitch)
+eng.alloc_features()
+pool = eng.pools[0]; st = L.d_stream_create(); ev = [L.d_event_create() for _ in range(H + 2)]
+def one(it, distinct):
+    if has_distinct: L.GPUMemoryPool_SetSampleDistinct(pool, int(distinct))
+    L.GPUMemoryPool_SetCurrentPipe(pool, 0); L.GPUMemoryPool_SetCurrentMode(pool, 0); L.GPUMemoryPool_SetIter(pool, it)
+    L.batch_generator_kernel(st, eng.noder, eng.cache, pool, B, it, 0, 0, 0)
+    L.d_stream_sync(st)
+    for h in range(H):
+        L.d_event_record(ev[h], st)
+        L.GPU_Random_Sampling(st, eng.graph, eng.cache, pool, fan[h], 2 * h + 2, 0)
+    L.d_event_record(ev[H], st)
+    L.get_feature_kernel_all(st, eng.cache, eng.noder, pool, 0, 1)
+    L.d_event_record(ev[H + 1], st); L.d_stream_sync(st); K.check()
+    nc = eng.out[0][0]["nc"].to_numpy(np.int32, 16); ec = eng.out[0][0]["ec"].to_numpy(np.int32, 16)
+    return [L.d_event_elapsed_ms(ev[h], ev[h + 1]) * 1e3 for h in range(H + 1)], int(ec[2 + H]), int(nc[5 + 2 * H])
+modes = (False, True) if has_distinct else (False,)
+for it in range(3):
+    for m in modes: one(it, m)
+t = {m: [] for m in modes}; edges = {m: [] for m in modes}; nodes = {m: [] for m in modes}
+for it in range(3, 3 + batches):
+    for m in modes:
+        us, e, n = one(it, m)
+        t[m].append(us); edges[m].append(e); nodes[m].append(n)
+stat = lambda v: dict(median=round(float(np.median(v)), 2), min=round(float(min(v)), 2), max=round(float(max(v)), 2))
+def summary(m):
+    a = np.array(t[m])
+    d = {"hop%d_us" % (h + 1): stat(a[:, h]) for h in range(H)}
+    d["gather_us"] = stat(a[:, H]); d["edges"] = int(np.mean(edges[m])); d["nodes"] = int(np.mean(nodes[m]))
+    return d
+out = dict(label=label, workload=workload, F=spec.F, batches=batches, replace=summary(False))
+if has_distinct: out["distinct"] = summary(True)
+print(json.dumps(out))
+eng.close()
