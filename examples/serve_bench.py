@@ -24,19 +24,20 @@ sys.path.insert(0, ROOT)
 
 def consume(epochs, hops):
     import legion1_amd.capi as K
+    from legion1_amd import layout
     lib = K.lib()
     lib.legion_ipc_client_open.restype = C.c_void_p
     c = C.c_void_p(lib.legion_ipc_client_open(-1))
     steps = (C.c_int32 * 3)()
     lib.legion_ipc_client_steps(c, steps)
     total = (steps[0] + steps[1]) * epochs + steps[2]
-    nc, ec = (C.c_int32 * 16)(), (C.c_int32 * 16)()
+    nc, ec = (C.c_int32 * layout.COUNTER_WORDS)(), (C.c_int32 * layout.COUNTER_WORDS)()
     edges = 0
     t0 = time.perf_counter()
     for _ in range(total):
         lib.legion_ipc_client_wait(c)
         lib.legion_ipc_client_read_counters(c, nc, ec)
-        edges += ec[2 + hops]
+        edges += layout.batch_edges(ec, hops)
         lib.legion_ipc_client_post(c)
     dt = time.perf_counter() - t0
     lib.legion_ipc_client_close(c)

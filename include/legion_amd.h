@@ -22,6 +22,7 @@
 
 #include <stdint.h>
 #include <stddef.h>
+#include "legion_batch_layout.h" /* the nc / ec counter arrays of a batch: LEGION_MAX_HOPS, LEGION_COUNTER_WORDS, legion_batch_nodes(), ... */
 
 #ifdef __cplusplus
 extern "C" {
@@ -30,7 +31,7 @@ extern "C" {
 #define LEGION_MAX_DEVICE 8      /* CUDA_IPC_Service.cu:14 MAX_DEVICE */
 #define LEGION_PIPELINE_DEPTH 2  /* Server.cu:15, CUDA_IPC_Service.cu:15 */
 #define LEGION_MEMORY_USAGE 7    /* CUDA_IPC_Service.cu:16: buffers per (device, pipe) */
-#define LEGION_MAX_HOPS 5        /* counter layout fits int32[16] up to 5 hops */
+/* LEGION_MAX_HOPS (5) and LEGION_COUNTER_WORDS (16) belong to the counter layout: legion_batch_layout.h */
 
 #define LEGION_TRAINMODE 0       /* Kernels.cu:10-12 */
 #define LEGION_VALIDMODE 1
@@ -360,7 +361,7 @@ void make_update_plan(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache, G
                       int32_t dev_id, int32_t mode);
 void update_cache(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                   int32_t dev_id, int32_t mode);
-/* Gather every level of the batch in one launch (rows [0, nc[5+2H]) ): same bytes as running
+/* Gather every level of the batch in one launch (rows [0, legion_batch_nodes(nc, H)), word nc[5 + 2H]): same bytes as running
  * get_feature_kernel for op 1,3,..,2H+1; used when the per-level overlap is not wanted. */
 void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                             int32_t dev_id, int in_memory);
@@ -368,10 +369,10 @@ void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
  * thing: summing them into their hop-(H-1) neighbours.  With GPUMemoryPool_SetAggLastHop(pool, 1) the last hop keeps its draws in a
  * buffer of the batch's pipe, and get_feature_kernel_agg -- called behind the last hop's GPU_Random_Sampling instead of the last
  * level's get_feature_kernel -- hands over, in the pipe's feature buffer:
- *   rows [0, n_in)        the feature rows of the levels < H, n_in = nc[3 + 2H] (gathered here unless get_feature_kernel gathered
+ *   rows [0, n_in)        the feature rows of the levels < H, n_in = legion_first_block_dst(nc, H) = nc[3 + 2H] (gathered here unless get_feature_kernel gathered
  *                         every one of these levels for this batch)
  *   rows [n_in, n_in + N) S[i, :] = ((0.0f + x[c(i, j0)]) + x[c(i, j1)]) + ... : the fp32 sum, in ascending slot order, of the rows
- *                         input slot i of the last hop drew (N = nc[4] at H = 1, ec[3] at H = 2, ec[1 + H] - ec[H] above; slot i is
+ *                         input slot i of the last hop drew (N = legion_hop_inputs(nc, ec, H): nc[4] at H = 1, else the edges of hop H - 1; slot i is
  *                         seed i at H = 1, else edge i of hop H - 1); a slot without draws gets a stored row of +0.0f.
  * nc, ec, ids, labels and both COO arrays are those of the default mode.  Sticky argument errors: mode off, called before the last
  * hop, a pre-sampling batch, rows * F >= 2^31, $LEGION_PEER_GATHER=exchange (the exchange moves rows, not sums).
@@ -382,7 +383,7 @@ int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p);
  * aggregated last hop.  With GPUMemoryPool_SetAggNorm(pool, 1) get_feature_kernel_agg writes into rows [n_in, n_in + N)
  *   S_w[i, :] = ((0.0f + fl(w[p0] * x[c0])) + fl(w[p1] * x[c1])) + ...   (the product and the add rounded separately, no FMA)
  * where p_j is the batch position of draw j (the src_off of its last-hop edge), w[p] = fl(1 / fl(sqrt((float)max(d[p], 1)))) and
- * d[p] = #{ e < ec[2 + H] : src_off[e] == p } is the out-degree of position p inside block 1.  Everything else is as in the plain
+ * d[p] = #{ e < legion_batch_edges(ec, H) : src_off[e] == p } is the out-degree of position p inside block 1.  Everything else is as in the plain
  * aggregated mode.  norm: 0 = none, 1 = out-degree rsqrt; any other value, a pool that does not aggregate the last hop and a pool that is
  * being captured are sticky argument errors.  Setting it allocates per pipe 4 bytes per id of a batch, 4 per slot of the largest hop and
  * a few KB on the current device.  GetAggOutDeg: d of the current pipe's last normalised batch (device, int32[n]; for tests). */
@@ -470,8 +471,8 @@ int32_t* IPCEnv_GetEdgeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
  * IPCEnv_SetMirror fills the mirror from the host (poisoned pipe). */
 void IPCEnv_MirrorCounters(IPCEnv* e, int32_t dev_id, int32_t current_pipe, void* stream);
 void IPCEnv_SetMirror(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t nc_fill, int32_t ec_fill);
-/* nc[word] (word < 16) or ec[word - 16] (16 <= word < 32) of the batch about to be posted, from the mirror IPCEnv_MirrorCounters queued (wait for that copy first); -1: not queued.
- * The runner compares nc[5 + 2H] with the rows of its feature buffer: a batch that reached more nodes had rows dropped by the bounded
+/* nc[word] (word < LEGION_COUNTER_WORDS) or ec[word - LEGION_COUNTER_WORDS] of the batch about to be posted, from the mirror IPCEnv_MirrorCounters queued (wait for that copy first); -1: not queued.
+ * The runner compares legion_batch_nodes(nc, H) with the rows of its feature buffer: a batch that reached more nodes had rows dropped by the bounded
  * gather (kernels.hip k_gather: "never write past the buffer") and its trainer will refuse it -- the server says so, once, and counts. */
 int32_t IPCEnv_MirroredNodeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t word);
 /* the row capacity of a device's feature buffers as published to its trainer (set by IPCEnv_InitializeFeaturesBuffer) */
@@ -530,9 +531,9 @@ int32_t legion_ipc_client_feature_rows(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c);
 int32_t legion_ipc_client_sampling(LegionIPCClient* c);
-/* both 16-int counters of the current pipe (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
+/* both counter arrays of the current pipe (legion_batch_layout.h draws them word by word) (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
  * a blocking device copy like the reference */
-void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16]);
+void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[LEGION_COUNTER_WORDS], int32_t h_edge_counter[LEGION_COUNTER_WORDS]);
 void legion_ipc_client_close(LegionIPCClient* c);             /* Finalize(), :141-156 */
 
 /* ---- Runner / Server: Server.h:137-165, Server.cu:43-369 ---------------------------------- */
@@ -551,7 +552,7 @@ void Runner_Initialize(Runner* r, RunnerParams* params);
 void Runner_InitializeFeaturesBuffer(Runner* r, RunnerParams* params);
 void Runner_RunPreSc(Runner* r, RunnerParams* params);
 /* RunOnce, Server.cu:301-328.  A batch an operator refused (sticky error): LEGION_ERR_EXIT exits like the reference;
- * LEGION_ERR_RETURN posts the pipe with every node-counter word = -1 (nc[0] == -1: "server failed", no valid batch has it)
+ * LEGION_ERR_RETURN posts the pipe with every node-counter word = -1 (nc[LEGION_NC_TOTAL] == -1: "server failed", no valid batch has it)
  * so that no consumer blocks forever on sem_w, and returns with the error still set. */
 void Runner_RunOnce(Runner* r, RunnerParams* params);
 void Runner_Finalize(Runner* r, RunnerParams* params);

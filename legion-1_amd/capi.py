@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from . import layout
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "liblegion_amd.so")
 
@@ -443,7 +445,7 @@ class Engine:
             pipes = []
             for q in range(self.depth):
                 o = dict(ids=DevBuf(n * 4), labels=DevBuf(self.batch_size * 4), src=DevBuf(n * 4), dst=DevBuf(n * 4),
-                         nc=DevBuf(64), ec=DevBuf(64), feat=None)
+                         nc=DevBuf(layout.COUNTER_BYTES), ec=DevBuf(layout.COUNTER_BYTES), feat=None)
                 L.GPUMemoryPool_SetSampledIds(pool, o["ids"].ptr, q)
                 L.GPUMemoryPool_SetLabels(pool, o["labels"].ptr, q)
                 L.GPUMemoryPool_SetAggSrcOf(pool, o["src"].ptr, q)
@@ -569,16 +571,15 @@ class Engine:
             normalised = self._norm.get((dev, pipe), False)
         o = self.out[dev][pipe]
         self.L.SetGPUDevice(dev)
-        nc = o["nc"].to_numpy(np.int32, 16)
-        ec = o["ec"].to_numpy(np.int32, 16)
+        nc = o["nc"].to_numpy(np.int32, layout.COUNTER_WORDS)
+        ec = o["ec"].to_numpy(np.int32, layout.COUNTER_WORDS)
         H = self.hops
-        n_nodes, n_edges = int(nc[5 + 2 * H]), int(ec[2 + H])
-        res = dict(nc=nc, ec=ec, ids=o["ids"].to_numpy(np.int32, n_nodes), labels=o["labels"].to_numpy(np.int32, int(nc[4])),
+        n_nodes, n_edges = layout.batch_nodes(nc, H), layout.batch_edges(ec, H)
+        res = dict(nc=nc, ec=ec, ids=o["ids"].to_numpy(np.int32, n_nodes), labels=o["labels"].to_numpy(np.int32, layout.level_size(nc, 0)),
                    src_off=o["src"].to_numpy(np.int32, n_edges), dst_off=o["dst"].to_numpy(np.int32, n_edges))
         if with_features and o["feat"] is not None and aggregated:
             # aggregated hand-off: rows [0, n_in) are features, rows [n_in, n_in + N) the last hop's neighbour sums per input slot
-            n_in = int(nc[3 + 2 * H])
-            runs = int(nc[4]) if H == 1 else int(ec[3]) if H == 2 else int(ec[1 + H] - ec[H])
+            n_in, runs = layout.first_block_dst(nc, H), layout.hop_inputs(nc, ec, H)
             cap = getattr(self, "feature_rows", n_in + runs)
             r_in = min(n_in, cap)
             r_sum = max(0, min(n_in + runs, cap) - n_in)

@@ -187,7 +187,7 @@ struct SamplerBuffers {
     int32_t aux_cap;        // elements per aux buffer
     int32_t ids_cap;        // elements of sampled_ids / agg_src_ids / agg_src_off / agg_dst_off (num_ids)
     int32_t V;              // entries of pos_map
-    bool aux_prepared;      // aux already holds -1 for nc[2] * count slots
+    bool aux_prepared;      // aux already holds -1 for nc[LEGION_NC_NEXT_INPUTS] * count slots
     int32_t* tile_edge;     // i32[max tiles]
     int32_t* tile_node;     // i32[max tiles]
     int2* tile_pre;         // int2[max tiles]: (edges, new nodes) in front of a tile inside its k_mark chunk
@@ -228,7 +228,7 @@ struct GatherArgs {
     const int32_t* sampled_ids;
     const int32_t* nc;
     float* dst;
-    int32_t off_idx, size_idx;                // nc[] indices of (offset, size); off_idx < 0 => offset 0
+    int32_t off_idx, size_idx;                // nc[] words of (offset, size), legion_idx_*; off_idx < 0 => offset 0
     int32_t dst_rows;                         // capacity of dst in rows (<= 0: unbounded)
     int32_t* rows_seen;                       // host-mapped word: the launch leaves its actual row count here (may be null)
     int32_t* hit_stats;                       // host-mapped {hits, rows}: the lookup pass of a SAMPLED batch adds its counts (may be null)
@@ -238,7 +238,7 @@ struct GatherArgs {
 };
 void launch_gather(hipStream_t s, const GatherArgs& a, int32_t rows_bound);
 // Aggregated last hop (kernels.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
-// slots, from the draws in cand[slot * f + j], into rows [nc[3 + 2 * hops], + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
+// slots, from the draws in cand[slot * f + j], into rows [legion_first_block_dst(nc, hops), + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
 // wdraw (normalised sums): the weight of every draw by slot, as launch_agg_norm_weights left it; null = plain sums.
 void launch_gather_sum(hipStream_t s, const GatherArgs& a, const int32_t* cand, int32_t cand_cap, const int32_t* ec, int32_t hops,
                        int32_t f, int32_t runs_bound, const float* wdraw = nullptr);
@@ -416,7 +416,7 @@ struct CacheController {              // PreSCCacheController, GPUCache.cu:239-5
     unsigned long long* node_access_time = nullptr;
     unsigned long long* edge_access_time = nullptr;
     int32_t iter = 0, max_ids = 0;
-    int32_t* d_max_ids = nullptr;     // device-side running max of nc[total]
+    int32_t* d_max_ids = nullptr;     // device-side running max of nc[LEGION_NC_TOTAL]
     int32_t node_capacity = 0, edge_capacity = 0;
     // direct-mapped replacements of the three BGHT maps (GPUCache.cu:315-321)
     int32_t* feat_map = nullptr;      // node_map_:       id -> global cache slot | -1

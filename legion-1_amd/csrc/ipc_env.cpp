@@ -32,6 +32,9 @@
 
 using namespace legion;
 
+constexpr int kWords = LEGION_COUNTER_WORDS;                   // one counter array (nc or ec); the mirror holds nc | ec
+constexpr size_t kCounterBytes = kWords * sizeof(int32_t);
+
 static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle must be 64 bytes (CUDA_IPC_Service.cu:34-37)");
 
 struct shmStruct {           // the reference's slab, byte for byte (CUDA_IPC_Service.cu:34-37, ipc_cuda_kernel.cu:31-34): 7180 bytes, nothing appended
@@ -51,10 +54,10 @@ struct shmExt {
     // of the pre-sampling epoch (Server.cu:275) and its trainer views [nc9, F] of them unchecked (ipc_cuda_kernel.cu:200): a batch with more
     // nodes reads past the allocation.  A client that knows the capacity refuses such a batch instead.
     int32_t feature_rows[LEGION_MAX_DEVICE];
-    // host mirror of the two 16-int counter arrays of every (device, pipe), filled by the server before it posts the pipe.  The reference's
+    // host mirror of the two counter arrays of every (device, pipe), filled by the server before it posts the pipe.  The reference's
     // trainer reads them with a blocking cudaMemcpy from the IPC device buffers (ipc_cuda_kernel.cu:195-196): on the legacy default stream that
     // copy waits for everything the trainer has queued.  A client that finds the magic set reads the mirror instead; buffers 5 / 6 stay valid.
-    int32_t counters[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH][32];   // nc[16] | ec[16]
+    int32_t counters[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH][2 * kWords];   // nc | ec
     // What ties this object to the LIVE slab: the object is only unlinked by IPCEnv_Finalize, so after a killed server a server WITHOUT the
     // extension (the reference's) would leave a stale one in place and a client would read stale hops / counters for good.  The server stores
     // a copy of the slab's step counts and a checksum of the first handle it registers per device; a client ignores an extension that does not
@@ -475,11 +478,11 @@ void IPCEnv_InitializeSamplesBuffer(IPCEnv* e, int32_t batch_size, int32_t num_i
         e->labels[device_id].push_back(ipc_alloc(e->shm, device_id, i, 2, (size_t)batch_size * sizeof(int32_t)));
         e->agg_src[device_id].push_back(ipc_alloc(e->shm, device_id, i, 3, (size_t)num_ids * sizeof(int32_t)));
         e->agg_dst[device_id].push_back(ipc_alloc(e->shm, device_id, i, 4, (size_t)num_ids * sizeof(int32_t)));
-        e->node_counter[device_id].push_back(ipc_alloc(e->shm, device_id, i, 5, 16 * sizeof(int32_t)));
-        e->edge_counter[device_id].push_back(ipc_alloc(e->shm, device_id, i, 6, 16 * sizeof(int32_t)));
+        e->node_counter[device_id].push_back(ipc_alloc(e->shm, device_id, i, 5, kCounterBytes));
+        e->edge_counter[device_id].push_back(ipc_alloc(e->shm, device_id, i, 6, kCounterBytes));
         if (i == 0 && e->ext) e->ext->handle_sum[device_id] = handle_checksum(&e->shm->memHandle[device_id][0][0]);
-        if (e->node_counter[device_id][i]) HIP_CHECK(hipMemset(e->node_counter[device_id][i], 0, 16 * sizeof(int32_t)));
-        if (e->edge_counter[device_id][i]) HIP_CHECK(hipMemset(e->edge_counter[device_id][i], 0, 16 * sizeof(int32_t)));
+        if (e->node_counter[device_id][i]) HIP_CHECK(hipMemset(e->node_counter[device_id][i], 0, kCounterBytes));
+        if (e->edge_counter[device_id][i]) HIP_CHECK(hipMemset(e->edge_counter[device_id][i], 0, kCounterBytes));
         // memory lock.  Stale semaphores of a crashed run are removed first (the reference only
         // unlinks in Finalize, CUDA_IPC_Service.cu:319-320, so a crash poisons the next start).
         const std::string ssri = sem_name("r", device_id, i), sswi = sem_name("w", device_id, i);
@@ -534,11 +537,11 @@ void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
     if (e && e->ext && device_id >= 0 && device_id < e->device_count) e->ext->feature_rows[device_id] = rows;
 }
-// nc[word] (word < 16) or ec[word - 16] of the batch about to be posted on (dev, pipe), from the host mirror IPCEnv_MirrorCounters queued (the caller has waited for
+// nc[word] (word < kWords) or ec[word - kWords] of the batch about to be posted on (dev, pipe), from the host mirror IPCEnv_MirrorCounters queued (the caller has waited for
 // that copy); -1 when the mirror of this batch was not queued
 int32_t IPCEnv_MirroredNodeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t word)
 {
-    if (!e || !e->ext || dev_id < 0 || dev_id >= e->device_count || word < 0 || word >= 32) return -1;
+    if (!e || !e->ext || dev_id < 0 || dev_id >= e->device_count || word < 0 || word >= 2 * kWords) return -1;
     const int q = current_pipe % e->pipeline_depth;
     if (!e->mirror_fresh[dev_id][q]) return -1;
     if (!e->shm_pinned) return e->mirror_stage[dev_id][q] ? e->mirror_stage[dev_id][q][word] : -1;
@@ -599,15 +602,15 @@ void IPCEnv_MirrorCounters(IPCEnv* e, int32_t dev_id, int32_t current_pipe, void
     const int q = current_pipe % e->pipeline_depth;
     int32_t* m = (int32_t*)&e->ext->counters[dev_id][q][0];
     if (!e->shm_pinned) {           // the runtime refused to page-lock the slab: queue the copies into pinned staging words, IPCPost moves them
-        if (!e->mirror_stage[dev_id][q] && hipHostMalloc((void**)&e->mirror_stage[dev_id][q], 32 * sizeof(int32_t), hipHostMallocPortable) != hipSuccess) {
+        if (!e->mirror_stage[dev_id][q] && hipHostMalloc((void**)&e->mirror_stage[dev_id][q], 2 * kCounterBytes, hipHostMallocPortable) != hipSuccess) {
             (void)hipGetLastError();
             e->mirror_stage[dev_id][q] = nullptr;
             return;                 // IPCPost copies synchronously instead
         }
         m = e->mirror_stage[dev_id][q];
     }
-    HIP_CHECK(hipMemcpyAsync(m, e->node_counter[dev_id][q], 16 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_CHECK(hipMemcpyAsync(m + 16, e->edge_counter[dev_id][q], 16 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_CHECK(hipMemcpyAsync(m, e->node_counter[dev_id][q], kCounterBytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_CHECK(hipMemcpyAsync(m + kWords, e->edge_counter[dev_id][q], kCounterBytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
     e->mirror_fresh[dev_id][q] = true;
 }
 int IPCEnv_SlabPinned(IPCEnv* e) { return e && e->shm_pinned ? 1 : 0; }
@@ -616,23 +619,23 @@ void IPCEnv_SetMirror(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t n
 {
     if (!e || !e->ext || dev_id < 0 || dev_id >= e->device_count) return;
     const int q = current_pipe % e->pipeline_depth;
-    for (int i = 0; i < 16; i++) { e->ext->counters[dev_id][q][i] = nc_fill; e->ext->counters[dev_id][q][16 + i] = ec_fill; }
-    if (e->mirror_stage[dev_id][q]) for (int i = 0; i < 32; i++) e->mirror_stage[dev_id][q][i] = i < 16 ? nc_fill : ec_fill;
+    for (int i = 0; i < kWords; i++) { e->ext->counters[dev_id][q][i] = nc_fill; e->ext->counters[dev_id][q][kWords + i] = ec_fill; }
+    if (e->mirror_stage[dev_id][q]) for (int i = 0; i < 2 * kWords; i++) e->mirror_stage[dev_id][q][i] = i < kWords ? nc_fill : ec_fill;
     e->mirror_fresh[dev_id][q] = true;
 }
 void IPCEnv_IPCPost(IPCEnv* e, int32_t dev_id, int32_t current_pipe)
 {
     const int q = current_pipe % e->pipeline_depth;
     if (e->ext && e->mirror_fresh[dev_id][q] && !e->shm_pinned && e->mirror_stage[dev_id][q])     // staged by a queued copy the caller has waited for
-        for (int i = 0; i < 32; i++) e->ext->counters[dev_id][q][i] = e->mirror_stage[dev_id][q][i];
+        for (int i = 0; i < 2 * kWords; i++) e->ext->counters[dev_id][q][i] = e->mirror_stage[dev_id][q][i];
     if (e->ext && e->ext->mirror_magic == kMirrorMagic && !e->mirror_fresh[dev_id][q] && !e->node_counter[dev_id].empty() && !no_device()) {
         // a producer that did not queue the mirror copy (a reference-style RunOnce on this library): copy now -- the batch is
         // complete when a pipe is posted, so a blocking copy is correct, merely slower than the queued one
         DeviceGuard guard(dev_id);
-        int32_t h[32];
-        if (hipMemcpy(h, e->node_counter[dev_id][q], 64, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(h + 16, e->edge_counter[dev_id][q], 64, hipMemcpyDeviceToHost) == hipSuccess)
-            for (int i = 0; i < 32; i++) e->ext->counters[dev_id][q][i] = h[i];
+        int32_t h[2 * kWords];
+        if (hipMemcpy(h, e->node_counter[dev_id][q], kCounterBytes, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(h + kWords, e->edge_counter[dev_id][q], kCounterBytes, hipMemcpyDeviceToHost) == hipSuccess)
+            for (int i = 0; i < 2 * kWords; i++) e->ext->counters[dev_id][q][i] = h[i];
         else { (void)hipGetLastError(); e->ext->mirror_magic = 0; }   // clients fall back to the device buffers
     }
     e->mirror_fresh[dev_id][q] = false;
@@ -898,16 +901,16 @@ int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_norm : 0; }
 int32_t legion_ipc_client_sampling(LegionIPCClient* c) { return (c && c->ext) ? c->ext->sampling : 0; }
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }
-void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[16], int32_t h_edge_counter[16])
+void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[LEGION_COUNTER_WORDS], int32_t h_edge_counter[LEGION_COUNTER_WORDS])
 {
     if (c->ext && c->ext->mirror_magic == kMirrorMagic) {
         // the server's host mirror of this pipe: no device copy, no implicit synchronisation with the trainer's own GPU work
         const volatile int32_t* m = &c->ext->counters[c->device][c->current_pipe][0];
-        for (int i = 0; i < 16; i++) { h_node_counter[i] = m[i]; h_edge_counter[i] = m[16 + i]; }
+        for (int i = 0; i < kWords; i++) { h_node_counter[i] = m[i]; h_edge_counter[i] = m[kWords + i]; }
         return;
     }
-    HIP_CHECK(hipMemcpy(h_node_counter, c->buf[c->current_pipe][5], 16 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(h_edge_counter, c->buf[c->current_pipe][6], 16 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_node_counter, c->buf[c->current_pipe][5], kCounterBytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_edge_counter, c->buf[c->current_pipe][6], kCounterBytes, hipMemcpyDeviceToHost));
 }
 void legion_ipc_client_close(LegionIPCClient* c)
 {

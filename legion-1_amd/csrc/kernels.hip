@@ -94,9 +94,6 @@ __device__ inline void distinct_resolve(int32_t* p, int32_t d, int32_t f)
 __device__ inline int lane_id() { return threadIdx.x & 63; }
 __device__ inline int wave_id() { return threadIdx.x >> 6; }
 
-// level (offset,size) slots of the generalised counter layout
-__device__ inline int32_t total_nodes(const int32_t* nc, int32_t hops) { return nc[5 + 2 * hops]; }
-
 // ------------------------------------------------------------------------------------------------
 // S1 + S2(op 0): seed batch
 // ------------------------------------------------------------------------------------------------
@@ -147,9 +144,10 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
             labels[idx] = all_labels[g % total_cap];
         }
     }
-    if (idx < 16) { // cudaMemsetAsync(counters) + update_counter(op 0), Kernels.cu:220-221,118-127
+    if (idx < LEGION_COUNTER_WORDS) { // cudaMemsetAsync(counters) + update_counter(op 0), Kernels.cu:220-221,118-127
+        constexpr int seeds = legion_idx_level_size(0);
         int32_t nv = 0;
-        if (idx == 0 || idx == 2 || idx == 4) nv = size;
+        if (idx == LEGION_NC_TOTAL || idx == LEGION_NC_NEXT_INPUTS || idx == seeds) nv = size;
         nc[idx] = nv;
         ec[idx] = 0;
     }
@@ -160,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
 // fallback when a hop's fan-out differs from what the previous launch prepared the slot states for
 __global__ void k_fill_aux(const int32_t* __restrict__ nc, int32_t count, int32_t* __restrict__ aux, int32_t aux_cap)
 {
-    const int64_t n = min((int64_t)nc[2] * count, (int64_t)aux_cap);
+    const int64_t n = min((int64_t)nc[LEGION_NC_NEXT_INPUTS] * count, (int64_t)aux_cap);
     for (int64_t i = threadIdx.x + (int64_t)blockDim.x * blockIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) aux[i] = -1;
 }
 __global__ void k_set_cursor(BatchCtl* ctl, int32_t counter, uint32_t epoch) { ctl->counter = counter; ctl->epoch = epoch; }
@@ -243,10 +241,10 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
     // the tile's rows hold at most TILE + 2 (f - 1) slots: the first row may begin f - 1 slots in front of the tile, the last end f - 1 behind it
     __shared__ int32_t s_pick[DISTINCT ? TILE + 2 * kDistinctMaxFanout : 1];
 
-    const int32_t N = a.nc[2];
+    const int32_t N = a.nc[LEGION_NC_NEXT_INPUTS];
     const int32_t f = a.count;
     const int32_t total = N * f; // int32 like the reference (Kernels.cu:375)
-    const int32_t* __restrict__ input = (a.op_id == 2) ? a.sampled_ids : a.agg_src_ids + a.ec[2];
+    const int32_t* __restrict__ input = (a.op_id == 2) ? a.sampled_ids : a.agg_src_ids + a.ec[LEGION_EC_INPUT_OFF];
     const int32_t n_tiles = (total + TILE - 1) / TILE;
     const int tid = threadIdx.x;
     const uint32_t epoch = a.ctl->epoch;
@@ -407,7 +405,7 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc,
 {
     constexpr int S = TILE / kBlock, W = kBlock / 64;
     __shared__ int32_t s_c[S * W];
-    const int32_t total = nc[2] * count;
+    const int32_t total = nc[LEGION_NC_NEXT_INPUTS] * count;
     const int32_t n_tiles = (total + TILE - 1) / TILE;
     const int lane = lane_id(), wave = wave_id();
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -415,8 +413,8 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc,
         // hop-start snapshot of the counters: k_write's last tile applies update_counter in place, so
         // its other workgroups must not read the live nc/ec
         HopState h;
-        h.edge_base = ec[0]; h.node_base = nc[0]; h.n_edges = 0; h.n_nodes = 0;
-        h.in_off = ec[2]; h.n_in = nc[2]; h.slots = total; h.pad = 0;
+        h.edge_base = ec[LEGION_EC_TOTAL]; h.node_base = nc[LEGION_NC_TOTAL]; h.n_edges = 0; h.n_nodes = 0;
+        h.in_off = ec[LEGION_EC_INPUT_OFF]; h.n_in = nc[LEGION_NC_NEXT_INPUTS]; h.slots = total; h.pad = 0;
         *hs = h;
     }
     const int32_t T = (n_tiles + (int32_t)gridDim.x - 1) / (int32_t)gridDim.x;     // tiles per chunk (k_write derives the same T)
@@ -478,22 +476,25 @@ __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc,
 }
 
 // ------------------------------------------------------------------------------------------------
-// S2: update_counter (Kernels.cu:128-149), H-hop layout: nc[1] == n_nodes, ec[1] == n_edges of this hop
+// S2: update_counter (Kernels.cu:128-149) behind hop hh, which found level hh (legion_batch_layout.h draws the words)
 // ------------------------------------------------------------------------------------------------
 __device__ inline void apply_update_counter(int32_t* nc, int32_t* ec, int32_t op_id, int32_t hops, int32_t n_nodes,
                                             int32_t n_edges)
 {
     const int32_t hh = op_id / 2;
-    nc[0] += n_nodes;
-    nc[3 + 2 * hh] = nc[1 + 2 * hh] + nc[2 + 2 * hh];
-    nc[4 + 2 * hh] = n_nodes;
-    if (hh == hops) nc[5 + 2 * hh] = nc[3 + 2 * hh] + nc[4 + 2 * hh];
-    nc[1] = 0;
-    nc[2] = n_edges;
-    ec[2 + hh] = (hh == 1 ? ec[3] : ec[1 + hh]) + n_edges;
-    ec[2] = ec[0];
-    ec[0] += n_edges;
-    ec[1] = 0;
+    const int off = legion_idx_level_offset(hh), size = legion_idx_level_size(hh);
+    nc[LEGION_NC_TOTAL] += n_nodes;
+    // nodes through level hh - 1, whose words lie one pair in front (addressed from level hh's: k_write keeps one base address)
+    nc[off] = nc[off - LEGION_LEVEL_WORDS] + nc[size - LEGION_LEVEL_WORDS];
+    nc[size] = n_nodes;
+    if (hh == hops) nc[legion_idx_nodes_through(hh)] = nc[off] + nc[size];
+    nc[LEGION_NC_HOP_NEW] = 0;
+    nc[LEGION_NC_NEXT_INPUTS] = n_edges;
+    const int32_t before = hh == 1 ? hh : hh - 1;        // edges through hop hh - 1; hop 1 reads its own word, which k_seed zeroed
+    ec[legion_idx_edges_through(hh)] = ec[legion_idx_edges_through(before)] + n_edges;
+    ec[LEGION_EC_INPUT_OFF] = ec[LEGION_EC_TOTAL];
+    ec[LEGION_EC_TOTAL] += n_edges;
+    ec[LEGION_EC_HOP] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -925,11 +926,6 @@ struct GatherSumArgs {
     int32_t cand_cap;        // elements of cand
     const float* wdraw;      // WT: the weight of every draw, by slot (k_draw_weights; the pipe's own buffer, cand_cap elements)
 };
-// input slots of the last hop, from the counters as apply_update_counter leaves them behind that hop (nc[2] is overwritten by then)
-__device__ inline int32_t last_hop_inputs(const int32_t* nc, const int32_t* ec, int32_t hops)
-{
-    return hops == 1 ? nc[4] : hops == 2 ? ec[3] : ec[1 + hops] - ec[hops];
-}
 
 // WT (normalised sums, "S5, normalised last hop" below): every row is scaled by its draw's weight before it is added, the product and the
 // add rounded separately -- S_w[i, :] = ((0.0f + fl(w0 * x0)) + fl(w1 * x1)) + ... -- which is what a trainer computes when it scales the
@@ -939,8 +935,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_sum(GatherSumArgs a)
 {
     constexpr int VEC = sizeof(VT) / 4;
     const GatherArgs& g = a.g;
-    const int32_t n_in = g.nc[3 + 2 * a.hops];
-    const int32_t runs = last_hop_inputs(g.nc, a.ec, a.hops);
+    const int32_t n_in = legion_first_block_dst(g.nc, a.hops);
+    const int32_t runs = legion_hop_inputs(g.nc, a.ec, a.hops);
     const int32_t C = g.F / VEC;
     const int64_t total = (int64_t)runs * C;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -1012,14 +1008,14 @@ __device__ inline int64_t agg_norm_chunk_len(int64_t total, int32_t chunks)
 }
 __device__ inline int64_t agg_norm_slots(const AggNormArgs& a)
 {
-    return min((int64_t)last_hop_inputs(a.nc, a.ec, a.hops) * a.f, (int64_t)a.cand_cap);
+    return min((int64_t)legion_hop_inputs(a.nc, a.ec, a.hops) * a.f, (int64_t)a.cand_cap);
 }
 
 __global__ __launch_bounds__(kBlock) void k_agg_norm_prep(AggNormArgs a)
 {
     constexpr int W = kBlock / 64;
     __shared__ int32_t s_w[W];
-    const int32_t n = min(a.nc[5 + 2 * a.hops], a.ids_cap);
+    const int32_t n = min(legion_batch_nodes(a.nc, a.hops), a.ids_cap);
     for (int32_t p = (int32_t)(blockIdx.x * kBlock + threadIdx.x); p < n; p += (int32_t)(gridDim.x * kBlock)) a.out_deg[p] = 0;
     const int64_t total = agg_norm_slots(a);
     const int64_t len = agg_norm_chunk_len(total, (int32_t)gridDim.x);
@@ -1039,7 +1035,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_norm_prep(AggNormArgs a)
 
 __global__ __launch_bounds__(kBlock) void k_block_out_deg(AggNormArgs a)
 {
-    const int32_t E = min(a.ec[2 + a.hops], a.ids_cap);
+    const int32_t E = min(legion_batch_edges(a.ec, a.hops), a.ids_cap);
     const int lane = lane_id();
     const int32_t stride = (int32_t)(gridDim.x * kBlock);
     for (int32_t base = (int32_t)(blockIdx.x * kBlock); base < E; base += stride) {   // whole waves: the lanes settle their repeats together
@@ -1076,8 +1072,8 @@ __global__ __launch_bounds__(kBlock) void k_draw_weights(AggNormArgs a)
     int32_t rank0 = 0;
 #pragma unroll
     for (int w = 0; w < W; w++) rank0 += s_w[w];
-    const int32_t e_in = a.hops == 1 ? 0 : a.ec[1 + a.hops];     // edges of the hops < H
-    const int32_t E = min(a.ec[2 + a.hops], a.ids_cap);
+    const int32_t e_in = legion_hop_edges_begin(a.ec, a.hops);   // edges of the hops < H
+    const int32_t E = min(legion_batch_edges(a.ec, a.hops), a.ids_cap);
     const int64_t total = agg_norm_slots(a);
     const int64_t len = agg_norm_chunk_len(total, (int32_t)gridDim.x);
     const int64_t lo = min((int64_t)blockIdx.x * len, total), hi = min(lo + len, total);
@@ -1217,7 +1213,7 @@ __global__ __launch_bounds__(kBlock) void k_hotness(const int32_t* __restrict__ 
                                                     int32_t hops, unsigned long long* __restrict__ access,
                                                     int32_t* __restrict__ max_ids)
 {
-    const int32_t n = hops > 0 ? total_nodes(nc, hops) : nc[0];
+    const int32_t n = hops > 0 ? legion_batch_nodes(nc, hops) : nc[LEGION_NC_TOTAL];
     // max_ids_ (GPUCache.cu:294-296) kept on the device: no blocking D2H per batch
     if (max_ids && blockIdx.x == 0 && threadIdx.x == 0) atomicMax(max_ids, n);
     for (int32_t i = threadIdx.x + blockDim.x * blockIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -1521,7 +1517,7 @@ void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_
 {
     const int l = (op_id - 1) / 2;
     LEGION_AUDIT_LAUNCH(s, "k_find_feat", LEGION_AW(cache_offset), LEGION_AL(sampled_ids), LEGION_AL(nc), LEGION_AL(feat_map));
-    k_find_feat<<<grid_for(bound, kBlock), kBlock, 0, s>>>(sampled_ids, cache_offset, nc, 3 + 2 * l, 4 + 2 * l, feat_map);
+    k_find_feat<<<grid_for(bound, kBlock), kBlock, 0, s>>>(sampled_ids, cache_offset, nc, legion_idx_level_offset(l), legion_idx_level_size(l), feat_map);
     HIP_CHECK_LAST();
 }
 

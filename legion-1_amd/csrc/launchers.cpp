@@ -185,7 +185,7 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
     g.rows_seen = nullptr; g.rows_hint = 0;
     g.hit_stats = nullptr;
     if (p->rows_seen && p->rows_seen_dev) { // slot: level of a per-level gather, or the last one for "all rows of the batch"
-        const int slot = off_idx < 0 ? kRowsSeenAll : (off_idx - 3) / 2;
+        const int slot = off_idx < 0 ? kRowsSeenAll : legion_idx_level(off_idx);
         g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
         g.rows_seen = p->rows_seen_dev + slot;
     }
@@ -200,7 +200,7 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
         g.row_ptr = p->row_ptr; // FindFeat + source selection as their own pass over the rows (k_row_ptrs)
         // the last gather of a batch: level `hops` of the per-level gathers, or the one gather over all rows
         // (a recorded batch graph would bake the decision in: graphs never sample)
-        if (!p->capturing && count_hits) g.hit_stats = GPUCache_HitSampling(cache, dev_id, off_idx < 0 || off_idx == 3 + 2 * p->hops, off_idx < 0 || off_idx == 3);
+        if (!p->capturing && count_hits) g.hit_stats = GPUCache_HitSampling(cache, dev_id, off_idx < 0 || off_idx == legion_idx_level_offset(p->hops), off_idx < 0 || off_idx == legion_idx_level_offset(0));
     }
     if (!g.table && !g.feat_map) { LEGION_ARG_ERROR("get_feature_kernel: no feature table"); return false; }
     return true;
@@ -215,7 +215,7 @@ static bool gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder
     if (!gather_args(g, cache, noder, p, dev_id, off_idx, size_idx, !p->agg_last_hop)) return false;
     launch_gather((hipStream_t)strm_hdl, g, rows_bound);
     // last counting launch of a sampled batch: the host may read the pinned {hits, rows} words once this event completes
-    if (g.hit_stats && (off_idx < 0 || off_idx == 3 + 2 * p->hops)) GPUCache_HitSamplingDone(cache, dev_id, strm_hdl);
+    if (g.hit_stats && (off_idx < 0 || off_idx == legion_idx_level_offset(p->hops))) GPUCache_HitSamplingDone(cache, dev_id, strm_hdl);
     return true;
 }
 
@@ -243,7 +243,7 @@ void get_feature_kernel(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, 
         if (l == memorypool->hops) legion_peer_exchange_gather(strm_hdl, cache, noder, memorypool, dev_id);
         return;
     }
-    if (gather_common(strm_hdl, cache, noder, memorypool, dev_id, 3 + 2 * l, 4 + 2 * l, memorypool->level_bound[l]))
+    if (gather_common(strm_hdl, cache, noder, memorypool, dev_id, legion_idx_level_offset(l), legion_idx_level_size(l), memorypool->level_bound[l]))
         memorypool->levels_gathered |= 1u << l;
 }
 
@@ -269,7 +269,7 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (norm && !p->agg_src_off[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the COO buffers of the current pipe are not set"); return; }
     if (!in_memory) return;
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, -1, 3 + 2 * H, false)) return;   // rows [0, nc[3 + 2H]); the hit counter belongs to the default mode's batches
+    if (!gather_args(g, cache, noder, p, dev_id, -1, legion_idx_level_offset(H), false)) return;   // rows [0, n_in): the levels < H; the hit counter belongs to the default mode's batches
     auto feedback = [&](int slot) {
         if (!p->rows_seen || !p->rows_seen_dev) return;
         g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
@@ -298,7 +298,7 @@ void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (!noder || !pool_ready(memorypool, "get_feature_kernel_all")) return;
     if (!in_memory) return;
     if (use_peer_exchange(cache, memorypool, dev_id)) { legion_peer_exchange_gather(strm_hdl, cache, noder, memorypool, dev_id); return; }
-    gather_common(strm_hdl, cache, noder, memorypool, dev_id, -1, 0, memorypool->num_ids); // rows [0, nc[0])
+    gather_common(strm_hdl, cache, noder, memorypool, dev_id, -1, LEGION_NC_TOTAL, memorypool->num_ids); // every row of the batch
 }
 
 // ---- owner-computes exchange variant of the gather (SURVEY 5 option b), one process per GPU ---------------------------------
@@ -312,7 +312,7 @@ int legion_exchange_plan(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder,
     if (!noder || !cache || !req_row || !req_dst || !counts || !pool_ready(memorypool, "legion_exchange_plan")) return -1;
     GPUMemoryPool* p = memorypool;
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, -1, 0, false)) return -1;      // the hit counter belongs to the lookup pass of k_row_ptrs
+    if (!gather_args(g, cache, noder, p, dev_id, -1, LEGION_NC_TOTAL, false)) return -1;      // the hit counter belongs to the lookup pass of k_row_ptrs
     if (!g.feat_map || !g.row_ptr || !p->cache_search_buffer) { LEGION_ARG_ERROR("legion_exchange_plan: needs a filled unified cache"); return -1; }
     launch_exchange_plan((hipStream_t)strm_hdl, g, dev_id % cache->Kg, cache->Kg, p->cache_search_buffer, counts, req_row, req_dst, p->num_ids);
     return error_pending() ? -1 : 0;
@@ -324,7 +324,7 @@ int legion_exchange_local(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder
     if (!noder || !cache || !pool_ready(memorypool, "legion_exchange_local")) return -1;
     GPUMemoryPool* p = memorypool;
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, -1, 0, false)) return -1;
+    if (!gather_args(g, cache, noder, p, dev_id, -1, LEGION_NC_TOTAL, false)) return -1;
     if (!g.row_ptr) { LEGION_ARG_ERROR("legion_exchange_local: needs a filled unified cache"); return -1; }
     g.row_ptr_ready = true;   // k_exch_fill resolved the local rows (and left the peers' rows without a source)
     launch_gather((hipStream_t)strm_hdl, g, p->num_ids);

@@ -71,11 +71,6 @@ struct Runner {
 // with its last rows missing and ipc_service.get_next refuses it (the reference's trainer reads past the allocation instead,
 // ipc_cuda_kernel.cu:200).  That is a trainer-side failure with no server-side trace -- so the server leaves one: the first such batch
 // is logged, all are counted (Runner_Finalize prints the total).
-// rows of the feature buffer an aggregated batch fills: n_in + N (the last hop's input slots), from its two counter arrays
-static int32_t agg_rows(const int32_t* nc, const int32_t* ec, int H)
-{
-    return nc[3 + 2 * H] + (H == 1 ? nc[4] : H == 2 ? ec[3] : ec[1 + H] - ec[H]);
-}
 
 // $LEGION_AGG_NORM: unset / empty = plain sums (0), "both" = out-degree rsqrt (1) and only on a server that aggregates the last hop.
 // Returns the mode, or -1 with the refusal in `why`.
@@ -103,11 +98,11 @@ static int32_t sampling_from_env(std::string& why)
 static void hand_over(Runner* r, IPCEnv* env, int pipe)
 {
     const int32_t rows = r->memorypool ? r->memorypool->feature_rows : 0;
-    int32_t nodes = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, 5 + 2 * r->hops);
+    int32_t nodes = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, legion_idx_nodes_through(r->hops));
     if (r->agg_last_hop && nodes >= 0) {     // the mirror is there: n_in + N rows (features, then one row of sums per input slot of the last hop)
-        int32_t nc[16], ec[16];
-        for (int i = 0; i < 16; i++) { nc[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, i); ec[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, 16 + i); }
-        nodes = agg_rows(nc, ec, r->hops);
+        int32_t nc[LEGION_COUNTER_WORDS], ec[LEGION_COUNTER_WORDS];
+        for (int i = 0; i < LEGION_COUNTER_WORDS; i++) { nc[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, i); ec[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, LEGION_COUNTER_WORDS + i); }
+        nodes = legion_agg_rows(nc, ec, r->hops);
     }
     if (rows > 0 && nodes > rows) {
         if (r->short_batches++ == 0)
@@ -150,7 +145,7 @@ static void wait_for_pipe(Runner* r, IPCEnv* env)
 }
 
 // LEGION_ERR_RETURN (embedding / tests) and a failed batch: never leave a trainer blocked on sem_w.  The batch in flight
-// is handed over as usual; the failed pipe is posted with nc[0] = -1 (every counter word 0xFFFFFFFF), which no valid
+// is handed over as usual; the failed pipe is posted with nc[LEGION_NC_TOTAL] = -1 (every counter word 0xFFFFFFFF), which no valid
 // batch produces -- a consumer must treat it as "server failed" (the reference's behaviour, exit(EXIT_FAILURE), is what
 // the default LEGION_ERR_EXIT mode does instead).
 static void post_poisoned(Runner* r, IPCEnv* env)
@@ -162,9 +157,9 @@ static void post_poisoned(Runner* r, IPCEnv* env)
     }
     (void)hipDeviceSynchronize();
     int32_t* nc = IPCEnv_GetNodeCounter(env, r->local_dev_id, r->current_pipe);
-    if (nc) (void)hipMemset(nc, 0xFF, 16 * sizeof(int32_t));
+    if (nc) (void)hipMemset(nc, 0xFF, LEGION_COUNTER_WORDS * sizeof(int32_t));
     int32_t* ec = IPCEnv_GetEdgeCounter(env, r->local_dev_id, r->current_pipe);   // no stale edge counts of the pipe's previous batch
-    if (ec) (void)hipMemset(ec, 0, 16 * sizeof(int32_t));
+    if (ec) (void)hipMemset(ec, 0, LEGION_COUNTER_WORDS * sizeof(int32_t));
     IPCEnv_SetMirror(env, r->local_dev_id, r->current_pipe, -1, 0);
     (void)hipGetLastError();
     IPCEnv_IPCPost(env, r->local_dev_id, r->current_pipe);
@@ -225,18 +220,15 @@ static bool run_graph(Runner* r, IPCEnv* env, int32_t batch_id)
 // (5.2 TB/s for rows that are not whole 128-byte lines).  A wrong guess costs a few per cent, never correctness.
 static void choose_gather(Runner* r, GPUCache* cache, IPCEnv* env, const int32_t* fanout)
 {
-    int32_t nc[16] = {0}, ec[16] = {0};
+    int32_t nc[LEGION_COUNTER_WORDS] = {0}, ec[LEGION_COUNTER_WORDS] = {0};
     const int32_t* dnc = IPCEnv_GetNodeCounter(env, r->local_dev_id, 0);
     const int32_t* dec = IPCEnv_GetEdgeCounter(env, r->local_dev_id, 0);
     if (!(dnc && dec && hipMemcpy(nc, dnc, sizeof(nc), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(ec, dec, sizeof(ec), hipMemcpyDeviceToHost) == hipSuccess)) {
         (void)hipGetLastError();
         return;
     }
-    double slots = 0.0, n_in = (double)nc[4];
-    for (int h = 1; h <= r->hops; h++) {
-        slots += n_in * (double)fanout[h - 1];
-        n_in = (double)(ec[2 + h] - (h > 1 ? ec[2 + h - 1] : 0));     // edges of hop h = input of hop h + 1
-    }
+    double slots = 0.0;
+    for (int h = 1; h <= r->hops; h++) slots += (double)legion_hop_inputs(nc, ec, h) * (double)fanout[h - 1];
     const double rows = (double)GPUCache_MaxIdNum(cache, r->local_dev_id);
     double gather_us = 0.0, sampler_us = 0.0;
     (void)legion_runner_gather_estimate(r->float_attr_len, rows, slots, &gather_us, &sampler_us);
@@ -404,11 +396,11 @@ void Runner_RunPreSc(Runner* r, RunnerParams* params)
     // the reference polls the (never recorded) updater event here, i.e. does not wait: batches of
     // the pre-sampling epoch are simply queued in order on stream 0.
     if (r->agg_last_hop) {   // ... except that sizing the buffer for max(n_in + N) needs both counter arrays of every batch
-        int32_t nc[16] = {0}, ec[16] = {0};
+        int32_t nc[LEGION_COUNTER_WORDS] = {0}, ec[LEGION_COUNTER_WORDS] = {0};
         HIP_CHECK(hipStreamSynchronize(r->streams[0]));
         HIP_CHECK(hipMemcpy(nc, r->memorypool->node_counter[r->memorypool->current_pipe], sizeof(nc), hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(ec, r->memorypool->edge_counter[r->memorypool->current_pipe], sizeof(ec), hipMemcpyDeviceToHost));
-        r->presc_max_rows = std::max(r->presc_max_rows, agg_rows(nc, ec, r->hops));
+        r->presc_max_rows = std::max(r->presc_max_rows, legion_agg_rows(nc, ec, r->hops));
     }
 }
 

@@ -543,7 +543,7 @@ void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm)
     if (norm && p->owns_scratch) alloc_agg_norm(p);
 }
 int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->agg_norm : 0; }
-// the current pipe's block out-degrees as the last normalised batch left them (int32[nc[5 + 2H]]); null before the mode was set
+// the current pipe's block out-degrees as the last normalised batch left them (int32[legion_batch_nodes(nc, H)]); null before the mode was set
 int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p)
 {
     if (!p || p->current_pipe < 0 || p->current_pipe >= (int)p->agg_out_deg.size()) return nullptr;

@@ -16,8 +16,8 @@
 #include "../../include/legion_amd.h"
 
 static LegionIPCClient* env = nullptr;
-static int32_t h_node_counter[16];
-static int32_t h_edge_counter[16];
+static int32_t h_node_counter[LEGION_COUNTER_WORDS];   // legion_batch_layout.h draws both arrays word by word
+static int32_t h_edge_counter[LEGION_COUNTER_WORDS];
 static int32_t g_hops = 2;
 static bool g_aggregated = false;   // the server hands the last hop over as neighbour sums (read once, in initialize)
 static int g_agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
@@ -66,15 +66,15 @@ static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated, i
     legion_ipc_client_wait(env); // env->Wait(), ipc_service.cpp:42
     legion_ipc_client_read_counters(env, h_node_counter, h_edge_counter);
     // a server that failed mid-batch posts the pipe with every node-counter word at -1 (runner.cpp, post_poisoned)
-    TORCH_CHECK(h_node_counter[0] >= 0, "ipc_service: the sampling server failed (poisoned batch posted)");
+    TORCH_CHECK(h_node_counter[LEGION_NC_TOTAL] >= 0, "ipc_service: the sampling server failed (poisoned batch posted)");
     const int dev = GetGPUDevice();
     const auto device = torch::Device(torch::kCUDA, dev);
     const auto i32 = torch::TensorOptions().dtype(torch::kI32).device(device);
     const auto f32 = torch::TensorOptions().dtype(torch::kF32).device(device);
     const int H = g_hops;
-    const int64_t n_nodes = h_node_counter[5 + 2 * H];
-    const int64_t n_in = h_node_counter[3 + 2 * H];
-    const int64_t n_runs = H == 1 ? h_node_counter[4] : H == 2 ? h_edge_counter[3] : h_edge_counter[1 + H] - h_edge_counter[H];
+    const int64_t n_nodes = legion_batch_nodes(h_node_counter, H);
+    const int64_t n_in = legion_first_block_dst(h_node_counter, H);
+    const int64_t n_runs = legion_hop_inputs(h_node_counter, h_edge_counter, H);
     const int64_t n_rows = aggregated ? n_in + n_runs : n_nodes;       // rows of the feature buffer this batch fills
     // the feature buffer holds a bounded number of rows (1.2 x the largest pre-sampled batch, Server.cu:275): a batch that reaches more
     // nodes must not be viewed as [n, F] (the reference does, unchecked: ipc_cuda_kernel.cu:200 -- a read past the allocation)
@@ -86,9 +86,9 @@ static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated, i
     std::vector<torch::Tensor> out;
     out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 0), {n_nodes}, i32));
     out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 1), {aggregated ? n_in : n_nodes, (int64_t)feature_dim}, f32));
-    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 2), {(int64_t)h_node_counter[5]}, i32));
+    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 2), {(int64_t)legion_nodes_through(h_node_counter, 0)}, i32));
     for (int k = 1; k <= H; k++) {
-        const int64_t n_edges = h_edge_counter[2 + (H - k + 1)]; // ec[4], ec[3] at H = 2 (ipc_cuda_kernel.cu:198-213)
+        const int64_t n_edges = legion_edges_through(h_edge_counter, H - k + 1); // block k: the hops 1..H-k+1 (ec[4], ec[3] at H = 2: ipc_cuda_kernel.cu:198-213)
         out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 3), {n_edges}, i32));
         out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 4), {n_edges}, i32));
     }
@@ -112,8 +112,8 @@ std::vector<int> get_block_size()
     std::vector<int> ret;
     const int H = g_hops;
     for (int k = 1; k <= H; k++) {
-        ret.push_back(h_node_counter[5 + 2 * (H - k + 1)]);
-        ret.push_back(h_node_counter[5 + 2 * (H - k)]);
+        ret.push_back(legion_nodes_through(h_node_counter, H - k + 1));
+        ret.push_back(legion_nodes_through(h_node_counter, H - k));
     }
     return ret;
 }

@@ -5,6 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 import legion1_amd.capi as K, legion1_amd.synth as S
+from legion1_amd import layout
 import bench
 workload, label = sys.argv[1], sys.argv[2]
 L = K.lib(); L.SetGPUDevice(0)
@@ -38,8 +39,8 @@ for it in range(3): one(it, False); one(it, True)
 t = {False: [], True: []}; shapes = []
 for it in range(3, 15):
     for agg in (False, True): t[agg].append(one(it, agg))
-    nc = eng.out[0][0]["nc"].to_numpy(np.int32, 16); ec = eng.out[0][0]["ec"].to_numpy(np.int32, 16)
-    shapes.append(dict(n=int(nc[5 + 2 * H]), n_in=int(nc[3 + 2 * H]), N=int(ec[1 + H] - ec[H]), E_H=int(ec[2 + H] - ec[1 + H])))
+    nc = eng.out[0][0]["nc"].to_numpy(np.int32, layout.COUNTER_WORDS); ec = eng.out[0][0]["ec"].to_numpy(np.int32, layout.COUNTER_WORDS)
+    shapes.append(dict(n=layout.batch_nodes(nc, H), n_in=layout.first_block_dst(nc, H), N=layout.hop_inputs(nc, ec, H), E_H=layout.hop_edges_end(ec, H) - layout.hop_edges_begin(ec, H)))
 m = {k: int(np.mean([s[k] for s in shapes])) for k in shapes[0]}
 F = spec.F
 print(json.dumps(dict(label=label, workload=workload, F=F, mean_shape=m,

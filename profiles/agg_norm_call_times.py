@@ -8,6 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 import legion1_amd.capi as K, legion1_amd.synth as S
+from legion1_amd import layout
 import bench
 workload, label = sys.argv[1], sys.argv[2]
 L = K.lib(); L.SetGPUDevice(0)
@@ -44,8 +45,8 @@ for it in range(3):
 t = {m: [] for m in modes}; shapes = []
 for it in range(3, 15):
     for m in modes: t[m].append(one(it, m))
-    nc = eng.out[0][0]["nc"].to_numpy(np.int32, 16); ec = eng.out[0][0]["ec"].to_numpy(np.int32, 16)
-    shapes.append(dict(n=int(nc[5 + 2 * H]), n_in=int(nc[3 + 2 * H]), N=int(ec[1 + H] - ec[H]), E=int(ec[2 + H]), E_H=int(ec[2 + H] - ec[1 + H])))
+    nc = eng.out[0][0]["nc"].to_numpy(np.int32, layout.COUNTER_WORDS); ec = eng.out[0][0]["ec"].to_numpy(np.int32, layout.COUNTER_WORDS)
+    shapes.append(dict(n=layout.batch_nodes(nc, H), n_in=layout.first_block_dst(nc, H), N=layout.hop_inputs(nc, ec, H), E=layout.batch_edges(ec, H), E_H=layout.hop_edges_end(ec, H) - layout.hop_edges_begin(ec, H)))
 m = {k: int(np.mean([s[k] for s in shapes])) for k in shapes[0]}
 stat = lambda v: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
 out = dict(label=label, workload=workload, F=spec.F, mean_shape=m, plain_sums_us=stat(t[False]))

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 import legion1_amd.capi as K, legion1_amd.synth as S
+from legion1_amd import layout
 import bench
 workload, label = sys.argv[1], sys.argv[2]
 batches = int(sys.argv[3]) if len(sys.argv) > 3 else 12
@@ -39,8 +40,8 @@ def one(it, distinct):
     L.d_event_record(ev[H], st)
     L.get_feature_kernel_all(st, eng.cache, eng.noder, pool, 0, 1)
     L.d_event_record(ev[H + 1], st); L.d_stream_sync(st); K.check()
-    nc = eng.out[0][0]["nc"].to_numpy(np.int32, 16); ec = eng.out[0][0]["ec"].to_numpy(np.int32, 16)
-    return [L.d_event_elapsed_ms(ev[h], ev[h + 1]) * 1e3 for h in range(H + 1)], int(ec[2 + H]), int(nc[5 + 2 * H])
+    nc = eng.out[0][0]["nc"].to_numpy(np.int32, layout.COUNTER_WORDS); ec = eng.out[0][0]["ec"].to_numpy(np.int32, layout.COUNTER_WORDS)
+    return [L.d_event_elapsed_ms(ev[h], ev[h + 1]) * 1e3 for h in range(H + 1)], layout.batch_edges(ec, H), layout.batch_nodes(nc, H)
 modes = (False, True) if has_distinct else (False,)
 for it in range(3):
     for m in modes: one(it, m)

@@ -84,7 +84,7 @@ def test_graphs_with_holes_and_short_rows(K, oracle, seed):
     feats = np.random.RandomState(100 + seed).rand(V, F).astype(np.float32)
     feats[::17] = np.float32(-0.0)                        # 0.0f + (-0.0f) = +0.0f: the sum starts from +0.0
     empty_runs = 0
-    for fan, B in (([3, 2], 50), ([5, 4, 3], 64), ([25, 10], 203), ([1, 1, 1, 1], 7), ([2], 1), ([6], 64)):
+    for fan, B in (([3, 2], 50), ([5, 4, 3], 64), ([25, 10], 203), ([1, 1, 1, 1], 7), ([2], 1), ([6], 64), ([2, 2, 2, 2, 2], 7)):
         orc = oracle.OracleRunner(indptr, indices, feats, V, F, B, fan)
         eng = make_engine(K, (V, F, indptr, indices, feats), B, fan, seeds=dict(train=[(seeds, labels[seeds])]))
         for counter in range(min(4, (len(seeds) + B - 1) // B)):
