@@ -929,7 +929,15 @@ void Server_Initialize(Server* s, int global_shard_count)
     {   // the hand-off switches, before any device is touched
         std::string why;
         if (agg_norm_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
-        if (sampling_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
+        const int32_t sampling = sampling_from_env(why);
+        if (sampling < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
+        // the launcher refuses such a hop per batch (launch_sample_hop): a server that booted would fail every batch, the pre-sampling epoch first
+        for (size_t h = 0; sampling == 1 && h < s->fanout.size(); h++)
+            if (s->fanout[h] > kDistinctMaxFanout) {
+                LEGION_ARG_ERROR(("Server_Initialize: LEGION_SAMPLING=distinct takes fan-outs of at most " + std::to_string(kDistinctMaxFanout) + ", hop " +
+                                  std::to_string(h + 1) + " has " + std::to_string(s->fanout[h]) + ": k_sample stages the picks of a tile's rows in static LDS").c_str());
+                return;
+            }
     }
     const Meta& m = s->meta;
     // from the first device call on the main thread works on GPU 0 unless a scope below says otherwise (the reference's main thread never

@@ -30,6 +30,7 @@ def main():
     except RuntimeError as e:
         assert "neighbour sums" in str(e) and "get_next_aggregated" in str(e), str(e)
     hops = ipc_service.get_hops()
+    sampling = ipc_service.sampling()
     if sys.argv[2] == "refuse":
         good = 0
         try:
@@ -59,7 +60,7 @@ def main():
         ipc_service.synchronize()
     ipc_service.finalize()
     with open(out_path, "w") as f:
-        json.dump(dict(steps=[train_steps, valid_steps, test_steps], hops=hops, batches=recs), f)
+        json.dump(dict(steps=[train_steps, valid_steps, test_steps], hops=hops, sampling=sampling, batches=recs), f)
 
 
 if __name__ == "__main__":

@@ -32,6 +32,7 @@ def main():
         except RuntimeError as e:
             assert all(w in str(e) for w in words), str(e)
     hops = ipc_service.get_hops()
+    sampling = ipc_service.sampling()
     train_steps, valid_steps, test_steps = ipc_service.get_steps()
     recs = []
     for b in range((train_steps + valid_steps) * epochs + test_steps):
@@ -48,7 +49,7 @@ def main():
         ipc_service.synchronize()
     ipc_service.finalize()
     with open(out_path, "w") as f:
-        json.dump(dict(steps=[train_steps, valid_steps, test_steps], hops=hops, batches=recs), f)
+        json.dump(dict(steps=[train_steps, valid_steps, test_steps], hops=hops, sampling=sampling, batches=recs), f)
 
 
 if __name__ == "__main__":

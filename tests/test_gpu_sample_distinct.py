@@ -10,6 +10,7 @@ import pytest
 import distinctref as D
 from aggref import expected_nbr_sum
 from conftest import KEYS_NO_FEATURES, assert_batch_equal
+from distinctcases import Statement, random_graph
 from gcnref import expected_nbr_sum_norm
 from harness import K, OUT, SERVER, assert_served_record, child_env, ipc_namespace, make_engine, replay_served, serve_sets, served  # noqa: F401  (K: the module-scoped library fixture)
 
@@ -21,16 +22,6 @@ F_GRID = (1, 2, 5, 10, 25, 64)
 
 def d_grid(f):
     return (f + 1, f + 2, 2 * f, 3 * f + 1, 10 * f + 3, 1000 + f)
-
-
-class Statement:
-    """tests/distinctref.py behind the oracle runner's run_batch signature (harness.replay_served)."""
-
-    def __init__(self, indptr, indices, feats, B, fan):
-        self.a, self.B, self.fan = (indptr, indices, feats), B, list(fan)
-
-    def run_batch(self, ids, lab, counter, mode=0, batch_size=None):
-        return D.run_batch(*self.a, ids, lab, self.B if batch_size is None else batch_size, counter, self.fan)
 
 
 def assert_bits(name, got, want):
@@ -50,21 +41,6 @@ def probe(K, rows, hops, deg, f):
     for b in bufs + [out]:
         b.free()
     return got
-
-
-def random_graph(seed, V, max_deg=40, hubs=5, hub_deg=300, holes=False, simple=False):
-    """degrees 0..max_deg around the fan-outs of the tests (rows with d <= f and d > f) and a few hubs; simple: no multi-edges"""
-    rng = np.random.RandomState(seed)
-    deg = rng.randint(0, max_deg + 1, size=V)
-    deg[rng.randint(0, V, hubs)] = min(hub_deg, V)
-    indptr = np.zeros(V + 1, np.int64)
-    indptr[1:] = np.cumsum(deg)
-    if simple:
-        indices = np.concatenate([rng.permutation(V)[:d] for d in deg]).astype(np.int32)
-    else:
-        indices = rng.randint(-1 if holes else 0, V, size=int(indptr[-1])).astype(np.int32)
-    labels = rng.randint(0, 9, size=V).astype(np.int32)
-    return indptr, indices, labels
 
 
 # ---------------------------------------------------------------------------------------------------
