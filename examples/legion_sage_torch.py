@@ -155,7 +155,9 @@ def worker(rank, world, args):
     train_steps, valid_steps, test_steps = ipc_service.get_steps()
     hops = ipc_service.get_hops() if hasattr(ipc_service, "get_hops") else 2
     if rank == 0:   # how the server's sampler draws (LEGION_SAMPLING): "replace" like the reference, or "distinct" neighbours per row
-        print("Server sampling mode: %s" % (ipc_service.sampling() if hasattr(ipc_service, "sampling") else "replace"), flush=True)
+        seed = ipc_service.sampling_seed() if hasattr(ipc_service, "sampling_seed") else None
+        print("Server sampling mode: %s, %s" % (ipc_service.sampling() if hasattr(ipc_service, "sampling") else "replace",
+                                                "the same batches every epoch (no LEGION_SAMPLING_SEED)" if seed is None else "seed %d: fresh draws per batch, reshuffled per epoch" % seed), flush=True)
     served_agg = bool(ipc_service.aggregated()) if hasattr(ipc_service, "aggregated") else False
     if served_agg != bool(args.aggregated):
         raise SystemExit("--aggregated must match the server: it %s the last hop (LEGION_AGG_LAST_HOP)" % ("aggregates" if served_agg else "does not aggregate"))

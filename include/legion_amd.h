@@ -400,6 +400,21 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
  * mode and a switch while the pool is being captured are sticky argument errors.  Nothing is allocated. */
 void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p);
+/* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
+ * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
+ * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list
+ * (a keyed bijection of the list indices; validation and test lists stay in file order).  iter is batch_generator_kernel's `counter`; the
+ * round is what GPUMemoryPool_BeginRound recorded last (0 at first).  Seed 0 is a seed; on = 0 is today's behaviour, bit for bit.
+ * BeginRound(stream, pool, noder, dev_id, round): records the round and, under a seed, (re)fills the pool's shuffled copy of (noder, dev_id)'s
+ * training list on `stream` -- pass the stream the batch generator runs on.  noder = NULL leaves the training list in file order (lists
+ * that are served verbatim, such as link-prediction thirds); the draws stay seeded.  The copy is allocated on first use.  Returns 0, or -1
+ * with a sticky error.  Both calls are refused while the pool is being captured; a training batch under a seed without a BeginRound for
+ * its list is a sticky error of batch_generator_kernel; LegionBatchGraph_Launch refuses a graph recorded in the other state (seeded /
+ * unseeded), while a new round or seed needs no new recording.  GetSampleSeed returns the flag and stores the seed (seed may be NULL). */
+void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed);
+int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed);
+int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* noder, int32_t dev_id, int32_t round);
+int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p);
 /* Owner-computes exchange variant of the feature gather (SURVEY 5 option b; the reference reads peer caches in-kernel over
  * NVLink, Kernels.cu:662-702 -- this is the collective formulation for one process per GPU, the all-to-all itself is RCCL /
  * hipMemcpyPeer in the caller: legion-1_amd/exchange.py).  plan (requester): rows of the batch cached on another clique member are
@@ -491,6 +506,11 @@ int32_t IPCEnv_GetAggNorm(const IPCEnv* e);
  * word reads 0. */
 void IPCEnv_SetSampling(IPCEnv* e, int32_t mode);
 int32_t IPCEnv_GetSampling(const IPCEnv* e);
+/* ... and, in two words appended behind that one, seeded sampling (GPUMemoryPool_SetSampleSeed; the runner sets them under
+ * LEGION_SAMPLING_SEED): a flag and the 32-bit seed.  The getters return the flag and store the seed (seed may be NULL).  A client of a
+ * server without the words reads "off". */
+void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed);
+int32_t IPCEnv_GetSamplingSeed(const IPCEnv* e, uint32_t* seed);
 int IPCEnv_SlabPinned(IPCEnv* e);   /* 1: the slab is page-locked (hipHostRegister), IPCEnv_MirrorCounters queues real asynchronous copies */
 void IPCEnv_IPCPost(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
 void IPCEnv_IPCWait(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
@@ -500,6 +520,7 @@ int IPCEnv_IPCTryWait(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t t
 int IPCEnv_HandoffSpinUs(void);
 void IPCEnv_Finalize(IPCEnv* e);
 int32_t IPCEnv_GetTrainStep(IPCEnv* e);
+int32_t IPCEnv_GetRound(IPCEnv* e, int32_t global_batch_id);   /* global_batch_id / (train + validation steps): the round of seeded sampling */
 /* extension: number of hops published to the trainer (stored after the reference's struct) */
 void IPCEnv_SetHops(IPCEnv* e, int32_t hops);
 /* Namespace for the POSIX shm / semaphore names ("" = the reference's literal names
@@ -531,6 +552,7 @@ int32_t legion_ipc_client_feature_rows(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c);
 int32_t legion_ipc_client_sampling(LegionIPCClient* c);
+int32_t legion_ipc_client_sampling_seed(LegionIPCClient* c, uint32_t* seed);
 /* both counter arrays of the current pipe (legion_batch_layout.h draws them word by word) (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
  * a blocking device copy like the reference */
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[LEGION_COUNTER_WORDS], int32_t h_edge_counter[LEGION_COUNTER_WORDS]);
@@ -621,6 +643,18 @@ void legion_rng_probe(void* stream, const int32_t* idx, const int32_t* deg, int3
 /* Distinct-mode probe: pos_out[m * f + j] = the neighbour position slot j of row row[m] of hop hop[m] takes at degree deg[m] and fan-out
  * f (1..64), computed ON THE GPU with k_sample's own device functions; -1 = the slot has no draw.  All pointers are device memory. */
 void legion_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos_out, int32_t n);
+/* Seeded-sampling probes (INTEGRATION.md "Seeded sampling"), computed ON THE GPU with the kernels' own device functions for the batch
+ * (seed, round, iter): the with-replacement position of (idx[i], deg[i]); the distinct positions as legion_distinct_probe lays them out;
+ * perm_out[g] = perm(g) of the round's shuffle for g < n.  The two host functions return W(seed, round, iter) and Ks(seed, round). */
+void legion_seeded_rng_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* idx, const int32_t* deg, int32_t* k_out, int32_t n);
+void legion_seeded_distinct_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* row, const int32_t* hop, const int32_t* deg,
+                                  int32_t f, int32_t* pos_out, int32_t n);
+void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, int32_t* perm_out);
+uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter);
+uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round);
+/* compute units of the current device as the sampler's persistent grids count them: a hop of more than 4 x this x 1024 slots makes a
+ * workgroup of k_sample run a second tile */
+int32_t legion_sampler_cu_count(void);
 
 #ifdef __cplusplus
 }

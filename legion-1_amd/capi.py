@@ -205,6 +205,10 @@ _SIGS = {
     "GPUMemoryPool_GetAggOutDeg": (vp, [vp]),
     "GPUMemoryPool_SetSampleDistinct": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetSampleDistinct": (C.c_int, [vp]),
+    "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
+    "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
+    "GPUMemoryPool_BeginRound": (C.c_int, [vp, vp, vp, i32, i32]),
+    "GPUMemoryPool_GetRound": (i32, [vp]),
     "legion_exchange_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "legion_exchange_local": (C.c_int, [vp, vp, vp, vp, i32]),
     "legion_exchange_serve": (None, [vp, vp, i32, vp, i32, vp]),
@@ -244,6 +248,7 @@ _SIGS = {
     "IPCEnv_SetAggLastHop": (None, [vp, i32]), "IPCEnv_GetAggLastHop": (i32, [vp]), "legion_ipc_client_agg_last_hop": (i32, [vp]),
     "IPCEnv_SetAggNorm": (None, [vp, i32]), "IPCEnv_GetAggNorm": (i32, [vp]), "legion_ipc_client_agg_norm": (i32, [vp]),
     "IPCEnv_SetSampling": (None, [vp, i32]), "IPCEnv_GetSampling": (i32, [vp]), "legion_ipc_client_sampling": (i32, [vp]),
+    "IPCEnv_SetSamplingSeed": (None, [vp, i32, u32]), "IPCEnv_GetSamplingSeed": (i32, [vp, vp]), "legion_ipc_client_sampling_seed": (i32, [vp, vp]),
     "legion_ipc_client_open": (vp, [i32]), "legion_ipc_client_wait": (None, [vp]),
     "legion_ipc_client_post": (None, [vp]), "legion_ipc_client_post_nosync": (None, [vp]), "legion_ipc_client_buffer": (vp, [vp, i32]),
     "legion_ipc_client_steps": (None, [vp, vp]), "legion_ipc_client_hops": (i32, [vp]), "legion_ipc_client_feature_rows": (i32, [vp]),
@@ -274,6 +279,12 @@ _SIGS = {
     "legion_copy_f4_cfg": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32]),
     "legion_rng_probe": (None, [vp, vp, vp, vp, i32]),
     "legion_distinct_probe": (None, [vp, vp, vp, vp, i32, vp, i32]),
+    "legion_seeded_rng_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32]),
+    "legion_seeded_distinct_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32, vp, i32]),
+    "legion_perm_probe": (None, [vp, u32, i32, i32, vp]),
+    "legion_seeded_draw_word": (u32, [u32, i32, i32]),
+    "legion_seeded_shuffle_key": (u32, [u32, i32]),
+    "legion_sampler_cu_count": (i32, []),
 }
 
 
@@ -458,6 +469,7 @@ class Engine:
         self.streams = [None] * self.G
         self._graphs = []
         self._agg = {}      # (dev, pipe) -> the pipe's last batch was handed over aggregated (run_batch(agg_last_hop=True))
+        self._seed_state = {}   # dev -> (seed or None, round) the pool was last put into (run_batch / capture_batch / run_graph)
         self._norm = {}     # (dev, pipe) -> ... with normalised sums (run_batch(agg_norm="both"))
         check()
 
@@ -476,8 +488,13 @@ class Engine:
 
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
-                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace"):
-        """sample: "replace" (the reference's draws with replacement) or "distinct" (GPUMemoryPool_SetSampleDistinct: min(degree, fan-out)
+                  batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
+                  seed=None, round=0):
+        """seed: None (the reference's draws: the same batch every epoch) or a uint32 (GPUMemoryPool_SetSampleSeed: the batch's draws come
+        from W(seed, round, counter) and a training batch reads the round's shuffled list); round: the epoch the batch belongs to.  Like
+        `sample`, both SET the pool's state on every call, and GPUMemoryPool_BeginRound runs when the seed, the round or the device's
+        training list changed.
+        sample: "replace" (the reference's draws with replacement) or "distinct" (GPUMemoryPool_SetSampleDistinct: min(degree, fan-out)
         distinct neighbours per row, pre-sampling batches included).  Like agg_last_hop and agg_norm, the argument SETS the pool's mode on
         every call: a mode switched on through GPUMemoryPool_SetSampleDistinct directly is switched back by a run_batch() without sample="distinct".
         agg_last_hop: the aggregated hand-off (get_feature_kernel_agg) -- feature rows of the levels < H (per level behind each hop,
@@ -495,6 +512,7 @@ class Engine:
         pool = self.pools[dev]
         if L.GPUMemoryPool_GetSampleDistinct(pool) != int(sample == "distinct"):
             L.GPUMemoryPool_SetSampleDistinct(pool, int(sample == "distinct"))
+        self._set_seed(dev, seed, round, stream)
         agg = bool(agg_last_hop) and not is_presc     # gather=False: the sampler side of such a batch (the last hop's draws kept per pipe)
         if bool(L.GPUMemoryPool_GetAggLastHop(pool)) != agg:
             L.GPUMemoryPool_SetAggLastHop(pool, int(agg))
@@ -525,10 +543,24 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
+    def _set_seed(self, dev, seed, round, stream):
+        """The pool's seeded state := (seed, round); BeginRound on `stream` when either changed (not callable inside a capture: there the
+        state is what capture_batch set before Begin)."""
+        L, pool = self.L, self.pools[dev]
+        want = (None if seed is None else int(seed) & 0xFFFFFFFF, int(round))
+        if self._seed_state.get(dev, (None, 0)) == want:
+            return
+        L.GPUMemoryPool_SetSampleSeed(pool, int(seed is not None), want[0] or 0)
+        L.GPUMemoryPool_BeginRound(stream, pool, self.noder, dev, want[1])
+        check()
+        self._seed_state[dev] = want
+
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace"):
-        """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph()."""
+                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0):
+        """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
+        seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
+        run_graph(..., seed=, round=)."""
         if sample not in ("replace", "distinct"):
             raise ValueError("sample: 'replace' or 'distinct'")
         L = self.L
@@ -540,11 +572,12 @@ class Engine:
             if self.streams[dev] is None:
                 self.streams[dev] = L.d_stream_create()
             stream = self.streams[dev]
+        self._set_seed(dev, seed, round, stream)     # the shuffled copy is allocated and filled here: not between Begin and End
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
-                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample)
+                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -552,9 +585,13 @@ class Engine:
         self._graphs.append(g)
         return (g, stream, dev)
 
-    def run_graph(self, handle, counter, sync=True):
+    def run_graph(self, handle, counter, sync=True, seed=False, round=None):
+        """seed / round: leave the pool's seeded state as it is (the defaults), or set it first like run_batch does (seed=None: unseeded)."""
         g, stream, dev = handle
         self.L.SetGPUDevice(dev)
+        if seed is not False or round is not None:
+            cur = self._seed_state.get(dev, (None, 0))
+            self._set_seed(dev, cur[0] if seed is False else seed, cur[1] if round is None else round, stream)
         if self.L.LegionBatchGraph_Launch(g, stream, int(counter)) != 0:
             check()
             raise RuntimeError("LegionBatchGraph_Launch failed")

@@ -142,6 +142,37 @@ __host__ __device__ inline uint32_t powmod31(uint32_t base, uint64_t e)
     return r;
 }
 
+// Seeded sampling (INTEGRATION.md "Seeded sampling"): the keys of a round and the draw word of a batch.  mix32 is the distinct mode's hash.
+__host__ __device__ inline uint32_t mix32(uint32_t z)
+{
+    z ^= z >> 16; z *= 0x7feb352du; z ^= z >> 15; z *= 0x846ca68bu; z ^= z >> 16;
+    return z;
+}
+constexpr uint32_t kShuffleTag = 0x53485546u, kDrawTag = 0x44524157u, kGolden = 0x9E3779B9u;
+__host__ __device__ inline uint32_t seeded_shuffle_key(uint32_t seed, uint32_t round) { return mix32(mix32(seed ^ kShuffleTag) ^ round); }
+__host__ __device__ inline uint32_t seeded_draw_key(uint32_t seed, uint32_t round) { return mix32(mix32(seed ^ kDrawTag) ^ round); }
+__host__ __device__ inline uint32_t seeded_draw_word(uint32_t seeded, uint32_t draw_key, int32_t counter) { return seeded ? mix32(draw_key ^ (uint32_t)counter) : 0u; }
+// the minstd seed of a batch: thrust::minstd_rand(s_b); 1 (the default-constructed engine, today's stream) for W = 0
+__host__ __device__ inline uint32_t seeded_stream_seed(uint32_t w) { return 1u + w % 2147483646u; }
+// The round's permutation of [0, n): a four-round Feistel network on b = bit_length(n - 1) rounded up to even bits, cycle-walked into
+// [0, n) (the domain has fewer than 4 n points).  Only k_shuffle_seeds and the probe run it: once per epoch, never per batch.
+__host__ __device__ inline uint32_t seeded_perm(uint32_t g, uint32_t n, uint32_t ks)
+{
+    if (n <= 1) return g;
+    uint32_t b = 0;
+    while (b < 32 && ((n - 1) >> b)) b++;
+    const uint32_t h = (b + 1) >> 1, m = (1u << h) - 1u;
+    uint32_t rk[4];
+    for (uint32_t q = 0; q < 4; q++) rk[q] = mix32(ks + q * kGolden);
+    uint32_t x = g;
+    do {
+        uint32_t L = x >> h, R = x & m;
+        for (uint32_t q = 0; q < 4; q++) { const uint32_t t = L ^ (mix32(R ^ rk[q]) & m); L = R; R = t; }
+        x = (L << h) | R;
+    } while (x >= n);
+    return x;
+}
+
 // unsigned division by a runtime constant (host precomputed): q = (n * m) >> 32 >> s, n < 2^31
 struct FastDiv {
     uint32_t d = 1, m = 0, s = 0;
@@ -162,9 +193,15 @@ struct CsrTables {                 // GPU_Memory_Graph_Storage.cu:45-133: the wh
     const int32_t* topo_row;       // int32[V] row in the owner's fragment (edge_offset_map)
 };
 
-struct BatchCtl {                  // device-resident batch cursor (see k_seed)
+struct BatchCtl {                  // device-resident batch cursor (see k_seed); 20 bytes, one line
     int32_t counter;               // batch index inside the seed list
     uint32_t epoch;                // position-table epoch of the running batch
+    // Seeded sampling (GPUMemoryPool_SetSampleSeed, INTEGRATION.md "Seeded sampling"): `draw` is the batch's draw word W -- what k_sample
+    // reads, beside `epoch` --, 0 with the mode off, which is today's stream (s_b = 1) and today's distinct key.  Whoever sets `counter`
+    // (k_seed host-driven, k_set_cursor, k_advance) sets it too, from the seeded flag and the round's key.
+    uint32_t draw;
+    uint32_t seeded;               // 0: mode off
+    uint32_t draw_key;             // mix32(mix32(S ^ kDrawTag) ^ round)
 };
 
 struct HopState {                  // written by the scan kernel, read by the write/resolve kernels
@@ -199,9 +236,12 @@ struct SamplerBuffers {
 void launch_seed(hipStream_t s, int32_t* batch_ids, int32_t* labels, int32_t batch_size, int32_t size, int32_t counter,
                  const int32_t* all_ids, const int32_t* all_labels, int32_t total_cap, pos_t* pos_map,
                  uint32_t epoch, BatchCtl* ctl, bool self_driven, int32_t* nc, int32_t* ec, int32_t* aux_next,
-                 int32_t f_next, int32_t aux_cap);
-void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch);
+                 int32_t f_next, int32_t aux_cap, uint32_t seeded = 0, uint32_t draw_key = 0);
+void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded = 0, uint32_t draw_key = 0);
+// out_ids[g] = ids[perm(g)], out_labels[g] = labels[perm(g)] for g < n under shuffle key ks (seeded_perm)
+void launch_shuffle_seeds(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, uint32_t ks, int32_t* out_ids, int32_t* out_labels);
 void launch_advance(hipStream_t s, BatchCtl* ctl);
+int sampler_cu_count();       // compute units the persistent grids are sized by (current device)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
                        int32_t hops, int32_t slots_bound, bool is_presc, bool distinct = false);
@@ -272,6 +312,10 @@ void launch_hotness(hipStream_t s, const int32_t* ids, const int32_t* nc, int32_
                     int32_t* max_ids, int32_t bound);
 void launch_rng_probe(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n);
 void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n);
+// the seeded counterparts (w = the batch's draw word) and perm(0 .. n - 1) of a round
+void launch_seeded_rng_probe(hipStream_t s, uint32_t w, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n);
+void launch_seeded_distinct_probe(hipStream_t s, uint32_t w, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n);
+void launch_perm_probe(hipStream_t s, uint32_t ks, int32_t n, int32_t* out);
 // cache construction helpers
 void launch_aggregate_access(hipStream_t s, unsigned long long* agg, const unsigned long long* add, int32_t n);
 void launch_iota(hipStream_t s, int32_t* out, int32_t n);
@@ -337,6 +381,19 @@ struct GPUMemoryPool {
     // Distinct-draw sampler mode (GPUMemoryPool_SetSampleDistinct): every hop of this pool, the pre-sampling hops included, draws
     // min(degree, fan-out) distinct neighbour positions per row (INTEGRATION.md "Sampling without replacement").  Nothing is allocated.
     bool sample_distinct = false;
+    // Seeded sampling (GPUMemoryPool_SetSampleSeed / GPUMemoryPool_BeginRound; INTEGRATION.md "Seeded sampling"): with `seeded` every batch
+    // draws from its own word W(seed, round, counter) and the training batches read the round's shuffled copy of the training list
+    // (shuf_ids / shuf_labels, filled by k_shuffle_seeds in BeginRound; allocated there on first use, never inside a capture).
+    // shuf_src: the seed set's list the copy was made of; shuf_valid: it holds the permutation of (seed, round).  shuf_file_order: BeginRound
+    // was told to leave the training list in file order (lists served verbatim, link-prediction thirds) -- the draws are still seeded.
+    bool seeded = false;
+    uint32_t seed = 0, round = 0;
+    int32_t* shuf_ids = nullptr;
+    int32_t* shuf_labels = nullptr;
+    int32_t shuf_cap = 0, shuf_n = 0;
+    const int32_t* shuf_src = nullptr;
+    bool shuf_valid = false, shuf_file_order = false;
+    bool seed_reads_shuffle = false;  // the last batch_generator_kernel (the recording's, inside a capture) read the shuffled copy
     std::vector<int32_t*> agg_out_deg, agg_chunk_cnt;
     std::vector<float*> agg_wdraw;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])

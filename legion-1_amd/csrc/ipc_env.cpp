@@ -77,6 +77,12 @@ struct shmExt {
     // agg_last_hop, agg_norm -- the layout of the older words, which holds; tests/test_sample_distinct_cpu.py finds this word in the mapped
     // object right behind agg_norm.)
     std::int32_t sampling;
+    // Appended behind sampling (nothing above moves; same spelling, for the same tests): seeded sampling (LEGION_SAMPLING_SEED, INTEGRATION.md
+    // "Seeded sampling").  sampling_seeded: 0 = the reference's draws, the same batches every epoch; 1 = fresh draws per batch and the
+    // training list reshuffled per epoch under sampling_seed.  Seed 0 is a seed: the flag says whether there is one.  A client of an
+    // older server reads 0, "off".
+    std::int32_t sampling_seeded;
+    std::uint32_t sampling_seed;
 };
 static const uint32_t kMirrorMagic = 0x4C474E43u;   // "LGNC"
 static uint32_t handle_checksum(const volatile void* h)
@@ -533,6 +539,13 @@ void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm) { if (e && e->ext) e->ext->agg_n
 int32_t IPCEnv_GetAggNorm(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_norm : 0; }
 void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->sampling = mode ? 1 : 0; }
 int32_t IPCEnv_GetSampling(const IPCEnv* e) { return (e && e->ext) ? e->ext->sampling : 0; }
+void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed) { if (e && e->ext) { e->ext->sampling_seed = on ? seed : 0u; e->ext->sampling_seeded = on ? 1 : 0; } }
+int32_t IPCEnv_GetSamplingSeed(const IPCEnv* e, uint32_t* seed)
+{
+    const bool on = e && e->ext && e->ext->sampling_seeded;
+    if (seed) *seed = on ? e->ext->sampling_seed : 0u;
+    return on ? 1 : 0;
+}
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
     if (e && e->ext && device_id >= 0 && device_id < e->device_count) e->ext->feature_rows[device_id] = rows;
@@ -713,6 +726,12 @@ void IPCEnv_Finalize(IPCEnv* e)
 }
 
 int32_t IPCEnv_GetTrainStep(IPCEnv* e) { return e->train_step; }
+// the round (epoch) a global batch belongs to: global_batch_id / (train + validation steps), so test batches get a round >= epochs
+int32_t IPCEnv_GetRound(IPCEnv* e, int32_t global_batch_id)
+{
+    const int32_t per = e ? e->train_step + e->valid_step : 0;
+    return per > 0 && global_batch_id >= 0 ? global_batch_id / per : 0;
+}
 void IPCEnv_SetHops(IPCEnv* e, int32_t hops) { if (e && e->ext) e->ext->hops = hops; }
 
 } // extern "C"
@@ -900,6 +919,12 @@ int32_t legion_ipc_client_hops(LegionIPCClient* c) { return c->hops; }
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_last_hop : 0; }
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_norm : 0; }
 int32_t legion_ipc_client_sampling(LegionIPCClient* c) { return (c && c->ext) ? c->ext->sampling : 0; }
+int32_t legion_ipc_client_sampling_seed(LegionIPCClient* c, uint32_t* seed)
+{
+    const bool on = c && c->ext && c->ext->sampling_seeded;
+    if (seed) *seed = on ? c->ext->sampling_seed : 0u;
+    return on ? 1 : 0;
+}
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[LEGION_COUNTER_WORDS], int32_t h_edge_counter[LEGION_COUNTER_WORDS])
 {

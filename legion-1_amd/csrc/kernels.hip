@@ -37,7 +37,8 @@
 //    else the final index in sampled_ids.
 //  * Row descriptors (start, degree) of a tile are fetched once per source row and staged in
 //    LDS -- the reference re-reads both int64 indptr words in each of the `count` lanes.
-//  * RNG: x = 48271^(idx+1) mod (2^31-1).  Per thread: one table lookup and one Mersenne
+//  * RNG: x = s_b * 48271^(idx+1) mod (2^31-1), s_b = 1 unless the pool is seeded (one more mul-mod per workgroup: the batch's s_b goes
+//    into the workgroup's base power).  Per thread: one table lookup and one Mersenne
 //    mul-mod per tile instead of Thrust's discard() chain of 2*log2(idx) 64-bit `%`.
 //    The final fp64 divide/multiply/truncate is kept verbatim -- it is what makes k bit exact.
 //  * All loop bounds come from device counters; launches are sized by static upper bounds, so
@@ -71,12 +72,8 @@ __device__ inline uint32_t fdiv(uint32_t n, const FastDiv& d)
 // Distinct-draw sampler mode (INTEGRATION.md "Sampling without replacement"): a row of degree d > f takes f distinct neighbour positions
 // by Floyd's algorithm over hashed randoms, a pure function of (hop, row of the hop's input list); d <= f takes every neighbour once.
 // All arithmetic is uint32 with wrap-around except the one 64-bit product.
-__host__ __device__ inline uint32_t mix32(uint32_t z)
-{
-    z ^= z >> 16; z *= 0x7feb352du; z ^= z >> 15; z *= 0x846ca68bu; z ^= z >> 16;
-    return z;
-}
-__device__ inline uint32_t distinct_key(uint32_t row, uint32_t hop) { return mix32(row + 0x9E3779B9u * hop); }
+// (mix32 lives in internal.h: the seeded mode's keys are formed on the host too.)  w: the batch's draw word, 0 with the seeded mode off.
+__device__ inline uint32_t distinct_key(uint32_t row, uint32_t hop, uint32_t w) { return mix32((row + 0x9E3779B9u * hop) ^ w); }
 __device__ inline uint32_t distinct_u(uint32_t key, uint32_t t) { return mix32(key ^ (0x85EBCA6Bu * (t + 1u))); }
 // In place: p[0, f) holds distinct_u(key, t) on entry and the row's f positions on return; d > f.  Sequential per row (pick t looks at the
 // picks before it): at most f (f - 1) / 2 compares.  p is LDS in k_sample, global memory in the probe.
@@ -101,7 +98,9 @@ __device__ inline int wave_id() { return threadIdx.x >> 6; }
 // (Kernels.cu:227), so the read offset is size*counter (restated, not "fixed").
 // SELF (captured batch graphs): the batch cursor and the table epoch live in device memory (BatchCtl),
 // advanced by k_advance at the end of every graph launch, so that the captured launch has no per-batch
-// arguments.  Host-driven launches pass both as arguments and publish them for the kernels that follow.
+// arguments.  Host-driven launches pass both as arguments and publish them for the kernels that follow, and with them the batch's
+// draw word (seeded sampling: BatchCtl::draw, 0 with the mode off).  In training mode under a seed all_ids / all_labels are the pool's
+// shuffled copy of the list (k_shuffle_seeds), read exactly as the file-order list is.
 template <bool SELF>
 __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids, int32_t* __restrict__ labels,
                                                  int32_t batch_size, int32_t size, int32_t counter,
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
                                                  pos_t* __restrict__ pos_map, uint32_t epoch,
                                                  BatchCtl* __restrict__ ctl, int32_t* __restrict__ nc,
                                                  int32_t* __restrict__ ec, int32_t* __restrict__ aux_next,
-                                                 int32_t f_next, int32_t aux_cap)
+                                                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key)
 {
     int32_t idx = threadIdx.x + blockDim.x * blockIdx.x;
     if (SELF) {
@@ -122,6 +121,9 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
     } else if (idx == 0) {
         ctl->counter = counter;
         ctl->epoch = epoch;
+        ctl->draw = seeded_draw_word(seeded, draw_key, counter);
+        ctl->seeded = seeded;
+        ctl->draw_key = draw_key;
     }
     if (idx < size) {
         int32_t g = size * counter + idx;
@@ -161,9 +163,30 @@ __global__ void k_fill_aux(const int32_t* __restrict__ nc, int32_t count, int32_
     const int64_t n = min((int64_t)nc[LEGION_NC_NEXT_INPUTS] * count, (int64_t)aux_cap);
     for (int64_t i = threadIdx.x + (int64_t)blockDim.x * blockIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) aux[i] = -1;
 }
-__global__ void k_set_cursor(BatchCtl* ctl, int32_t counter, uint32_t epoch) { ctl->counter = counter; ctl->epoch = epoch; }
-// end of a captured batch: next batch, next (smaller) epoch
-__global__ void k_advance(BatchCtl* ctl) { ctl->counter += 1; ctl->epoch -= 1; }
+__global__ void k_set_cursor(BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded, uint32_t draw_key)
+{
+    ctl->counter = counter; ctl->epoch = epoch;
+    ctl->draw = seeded_draw_word(seeded, draw_key, counter); ctl->seeded = seeded; ctl->draw_key = draw_key;
+}
+// end of a captured batch: next batch, next (smaller) epoch, the next batch's draw word
+__global__ void k_advance(BatchCtl* ctl)
+{
+    const int32_t counter = ctl->counter + 1;
+    ctl->counter = counter; ctl->epoch -= 1;
+    ctl->draw = seeded_draw_word(ctl->seeded, ctl->draw_key, counter);
+}
+
+// Seeded sampling: the round's shuffled copy of a training list, one thread per list index.  k_seed reads the copy exactly as it reads the
+// file-order list; the cycle walk of seeded_perm runs here, once per epoch, and nowhere else.
+__global__ __launch_bounds__(kBlock) void k_shuffle_seeds(const int32_t* __restrict__ ids, const int32_t* __restrict__ labels, int32_t n, uint32_t ks,
+                                                          int32_t* __restrict__ out_ids, int32_t* __restrict__ out_labels)
+{
+    const int32_t g = threadIdx.x + blockDim.x * blockIdx.x;
+    if (g >= n) return;
+    const uint32_t p = seeded_perm((uint32_t)g, (uint32_t)n, ks);   // < n
+    out_ids[g] = ids[p];
+    out_labels[g] = labels[p];
+}
 
 // S7: ClearPosMap (Kernels.cu:750-756) has no kernel here: position-table entries carry the batch epoch
 // in their upper 32 bits, so entries of older batches are simply stale (see the table format below).
@@ -248,13 +271,15 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
     const int32_t n_tiles = (total + TILE - 1) / TILE;
     const int tid = threadIdx.x;
     const uint32_t epoch = a.ctl->epoch;
+    const uint32_t draw = a.ctl->draw;   // the batch's draw word (seeded sampling), same line as the epoch; 0 = mode off
 
     if ((int32_t)blockIdx.x >= n_tiles) return;
 
-    // per-thread RNG state: x[s] = 48271^(tile*TILE + tid + 256*s + 1) (the distinct mode draws from the hash: no stream)
+    // per-thread RNG state: x[s] = s_b * 48271^(tile*TILE + tid + 256*s + 1) (the distinct mode draws from the hash: no stream)
     uint32_t x[TILE / kBlock];
     if constexpr (!DISTINCT) {
-        uint32_t base = powmod31(a.a_tile, (uint64_t)blockIdx.x); // uniform per workgroup
+        // uniform per workgroup; the seeded stream is the unseeded one times the batch's s_b (1 with the mode off: mulmod31(b, 1) == b)
+        uint32_t base = mulmod31(powmod31(a.a_tile, (uint64_t)blockIdx.x), seeded_stream_seed(draw));
 #pragma unroll
         for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(base, a.pow_tab[tid + kBlock * s]);
     }
@@ -297,7 +322,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             const uint32_t hop = (uint32_t)a.op_id >> 1;
             for (int32_t p = tid; p < nrows * f; p += kBlock) {
                 const uint32_t rr = fdiv((uint32_t)p, a.fdiv);
-                s_pick[p] = (int32_t)distinct_u(distinct_key((uint32_t)i0 + rr, hop), (uint32_t)p - rr * (uint32_t)f);
+                s_pick[p] = (int32_t)distinct_u(distinct_key((uint32_t)i0 + rr, hop, draw), (uint32_t)p - rr * (uint32_t)f);
             }
         }
         __syncthreads();
@@ -1228,12 +1253,25 @@ __global__ void k_rng_probe(const int32_t* idx, const int32_t* deg, int32_t* k, 
     if (i < n) k[i] = sample_index(powmod31(kA, (uint64_t)idx[i] + 1ull), deg[i]);
 }
 
+// seeded stream: x = s_b * 48271^(idx + 1), as k_sample forms it (base times the slot's power)
+__global__ void k_seeded_rng_probe(uint32_t w, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n)
+{
+    int32_t i = threadIdx.x + blockDim.x * blockIdx.x;
+    if (i < n) k[i] = sample_index(mulmod31(seeded_stream_seed(w), powmod31(kA, (uint64_t)idx[i] + 1ull)), deg[i]);
+}
+__global__ void k_perm_probe(uint32_t ks, int32_t n, int32_t* out)
+{
+    const int32_t g = threadIdx.x + blockDim.x * blockIdx.x;
+    if (g < n) out[g] = (int32_t)seeded_perm((uint32_t)g, (uint32_t)n, ks);
+}
+
 // ------------------------------------------------------------------------------------------------
 // cache construction kernels (one-off; S8 / S9)
 // ------------------------------------------------------------------------------------------------
 // The distinct mode's positions of n rows, by the device functions k_sample<.., DISTINCT> runs: pos[m * f + j] = neighbour position of slot j
-// of row row[m] of hop hop[m] at degree deg[m], -1 = no draw.  One thread per row; the row's f words of pos are its work space.
-__global__ void k_distinct_probe(const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
+// of row row[m] of hop hop[m] at degree deg[m], -1 = no draw.  One thread per row; the row's f words of pos are its work space.  w: the
+// batch's draw word (legion_seeded_distinct_probe), 0 = the seeded mode off.
+__global__ void k_distinct_probe(uint32_t w, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
 {
     const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
     if (m >= n) return;
@@ -1243,7 +1281,7 @@ __global__ void k_distinct_probe(const int32_t* row, const int32_t* hop, const i
         for (int32_t j = 0; j < f; j++) out[j] = j < d ? j : -1;
         return;
     }
-    const uint32_t key = distinct_key((uint32_t)row[m], (uint32_t)hop[m]);
+    const uint32_t key = distinct_key((uint32_t)row[m], (uint32_t)hop[m], w);
     for (int32_t t = 0; t < f; t++) out[t] = (int32_t)distinct_u(key, (uint32_t)t);
     distinct_resolve(out, d, f);
 }
@@ -1421,19 +1459,26 @@ static uint32_t* pow_table()
 void launch_seed(hipStream_t s, int32_t* batch_ids, int32_t* labels, int32_t batch_size, int32_t size, int32_t counter,
                  const int32_t* all_ids, const int32_t* all_labels, int32_t total_cap, pos_t* pos_map,
                  uint32_t epoch, BatchCtl* ctl, bool self_driven, int32_t* nc, int32_t* ec, int32_t* aux_next,
-                 int32_t f_next, int32_t aux_cap)
+                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key)
 {
     const int32_t bound = self_driven ? batch_size : size;
     int blocks = bound > 0 ? (bound - 1) / kBlock + 1 : 1;
     LEGION_AUDIT_LAUNCH(s, "k_seed", LEGION_AW(batch_ids), LEGION_AW(labels), LEGION_AW(pos_map), LEGION_AW(ctl), LEGION_AW(nc), LEGION_AW(ec), LEGION_AW(aux_next), LEGION_AL(all_ids), LEGION_AL(all_labels));
-    if (self_driven) k_seed<true><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap);
-    else k_seed<false><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap);
+    if (self_driven) k_seed<true><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key);
+    else k_seed<false><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key);
     HIP_CHECK_LAST();
 }
-void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch)
+void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded, uint32_t draw_key)
 {
     LEGION_AUDIT_LAUNCH(s, "k_set_cursor", LEGION_AW(ctl));
-    k_set_cursor<<<1, 1, 0, s>>>(ctl, counter, epoch);
+    k_set_cursor<<<1, 1, 0, s>>>(ctl, counter, epoch, seeded, draw_key);
+    HIP_CHECK_LAST();
+}
+void launch_shuffle_seeds(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, uint32_t ks, int32_t* out_ids, int32_t* out_labels)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_shuffle_seeds", LEGION_AW(out_ids), LEGION_AW(out_labels), LEGION_AL(ids), LEGION_AL(labels));
+    k_shuffle_seeds<<<(n + kBlock - 1) / kBlock, kBlock, 0, s>>>(ids, labels, n, ks, out_ids, out_labels);
     HIP_CHECK_LAST();
 }
 void launch_advance(hipStream_t s, BatchCtl* ctl)
@@ -1443,6 +1488,7 @@ void launch_advance(hipStream_t s, BatchCtl* ctl)
     HIP_CHECK_LAST();
 }
 void warm_static_tables() { (void)pow_table(); (void)cu_count(); }
+int sampler_cu_count() { return cu_count(); }
 
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
@@ -1670,12 +1716,30 @@ void launch_hotness(hipStream_t s, const int32_t* ids, const int32_t* nc, int32_
     HIP_CHECK_LAST();
 }
 
-void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
+void launch_seeded_distinct_probe(hipStream_t s, uint32_t w, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
 {
     if (n <= 0) return;
     if (f < 1 || f > kDistinctMaxFanout) { LEGION_ARG_ERROR("legion_distinct_probe: distinct sampling takes a fan-out of 1 to 64"); return; }
     LEGION_AUDIT_LAUNCH(s, "k_distinct_probe", LEGION_AW(pos), LEGION_AL(row), LEGION_AL(hop), LEGION_AL(deg));
-    k_distinct_probe<<<(n + 255) / 256, 256, 0, s>>>(row, hop, deg, f, pos, n);
+    k_distinct_probe<<<(n + 255) / 256, 256, 0, s>>>(w, row, hop, deg, f, pos, n);
+    HIP_CHECK_LAST();
+}
+void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
+{
+    launch_seeded_distinct_probe(s, 0u, row, hop, deg, f, pos, n);
+}
+void launch_seeded_rng_probe(hipStream_t s, uint32_t w, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_seeded_rng_probe", LEGION_AW(k), LEGION_AL(idx), LEGION_AL(deg));
+    k_seeded_rng_probe<<<(n + 255) / 256, 256, 0, s>>>(w, idx, deg, k, n);
+    HIP_CHECK_LAST();
+}
+void launch_perm_probe(hipStream_t s, uint32_t ks, int32_t n, int32_t* out)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_perm_probe", LEGION_AW(out));
+    k_perm_probe<<<(n + 255) / 256, 256, 0, s>>>(ks, n, out);
     HIP_CHECK_LAST();
 }
 void launch_rng_probe(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n)

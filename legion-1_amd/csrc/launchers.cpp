@@ -48,6 +48,19 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     if (all_labels == nullptr) { log_out() << "invalid label ptr\n"; return; }
 
     GPUMemoryPool* p = memorypool;
+    // Seeded sampling: a training batch reads the round's shuffled copy of the list (same length, same indexing) unless the round was
+    // begun in file order; the draw word of the batch comes from the pool's (seed, round) and the counter.
+    const uint32_t seeded = p->seeded ? 1u : 0u, draw_key = p->seeded ? seeded_draw_key(p->seed, p->round) : 0u;
+    p->seed_reads_shuffle = false;
+    if (p->seeded && mode == LEGION_TRAINMODE && !p->shuf_file_order) {
+        if (!p->shuf_valid || p->shuf_src != set.ids || p->shuf_n != total_cap) {
+            LEGION_ARG_ERROR("batch_generator_kernel: seeded sampling (GPUMemoryPool_SetSampleSeed) serves training batches from the round's shuffled list: call GPUMemoryPool_BeginRound for this device's training list first");
+            return;
+        }
+        all_ids = p->shuf_ids;
+        all_labels = p->shuf_labels;
+        p->seed_reads_shuffle = true;
+    }
     const int q = p->current_pipe;
     if (p->device_id != dev_id && audit::on()) {   // the pool starts serving this GPU: its scratch and its output buffers must live there
         LEGION_AUDIT_OWNER(p->pos_map, dev_id, "batch_generator_kernel: scratch of the memory pool");
@@ -69,7 +82,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         // device, `counter` is ignored, bounds are those of a full batch.
         if (batch_size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
         launch_seed(s, p->sampled_ids[q], p->labels[q], batch_size, batch_size, 0, all_ids, all_labels, total_cap, p->pos_map, 0,
-                    p->ctl, true, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots);
+                    p->ctl, true, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key);
         p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0];
         p->bound_n = batch_size > 0 ? batch_size : 0;
         p->bound_nodes = p->bound_n;
@@ -87,7 +100,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     int32_t size = ((batch_size * (counter + 1)) >= total_cap) ? (total_cap - batch_size * counter) : batch_size;
     if (size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
     launch_seed(s, p->sampled_ids[q], p->labels[q], batch_size, size, counter, all_ids, all_labels, total_cap, p->pos_map, epoch,
-                p->ctl, false, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots);
+                p->ctl, false, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key);
     p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0]; // k_seed prepared the slot states of hop 1
     p->bound_n = size > 0 ? size : 0;
     p->bound_nodes = p->bound_n;

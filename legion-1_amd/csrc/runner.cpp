@@ -7,6 +7,7 @@
 #include "internal.h"
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cstring>
 #include <fcntl.h>
@@ -58,6 +59,13 @@ struct Runner {
     // $LEGION_SAMPLING=replace|distinct (unset = replace): distinct = every hop, the pre-sampling epoch included, draws min(degree, fan-out)
     // distinct neighbours per row (GPUMemoryPool_SetSampleDistinct; INTEGRATION.md "Sampling without replacement").
     int32_t sampling = 0;
+    // $LEGION_SAMPLING_SEED=<uint32> (unset = off): every batch draws from its own word and the training list is reshuffled every round
+    // (GPUMemoryPool_SetSampleSeed / BeginRound; INTEGRATION.md "Seeded sampling").  round: the one the pool was last told, -1 = none yet.
+    // lists_verbatim: the training lists are served as they are (meta flag 2, link-prediction thirds): never shuffled, draws still seeded.
+    bool seeded = false;
+    uint32_t seed = 0;
+    int32_t round = -1;
+    bool lists_verbatim = false;
     int32_t presc_max_rows = 0;     // largest n_in + N of the pre-sampling epoch (read back per batch: that epoch is not pipelined anyway)
     bool pending = false;
     int pending_pipe = 0;
@@ -93,6 +101,35 @@ static int32_t sampling_from_env(std::string& why)
     if (strcmp(n, "distinct") == 0) return 1;
     why = std::string("LEGION_SAMPLING=") + n + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row)";
     return -1;
+}
+
+// $LEGION_SAMPLING_SEED: unset / empty = off; else a decimal or 0x hex integer in [0, 2^32).  Returns 0 (off), 1 (on, the seed in `seed`), or
+// -1 with the refusal in `why`.
+static int32_t sampling_seed_from_env(uint32_t& seed, std::string& why)
+{
+    const char* n = getenv("LEGION_SAMPLING_SEED");
+    seed = 0;
+    if (!n || !n[0]) return 0;
+    const bool hex = n[0] == '0' && (n[1] == 'x' || n[1] == 'X');
+    const char* digits = hex ? n + 2 : n;
+    bool ok = digits[0] != 0 && strlen(digits) <= 16;
+    for (const char* c = digits; ok && *c; c++) ok = hex ? isxdigit((unsigned char)*c) != 0 : isdigit((unsigned char)*c) != 0;
+    unsigned long long v = 0;
+    if (ok) { v = strtoull(digits, nullptr, hex ? 16 : 10); ok = v <= 0xFFFFFFFFull; }
+    if (!ok) { why = std::string("LEGION_SAMPLING_SEED=") + n + " is not a sampling seed: a decimal or 0x hex integer in [0, 2^32), or unset (the same batches every epoch)"; return -1; }
+    seed = (uint32_t)v;
+    return 1;
+}
+
+// Seeded sampling: tell the pool the round, on the stream the batch generator runs on (the shuffled copy is refilled in front of the round's
+// first k_seed and behind the last one of the round before).
+static void begin_round(Runner* r, GPUNodeStorage* noder, int32_t round)
+{
+    if (!r->seeded || r->round == round) return;
+    if (r->lists_verbatim && r->round < 0)
+        log_out() << r->local_dev_id << " Seeded sampling: the training lists are served verbatim (meta flag 2): not shuffled, the draws are seeded\n";
+    GPUMemoryPool_BeginRound(r->streams[0], r->memorypool, r->lists_verbatim ? nullptr : noder, r->local_dev_id, round);
+    r->round = round;
 }
 
 static void hand_over(Runner* r, IPCEnv* env, int pipe)
@@ -268,6 +305,12 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
         if (sampling < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
         r->sampling = sampling;
     }
+    {
+        std::string why;
+        const int32_t on = sampling_seed_from_env(r->seed, why);
+        if (on < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
+        r->seeded = on == 1;
+    }
     r->local_dev_id = params->device_id;
     DeviceGuard guard(r->local_dev_id);
     GPUCache* cache = (GPUCache*)params->cache;
@@ -316,6 +359,9 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     GPUMemoryPool_SetSampleDistinct(r->memorypool, r->sampling);   // before the pre-sampling epoch: the hotness profile sees what will be served
     IPCEnv_SetSampling(env, r->sampling);                          // what a trainer reads: ipc_service.sampling()
     log_out() << r->local_dev_id << " Sampling: " << (r->sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
+    GPUMemoryPool_SetSampleSeed(r->memorypool, r->seeded ? 1 : 0, r->seed);
+    IPCEnv_SetSamplingSeed(env, r->seeded ? 1 : 0, r->seed);      // what a trainer reads: ipc_service.sampling_seed()
+    if (r->seeded) log_out() << r->local_dev_id << " Sampling seed: " << r->seed << " (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch\n";
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");
     LEGION_AUDIT_STREAM(r->streams[1], r->local_dev_id, "Runner_Initialize: gather stream");
@@ -389,6 +435,7 @@ void Runner_RunPreSc(Runner* r, RunnerParams* params)
     DeviceGuard guard(r->local_dev_id);
     GPUMemoryPool_SetCurrentMode(r->memorypool, 0);
     GPUMemoryPool_SetIter(r->memorypool, params->global_batch_id);
+    begin_round(r, (GPUNodeStorage*)params->noder, 0);   // the pre-sampling epoch is the first served epoch's draws
     for (int i = 0; i < r->op_num; i += 2) {
         r->op_params[i]->is_presc = 1;
         Operator_run(r->op_factory[i], r->op_params[i]);
@@ -413,6 +460,7 @@ void Runner_RunOnce(Runner* r, RunnerParams* params)
     r->mode = IPCEnv_GetCurrentMode(env, batch_id);
     GPUMemoryPool_SetCurrentMode(r->memorypool, r->mode);
     GPUMemoryPool_SetIter(r->memorypool, IPCEnv_GetLocalBatchId(env, batch_id));
+    begin_round(r, (GPUNodeStorage*)params->noder, IPCEnv_GetRound(env, batch_id));
     wait_for_pipe(r, env);
     if (r->use_graph && r->mode >= 0 && r->mode < 3) {
         if (!run_graph(r, env, batch_id)) {
@@ -902,6 +950,7 @@ void start_runners(Server* s)
         p->in_memory = 1;
         s->params[i] = p;
         s->runners[i] = NewGPURunner();
+        s->runners[i]->lists_verbatim = s->meta.partition == 2;
         Runner_Initialize(s->runners[i], p);
     }
 }
@@ -931,6 +980,8 @@ void Server_Initialize(Server* s, int global_shard_count)
         if (agg_norm_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
         const int32_t sampling = sampling_from_env(why);
         if (sampling < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
+        uint32_t seed = 0;
+        if (sampling_seed_from_env(seed, why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
         // the launcher refuses such a hop per batch (launch_sample_hop): a server that booted would fail every batch, the pre-sampling epoch first
         for (size_t h = 0; sampling == 1 && h < s->fanout.size(); h++)
             if (s->fanout[h] > kDistinctMaxFanout) {

@@ -236,4 +236,23 @@ void legion_distinct_probe(void* stream, const int32_t* row, const int32_t* hop,
     launch_distinct_probe((hipStream_t)stream, row, hop, deg, f, pos_out, n);
 }
 
+
+// the seeded mode's probes: (seed, round, iter) -> the draw word / the shuffle key, formed by the functions the launchers use
+void legion_seeded_rng_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* idx, const int32_t* deg, int32_t* k_out, int32_t n)
+{
+    launch_seeded_rng_probe((hipStream_t)stream, seeded_draw_word(1u, seeded_draw_key(seed, (uint32_t)round), iter), idx, deg, k_out, n);
+}
+void legion_seeded_distinct_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f,
+                                  int32_t* pos_out, int32_t n)
+{
+    launch_seeded_distinct_probe((hipStream_t)stream, seeded_draw_word(1u, seeded_draw_key(seed, (uint32_t)round), iter), row, hop, deg, f, pos_out, n);
+}
+void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, int32_t* perm_out)
+{
+    launch_perm_probe((hipStream_t)stream, seeded_shuffle_key(seed, (uint32_t)round), n, perm_out);
+}
+uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter) { return seeded_draw_word(1u, seeded_draw_key(seed, (uint32_t)round), iter); }
+int32_t legion_sampler_cu_count(void) { return sampler_cu_count(); }
+uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round) { return seeded_shuffle_key(seed, (uint32_t)round); }
+
 } // extern "C"

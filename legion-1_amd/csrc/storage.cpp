@@ -561,6 +561,62 @@ void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on)
 }
 int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->sample_distinct ? 1 : 0; }
 
+// Seeded sampling (INTEGRATION.md "Seeded sampling"): on = every batch of this pool draws from its own word W(seed, round, counter) -- the
+// minstd stream seeded per batch, the distinct mode's row key XORed with W -- and its training batches read the round's shuffled copy of
+// the training list (GPUMemoryPool_BeginRound).  Seed 0 is a seed like any other; off = today's bits.  A captured batch graph keeps the
+// state it was recorded in, so the switch is refused while one is being recorded.  Nothing is allocated here.
+void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleSeed: null pool"); return; }
+    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleSeed: the pool is being captured"); return; }
+    if (p->seed != seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
+    p->seeded = on != 0;
+    p->seed = seed;
+    p->ctl_synced = false;   // ctl holds the other state's draw word: a batch graph must reset the cursor
+}
+int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed)
+{
+    if (seed) *seed = p ? p->seed : 0;
+    return p && p->seeded ? 1 : 0;
+}
+int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p) { return p ? (int32_t)p->round : 0; }
+
+// A new round (the trainer's epoch) begins: the draw words and the shuffle of the batches that follow are those of `round`.  Under a seed the
+// pool's shuffled copy of (noder, dev_id)'s training list is (re)filled on `stream` -- the stream the batch generator runs on, so that the
+// first k_seed of the round is ordered behind it.  noder == null: the training list stays in file order (lists served verbatim, e.g.
+// link-prediction thirds); the draws are seeded all the same.  With the mode off the round is recorded and nothing is launched.
+int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* noder, int32_t dev_id, int32_t round)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: null pool"); return -1; }
+    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: the pool is being captured (a round begins between batches, not inside a recording)"); return -1; }
+    if (round < 0) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: negative round"); return -1; }
+    if (p->round != (uint32_t)round) p->shuf_valid = false;   // whatever the mode: the copy holds another round's permutation
+    p->round = (uint32_t)round;
+    p->ctl_synced = false;   // the next replay resets the cursor: k_set_cursor carries the round's draw key
+    if (!p->seeded) return 0;
+    p->shuf_file_order = noder == nullptr;
+    p->shuf_valid = false;
+    if (!noder) return 0;
+    if (!p->owns_scratch) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: GPUMemoryPool_AllocateScratch was not called"); return -1; }
+    const GPUNodeStorage::SeedSet& set = noder->seed_set(LEGION_TRAINMODE, dev_id);
+    if (set.num > 0 && (!set.ids || !set.labels)) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: the training list of this device is not built"); return -1; }
+    if (set.num > p->shuf_cap || !p->shuf_ids) {   // first use, or a longer list: batches that read the old copy may still be in flight
+        HIP_CHECK(hipDeviceSynchronize());
+        if (p->shuf_ids) (void)hipFree(p->shuf_ids);
+        if (p->shuf_labels) (void)hipFree(p->shuf_labels);
+        p->shuf_ids = p->shuf_labels = nullptr;
+        p->shuf_cap = std::max(set.num, 1);
+        HIP_CHECK(hipMalloc(&p->shuf_ids, (size_t)p->shuf_cap * sizeof(int32_t)));
+        HIP_CHECK(hipMalloc(&p->shuf_labels, (size_t)p->shuf_cap * sizeof(int32_t)));
+        if (!p->shuf_ids || !p->shuf_labels) return -1;
+    }
+    launch_shuffle_seeds((hipStream_t)stream, set.ids, set.labels, set.num, seeded_shuffle_key(p->seed, p->round), p->shuf_ids, p->shuf_labels);
+    p->shuf_n = set.num;
+    p->shuf_src = set.ids;
+    p->shuf_valid = true;
+    return error_pending() ? -1 : 0;
+}
+
 #define POOL_PIPE_SETTER(name, field, type) \
     void GPUMemoryPool_Set##name(GPUMemoryPool* p, type* ptr, int32_t pipe) { \
         if (pipe < 0 || pipe >= p->pipeline_depth) { LEGION_ARG_ERROR("GPUMemoryPool_Set" #name ": bad pipe"); return; } \
@@ -600,6 +656,9 @@ void GPUMemoryPool_Finalize(GPUMemoryPool* p)
     for (auto& c : p->agg_out_deg) { (void)hipFree(c); c = nullptr; }
     for (auto& c : p->agg_wdraw) { (void)hipFree(c); c = nullptr; }
     for (auto& c : p->agg_chunk_cnt) { (void)hipFree(c); c = nullptr; }
+    if (p->shuf_ids) (void)hipFree(p->shuf_ids);
+    if (p->shuf_labels) (void)hipFree(p->shuf_labels);
+    p->shuf_ids = p->shuf_labels = nullptr; p->shuf_cap = p->shuf_n = 0; p->shuf_src = nullptr; p->shuf_valid = false;
     p->pos_map = nullptr; p->cand = nullptr; p->tile_edge = p->tile_node = nullptr; p->hop_state = nullptr;
     p->cache_search_buffer = p->agg_src_ids = p->tmp_part_off = nullptr; p->tmp_part_ind = nullptr;
     p->owns_scratch = false;

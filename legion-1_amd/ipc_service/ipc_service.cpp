@@ -21,6 +21,8 @@ static int32_t h_edge_counter[LEGION_COUNTER_WORDS];
 static int32_t g_hops = 2;
 static bool g_aggregated = false;   // the server hands the last hop over as neighbour sums (read once, in initialize)
 static int g_agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
+static bool g_seeded = false;       // seeded sampling (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch
+static uint32_t g_seed = 0;         // ... the seed (0 is a seed: g_seeded says whether there is one)
 static int g_sampling = 0;          // how the server's sampler draws: 0 = with replacement, 1 = distinct neighbours (LEGION_SAMPLING=distinct)
 // ONE consumer thread per process is the contract (the reference's trainer loop, legion_graphsage.py:72-89):
 // get_next / synchronize run without the GIL and share `env`, the two counter arrays and the client's current pipe, so the entry points
@@ -40,6 +42,7 @@ void InitializeIPC()
     g_aggregated = legion_ipc_client_agg_last_hop(env) != 0;
     g_agg_norm = legion_ipc_client_agg_norm(env);
     g_sampling = legion_ipc_client_sampling(env);
+    g_seeded = legion_ipc_client_sampling_seed(env, &g_seed) != 0;
 }
 
 void FinalizeIPC()
@@ -103,6 +106,7 @@ std::vector<torch::Tensor> get_next_aggregated_norm(int feature_dim) { return ne
 bool aggregated() { require_env(); return g_aggregated; }
 int aggregate_norm() { require_env(); return g_agg_norm; }
 const char* sampling() { require_env(); return g_sampling ? "distinct" : "replace"; }
+pybind11::object sampling_seed() { require_env(); return g_seeded ? pybind11::object(pybind11::int_(g_seed)) : pybind11::object(pybind11::none()); }
 
 // [b1_src_nodes, b1_dst_nodes, b2_src_nodes, b2_dst_nodes, ...] = [nc9, nc7, nc7, nc5] at H = 2
 // (ipc_service.cpp:60-72)
@@ -147,6 +151,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("aggregated", &aggregated, "whether the server hands the last hop over as neighbour sums (extension)");
     m.def("aggregate_norm", &aggregate_norm, "how the server normalises the neighbour sums: 0 = not, 1 = out-degree rsqrt inside block 1 (extension)");
     m.def("sampling", &sampling, "how the server's sampler draws: \"replace\" (with replacement, the default) or \"distinct\" (LEGION_SAMPLING=distinct; extension)");
+    m.def("sampling_seed", &sampling_seed, "the server's sampling seed (LEGION_SAMPLING_SEED: fresh draws per batch, the training list reshuffled per epoch), or None: the same batches every epoch (extension)");
     m.def("get_block_size", &get_block_size, "get dgl block size");
     m.def("get_steps", &get_steps, "get steps");
     m.def("initialize", &InitializeIPC, "InitializeIPC");

@@ -55,6 +55,8 @@ def main(argv=None):
     ap.add_argument("--sampling", type=str, default=None, choices=["replace", "distinct"], help="extension: how a row draws its neighbours "
                     "(LEGION_SAMPLING for the server): replace = with replacement like the reference (the default), distinct = "
                     "min(degree, fan-out) distinct neighbours per row")
+    ap.add_argument("--sampling_seed", type=int, default=None, help="extension: a 32-bit seed (LEGION_SAMPLING_SEED for the server): every batch "
+                    "draws afresh and the training list is reshuffled every epoch; without it every epoch is the same epoch, like the reference's")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
@@ -68,6 +70,8 @@ def main(argv=None):
     env = dict(os.environ)
     if args.sampling is not None:
         env["LEGION_SAMPLING"] = args.sampling
+    if args.sampling_seed is not None:
+        env["LEGION_SAMPLING_SEED"] = str(args.sampling_seed)
     return subprocess.call(cmd, env=env)
 
 

@@ -1,0 +1,312 @@
+"""Seeded sampling on the CPU: the NumPy statement of tests/seededref.py against the issue's known answers, the properties a per-epoch
+shuffle and a per-batch seed must have, Thrust's own seeded engine, the mode off against tests/pyref.py and tests/distinctref.py, and the
+switch through the layers that need no GPU (the pool, the "<name>_ext" words, ipc_service, launch_server.py, the `legion` binary's boot)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import distinctref as D
+import pyref
+import seededref as R
+from conftest import ROOT
+
+def small_graph(seed, V=300, holes=True):
+    """tests/test_sample_distinct_cpu.py's graph: degrees 0..11, four hubs of 90, -1 entries"""
+    rng = np.random.RandomState(seed)
+    deg = rng.randint(0, 12, size=V)
+    deg[rng.randint(0, V, 4)] = 90
+    indptr = np.zeros(V + 1, np.int64)
+    indptr[1:] = np.cumsum(deg)
+    indices = rng.randint(-1 if holes else 0, V, size=int(indptr[-1])).astype(np.int32)
+    labels = rng.randint(0, 9, size=V).astype(np.int32)
+    feats = rng.rand(V, 5).astype(np.float32)
+    seeds = rng.permutation(V)[:97].astype(np.int32)
+    return indptr, indices, feats, labels, seeds
+
+
+def _server_script(ns, hops, body):
+    """(preamble, script) of a device-free IPC server process: one GPU, 3601 / 700 / 300 seeds at batch 500 -> steps [7, 2, 1]"""
+    pre = ("import os, sys, ctypes as C; sys.path.insert(0, %r)\n"
+           "os.environ['LEGION_IPC_NO_DEVICE'] = '1'; os.environ['LEGION_IPC_NAMESPACE'] = %r\n") % (ROOT, ns)
+    return pre, pre + ("import numpy as np, subprocess\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
+                       "e = L.NewIPCEnv(1)\n"
+                       "info = K.LegionBuildInfo(); info.partition_count = 1; info.epoch = 1; info.raw_batch_size = 500\n"
+                       "tr, va, te = (np.array([x], np.int32) for x in (3601, 700, 300))\n"
+                       "info.training_set_num, info.validation_set_num, info.testing_set_num = tr.ctypes.data, va.ctypes.data, te.ctypes.data\n"
+                       "L.IPCEnv_Coordinate(e, C.byref(info)); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); L.IPCEnv_SetHops(e, %d); K.check()\n"
+                       % hops) + body + "L.IPCEnv_Finalize(e); print('SERVER_OK')\n"
+
+
+N_LIST = (1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 203, 256, 257, 1000, 4097, 65537, 100003)
+SR_PAIRS = ((0, 0), (1, 1), (12345, 3), (0xFFFFFFFF, 7))
+W_KAT = 0xd66bf856
+
+
+# ---- known answers ---------------------------------------------------------------------------------
+def test_key_known_answers():
+    assert R.Ks(12345, 3) == 0x57a3ec80 and R.Ks(0, 0) == 0x43bf248e
+    assert R.W(12345, 3, 2) == W_KAT and R.s_b(W_KAT) == 1449916505
+    assert R.W(0, 0, 0) == 0x77bb992c
+
+
+def test_perm_known_answers():
+    assert R.perm(203, 0x57a3ec80)[:8].tolist() == [97, 64, 43, 85, 38, 200, 142, 99]
+    assert [R.perm_scalar(g, 203, 0x57a3ec80) for g in range(8)] == [97, 64, 43, 85, 38, 200, 142, 99]
+    assert R.perm(10, 0x43bf248e).tolist() == [5, 1, 7, 2, 3, 9, 0, 6, 8, 4]
+    assert R.perm(0, 5).tolist() == [] and R.perm(1, 5).tolist() == [0]
+
+
+def test_replace_known_answers():
+    assert R.replace_index([0, 1, 2, 999999], [1000] * 4, W_KAT).tolist() == [130, 473, 774, 996]
+    # the mode off is pyref's stream
+    idx = [0, 1, 2, 999999, 2 ** 31 - 2]
+    assert R.replace_index(idx, [1000] * 5, 0).tolist() == [pyref.sample_index(i, 1000) for i in idx]
+    assert R.minstd_values(idx).tolist() == [pyref.minstd_value(i) for i in idx]
+
+
+def test_distinct_known_answers():
+    assert R.picks_scalar(0, 1, 6, 5, W_KAT) == [1, 0, 3, 4, 2]
+    assert R.picks_scalar(12345, 3, 1000, 25, W_KAT)[:8] == [554, 621, 767, 223, 429, 371, 34, 170]
+    assert R.picks_scalar(199999, 1, 2000000000, 5, W_KAT) == [213940653, 337251786, 41287048, 39838029, 1676941256]
+    # the restatement reproduces the documented unseeded picks
+    assert R.picks_scalar(0, 1, 6, 5) == D.picks_scalar(0, 1, 6, 5) == [0, 2, 3, 4, 5]
+    assert R.picks_scalar(199999, 1, 2000000000, 5) == D.picks_scalar(199999, 1, 2000000000, 5)
+    got = R.distinct_positions(W_KAT)([0, 12345, 199999, 7], [1, 3, 1, 2], [6, 1000, 2000000000, 3], 5)
+    assert got.tolist() == [R.picks_scalar(i, h, d, 5, W_KAT) for i, h, d in ((0, 1, 6), (12345, 3, 1000), (199999, 1, 2000000000), (7, 2, 3))]
+    rows = np.arange(300)
+    assert np.array_equal(R.distinct_positions(0)(rows, 2, np.full(300, 40), 7), D.positions(rows, 2, np.full(300, 40), 7))
+
+
+# ---- the shuffle -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("S,r", SR_PAIRS)
+def test_perm_is_a_bijection(S, r):
+    ks = R.Ks(S, r)
+    for n in N_LIST:
+        p = R.perm(n, ks)
+        assert p.shape == (n,) and np.array_equal(np.sort(p), np.arange(n)), (S, r, n)
+        for g in (0, n // 2, n - 1):
+            assert R.perm_scalar(g, n, ks) == p[g]
+
+
+def test_rounds_differ():
+    for n in (17, 203, 100003):
+        assert not np.array_equal(R.perm(n, R.Ks(12345, 0)), R.perm(n, R.Ks(12345, 1)))
+    assert R.W(12345, 0, 4) != R.W(12345, 1, 4) and R.W(12345, 0, 4) != R.W(12345, 0, 5) and R.W(0, 0, 0) != 0
+
+
+def test_first_seed_is_uniform_over_the_rounds():
+    """perm(0) over rounds 0..19999 at n = 50, S = 9: chi-square with 49 degrees of freedom (the issue computed 52.6)."""
+    n, rounds = 50, 20000
+    c = np.bincount([R.perm_scalar(0, n, R.Ks(9, r)) for r in range(rounds)], minlength=n).astype(np.float64)
+    X = float(((c - rounds / n) ** 2 / (rounds / n)).sum())
+    print("chi-square of perm(0): %.1f, cap %.1f" % (X, D.chi2_cap(49)))
+    assert X <= D.chi2_cap(49)
+
+
+def test_stream_seed_range():
+    rng = np.random.RandomState(1)
+    ws = np.concatenate([rng.randint(0, 2 ** 32, size=100000, dtype=np.uint64), [0, 1, 2147483645, 2147483646, 2147483647, 2 ** 32 - 1]])
+    sb = np.array([R.s_b(int(w)) for w in ws])
+    assert sb.min() >= 1 and sb.max() <= 2 ** 31 - 2
+    assert R.s_b(0) == 1 and R.s_b(2147483646) == 1 and R.s_b(2147483645) == 2147483646
+
+
+# ---- Thrust's own seeded engine --------------------------------------------------------------------
+def test_seeded_stream_is_thrusts(tmp_path):
+    """thrust::minstd_rand(s_b), discard(idx), uniform_int_distribution<int>(0, deg - 1), compiled here from the ROCm install's headers for
+    the host: a few hundred (s_b, idx, deg), idx up to 2^31 - 2."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "thrust_seeded_probe")
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "--offload-arch=gfx950", "-x", "hip", os.path.join(ROOT, "tests", "thrust_seeded_probe.cpp"), "-o", exe])
+    rng = np.random.RandomState(7)
+    ws = [0, W_KAT, R.W(0, 0, 0), 2147483645, 2 ** 32 - 1] + rng.randint(0, 2 ** 32, size=55, dtype=np.uint64).tolist()
+    idxs = [0, 1, 2, 999999, 2 ** 31 - 2, 2 ** 31 - 3, 2 ** 31 - 1025] + rng.randint(0, 2 ** 31 - 1, size=5).tolist()
+    degs = [1, 2, 3, 1000, 2 ** 31 - 1] + rng.randint(1, 100000, size=3).tolist()
+    cases = [(R.s_b(w), int(rng.choice(idxs)) if n % 3 else idxs[n % len(idxs)], degs[n % len(degs)], w) for n, w in enumerate(ws * 6)]
+    assert len(cases) >= 300
+    text = "".join("%d %d %d\n" % c[:3] for c in cases)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120, check=True).stdout.split("\n")
+    got = np.array([int(line.split()[3]) for line in out if line])
+    assert len(got) == len(cases)
+    for w in set(c[3] for c in cases):
+        sel = [n for n, c in enumerate(cases) if c[3] == w]
+        want = R.replace_index([cases[n][1] for n in sel], [cases[n][2] for n in sel], w)
+        assert np.array_equal(got[sel], want), (hex(w), got[sel], want)
+
+
+# ---- the mode off and the whole batch ----------------------------------------------------------------
+@pytest.mark.parametrize("seed", [0, 1])
+def test_mode_off_is_todays_batch(seed):
+    indptr, indices, feats, labels, seeds = small_graph(seed)
+    dup = np.concatenate([seeds[:20], seeds[5:15]])
+    for fan, B, ids in (([3, 2], 40, seeds), ([5, 4, 3], 50, seeds), ([4], 30, dup), ([6, 3], 97, seeds)):
+        lab = labels[ids]
+        for counter in range(min(3, (len(ids) + B - 1) // B)):
+            want = pyref.run_batch(indptr, indices, feats, ids, lab, B, counter, fan)
+            got = R.run_batch(indptr, indices, feats, ids, lab, B, counter, fan)
+            for k in want:
+                assert np.array_equal(want[k], got[k]) and want[k].dtype == got[k].dtype, (fan, counter, k)
+            want = D.run_batch(indptr, indices, feats, ids, lab, B, counter, fan)
+            got = R.run_batch(indptr, indices, feats, ids, lab, B, counter, fan, sample="distinct")
+            for k in ("nc", "ec", "ids", "labels", "src_off", "dst_off", "features"):
+                assert np.array_equal(want[k], got[k]), (fan, counter, k)
+
+
+def test_seeded_epochs_draw_disjoint_full_batches_and_differ():
+    indptr, indices, feats, labels, seeds = small_graph(0)
+    B, fan, S = 25, [3, 2], 77
+    epochs = []
+    for rnd in (0, 1):
+        got = [R.run_batch(indptr, indices, feats, seeds, labels[seeds], B, c, fan, seed=S, round=rnd) for c in range(4)]
+        first = np.concatenate([b["ids"][:B] for b in got[:3]])            # 97 = 3 x 25 + 22: the full batches (the short one reads at
+        assert len(np.unique(first)) == 3 * B and np.isin(first, seeds).all()   # size * counter, the reference's offset, and overlaps them)
+        assert got[3]["nc"][4] == 22 and np.isin(got[3]["ids"][:22], seeds).all()
+        for b in got:
+            assert np.array_equal(b["labels"], labels[b["ids"][:len(b["labels"])]])
+        epochs.append(got)
+    assert not np.array_equal(epochs[0][0]["ids"], epochs[1][0]["ids"])
+    valid = R.run_batch(indptr, indices, feats, seeds, labels[seeds], B, 1, fan, seed=S, round=1, mode=1)
+    assert np.array_equal(valid["ids"][:B], seeds[B:2 * B])                # validation lists stay in file order
+    off = R.run_batch(indptr, indices, feats, seeds, labels[seeds], B, 1, fan)
+    assert not np.array_equal(valid["src_off"], off["src_off"])            # ... their draws are seeded
+    assert not np.array_equal(R.run_batch(indptr, indices, feats, seeds, labels[seeds], B, 0, fan, seed=0)["ids"],
+                              R.run_batch(indptr, indices, feats, seeds, labels[seeds], B, 0, fan)["ids"])   # seed 0 is a seed
+
+
+# ---- the switch through the layers that need no GPU ------------------------------------------------
+NEW_SYMBOLS = ("GPUMemoryPool_SetSampleSeed", "GPUMemoryPool_GetSampleSeed", "GPUMemoryPool_BeginRound", "IPCEnv_SetSamplingSeed",
+               "IPCEnv_GetSamplingSeed", "legion_ipc_client_sampling_seed", "legion_seeded_rng_probe", "legion_seeded_distinct_probe",
+               "legion_perm_probe")
+
+
+def test_capi_table_and_header_name_the_new_symbols():
+    import inspect
+    import legion1_amd.capi as K
+    L = K.lib()
+    header = open(os.path.join(ROOT, "include", "legion_amd.h")).read()
+    for name in NEW_SYMBOLS:
+        assert name in K._SIGS and name + "(" in header and getattr(L, name)
+    for fn in (K.Engine.run_batch, K.Engine.capture_batch):
+        p = inspect.signature(fn).parameters
+        assert p["seed"].default is None and p["round"].default == 0
+
+
+def test_host_keys_are_the_statements():
+    import legion1_amd.capi as K
+    L = K.lib()
+    for S, r in SR_PAIRS:
+        assert L.legion_seeded_shuffle_key(S, r) == R.Ks(S, r)
+        for c in (0, 1, 40, 2 ** 31 - 1):
+            assert L.legion_seeded_draw_word(S, r, c) == R.W(S, r, c)
+
+
+def test_pool_switch_without_a_gpu():
+    """The mode lives in the pool: off by default, seed 0 is a seed, set and read back without a device; with the mode off BeginRound
+    records the round and launches nothing; null pools are refused by name."""
+    import ctypes as C
+    import legion1_amd.capi as K
+    L = K.lib()
+    L.legion_set_error_mode(K.ERR_RETURN)
+    pool = L.NewGPUMemoryPool(2)
+    seed = C.c_uint32(99)
+    try:
+        assert L.GPUMemoryPool_GetSampleSeed(pool, C.byref(seed)) == 0 and seed.value == 0
+        for on, s in ((1, 0), (1, 0xFFFFFFFF), (0, 5), (7, 12345)):
+            L.GPUMemoryPool_SetSampleSeed(pool, on, s)
+            assert not L.legion_last_error()
+            assert L.GPUMemoryPool_GetSampleSeed(pool, C.byref(seed)) == int(on != 0) and seed.value == s
+            assert L.GPUMemoryPool_GetSampleSeed(pool, None) == int(on != 0)
+        L.GPUMemoryPool_SetSampleSeed(pool, 0, 0)
+        assert L.GPUMemoryPool_BeginRound(None, pool, None, 0, 3) == 0 and L.GPUMemoryPool_GetRound(pool) == 3 and not L.legion_last_error()
+        assert L.GPUMemoryPool_BeginRound(None, pool, None, 0, -1) == -1
+        assert "GPUMemoryPool_BeginRound: negative round" in (L.legion_last_error() or b"").decode()
+        L.legion_clear_error()
+        L.GPUMemoryPool_SetSampleSeed(None, 1, 1)
+        assert "GPUMemoryPool_SetSampleSeed: null pool" in (L.legion_last_error() or b"").decode()
+        L.legion_clear_error()
+        assert L.GPUMemoryPool_BeginRound(None, None, None, 0, 0) == -1
+        assert "GPUMemoryPool_BeginRound: null pool" in (L.legion_last_error() or b"").decode()
+        assert L.GPUMemoryPool_GetSampleSeed(None, None) == 0
+    finally:
+        L.legion_clear_error()
+        L.GPUMemoryPool_Delete(pool)
+
+
+def test_seed_words_round_trip_without_a_gpu():
+    """The two words behind `sampling` in the "<name>_ext" object, with the device-free IPC env: a server sets them, a client process and
+    ipc_service.sampling_seed() read them ("off" from a server that never set them, and after they are cleared); every older getter reads
+    what it read."""
+    ns = "cpuipc_seed%d_" % os.getpid()
+    pre, _ = _server_script(ns, 3, "")
+    client = pre + ("sys.path.insert(0, %r)\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
+                    "c = C.c_void_p(L.legion_ipc_client_open(0)); K.check(); assert c.value\n"
+                    "s = (C.c_int32 * 3)(); L.legion_ipc_client_steps(c, s); sd = C.c_uint32(77)\n"
+                    "on = L.legion_ipc_client_sampling_seed(c, C.byref(sd))\n"
+                    "print('CLIENT', on, sd.value, L.legion_ipc_client_sampling(c), L.legion_ipc_client_agg_norm(c), L.legion_ipc_client_agg_last_hop(c), "
+                    "L.legion_ipc_client_hops(c), L.legion_ipc_client_feature_rows(c), list(s)); L.legion_ipc_client_close(c)\n"
+                    "import torch, ipc_service\nipc_service.initialize(); print('SERVICE', repr(ipc_service.sampling_seed()), ipc_service.sampling()); ipc_service.finalize()\n"
+                    ) % os.path.join(ROOT, "legion-1_amd", "ipc_service")
+    body = ("sd = C.c_uint32(1)\nassert L.IPCEnv_GetSamplingSeed(e, C.byref(sd)) == 0 and sd.value == 0\n"
+            "L.IPCEnv_SetFeatureRows(e, 0, 4321)\n"
+            "ext = [f for f in os.listdir('/dev/shm') if %r in f and f.endswith('_ext')]; assert len(ext) == 1, ext\n"
+            "words = lambda: np.fromfile('/dev/shm/' + ext[0], dtype=np.uint32)\n"
+            "w0 = words(); L.IPCEnv_SetSampling(e, 1); at = np.nonzero(w0 != words())[0]; L.IPCEnv_SetSampling(e, 0); assert len(at) == 1\n"
+            "w0 = words(); L.IPCEnv_SetSamplingSeed(e, 1, 0xDEADBEEF); w1 = words(); ch = np.nonzero(w0 != w1)[0]\n"
+            "assert ch.tolist() == [at[0] + 1, at[0] + 2] and w1[ch].tolist() == [1, 0xDEADBEEF], (at, ch, w1[ch])\n"
+            "for on, seed, samp, agg, norm in ((0, 0, 0, 0, 0), (1, 12345, 0, 0, 0), (1, 0, 1, 1, 1), (1, 0xFFFFFFFF, 1, 1, 0), (0, 9, 1, 0, 0)):\n"
+            "    L.IPCEnv_SetAggLastHop(e, agg); L.IPCEnv_SetAggNorm(e, norm); L.IPCEnv_SetSampling(e, samp); L.IPCEnv_SetSamplingSeed(e, on, seed)\n"
+            "    assert (L.IPCEnv_GetSamplingSeed(e, C.byref(sd)), sd.value) == (on, seed if on else 0)\n"
+            "    assert (L.IPCEnv_GetSampling(e), L.IPCEnv_GetAggNorm(e), L.IPCEnv_GetAggLastHop(e)) == (samp, norm, agg)\n"
+            "    r = subprocess.run([sys.executable, '-c', %r], capture_output=True, text=True, timeout=120)\n"
+            "    print(r.stdout.strip(), r.stderr[-500:])\n"
+            "    assert 'CLIENT %%d %%d %%d %%d %%d 3 4321 [7, 2, 1]' %% (on, seed if on else 0, samp, norm, agg) in r.stdout\n"
+            "    assert 'SERVICE %%s %%s' %% (repr(seed) if on else 'None', 'distinct' if samp else 'replace') in r.stdout\n") % (ns, client)
+    _, server = _server_script(ns, 3, body)
+    r = subprocess.run([sys.executable, "-c", server], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "SERVER_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    assert not [f for f in os.listdir("/dev/shm") if ns in f]
+
+
+def test_launch_server_sets_the_variable_for_the_child(tmp_path):
+    """launch_server.py --sampling_seed N: LEGION_SAMPLING_SEED reaches the server process (a stand-in that prints it); without the flag
+    the caller's environment passes through."""
+    work = tmp_path / "pkg"
+    (work / "csrc").mkdir(parents=True)
+    (work / "launch_server.py").write_text(open(os.path.join(ROOT, "legion-1_amd", "launch_server.py")).read())
+    stand_in = work / "csrc" / "legion"
+    stand_in.write_text("#!/bin/sh\necho \"SEED=[${LEGION_SAMPLING_SEED}] SAMPLING=[${LEGION_SAMPLING}]\"\n")
+    stand_in.chmod(0o755)
+    env = {k: v for k, v in os.environ.items() if k not in ("LEGION_SAMPLING_SEED", "LEGION_SAMPLING")}
+
+    def run(*flags, **more):
+        return subprocess.run([sys.executable, str(work / "launch_server.py"), "--dataset", "PR", "--gpu_number", "1"] + list(flags),
+                              cwd=str(tmp_path), env=dict(env, **more), capture_output=True, text=True, timeout=60)
+
+    assert "SEED=[12345] SAMPLING=[]" in run("--sampling_seed", "12345").stdout
+    assert "SEED=[0] SAMPLING=[distinct]" in run("--sampling_seed", "0", "--sampling", "distinct", LEGION_SAMPLING_SEED="7").stdout
+    assert "SEED=[] SAMPLING=[]" in run().stdout
+    assert "SEED=[0x10] SAMPLING=[]" in run(LEGION_SAMPLING_SEED="0x10").stdout
+    r = run("--sampling_seed", "many")
+    assert r.returncode != 0 and "invalid int value" in r.stderr
+
+
+@pytest.mark.parametrize("value", ["abc", "-1", "4294967296", "0x", "12 ", "0x100000000"])
+def test_boot_refuses_a_malformed_seed(tmp_path, value):
+    """The `legion` binary refuses a LEGION_SAMPLING_SEED that is no integer in [0, 2^32) by name, at boot, before any device is touched:
+    exit code 1."""
+    import legion1_amd.synth as synth
+    server = os.path.join(ROOT, "legion-1_amd", "csrc", "legion")
+    spec = synth.spec_for("products", scale=0.004)
+    meta = str(tmp_path / "meta_config")
+    with open(meta, "w") as f:
+        f.write("%s 512 %d 0 %d %d 0 0 %d 1 0\n" % (str(tmp_path / "nowhere") + "/", spec.V, spec.F, min(spec.n_train, 1000), 1 << 30))
+    env = dict(os.environ, LEGION_SAMPLING_SEED=value, LEGION_IPC_NAMESPACE="cpuseed%d_" % os.getpid())
+    for k in ("LEGION_SAMPLING", "LEGION_AGG_NORM", "LEGION_AGG_LAST_HOP"):
+        env.pop(k, None)
+    r = subprocess.run([server, "1", "0", "10,5", meta], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
+    said = r.stdout + r.stderr
+    assert r.returncode == 1 and "Server_Initialize:" in said and "LEGION_SAMPLING_SEED=%s is not a sampling seed" % value in said, said[-2000:]
+    assert "[0, 2^32)" in said
