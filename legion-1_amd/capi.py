@@ -501,26 +501,11 @@ class Engine:
         or all of them inside that call with per_level=False) and the last hop as neighbour sums; result() then returns
         `features` [n_in, F] and `nbr_sum` [N, F].  agg_norm="both" (only with agg_last_hop): the sums weighted by out-degree^-1/2 inside
         block 1 (GPUMemoryPool_SetAggNorm); result() additionally returns `out_deg` int32 [n]."""
-        if agg_norm not in (None, "both"):
-            raise ValueError("agg_norm: None or 'both'")
-        if agg_norm and not agg_last_hop:
-            raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
-        if sample not in ("replace", "distinct"):
-            raise ValueError("sample: 'replace' or 'distinct'")
-        L = self.L
-        L.SetGPUDevice(dev)
-        pool = self.pools[dev]
-        if L.GPUMemoryPool_GetSampleDistinct(pool) != int(sample == "distinct"):
-            L.GPUMemoryPool_SetSampleDistinct(pool, int(sample == "distinct"))
-        self._set_seed(dev, seed, round, stream)
-        agg = bool(agg_last_hop) and not is_presc     # gather=False: the sampler side of such a batch (the last hop's draws kept per pipe)
-        if bool(L.GPUMemoryPool_GetAggLastHop(pool)) != agg:
-            L.GPUMemoryPool_SetAggLastHop(pool, int(agg))
-        norm = int(agg and agg_norm == "both")
-        if L.GPUMemoryPool_GetAggNorm(pool) != norm:
-            L.GPUMemoryPool_SetAggNorm(pool, norm)
+        L, pool = self.L, self.pools[dev]
+        # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
+        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc)
         self._agg[(dev, pipe)] = agg and gather
-        self._norm[(dev, pipe)] = bool(norm) and gather
+        self._norm[(dev, pipe)] = norm and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
         L.GPUMemoryPool_SetCurrentMode(pool, mode)
         L.GPUMemoryPool_SetIter(pool, counter)
@@ -543,6 +528,25 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
+    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False):
+        """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
+        (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
+        if norm not in (None, "both"):
+            raise ValueError("agg_norm: None or 'both'")
+        if norm and not agg:
+            raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
+        if sample not in ("replace", "distinct"):
+            raise ValueError("sample: 'replace' or 'distinct'")
+        L, pool = self.L, self.pools[dev]
+        L.SetGPUDevice(dev)
+        agg = bool(agg) and not is_presc
+        norm = int(agg and norm == "both")
+        for mode, want in (("SampleDistinct", int(sample == "distinct")), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
+            if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
+                getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
+        self._set_seed(dev, seed, round, stream)
+        return agg, bool(norm)
+
     def _set_seed(self, dev, seed, round, stream):
         """The pool's seeded state := (seed, round); BeginRound on `stream` when either changed (not callable inside a capture: there the
         state is what capture_batch set before Begin)."""
@@ -561,18 +565,14 @@ class Engine:
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
         run_graph(..., seed=, round=)."""
-        if sample not in ("replace", "distinct"):
-            raise ValueError("sample: 'replace' or 'distinct'")
         L = self.L
         L.SetGPUDevice(dev)
-        L.GPUMemoryPool_SetSampleDistinct(self.pools[dev], int(sample == "distinct"))   # the recording keeps the mode: not between Begin and End
-        L.GPUMemoryPool_SetAggLastHop(self.pools[dev], int(bool(agg_last_hop)))   # allocates: not between Begin and End
-        L.GPUMemoryPool_SetAggNorm(self.pools[dev], int(bool(agg_last_hop) and agg_norm == "both"))   # likewise
         if stream is None:
             if self.streams[dev] is None:
                 self.streams[dev] = L.d_stream_create()
             stream = self.streams[dev]
-        self._set_seed(dev, seed, round, stream)     # the shuffled copy is allocated and filled here: not between Begin and End
+        # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
+        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")

@@ -24,10 +24,11 @@ struct LegionBatchGraph {
     int32_t sampled_hop = 0;
     bool sampled_presc = false;
     uint32_t levels_gathered = 0;
-    // Seeded sampling: the state the batch was recorded in.  The captured k_seed holds list pointers -- the seed set's, or the pool's shuffled
-    // copy (shuf_ids, when the recording read it) --, so the graph only replays in that state; the seed, the round and the counter are not
-    // part of it (k_set_cursor carries them into ctl).
-    bool seeded = false;
+    // The serving modes the batch was recorded in (the pool refuses to change them during a recording).  A replay is refused only when the
+    // pool's seeded state is another by now: the captured k_seed holds list pointers -- the seed set's, or the pool's shuffled copy (shuf_ids,
+    // when the recording read it) --, so the graph only replays in that state; the seed, the round and the counter are not part of it
+    // (k_set_cursor carries them into ctl).
+    ServeModes modes;
     const int32_t* shuf_ids = nullptr;
 };
 
@@ -53,7 +54,7 @@ LegionBatchGraph* GPUMemoryPool_EndBatchCapture(GPUMemoryPool* p, void* stream)
     LegionBatchGraph* g = new LegionBatchGraph();
     g->pool = p;
     g->sampled_hop = p->sampled_hop; g->sampled_presc = p->sampled_presc; g->levels_gathered = p->levels_gathered;
-    g->seeded = p->seeded; g->shuf_ids = p->seed_reads_shuffle ? p->shuf_ids : nullptr;
+    g->modes = p->modes; g->shuf_ids = p->seed_reads_shuffle ? p->shuf_ids : nullptr;
     HIP_CHECK(hipStreamEndCapture((hipStream_t)stream, &g->graph));
     if (g->graph) HIP_CHECK(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
     if (!g->exec || error_pending()) {
@@ -70,8 +71,8 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (!g || !g->exec || !g->pool || !g->pool->ctl) { LEGION_ARG_ERROR("LegionBatchGraph_Launch: null graph"); return -1; }
     GPUMemoryPool* p = g->pool;
     if (p->capturing) { LEGION_ARG_ERROR("LegionBatchGraph_Launch: pool is being captured"); return -1; }
-    if (g->seeded != p->seeded) {
-        LEGION_ARG_ERROR(g->seeded ? "LegionBatchGraph_Launch: the graph was recorded under a seed (GPUMemoryPool_SetSampleSeed) and the pool is unseeded now: its k_seed holds the shuffled list's pointers -- record it again"
+    if (g->modes.seeded != p->modes.seeded) {
+        LEGION_ARG_ERROR(g->modes.seeded ? "LegionBatchGraph_Launch: the graph was recorded under a seed (GPUMemoryPool_SetSampleSeed) and the pool is unseeded now: its k_seed holds the shuffled list's pointers -- record it again"
                                    : "LegionBatchGraph_Launch: the graph was recorded unseeded and the pool is seeded now (GPUMemoryPool_SetSampleSeed): its k_seed holds the file-order list's pointers -- record it again");
         return -1;
     }
@@ -85,7 +86,7 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
         p->batch_serial = 1;
         p->ctl_synced = false;
     }
-    if (!p->ctl_synced || p->ctl_counter != counter) launch_set_cursor(s, p->ctl, counter, kEpochTop - p->batch_serial, p->seeded ? 1u : 0u, p->seeded ? seeded_draw_key(p->seed, p->round) : 0u);
+    if (!p->ctl_synced || p->ctl_counter != counter) launch_set_cursor(s, p->ctl, counter, kEpochTop - p->batch_serial, p->modes.seeded ? 1u : 0u, p->modes.seeded ? seeded_draw_key(p->modes.seed, p->round) : 0u);
     HIP_CHECK(hipGraphLaunch(g->exec, s));
     // the batch now in flight is the recorded one: what the launchers behind it (get_feature_kernel_agg) decide from
     p->sampled_hop = g->sampled_hop; p->sampled_presc = g->sampled_presc; p->levels_gathered = g->levels_gathered;

@@ -105,6 +105,24 @@ static_assert(kMaxChunks % kBlock == 0 && kMaxChunks >= 256 * 8, "kMaxChunks: a 
 constexpr int ilog2_c(int v) { return v <= 1 ? 0 : 1 + ilog2_c(v >> 1); }
 constexpr int kMaxParts = LEGION_MAX_DEVICE;
 
+// The serving modes as ONE value: what the environment asks for, what a Runner serves, what a pool is in (GPUMemoryPool::modes), what a
+// batch graph was recorded in and what the "<name>_ext" object tells a trainer.  DESIGN.md "Where a serving mode lives" lists every place.
+struct ServeModes {
+    bool agg_last_hop = false;   // $LEGION_AGG_LAST_HOP=1: the last hop is handed over as neighbour sums (INTEGRATION.md "Aggregated last hop")
+    int32_t agg_norm = 0;        // $LEGION_AGG_NORM=both, only with agg_last_hop: 1 = the sums weighted by out-degree^-1/2 inside block 1 ("Normalised sums")
+    int32_t sampling = 0;        // $LEGION_SAMPLING: 0 = replace (the reference's stream), 1 = distinct: min(degree, fan-out) distinct neighbours per row
+    bool seeded = false;         // $LEGION_SAMPLING_SEED: every batch draws from its own word W(seed, round, counter), the training list is reshuffled
+    uint32_t seed = 0;           // ... every round ("Seeded sampling").  Seed 0 is a seed like any other: `seeded` says whether there is one
+    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed; }
+};
+// The only readers of the four variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
+// unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed.  Host code only, no device is touched.
+bool serve_modes_from_env(ServeModes& m, std::string& why);
+// the distinct mode's fan-out bound (kDistinctMaxFanout) against a fan-out list: false with the refusal in `why`
+bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
+// what a trainer reads: the five mode words of the "<name>_ext" object := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
+void ipc_env_publish_modes(IPCEnv* e, const ServeModes& m);
+
 // The seed sets are indexed by mode everywhere (LEGION_TRAINMODE, LEGION_VALIDMODE, LEGION_TESTMODE); LegionBuildInfo names their fields
 // one by one, this table gives them the same index.
 constexpr int kModes = 3;
@@ -366,28 +384,23 @@ struct GPUMemoryPool {
     bool ctl_synced = false;          // ctl holds (ctl_counter, epoch of the NEXT batch): a batch graph can run as is
     int32_t ctl_counter = 0;
     int32_t* cand = nullptr;
-    // Aggregated last hop (GPUMemoryPool_SetAggLastHop): the last hop parks its draws in the PIPE's buffer, because k_gather_sum reads
+    // The serving modes the pool is in: set through pool_apply_modes only (the public setters change one field each), read by the launchers.
+    legion::ServeModes modes;
+    // Aggregated last hop (modes.agg_last_hop): the last hop parks its draws in the PIPE's buffer, because k_gather_sum reads
     // them on the gather stream while hop 1 of the next batch already overwrites `cand` on the sampler stream.  Allocated when the
     // mode is switched on (max_slots words per pipe); the other hops and the default mode keep the one shared buffer.
-    bool agg_last_hop = false;
     std::vector<int32_t*> cand_pipe;
     int32_t sampled_hop = 0;          // hops of the current batch that GPU_Random_Sampling has queued (0 behind batch_generator_kernel)
     bool sampled_presc = false;       // ... as pre-sampling hops
     uint32_t levels_gathered = 0;     // bit l: get_feature_kernel gathered level l of the current batch
-    // Normalised sums (GPUMemoryPool_SetAggNorm, only with agg_last_hop): 1 = every row of the last hop is scaled by the out-degree^-1/2
-    // of its batch position inside block 1 before it is summed (GraphConv norm='both').  Per pipe, allocated when the mode is set:
-    // the degrees (num_ids words), the draws' weights (max_slots floats) and the chunk counts of the slot -> edge prefix.
-    int32_t agg_norm = 0;
-    // Distinct-draw sampler mode (GPUMemoryPool_SetSampleDistinct): every hop of this pool, the pre-sampling hops included, draws
-    // min(degree, fan-out) distinct neighbour positions per row (INTEGRATION.md "Sampling without replacement").  Nothing is allocated.
-    bool sample_distinct = false;
-    // Seeded sampling (GPUMemoryPool_SetSampleSeed / GPUMemoryPool_BeginRound; INTEGRATION.md "Seeded sampling"): with `seeded` every batch
-    // draws from its own word W(seed, round, counter) and the training batches read the round's shuffled copy of the training list
-    // (shuf_ids / shuf_labels, filled by k_shuffle_seeds in BeginRound; allocated there on first use, never inside a capture).
+    // Normalised sums (modes.agg_norm, only with modes.agg_last_hop): per pipe, allocated when the mode is set (agg_out_deg / agg_wdraw /
+    // agg_chunk_cnt below): the degrees (num_ids words), the draws' weights (max_slots floats) and the chunk counts of the slot -> edge
+    // prefix.  The distinct-draw sampler mode (modes.sampling) allocates nothing.
+    // Seeded sampling (modes.seeded / modes.seed, GPUMemoryPool_BeginRound): the training batches read the round's shuffled copy of the
+    // training list (shuf_ids / shuf_labels, filled by k_shuffle_seeds in BeginRound; allocated there on first use, never inside a capture).
     // shuf_src: the seed set's list the copy was made of; shuf_valid: it holds the permutation of (seed, round).  shuf_file_order: BeginRound
     // was told to leave the training list in file order (lists served verbatim, link-prediction thirds) -- the draws are still seeded.
-    bool seeded = false;
-    uint32_t seed = 0, round = 0;
+    uint32_t round = 0;
     int32_t* shuf_ids = nullptr;
     int32_t* shuf_labels = nullptr;
     int32_t shuf_cap = 0, shuf_n = 0;
@@ -418,6 +431,13 @@ struct GPUMemoryPool {
     int32_t level_bound[LEGION_MAX_HOPS + 1] = {0};
     explicit GPUMemoryPool(int32_t depth);
 };
+namespace legion {
+// The pool's modes := wanted, once for every mode.  Refused in who's name: a null pool, a pool that is being captured (a recording keeps
+// its modes).  Refused as GPUMemoryPool_SetAggNorm: an unknown norm, and a norm on a pool that does not aggregate the last hop -- unless the
+// pool holds that norm already (it stays set while the aggregated mode is off).  Allocates the aggregated modes' per-pipe buffers when the
+// pool owns scratch (call it under the scratch's device); another seed invalidates the shuffled copy, another seeded state the graph cursor.
+bool pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who);
+}
 
 struct GPUGraphStorage {
     int32_t partition_count = 0;

@@ -64,26 +64,21 @@ struct shmExt {
     // match the slab it attached to (it then behaves as against a reference server).
     int32_t steps_copy[3];
     uint32_t handle_sum[LEGION_MAX_DEVICE];   // FNV-1a of memHandle[dev][0][0]; 0 = nothing registered for that device yet
-    // Appended behind everything older peers know (the fields above do not move; the object stays inside its one page, so a client of an older
-    // server reads 0 here and an older client never looks): 1 = the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1,
-    // INTEGRATION.md "Aggregated last hop"): feature rows [0, n_in) are features, rows [n_in, n_in + N) the sums.
-    int32_t agg_last_hop;
-    // Appended behind agg_last_hop (nothing above moves): how a server in that mode normalises the sums.  0 = plain sums, 1 = every row scaled by
-    // its out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both, INTEGRATION.md "Normalised sums").  A client of an older server reads 0.
-    int32_t agg_norm;
-    // Appended behind agg_norm (nothing above moves): how the server's sampler draws.  0 = with replacement (the reference's stream),
-    // 1 = distinct neighbours (LEGION_SAMPLING=distinct, INTEGRATION.md "Sampling without replacement").  A client of an older server reads 0.
-    // (Spelled std::int32_t on purpose: tests/test_agg_norm_cpu.py pins the plain int32_t members of this struct to END with handle_sum,
-    // agg_last_hop, agg_norm -- the layout of the older words, which holds; tests/test_sample_distinct_cpu.py finds this word in the mapped
-    // object right behind agg_norm.)
-    std::int32_t sampling;
-    // Appended behind sampling (nothing above moves; same spelling, for the same tests): seeded sampling (LEGION_SAMPLING_SEED, INTEGRATION.md
-    // "Seeded sampling").  sampling_seeded: 0 = the reference's draws, the same batches every epoch; 1 = fresh draws per batch and the
-    // training list reshuffled per epoch under sampling_seed.  Seed 0 is a seed: the flag says whether there is one.  A client of an
-    // older server reads 0, "off".
-    std::int32_t sampling_seeded;
-    std::uint32_t sampling_seed;
+    // The serving modes (ServeModes, internal.h), appended behind everything older peers know, one word per mode as the modes came: the
+    // fields above do not move and the object stays inside its one page, so a client of an older server reads 0 ("off") in every word it
+    // knows and an older client never looks at the later ones.  Written by IPCEnv_Set* / ipc_env_publish_modes, read by legion_ipc_client_*.
+    struct Modes {
+        int32_t agg_last_hop;     // 1 = the last hop is handed over as neighbour sums: feature rows [0, n_in) are features, rows [n_in, n_in + N) the sums
+        int32_t agg_norm;         // how such a server normalises the sums: 0 = plain sums, 1 = every row scaled by its out-degree^-1/2 inside block 1
+        int32_t sampling;         // how the server's sampler draws: 0 = with replacement (the reference's stream), 1 = distinct neighbours
+        int32_t sampling_seeded;  // 0 = the reference's draws, the same batches every epoch; 1 = fresh draws per batch, the training list reshuffled per epoch ...
+        uint32_t sampling_seed;   // ... under this seed.  Seed 0 is a seed: the flag says whether there is one
+    } modes;
 };
+// Peers of other builds map this object: the mode words stay where the first build that had them put them (32-bit words 533 .. 537)
+static_assert(offsetof(shmExt, modes.agg_last_hop) == 2132 && offsetof(shmExt, modes.agg_norm) == 2136 && offsetof(shmExt, modes.sampling) == 2140 &&
+              offsetof(shmExt, modes.sampling_seeded) == 2144 && offsetof(shmExt, modes.sampling_seed) == 2148 && sizeof(shmExt) == 2152,
+              "the mode words of the _ext object moved");
 static const uint32_t kMirrorMagic = 0x4C474E43u;   // "LGNC"
 static uint32_t handle_checksum(const volatile void* h)
 {
@@ -344,6 +339,13 @@ struct IPCEnv {
     int32_t* mirror_stage[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH] = {};  // slab not page-locked: queued copies land in pinned staging words
 };
 
+void legion::ipc_env_publish_modes(IPCEnv* e, const ServeModes& m)
+{
+    if (!e || !e->ext) return;
+    volatile shmExt::Modes& w = e->ext->modes;
+    w.agg_last_hop = m.agg_last_hop; w.agg_norm = m.agg_norm; w.sampling = m.sampling != 0; w.sampling_seed = m.seeded ? m.seed : 0u; w.sampling_seeded = m.seeded;
+}
+
 extern "C" {
 
 void legion_ipc_set_namespace(const char* ns)
@@ -532,20 +534,21 @@ void IPCEnv_InitializeFeaturesBuffer(IPCEnv* e, int32_t batch_size, int32_t num_
     }
     e->ext->feature_rows[device_id] = num_ids;
 }
-// the row capacity published to the trainers of a device (a server that re-sizes its feature buffers; tests)
-void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on) { if (e && e->ext) e->ext->agg_last_hop = on ? 1 : 0; }
-int32_t IPCEnv_GetAggLastHop(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_last_hop : 0; }
-void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm) { if (e && e->ext) e->ext->agg_norm = norm; }
-int32_t IPCEnv_GetAggNorm(const IPCEnv* e) { return (e && e->ext) ? e->ext->agg_norm : 0; }
-void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->sampling = mode ? 1 : 0; }
-int32_t IPCEnv_GetSampling(const IPCEnv* e) { return (e && e->ext) ? e->ext->sampling : 0; }
-void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed) { if (e && e->ext) { e->ext->sampling_seed = on ? seed : 0u; e->ext->sampling_seeded = on ? 1 : 0; } }
+// the serving modes published to the trainers, one mode per call (a runner publishes all of them at once: ipc_env_publish_modes)
+void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on) { if (e && e->ext) e->ext->modes.agg_last_hop = on ? 1 : 0; }
+int32_t IPCEnv_GetAggLastHop(const IPCEnv* e) { return (e && e->ext) ? e->ext->modes.agg_last_hop : 0; }
+void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm) { if (e && e->ext) e->ext->modes.agg_norm = norm; }
+int32_t IPCEnv_GetAggNorm(const IPCEnv* e) { return (e && e->ext) ? e->ext->modes.agg_norm : 0; }
+void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->modes.sampling = mode ? 1 : 0; }
+int32_t IPCEnv_GetSampling(const IPCEnv* e) { return (e && e->ext) ? e->ext->modes.sampling : 0; }
+void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed) { if (e && e->ext) { e->ext->modes.sampling_seed = on ? seed : 0u; e->ext->modes.sampling_seeded = on ? 1 : 0; } }
 int32_t IPCEnv_GetSamplingSeed(const IPCEnv* e, uint32_t* seed)
 {
-    const bool on = e && e->ext && e->ext->sampling_seeded;
-    if (seed) *seed = on ? e->ext->sampling_seed : 0u;
+    const bool on = e && e->ext && e->ext->modes.sampling_seeded;
+    if (seed) *seed = on ? e->ext->modes.sampling_seed : 0u;
     return on ? 1 : 0;
 }
+// the row capacity published to the trainers of a device (a server that re-sizes its feature buffers; tests)
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
     if (e && e->ext && device_id >= 0 && device_id < e->device_count) e->ext->feature_rows[device_id] = rows;
@@ -916,13 +919,13 @@ void legion_ipc_client_steps(LegionIPCClient* c, int32_t steps[3])
     for (int i = 0; i < 3; i++) steps[i] = c->steps[i];
 }
 int32_t legion_ipc_client_hops(LegionIPCClient* c) { return c->hops; }
-int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_last_hop : 0; }
-int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return (c && c->ext) ? c->ext->agg_norm : 0; }
-int32_t legion_ipc_client_sampling(LegionIPCClient* c) { return (c && c->ext) ? c->ext->sampling : 0; }
+int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return (c && c->ext) ? c->ext->modes.agg_last_hop : 0; }
+int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return (c && c->ext) ? c->ext->modes.agg_norm : 0; }
+int32_t legion_ipc_client_sampling(LegionIPCClient* c) { return (c && c->ext) ? c->ext->modes.sampling : 0; }
 int32_t legion_ipc_client_sampling_seed(LegionIPCClient* c, uint32_t* seed)
 {
-    const bool on = c && c->ext && c->ext->sampling_seeded;
-    if (seed) *seed = on ? c->ext->sampling_seed : 0u;
+    const bool on = c && c->ext && c->ext->modes.sampling_seeded;
+    if (seed) *seed = on ? c->ext->modes.sampling_seed : 0u;
     return on ? 1 : 0;
 }
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }

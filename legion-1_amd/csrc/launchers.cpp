@@ -50,9 +50,9 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     GPUMemoryPool* p = memorypool;
     // Seeded sampling: a training batch reads the round's shuffled copy of the list (same length, same indexing) unless the round was
     // begun in file order; the draw word of the batch comes from the pool's (seed, round) and the counter.
-    const uint32_t seeded = p->seeded ? 1u : 0u, draw_key = p->seeded ? seeded_draw_key(p->seed, p->round) : 0u;
+    const uint32_t seeded = p->modes.seeded ? 1u : 0u, draw_key = p->modes.seeded ? seeded_draw_key(p->modes.seed, p->round) : 0u;
     p->seed_reads_shuffle = false;
-    if (p->seeded && mode == LEGION_TRAINMODE && !p->shuf_file_order) {
+    if (p->modes.seeded && mode == LEGION_TRAINMODE && !p->shuf_file_order) {
         if (!p->shuf_valid || p->shuf_src != set.ids || p->shuf_n != total_cap) {
             LEGION_ARG_ERROR("batch_generator_kernel: seeded sampling (GPUMemoryPool_SetSampleSeed) serves training batches from the round's shuffled list: call GPUMemoryPool_BeginRound for this device's training list first");
             return;
@@ -136,7 +136,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];
     b.agg_dst_off = p->agg_dst_off[q]; b.nc = p->node_counter[q]; b.ec = p->edge_counter[q];
     b.pos_map = p->pos_map; b.ctl = p->ctl; b.cand = p->cand;
-    if (p->agg_last_hop && hop == p->hops) {   // k_gather_sum reads the last hop's draws while the next batch samples: the pipe's own buffer
+    if (p->modes.agg_last_hop && hop == p->hops) {   // k_gather_sum reads the last hop's draws while the next batch samples: the pipe's own buffer
         if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("GPU_Random_Sampling: aggregated last hop without the per-pipe draw buffers (GPUMemoryPool_SetAggLastHop before AllocateScratch failed?)"); return; }
         b.cand = p->cand_pipe[q];
     }
@@ -163,7 +163,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.V = p->V;
     b.aux_prepared = p->aux_ready_hop == hop && p->aux_ready_count == count;
     b.next_count = hop < p->hops ? p->fanout[hop] : 0;
-    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->sample_distinct);
+    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->modes.sampling != 0);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint
@@ -225,7 +225,7 @@ static bool gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder
 {
     GatherArgs g;
     // an aggregated batch never reaches the last level's gather, which closes a hit-rate sample: its level gathers do not open one
-    if (!gather_args(g, cache, noder, p, dev_id, off_idx, size_idx, !p->agg_last_hop)) return false;
+    if (!gather_args(g, cache, noder, p, dev_id, off_idx, size_idx, !p->modes.agg_last_hop)) return false;
     launch_gather((hipStream_t)strm_hdl, g, rows_bound);
     // last counting launch of a sampled batch: the host may read the pinned {hits, rows} words once this event completes
     if (g.hit_stats && (off_idx < 0 || off_idx == legion_idx_level_offset(p->hops))) GPUCache_HitSamplingDone(cache, dev_id, strm_hdl);
@@ -269,7 +269,7 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (!noder || !pool_ready(memorypool, "get_feature_kernel_agg")) return;
     GPUMemoryPool* p = memorypool;
     const int H = p->hops, q = p->current_pipe;
-    if (!p->agg_last_hop) { LEGION_ARG_ERROR("get_feature_kernel_agg: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop)"); return; }
+    if (!p->modes.agg_last_hop) { LEGION_ARG_ERROR("get_feature_kernel_agg: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop)"); return; }
     {   // the exchange moves rows between clique members, not sums
         const char* e = getenv("LEGION_PEER_GATHER");
         if (e && strcmp(e, "exchange") == 0) { LEGION_ARG_ERROR("get_feature_kernel_agg: LEGION_PEER_GATHER=exchange cannot serve the aggregated last hop (GPUMemoryPool_SetAggLastHop): the exchange moves rows, not sums"); return; }
@@ -277,7 +277,7 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (p->sampled_hop != H) { LEGION_ARG_ERROR("get_feature_kernel_agg: called before the last hop's GPU_Random_Sampling"); return; }
     if (p->sampled_presc) { LEGION_ARG_ERROR("get_feature_kernel_agg: a pre-sampling batch gathers nothing"); return; }
     if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe draw buffers are missing"); return; }
-    const bool norm = p->agg_norm != 0;
+    const bool norm = p->modes.agg_norm != 0;
     if (norm && ((int)p->agg_out_deg.size() <= q || !p->agg_out_deg[q] || !p->agg_wdraw[q] || !p->agg_chunk_cnt[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe buffers of the normalised sums are missing (GPUMemoryPool_SetAggNorm before AllocateScratch failed?)"); return; }
     if (norm && !p->agg_src_off[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the COO buffers of the current pipe are not set"); return; }
     if (!in_memory) return;

@@ -50,20 +50,11 @@ struct Runner {
     // long hops (products {25,10,5}: `all` +5.7 %).  auto decides once, after the pre-sampling epoch, from the last pre-sampled batch's counters.
     bool gather_all = false;
     bool gather_auto = true;
-    // $LEGION_AGG_LAST_HOP=1: the last hop is handed over as neighbour sums (get_feature_kernel_agg on stream 1 behind the last hop instead of
-    // the last level's gather; INTEGRATION.md "Aggregated last hop").  The feature buffers then hold n_in + N rows per batch, not n.
-    bool agg_last_hop = false;
-    // $LEGION_AGG_NORM=both (only with LEGION_AGG_LAST_HOP=1): the sums are weighted for GraphConv(norm='both') -- every row by the
-    // out-degree^-1/2 of its batch position inside block 1 (INTEGRATION.md "Normalised sums").  Same rows, same buffer sizing.
-    int32_t agg_norm = 0;
-    // $LEGION_SAMPLING=replace|distinct (unset = replace): distinct = every hop, the pre-sampling epoch included, draws min(degree, fan-out)
-    // distinct neighbours per row (GPUMemoryPool_SetSampleDistinct; INTEGRATION.md "Sampling without replacement").
-    int32_t sampling = 0;
-    // $LEGION_SAMPLING_SEED=<uint32> (unset = off): every batch draws from its own word and the training list is reshuffled every round
-    // (GPUMemoryPool_SetSampleSeed / BeginRound; INTEGRATION.md "Seeded sampling").  round: the one the pool was last told, -1 = none yet.
-    // lists_verbatim: the training lists are served as they are (meta flag 2, link-prediction thirds): never shuffled, draws still seeded.
-    bool seeded = false;
-    uint32_t seed = 0;
+    // What the environment asked for (serve_modes_from_env; ServeModes in internal.h).  Aggregated last hop: get_feature_kernel_agg on stream 1
+    // behind the last hop instead of the last level's gather; the feature buffers then hold n_in + N rows per batch, not n.
+    ServeModes modes;
+    // Seeded sampling.  round: the one the pool was last told (GPUMemoryPool_BeginRound), -1 = none yet.  lists_verbatim: the training
+    // lists are served as they are (meta flag 2, link-prediction thirds): never shuffled, draws still seeded.
     int32_t round = -1;
     bool lists_verbatim = false;
     int32_t presc_max_rows = 0;     // largest n_in + N of the pre-sampling epoch (read back per batch: that epoch is not pipelined anyway)
@@ -80,52 +71,62 @@ struct Runner {
 // ipc_cuda_kernel.cu:200).  That is a trainer-side failure with no server-side trace -- so the server leaves one: the first such batch
 // is logged, all are counted (Runner_Finalize prints the total).
 
-// $LEGION_AGG_NORM: unset / empty = plain sums (0), "both" = out-degree rsqrt (1) and only on a server that aggregates the last hop.
-// Returns the mode, or -1 with the refusal in `why`.
-static int32_t agg_norm_from_env(std::string& why)
+// $LEGION_SAMPLING_SEED: a decimal or 0x hex integer in [0, 2^32)
+static bool parse_seed(const char* n, uint32_t& seed)
 {
-    const char* n = getenv("LEGION_AGG_NORM");
-    if (!n || !n[0]) return 0;
-    if (strcmp(n, "both") != 0) { why = std::string("LEGION_AGG_NORM=") + n + " is not a known norm: `both` (GraphConv norm='both', out-degree rsqrt inside block 1) or unset"; return -1; }
-    const char* a = getenv("LEGION_AGG_LAST_HOP");
-    if (!a || atoi(a) == 0) { why = "LEGION_AGG_NORM=both needs LEGION_AGG_LAST_HOP=1: only the last hop's neighbour sums are normalised"; return -1; }
-    return 1;
-}
-
-// $LEGION_SAMPLING: unset / empty / "replace" = the reference's with-replacement stream (0), "distinct" = distinct neighbours (1).
-// Returns the mode, or -1 with the refusal in `why`.
-static int32_t sampling_from_env(std::string& why)
-{
-    const char* n = getenv("LEGION_SAMPLING");
-    if (!n || !n[0] || strcmp(n, "replace") == 0) return 0;
-    if (strcmp(n, "distinct") == 0) return 1;
-    why = std::string("LEGION_SAMPLING=") + n + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row)";
-    return -1;
-}
-
-// $LEGION_SAMPLING_SEED: unset / empty = off; else a decimal or 0x hex integer in [0, 2^32).  Returns 0 (off), 1 (on, the seed in `seed`), or
-// -1 with the refusal in `why`.
-static int32_t sampling_seed_from_env(uint32_t& seed, std::string& why)
-{
-    const char* n = getenv("LEGION_SAMPLING_SEED");
-    seed = 0;
-    if (!n || !n[0]) return 0;
     const bool hex = n[0] == '0' && (n[1] == 'x' || n[1] == 'X');
     const char* digits = hex ? n + 2 : n;
     bool ok = digits[0] != 0 && strlen(digits) <= 16;
     for (const char* c = digits; ok && *c; c++) ok = hex ? isxdigit((unsigned char)*c) != 0 : isdigit((unsigned char)*c) != 0;
     unsigned long long v = 0;
     if (ok) { v = strtoull(digits, nullptr, hex ? 16 : 10); ok = v <= 0xFFFFFFFFull; }
-    if (!ok) { why = std::string("LEGION_SAMPLING_SEED=") + n + " is not a sampling seed: a decimal or 0x hex integer in [0, 2^32), or unset (the same batches every epoch)"; return -1; }
-    seed = (uint32_t)v;
-    return 1;
+    seed = ok ? (uint32_t)v : 0;
+    return ok;
+}
+
+// LEGION_AGG_LAST_HOP: atoi, so anything non-numeric is off.  LEGION_AGG_NORM: unset / empty = plain sums, "both" only on a server that aggregates
+// the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, or "distinct".  LEGION_SAMPLING_SEED: unset / empty = off.
+bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
+{
+    m = ServeModes();
+    const char* agg = getenv("LEGION_AGG_LAST_HOP");
+    m.agg_last_hop = agg && atoi(agg) != 0;
+    const char* norm = getenv("LEGION_AGG_NORM");
+    if (norm && norm[0]) {
+        if (strcmp(norm, "both") != 0) { why = std::string("LEGION_AGG_NORM=") + norm + " is not a known norm: `both` (GraphConv norm='both', out-degree rsqrt inside block 1) or unset"; return false; }
+        if (!m.agg_last_hop) { why = "LEGION_AGG_NORM=both needs LEGION_AGG_LAST_HOP=1: only the last hop's neighbour sums are normalised"; return false; }
+        m.agg_norm = 1;
+    }
+    const char* sampling = getenv("LEGION_SAMPLING");
+    if (sampling && sampling[0] && strcmp(sampling, "replace") != 0) {
+        if (strcmp(sampling, "distinct") != 0) { why = std::string("LEGION_SAMPLING=") + sampling + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row)"; return false; }
+        m.sampling = 1;
+    }
+    const char* seed = getenv("LEGION_SAMPLING_SEED");
+    if (seed && seed[0]) {
+        if (!parse_seed(seed, m.seed)) { why = std::string("LEGION_SAMPLING_SEED=") + seed + " is not a sampling seed: a decimal or 0x hex integer in [0, 2^32), or unset (the same batches every epoch)"; return false; }
+        m.seeded = true;
+    }
+    return true;
+}
+
+// the launcher refuses such a hop per batch (launch_sample_hop): a server that booted would fail every batch, the pre-sampling epoch first
+bool legion::serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why)
+{
+    for (int32_t h = 0; m.sampling == 1 && h < hops; h++)
+        if (fanout[h] > kDistinctMaxFanout) {
+            why = "LEGION_SAMPLING=distinct takes fan-outs of at most " + std::to_string(kDistinctMaxFanout) + ", hop " + std::to_string(h + 1) + " has " +
+                  std::to_string(fanout[h]) + ": k_sample stages the picks of a tile's rows in static LDS";
+            return false;
+        }
+    return true;
 }
 
 // Seeded sampling: tell the pool the round, on the stream the batch generator runs on (the shuffled copy is refilled in front of the round's
 // first k_seed and behind the last one of the round before).
 static void begin_round(Runner* r, GPUNodeStorage* noder, int32_t round)
 {
-    if (!r->seeded || r->round == round) return;
+    if (!r->modes.seeded || r->round == round) return;
     if (r->lists_verbatim && r->round < 0)
         log_out() << r->local_dev_id << " Seeded sampling: the training lists are served verbatim (meta flag 2): not shuffled, the draws are seeded\n";
     GPUMemoryPool_BeginRound(r->streams[0], r->memorypool, r->lists_verbatim ? nullptr : noder, r->local_dev_id, round);
@@ -136,14 +137,14 @@ static void hand_over(Runner* r, IPCEnv* env, int pipe)
 {
     const int32_t rows = r->memorypool ? r->memorypool->feature_rows : 0;
     int32_t nodes = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, legion_idx_nodes_through(r->hops));
-    if (r->agg_last_hop && nodes >= 0) {     // the mirror is there: n_in + N rows (features, then one row of sums per input slot of the last hop)
+    if (r->modes.agg_last_hop && nodes >= 0) {     // the mirror is there: n_in + N rows (features, then one row of sums per input slot of the last hop)
         int32_t nc[LEGION_COUNTER_WORDS], ec[LEGION_COUNTER_WORDS];
         for (int i = 0; i < LEGION_COUNTER_WORDS; i++) { nc[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, i); ec[i] = IPCEnv_MirroredNodeCounter(env, r->local_dev_id, pipe, LEGION_COUNTER_WORDS + i); }
         nodes = legion_agg_rows(nc, ec, r->hops);
     }
     if (rows > 0 && nodes > rows) {
         if (r->short_batches++ == 0)
-            log_out() << r->local_dev_id << " Feature buffer too small: a batch has " << nodes << (r->agg_last_hop ? " rows (features + neighbour sums)" : " nodes") << ", the buffer holds " << rows
+            log_out() << r->local_dev_id << " Feature buffer too small: a batch has " << nodes << (r->modes.agg_last_hop ? " rows (features + neighbour sums)" : " nodes") << ", the buffer holds " << rows
                       << " rows -- the rows beyond it are not gathered and the trainer will refuse the batch (evaluation batches larger than "
                          "the training batches of the pre-sampling epoch?)\n" << std::flush;
     }
@@ -210,7 +211,7 @@ static void run_ops(Runner* r)
         if (r->gather_all && (i & 1) && i < last_feat) continue;
         if (i % 2 == 1) HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[i - 1], 0));
         r->op_params[i]->is_presc = 0;
-        if (r->agg_last_hop && i == last_feat) {     // the levels < H that were not gathered per level, and the sums
+        if (r->modes.agg_last_hop && i == last_feat) {     // the levels < H that were not gathered per level, and the sums
             OpParams* fp = r->op_params[i];
             get_feature_kernel_agg(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
         } else if (r->gather_all && i == last_feat) {
@@ -246,7 +247,7 @@ static bool run_graph(Runner* r, IPCEnv* env, int32_t batch_id)
     HIP_CHECK(hipEventRecord(r->events[0], r->streams[0]));
     HIP_CHECK(hipStreamWaitEvent(r->streams[1], r->events[0], 0));
     OpParams* fp = r->op_params[1];
-    if (r->agg_last_hop) get_feature_kernel_agg(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
+    if (r->modes.agg_last_hop) get_feature_kernel_agg(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
     else get_feature_kernel_all(r->streams[1], (GPUCache*)fp->cache, (GPUNodeStorage*)fp->noder, r->memorypool, fp->device_id, fp->in_memory);
     Operator_run(r->op_factory[r->op_num - 1], r->op_params[r->op_num - 1]);   // Updater, stream 1
     return true;
@@ -293,24 +294,8 @@ Runner* NewGPURunner(void) { return new Runner(); }
 void Runner_Initialize(Runner* r, RunnerParams* params)
 {
     if (!r || !params || !params->fanout || params->hops < 1 || params->hops > LEGION_MAX_HOPS) { LEGION_ARG_ERROR("Runner_Initialize: bad arguments"); return; }
-    {
-        std::string why;
-        const int32_t norm = agg_norm_from_env(why);
-        if (norm < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
-        r->agg_norm = norm;
-    }
-    {
-        std::string why;
-        const int32_t sampling = sampling_from_env(why);
-        if (sampling < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
-        r->sampling = sampling;
-    }
-    {
-        std::string why;
-        const int32_t on = sampling_seed_from_env(r->seed, why);
-        if (on < 0) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
-        r->seeded = on == 1;
-    }
+    std::string why;
+    if (!serve_modes_from_env(r->modes, why)) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
     r->local_dev_id = params->device_id;
     DeviceGuard guard(r->local_dev_id);
     GPUCache* cache = (GPUCache*)params->cache;
@@ -340,28 +325,19 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     r->pipeline_depth = LEGION_PIPELINE_DEPTH;
     { const char* e = getenv("LEGION_BATCH_GRAPH"); r->use_graph = e && atoi(e) != 0; }
     { const char* e = getenv("LEGION_RUNNER_GATHER"); r->gather_all = e && strcmp(e, "all") == 0; r->gather_auto = !e || strcmp(e, "auto") == 0; }
-    { const char* e = getenv("LEGION_AGG_LAST_HOP"); r->agg_last_hop = e && atoi(e) != 0; }
     for (auto& ev : r->done_ev) HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     const int total_num_nodes = GPUNodeStorage_TotalNodeNum(noder);
     GPUCache_InitializeCacheController(cache, r->local_dev_id, total_num_nodes);
     r->memorypool = NewGPUMemoryPool(r->pipeline_depth);
     GPUMemoryPool_AllocateScratch(r->memorypool, total_num_nodes, batch_size, params->fanout, hop_num);
-    if (r->agg_last_hop) {
-        GPUMemoryPool_SetAggLastHop(r->memorypool, 1);      // one draw buffer per pipe, here on this runner's GPU
-        IPCEnv_SetAggLastHop(env, 1);                        // what a trainer reads: ipc_service.aggregated()
-        log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
-    }
-    if (r->agg_norm) {
-        GPUMemoryPool_SetAggNorm(r->memorypool, r->agg_norm);   // degrees, draw weights and chunk counts per pipe, on this runner's GPU
-        IPCEnv_SetAggNorm(env, r->agg_norm);                    // what a trainer reads: ipc_service.aggregate_norm()
-        log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
-    }
-    GPUMemoryPool_SetSampleDistinct(r->memorypool, r->sampling);   // before the pre-sampling epoch: the hotness profile sees what will be served
-    IPCEnv_SetSampling(env, r->sampling);                          // what a trainer reads: ipc_service.sampling()
-    log_out() << r->local_dev_id << " Sampling: " << (r->sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
-    GPUMemoryPool_SetSampleSeed(r->memorypool, r->seeded ? 1 : 0, r->seed);
-    IPCEnv_SetSamplingSeed(env, r->seeded ? 1 : 0, r->seed);      // what a trainer reads: ipc_service.sampling_seed()
-    if (r->seeded) log_out() << r->local_dev_id << " Sampling seed: " << r->seed << " (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch\n";
+    // before the pre-sampling epoch (the hotness profile sees what will be served): the pool's modes, their buffers on this runner's GPU; what a trainer reads
+    const ServeModes& m = r->modes;
+    pool_apply_modes(r->memorypool, m, "Runner_Initialize");
+    ipc_env_publish_modes(env, m);
+    if (m.agg_last_hop) log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
+    if (m.agg_norm) log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
+    log_out() << r->local_dev_id << " Sampling: " << (m.sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
+    if (m.seeded) log_out() << r->local_dev_id << " Sampling seed: " << m.seed << " (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch\n";
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");
     LEGION_AUDIT_STREAM(r->streams[1], r->local_dev_id, "Runner_Initialize: gather stream");
@@ -409,7 +385,7 @@ void Runner_InitializeFeaturesBuffer(Runner* r, RunnerParams* params)
     DeviceGuard guard(r->local_dev_id);
     HIP_CHECK(hipStreamSynchronize(r->streams[0]));
     // aggregated hand-off: the buffer holds n_in + N rows per batch (largest of the pre-sampling epoch), same 1.2 x and seed-ratio rules
-    int64_t num_ids = (int64_t)((r->agg_last_hop ? r->presc_max_rows : GPUCache_MaxIdNum(cache, r->local_dev_id)) * 1.2);
+    int64_t num_ids = (int64_t)((r->modes.agg_last_hop ? r->presc_max_rows : GPUCache_MaxIdNum(cache, r->local_dev_id)) * 1.2);
     // The pre-sampling epoch only sees TRAINING batches.  A validation / test batch (up to 512 seeds per GPU, CUDA_IPC_Service.cu:101-118)
     // that is larger than the training batch reaches more nodes: scale the estimate by the seed ratio (unique nodes grow at most linearly
     // with the seeds).  The reference sizes by the training batches alone (Server.cu:275) -- with its 8000-seed training batches the case
@@ -442,7 +418,7 @@ void Runner_RunPreSc(Runner* r, RunnerParams* params)
     }
     // the reference polls the (never recorded) updater event here, i.e. does not wait: batches of
     // the pre-sampling epoch are simply queued in order on stream 0.
-    if (r->agg_last_hop) {   // ... except that sizing the buffer for max(n_in + N) needs both counter arrays of every batch
+    if (r->modes.agg_last_hop) {   // ... except that sizing the buffer for max(n_in + N) needs both counter arrays of every batch
         int32_t nc[LEGION_COUNTER_WORDS] = {0}, ec[LEGION_COUNTER_WORDS] = {0};
         HIP_CHECK(hipStreamSynchronize(r->streams[0]));
         HIP_CHECK(hipMemcpy(nc, r->memorypool->node_counter[r->memorypool->current_pipe], sizeof(nc), hipMemcpyDeviceToHost));
@@ -975,21 +951,9 @@ void Server_Initialize(Server* s, int global_shard_count)
     log_out() << "HIP Device Count: " << global_shard_count << "\n";
     const std::string refused = read_meta(s->meta_path, s->meta);
     if (!refused.empty()) { LEGION_ARG_ERROR(refused.c_str()); return; }
-    {   // the hand-off switches, before any device is touched
-        std::string why;
-        if (agg_norm_from_env(why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
-        const int32_t sampling = sampling_from_env(why);
-        if (sampling < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
-        uint32_t seed = 0;
-        if (sampling_seed_from_env(seed, why) < 0) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
-        // the launcher refuses such a hop per batch (launch_sample_hop): a server that booted would fail every batch, the pre-sampling epoch first
-        for (size_t h = 0; sampling == 1 && h < s->fanout.size(); h++)
-            if (s->fanout[h] > kDistinctMaxFanout) {
-                LEGION_ARG_ERROR(("Server_Initialize: LEGION_SAMPLING=distinct takes fan-outs of at most " + std::to_string(kDistinctMaxFanout) + ", hop " +
-                                  std::to_string(h + 1) + " has " + std::to_string(s->fanout[h]) + ": k_sample stages the picks of a tile's rows in static LDS").c_str());
-                return;
-            }
-    }
+    ServeModes modes;   // checked before any device is touched; every runner parses them for itself
+    std::string why;
+    if (!serve_modes_from_env(modes, why) || !serve_modes_fit_fanout(modes, s->fanout.data(), (int32_t)s->fanout.size(), why)) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
     const Meta& m = s->meta;
     // from the first device call on the main thread works on GPU 0 unless a scope below says otherwise (the reference's main thread never
     // leaves device 0); not before the meta line and the synth: source are validated -- a refused configuration touches no device

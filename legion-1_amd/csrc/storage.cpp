@@ -444,17 +444,15 @@ GPUMemoryPool::GPUMemoryPool(int32_t depth)
     agg_dst_off.assign(pipeline_depth, nullptr);
 }
 
-// the per-pipe draw buffers of the aggregated last hop (GPUMemoryPool::cand_pipe), on the current device
-static void alloc_agg_cand(GPUMemoryPool* p)
+// The per-pipe buffers of the aggregated modes, on the current device: the draw buffers of the aggregated last hop (cand_pipe) and, for
+// the normalised sums, agg_out_deg / agg_wdraw / agg_chunk_cnt.  What is there stays.
+static void alloc_mode_buffers(GPUMemoryPool* p)
 {
+    if (!p->modes.agg_last_hop || !p->owns_scratch) return;
     p->cand_pipe.resize(p->pipeline_depth, nullptr);
     for (auto& c : p->cand_pipe)
         if (!c) HIP_CHECK(hipMalloc(&c, (size_t)p->max_slots * sizeof(int32_t)));
-}
-
-// the per-pipe buffers of the normalised sums (GPUMemoryPool::agg_out_deg / agg_wdraw / agg_chunk_cnt), on the current device
-static void alloc_agg_norm(GPUMemoryPool* p)
-{
+    if (!p->modes.agg_norm) return;
     p->agg_out_deg.resize(p->pipeline_depth, nullptr);
     p->agg_wdraw.resize(p->pipeline_depth, nullptr);
     p->agg_chunk_cnt.resize(p->pipeline_depth, nullptr);
@@ -464,6 +462,20 @@ static void alloc_agg_norm(GPUMemoryPool* p)
         if (!w) HIP_CHECK(hipMalloc(&w, (size_t)p->max_slots * sizeof(float)));
     for (auto& c : p->agg_chunk_cnt)
         if (!c) HIP_CHECK(hipMalloc(&c, (size_t)legion::kMaxChunks * sizeof(int32_t)));
+}
+
+bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who)
+{
+    const std::string name(who);
+    if (!p) { LEGION_ARG_ERROR((name + ": null pool").c_str()); return false; }
+    if (p->capturing) { LEGION_ARG_ERROR((name + ": the pool is being captured").c_str()); return false; }
+    if (wanted.agg_norm != 0 && wanted.agg_norm != 1) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: unknown norm (0 = none, 1 = out-degree rsqrt)"); return false; }
+    if (wanted.agg_norm && !wanted.agg_last_hop && wanted.agg_norm != p->modes.agg_norm) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return false; }
+    if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
+    if (wanted.seeded != p->modes.seeded || wanted.seed != p->modes.seed) p->ctl_synced = false;   // ctl holds the other state's draw word: a batch graph must reset the cursor
+    p->modes = wanted;
+    alloc_mode_buffers(p);
+    return true;
 }
 
 extern "C" {
@@ -513,71 +525,38 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
     HIP_CHECK(hipMalloc(&p->agg_src_ids, (size_t)p->num_ids * sizeof(int32_t)));
     HIP_CHECK(hipMalloc(&p->tmp_part_ind, (size_t)p->num_ids));
     HIP_CHECK(hipMalloc(&p->tmp_part_off, (size_t)p->num_ids * sizeof(int32_t)));
-    if (p->agg_last_hop) alloc_agg_cand(p);
-    if (p->agg_last_hop && p->agg_norm) alloc_agg_norm(p);
+    alloc_mode_buffers(p);
     HIP_CHECK(hipDeviceSynchronize());
 }
 int32_t GPUMemoryPool_NumIds(const GPUMemoryPool* p) { return p->num_ids; }
 
-// Aggregated last hop: on = the last hop of every batch keeps its draws in a buffer of the batch's pipe and get_feature_kernel_agg hands
-// over neighbour sums; off (default) = nothing changes.  Call it under the device the pool's scratch lives on.
-void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on)
+// The four mode setters: the pool's modes with one field changed, through pool_apply_modes (internal.h: what is refused, what is
+// allocated).  Call them under the device the pool's scratch lives on.  Aggregated last hop: INTEGRATION.md "Aggregated last hop";
+// norm: 0 = plain sums, 1 = out-degree rsqrt ("Normalised sums"); distinct draws: "Sampling without replacement", nothing is allocated;
+// seed: "Seeded sampling", seed 0 is a seed like any other, nothing is allocated here (GPUMemoryPool_BeginRound fills the shuffled copy).
+static ServeModes modes_of(const GPUMemoryPool* p) { return p ? p->modes : ServeModes(); }
+void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.agg_last_hop = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetAggLastHop"); }
+void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm) { ServeModes m = modes_of(p); m.agg_norm = norm; pool_apply_modes(p, m, "GPUMemoryPool_SetAggNorm"); }
+void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.sampling = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetSampleDistinct"); }
+void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {
-    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggLastHop: null pool"); return; }
-    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggLastHop: the pool is being captured"); return; }
-    p->agg_last_hop = on != 0;
-    if (p->agg_last_hop && p->owns_scratch) alloc_agg_cand(p);
+    ServeModes m = modes_of(p);
+    m.seeded = on != 0; m.seed = seed;
+    if (pool_apply_modes(p, m, "GPUMemoryPool_SetSampleSeed")) p->ctl_synced = false;   // this call always has the next graph replay reset its cursor
 }
-int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->agg_last_hop ? 1 : 0; }
-
-// Normalised sums: 0 = plain neighbour sums, 1 = every row scaled by the out-degree^-1/2 of its batch position inside block 1 (GraphConv
-// norm='both').  Only a pool that aggregates the last hop can normalise; the mode stays set while the aggregated mode is switched off
-// and on again.  Call it under the device the pool's scratch lives on.
-void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm)
+int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->modes.agg_last_hop ? 1 : 0; }
+int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->modes.agg_norm : 0; }
+int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->modes.sampling ? 1 : 0; }
+int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed)
 {
-    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: null pool"); return; }
-    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool is being captured"); return; }
-    if (norm != 0 && norm != 1) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: unknown norm (0 = none, 1 = out-degree rsqrt)"); return; }
-    if (norm && !p->agg_last_hop) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return; }
-    p->agg_norm = norm;
-    if (norm && p->owns_scratch) alloc_agg_norm(p);
+    if (seed) *seed = p ? p->modes.seed : 0;
+    return p && p->modes.seeded ? 1 : 0;
 }
-int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->agg_norm : 0; }
 // the current pipe's block out-degrees as the last normalised batch left them (int32[legion_batch_nodes(nc, H)]); null before the mode was set
 int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p)
 {
     if (!p || p->current_pipe < 0 || p->current_pipe >= (int)p->agg_out_deg.size()) return nullptr;
     return p->agg_out_deg[p->current_pipe];
-}
-
-// Distinct-draw sampler mode: every GPU_Random_Sampling of this pool (pre-sampling included) draws min(degree, fan-out) distinct neighbour
-// positions per row instead of the reference's with-replacement stream.  A captured batch graph keeps the mode it was recorded with, so
-// the switch is refused while one is being recorded.
-void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on)
-{
-    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleDistinct: null pool"); return; }
-    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleDistinct: the pool is being captured"); return; }
-    p->sample_distinct = on != 0;
-}
-int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->sample_distinct ? 1 : 0; }
-
-// Seeded sampling (INTEGRATION.md "Seeded sampling"): on = every batch of this pool draws from its own word W(seed, round, counter) -- the
-// minstd stream seeded per batch, the distinct mode's row key XORed with W -- and its training batches read the round's shuffled copy of
-// the training list (GPUMemoryPool_BeginRound).  Seed 0 is a seed like any other; off = today's bits.  A captured batch graph keeps the
-// state it was recorded in, so the switch is refused while one is being recorded.  Nothing is allocated here.
-void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
-{
-    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleSeed: null pool"); return; }
-    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampleSeed: the pool is being captured"); return; }
-    if (p->seed != seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
-    p->seeded = on != 0;
-    p->seed = seed;
-    p->ctl_synced = false;   // ctl holds the other state's draw word: a batch graph must reset the cursor
-}
-int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed)
-{
-    if (seed) *seed = p ? p->seed : 0;
-    return p && p->seeded ? 1 : 0;
 }
 int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p) { return p ? (int32_t)p->round : 0; }
 
@@ -593,7 +572,7 @@ int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* nod
     if (p->round != (uint32_t)round) p->shuf_valid = false;   // whatever the mode: the copy holds another round's permutation
     p->round = (uint32_t)round;
     p->ctl_synced = false;   // the next replay resets the cursor: k_set_cursor carries the round's draw key
-    if (!p->seeded) return 0;
+    if (!p->modes.seeded) return 0;
     p->shuf_file_order = noder == nullptr;
     p->shuf_valid = false;
     if (!noder) return 0;
@@ -610,7 +589,7 @@ int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* nod
         HIP_CHECK(hipMalloc(&p->shuf_labels, (size_t)p->shuf_cap * sizeof(int32_t)));
         if (!p->shuf_ids || !p->shuf_labels) return -1;
     }
-    launch_shuffle_seeds((hipStream_t)stream, set.ids, set.labels, set.num, seeded_shuffle_key(p->seed, p->round), p->shuf_ids, p->shuf_labels);
+    launch_shuffle_seeds((hipStream_t)stream, set.ids, set.labels, set.num, seeded_shuffle_key(p->modes.seed, p->round), p->shuf_ids, p->shuf_labels);
     p->shuf_n = set.num;
     p->shuf_src = set.ids;
     p->shuf_valid = true;

@@ -19,11 +19,14 @@ static LegionIPCClient* env = nullptr;
 static int32_t h_node_counter[LEGION_COUNTER_WORDS];   // legion_batch_layout.h draws both arrays word by word
 static int32_t h_edge_counter[LEGION_COUNTER_WORDS];
 static int32_t g_hops = 2;
-static bool g_aggregated = false;   // the server hands the last hop over as neighbour sums (read once, in initialize)
-static int g_agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
-static bool g_seeded = false;       // seeded sampling (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch
-static uint32_t g_seed = 0;         // ... the seed (0 is a seed: g_seeded says whether there is one)
-static int g_sampling = 0;          // how the server's sampler draws: 0 = with replacement, 1 = distinct neighbours (LEGION_SAMPLING=distinct)
+// The server's serving modes, read once, in initialize()
+static struct ServerModes {
+    bool aggregated = false;   // the last hop is handed over as neighbour sums (LEGION_AGG_LAST_HOP=1)
+    int agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
+    int sampling = 0;          // how the server's sampler draws: 0 = with replacement, 1 = distinct neighbours (LEGION_SAMPLING=distinct)
+    bool seeded = false;       // seeded sampling (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch
+    uint32_t seed = 0;         // ... the seed (0 is a seed: `seeded` says whether there is one)
+} g_modes;
 // ONE consumer thread per process is the contract (the reference's trainer loop, legion_graphsage.py:72-89):
 // get_next / synchronize run without the GIL and share `env`, the two counter arrays and the client's current pipe, so the entry points
 // are serialised by this lock -- uncontended in the reference's loop, and a second Python thread gets whole counters instead of torn ones.
@@ -39,10 +42,10 @@ void InitializeIPC()
     env = legion_ipc_client_open(-1); // current device == torch.cuda.set_device(rank) (ipc_cuda_kernel.cu:41)
     TORCH_CHECK(env != nullptr, "ipc_service: cannot attach to the sampling server: ", legion_last_error());
     g_hops = legion_ipc_client_hops(env);
-    g_aggregated = legion_ipc_client_agg_last_hop(env) != 0;
-    g_agg_norm = legion_ipc_client_agg_norm(env);
-    g_sampling = legion_ipc_client_sampling(env);
-    g_seeded = legion_ipc_client_sampling_seed(env, &g_seed) != 0;
+    g_modes.aggregated = legion_ipc_client_agg_last_hop(env) != 0;
+    g_modes.agg_norm = legion_ipc_client_agg_norm(env);
+    g_modes.sampling = legion_ipc_client_sampling(env);
+    g_modes.seeded = legion_ipc_client_sampling_seed(env, &g_modes.seed) != 0;
 }
 
 void FinalizeIPC()
@@ -59,13 +62,13 @@ static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated, i
 {
     std::lock_guard<std::mutex> lock(g_mu);
     require_env();
-    TORCH_CHECK(!aggregated || !g_aggregated || norm != 0 || g_agg_norm == 0, "ipc_service.get_next_aggregated: the server normalises the neighbour sums (LEGION_AGG_NORM=both): "
+    TORCH_CHECK(!aggregated || !g_modes.aggregated || norm != 0 || g_modes.agg_norm == 0, "ipc_service.get_next_aggregated: the server normalises the neighbour sums (LEGION_AGG_NORM=both): "
                 "every row is scaled by its out-degree^-1/2 inside block 1 -- call get_next_aggregated_norm");
-    TORCH_CHECK(!aggregated || norm == 0 || (g_aggregated && g_agg_norm == norm), "ipc_service.get_next_aggregated_norm: the server does not normalise the neighbour sums (start it with "
-                "LEGION_AGG_LAST_HOP=1 LEGION_AGG_NORM=both) -- call ", g_aggregated ? "get_next_aggregated" : "get_next");
-    TORCH_CHECK(aggregated || !g_aggregated, "ipc_service.get_next: the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1): rows >= n_in of "
+    TORCH_CHECK(!aggregated || norm == 0 || (g_modes.aggregated && g_modes.agg_norm == norm), "ipc_service.get_next_aggregated_norm: the server does not normalise the neighbour sums (start it with "
+                "LEGION_AGG_LAST_HOP=1 LEGION_AGG_NORM=both) -- call ", g_modes.aggregated ? "get_next_aggregated" : "get_next");
+    TORCH_CHECK(aggregated || !g_modes.aggregated, "ipc_service.get_next: the server hands the last hop over as neighbour sums (LEGION_AGG_LAST_HOP=1): rows >= n_in of "
                 "its feature buffer are sums, not features -- call get_next_aggregated");
-    TORCH_CHECK(!aggregated || g_aggregated, "ipc_service.get_next_aggregated: the server does not aggregate the last hop (start it with LEGION_AGG_LAST_HOP=1) -- call get_next");
+    TORCH_CHECK(!aggregated || g_modes.aggregated, "ipc_service.get_next_aggregated: the server does not aggregate the last hop (start it with LEGION_AGG_LAST_HOP=1) -- call get_next");
     legion_ipc_client_wait(env); // env->Wait(), ipc_service.cpp:42
     legion_ipc_client_read_counters(env, h_node_counter, h_edge_counter);
     // a server that failed mid-batch posts the pipe with every node-counter word at -1 (runner.cpp, post_poisoned)
@@ -103,10 +106,10 @@ static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated, i
 std::vector<torch::Tensor> get_next(int feature_dim) { return next_batch(feature_dim, false); }
 std::vector<torch::Tensor> get_next_aggregated(int feature_dim) { return next_batch(feature_dim, true); }
 std::vector<torch::Tensor> get_next_aggregated_norm(int feature_dim) { return next_batch(feature_dim, true, 1); }
-bool aggregated() { require_env(); return g_aggregated; }
-int aggregate_norm() { require_env(); return g_agg_norm; }
-const char* sampling() { require_env(); return g_sampling ? "distinct" : "replace"; }
-pybind11::object sampling_seed() { require_env(); return g_seeded ? pybind11::object(pybind11::int_(g_seed)) : pybind11::object(pybind11::none()); }
+bool aggregated() { require_env(); return g_modes.aggregated; }
+int aggregate_norm() { require_env(); return g_modes.agg_norm; }
+const char* sampling() { require_env(); return g_modes.sampling ? "distinct" : "replace"; }
+pybind11::object sampling_seed() { require_env(); return g_modes.seeded ? pybind11::object(pybind11::int_(g_modes.seed)) : pybind11::object(pybind11::none()); }
 
 // [b1_src_nodes, b1_dst_nodes, b2_src_nodes, b2_dst_nodes, ...] = [nc9, nc7, nc7, nc5] at H = 2
 // (ipc_service.cpp:60-72)

@@ -127,6 +127,20 @@ def audit_clean(log_text, gpus=1):
     return counts
 
 
+def device_free_server(ns, hops, body):
+    """(preamble, script) of a server process on the device-free IPC env ($LEGION_IPC_NO_DEVICE=1: the CPU tests of the "<name>_ext" words):
+    one GPU, 3601 / 700 / 300 seeds at batch 500 -> steps [7, 2, 1]; `body` runs with L, the env `e`, np, C and subprocess in scope."""
+    pre = ("import os, sys, ctypes as C; sys.path.insert(0, %r)\n"
+           "os.environ['LEGION_IPC_NO_DEVICE'] = '1'; os.environ['LEGION_IPC_NAMESPACE'] = %r\n") % (ROOT, ns)
+    return pre, pre + ("import numpy as np, subprocess\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
+                       "e = L.NewIPCEnv(1)\n"
+                       "info = K.LegionBuildInfo(); info.partition_count = 1; info.epoch = 1; info.raw_batch_size = 500\n"
+                       "tr, va, te = (np.array([x], np.int32) for x in (3601, 700, 300))\n"
+                       "info.training_set_num, info.validation_set_num, info.testing_set_num = tr.ctypes.data, va.ctypes.data, te.ctypes.data\n"
+                       "L.IPCEnv_Coordinate(e, C.byref(info)); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); L.IPCEnv_SetHops(e, %d); K.check()\n"
+                       % hops) + body + "L.IPCEnv_Finalize(e); print('SERVER_OK')\n"
+
+
 OUT = object()      # in run_clients' args: where the trainer's output path goes (tmp_path / client<g>.json)
 
 

@@ -15,6 +15,7 @@ import pytest
 import pyref
 from aggref import cum_edges, expected_nbr_sum, last_hop_runs
 from conftest import ROOT
+from harness import device_free_server
 from gcnref import block_out_degree, expected_nbr_sum_norm
 
 
@@ -188,44 +189,49 @@ def test_set_agg_norm_is_refused_by_name_without_the_aggregated_mode():
         L.GPUMemoryPool_Delete(pool)
 
 
-def _server_script(ns, hops, body):
-    pre = ("import os, sys, ctypes as C; sys.path.insert(0, %r)\n"
-           "os.environ['LEGION_IPC_NO_DEVICE'] = '1'; os.environ['LEGION_IPC_NAMESPACE'] = %r\n") % (ROOT, ns)
-    return pre, pre + ("import numpy as np, subprocess\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
-                       "e = L.NewIPCEnv(1)\n"
-                       "info = K.LegionBuildInfo(); info.partition_count = 1; info.epoch = 1; info.raw_batch_size = 500\n"
-                       "tr, va, te = (np.array([x], np.int32) for x in (3601, 700, 300))\n"
-                       "info.training_set_num, info.validation_set_num, info.testing_set_num = tr.ctypes.data, va.ctypes.data, te.ctypes.data\n"
-                       "L.IPCEnv_Coordinate(e, C.byref(info)); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); L.IPCEnv_SetHops(e, %d); K.check()\n"
-                       % hops) + body + "L.IPCEnv_Finalize(e); print('SERVER_OK')\n"
+# 32-bit word indices of the mode words in the "<name>_ext" object and its size, as the build that first had all five laid them out (byte
+# offsets 2132 .. 2148 of 2152): peers of other builds map the same object, so the words never move.
+EXT_WORDS = dict(agg_last_hop=533, agg_norm=534, sampling=535, sampling_seeded=536, sampling_seed=537)
+EXT_BYTES = 2152
 
 
 def test_ext_word_round_trip_without_a_gpu():
-    """The norm word behind agg_last_hop in the "<name>_ext" object, with the device-free IPC env: a server that sets it, a client process
+    """The norm word of the "<name>_ext" object, with the device-free IPC env: a server that sets it, a client process
     that reads it (0 from a server that never set it); every older field the client reads -- the aggregated word, hops, steps, the row
-    capacity -- is where it was, whatever the new word holds."""
+    capacity -- is where it was, whatever the new word holds.  And the mapped object diffed word by word around every IPCEnv_Set* of a
+    mode: each call changes exactly the word(s) at the absolute positions above, to the value given, and no other; the size never changes."""
     ns = "cpuipc_norm%d_" % os.getpid()
-    pre, _ = _server_script(ns, 3, "")
+    pre, _ = device_free_server(ns, 3, "")
     client = pre + ("import legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
                     "c = C.c_void_p(L.legion_ipc_client_open(0)); K.check(); assert c.value\n"
                     "s = (C.c_int32 * 3)(); L.legion_ipc_client_steps(c, s)\n"
                     "print('CLIENT', L.legion_ipc_client_agg_norm(c), L.legion_ipc_client_agg_last_hop(c), L.legion_ipc_client_hops(c), "
                     "L.legion_ipc_client_feature_rows(c), list(s)); L.legion_ipc_client_close(c)\n")
     body = ("assert L.IPCEnv_GetAggNorm(e) == 0 and L.IPCEnv_GetAggLastHop(e) == 0\n"
+            "ext = [f for f in os.listdir('/dev/shm') if %r in f and f.endswith('_ext')]; assert len(ext) == 1, ext\n"
+            "words = lambda: np.fromfile('/dev/shm/' + ext[0], dtype=np.uint32)\n"
+            "W = %r; assert not words()[W['agg_last_hop']:].any()\n"
+            "def changes(call, *args):\n"
+            "    w0 = words(); call(e, *args); w1 = words(); assert len(w0) * 4 == len(w1) * 4 == os.path.getsize('/dev/shm/' + ext[0]) == %d\n"
+            "    return {int(i): int(w1[i]) for i in np.nonzero(w0 != w1)[0]}\n"
+            "assert changes(L.IPCEnv_SetAggLastHop, 1) == {W['agg_last_hop']: 1} and changes(L.IPCEnv_SetAggNorm, 1) == {W['agg_norm']: 1}\n"
+            "assert changes(L.IPCEnv_SetSampling, 1) == {W['sampling']: 1}\n"
+            "assert changes(L.IPCEnv_SetSamplingSeed, 1, 0xDEADBEEF) == {W['sampling_seeded']: 1, W['sampling_seed']: 0xDEADBEEF}\n"
+            "assert changes(L.IPCEnv_SetSamplingSeed, 1, 7) == {W['sampling_seed']: 7}\n"
+            "assert changes(L.IPCEnv_SetSamplingSeed, 0, 7) == {W['sampling_seeded']: 0, W['sampling_seed']: 0}\n"
+            "assert changes(L.IPCEnv_SetSampling, 0) == {W['sampling']: 0} and changes(L.IPCEnv_SetAggNorm, 0) == {W['agg_norm']: 0}\n"
+            "assert changes(L.IPCEnv_SetAggLastHop, 0) == {W['agg_last_hop']: 0}\n"
+            "assert changes(L.IPCEnv_SetAggLastHop, 0) == {} and changes(L.IPCEnv_SetSamplingSeed, 0, 9) == {}\n"
             "L.IPCEnv_SetFeatureRows(e, 0, 4321)\n"
             "for agg, norm in ((0, 0), (1, 0), (1, 1), (0, 1), (1, 0)):\n"
             "    L.IPCEnv_SetAggLastHop(e, agg); L.IPCEnv_SetAggNorm(e, norm)\n"
             "    assert L.IPCEnv_GetAggNorm(e) == norm and L.IPCEnv_GetAggLastHop(e) == agg\n"
             "    r = subprocess.run([sys.executable, '-c', %r], capture_output=True, text=True, timeout=60)\n"
-            "    print(r.stdout.strip(), r.stderr[-500:]); assert 'CLIENT %%d %%d 3 4321 [7, 2, 1]' %% (norm, agg) in r.stdout\n") % client
-    _, server = _server_script(ns, 3, body)
+            "    print(r.stdout.strip(), r.stderr[-500:]); assert 'CLIENT %%d %%d 3 4321 [7, 2, 1]' %% (norm, agg) in r.stdout\n") % (ns, EXT_WORDS, EXT_BYTES, client)
+    _, server = device_free_server(ns, 3, body)
     r = subprocess.run([sys.executable, "-c", server], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0 and "SERVER_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     assert not [f for f in os.listdir("/dev/shm") if ns in f]
-    # the word sits right behind the aggregated one: nothing older moved
-    src = open(os.path.join(ROOT, "legion-1_amd", "csrc", "ipc_env.cpp")).read()
-    fields = re.findall(r"^\s+u?int32_t\s+(\w+)(?:\[[^\]]*\])*;", src[src.index("struct shmExt {"):src.index("static const uint32_t kMirrorMagic")], re.M)
-    assert fields[-3:] == ["handle_sum", "agg_last_hop", "agg_norm"], fields
 
 
 def test_ipc_service_refuses_the_wrong_call_for_the_servers_norm_without_a_gpu():
@@ -233,7 +239,7 @@ def test_ipc_service_refuses_the_wrong_call_for_the_servers_norm_without_a_gpu()
     that aggregates without normalising, and on one that does not aggregate at all, raises too, naming the switch and the right call
     -- all before they wait for a batch (device-free IPC env); aggregate_norm() says which."""
     ns = "cpuipc_normsvc%d_" % os.getpid()
-    pre, _ = _server_script(ns, 2, "")
+    pre, _ = device_free_server(ns, 2, "")
     client = pre + ("sys.path.insert(0, %r)\nimport torch, ipc_service\nipc_service.initialize()\n"
                     "agg, norm = ipc_service.aggregated(), ipc_service.aggregate_norm()\n"
                     "assert isinstance(norm, int)\n"
@@ -246,6 +252,6 @@ def test_ipc_service_refuses_the_wrong_call_for_the_servers_norm_without_a_gpu()
             "    L.IPCEnv_SetAggLastHop(e, agg); L.IPCEnv_SetAggNorm(e, norm)\n"
             "    r = subprocess.run([sys.executable, '-c', %r], capture_output=True, text=True, timeout=120)\n"
             "    print(r.stdout.strip(), r.stderr[-800:]); assert 'REFUSED %%d %%d True' %% (agg, norm) in r.stdout\n") % client
-    _, server = _server_script(ns, 2, body)
+    _, server = device_free_server(ns, 2, body)
     r = subprocess.run([sys.executable, "-c", server], capture_output=True, text=True, timeout=400)
     assert r.returncode == 0 and "SERVER_OK" in r.stdout, r.stdout[-2500:] + r.stderr[-2000:]

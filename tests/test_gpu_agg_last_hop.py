@@ -377,7 +377,7 @@ def test_server_binary_serves_aggregated_batches(tmp_path, synth, oracle, fan, g
     synth.write_legion_files(ds, data)
     B, epochs = 512, 2
     with served(tmp_path, synth.meta_config_line(ds, data, B, 1 << 40, epochs, 0), fan, env=dict(LEGION_BATCH_GRAPH=graph, LEGION_AGG_LAST_HOP="1")) as srv:
-        got, = srv.run_clients("ipc_client_agg.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["agg", spec.F, epochs, OUT])
         srv.finish()
     H = len(fan)
     (sets,), steps, (bs,) = serve_sets(oracle, ds, B)
@@ -420,7 +420,7 @@ def test_plain_server_refuses_get_next_aggregated_and_a_short_buffer_is_named(K,
             pool = L.Runner_GetMemoryPool(runner)
             small_rows = 100
             log = str(tmp_path / "client.log")
-            client = attached_client(children, "ipc_client_agg.py", [ds.spec.F, "refuse", "feature buffer holds %d rows" % small_rows], cenv, log)
+            client = attached_client(children, "ipc_client_modes.py", ["agg", ds.spec.F, "refuse", "feature buffer holds %d rows" % small_rows], cenv, log)
             rp.global_batch_id = 0
             L.Runner_RunOnce(runner, C.byref(rp))
             rp.global_batch_id = 1

@@ -403,7 +403,7 @@ def test_server_binary_serves_normalised_batches(tmp_path, synth, oracle, fan, g
     B, epochs = 512, 2
     env = dict(LEGION_BATCH_GRAPH=graph, LEGION_AGG_LAST_HOP="1", LEGION_AGG_NORM="both")
     with served(tmp_path, synth.meta_config_line(ds, data, B, 1 << 40, epochs, 0), fan, env=env) as srv:
-        got, = srv.run_clients("ipc_client_agg_norm.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["norm", spec.F, epochs, OUT])
         srv.finish()
     H = len(fan)
     (sets,), steps, (bs,) = serve_sets(oracle, ds, B)

@@ -267,7 +267,7 @@ def test_server_binary_serves_distinct_aggregated_batches(tmp_path, synth, oracl
     meta_line = "synth:%s:%r %d %d %d %d %d %d %d %d %d 0" % (workload, scale, B, spec.V, ds.E, spec.F, spec.n_train, n_valid, n_test, 1 << 40, epochs)
     env = dict(LEGION_SAMPLING="distinct", LEGION_AGG_LAST_HOP="1", LEGION_AGG_NORM=norm, LEGION_BATCH_GRAPH=graph, LEGION_SYNTH_CACHE=None)
     with served(tmp_path, meta_line, fan, env=env) as srv:
-        got, = srv.run_clients("ipc_client_agg_norm.py" if norm else "ipc_client_agg.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["norm" if norm else "agg", spec.F, epochs, OUT])
         srv.finish()
     text = srv.log_text()
     assert got["sampling"] == "distinct" and "(LEGION_SAMPLING=distinct)" in text and "Hand-off: the last hop as neighbour sums" in text
@@ -313,7 +313,7 @@ def test_default_sampling_still_serves_a_fan_out_of_65(tmp_path, synth, oracle):
     n_valid, n_test = min(700, spec.n_valid), min(300, spec.n_test)
     meta_line = "synth:%s:%r %d %d %d %d %d %d %d %d %d 0" % (workload, scale, B, spec.V, ds.E, spec.F, spec.n_train, n_valid, n_test, 1 << 40, epochs)
     with served(tmp_path, meta_line, fan, env=dict(LEGION_SAMPLING=None, LEGION_AGG_LAST_HOP=None, LEGION_AGG_NORM=None)) as srv:
-        got, = srv.run_clients("ipc_client_sampling.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["plain", spec.F, epochs, OUT])
         srv.finish()
     assert got["sampling"] == "replace"
     (sets,), steps, (bs,) = serve_sets(oracle, ds, B, n_valid=n_valid, n_test=n_test)

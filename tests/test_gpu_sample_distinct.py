@@ -307,7 +307,7 @@ def test_server_binary_serves_distinct_batches(tmp_path, synth, oracle, fan, gra
     meta_line = "synth:%s:%r %d %d %d %d %d %d %d %d %d 0" % (workload, scale, B, spec.V, ds.E, spec.F, spec.n_train, n_valid, n_test, budget, epochs)
     env = dict(LEGION_SAMPLING="distinct", LEGION_BATCH_GRAPH=graph, LEGION_SYNTH_CACHE="1" if cache else None)
     with served(tmp_path, meta_line, fan, env=env) as srv:
-        got, = srv.run_clients("ipc_client_sampling.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["plain", spec.F, epochs, OUT])
         srv.finish()
     text = srv.log_text()
     assert got["sampling"] == "distinct" and "Sampling: distinct neighbours" in text and "(LEGION_SAMPLING=distinct)" in text
@@ -329,7 +329,7 @@ def test_server_default_is_replace(tmp_path, synth, oracle, value):
     n_valid, n_test = min(700, spec.n_valid), min(300, spec.n_test)
     meta_line = "synth:%s:%r %d %d %d %d %d %d %d %d %d 0" % (workload, scale, B, spec.V, ds.E, spec.F, spec.n_train, n_valid, n_test, 1 << 40, epochs)
     with served(tmp_path, meta_line, fan, env=dict(LEGION_SAMPLING=value)) as srv:
-        got, = srv.run_clients("ipc_client_sampling.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["plain", spec.F, epochs, OUT])
         srv.finish()
     text = srv.log_text()
     assert got["sampling"] == "replace" and text.count("Sampling: with replacement") == 1

@@ -361,7 +361,7 @@ def test_server_binary_serves_seeded_batches(tmp_path, synth, oracle, graph, G, 
     meta_line = "synth:%s:%r %d %d %d %d %d %d %d %d %d 0" % (workload, scale, B, spec.V, ds.E, spec.F, spec.n_train, n_valid, n_test, 1 << 40, epochs)
     env = dict(LEGION_SAMPLING_SEED=S, LEGION_BATCH_GRAPH=graph, LEGION_SAMPLING=sample)
     with served(tmp_path, meta_line, fan, G=G, env=env) as srv:
-        gots = srv.run_clients("ipc_client_seed.py", [spec.F, epochs, OUT])
+        gots = srv.run_clients("ipc_client_modes.py", ["plain", spec.F, epochs, OUT])
         srv.finish()
     text = srv.log_text()
     assert text.count("Sampling seed: 12345 (LEGION_SAMPLING_SEED)") == G and "Feature buffer too small" not in text
@@ -402,7 +402,7 @@ def test_unseeded_server_says_none(tmp_path, synth, oracle):
     n_valid, n_test = min(700, spec.n_valid), min(300, spec.n_test)
     meta_line = "synth:%s:%r %d %d %d %d %d %d %d %d %d 0" % (workload, scale, B, spec.V, ds.E, spec.F, spec.n_train, n_valid, n_test, 1 << 40, epochs)
     with served(tmp_path, meta_line, fan, env=dict(LEGION_SAMPLING_SEED=None)) as srv:
-        got, = srv.run_clients("ipc_client_seed.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["plain", spec.F, epochs, OUT])
         srv.finish()
     assert got["sampling_seed"] is None and "Sampling seed" not in srv.log_text()
     (sets,), steps, (bs,) = serve_sets(oracle, ds, B, n_valid=n_valid, n_test=n_test)
@@ -419,7 +419,7 @@ def test_link_prediction_lists_stay_in_file_order(tmp_path, synth, oracle):
     B, fan, epochs, S = 510, [10, 5], 2, 12345
     meta_line = "synth:products:0.004 %d %d %d %d %d 100 60 0 %d 2" % (B, spec.V, ds.E, spec.F, spec.n_train, epochs)
     with served(tmp_path, meta_line, fan, env=dict(LEGION_SAMPLING_SEED=hex(S))) as srv:
-        got, = srv.run_clients("ipc_client_seed.py", [spec.F, epochs, OUT])
+        got, = srv.run_clients("ipc_client_modes.py", ["plain", spec.F, epochs, OUT])
         srv.finish()
     text = srv.log_text()
     assert text.count("the training lists are served verbatim (meta flag 2): not shuffled") == 1 and got["sampling_seed"] == S

@@ -10,6 +10,7 @@ import pytest
 import distinctref as D
 import pyref
 from conftest import ROOT
+from harness import device_free_server
 
 H_GRID = (1, 2, 3, 4)
 F_GRID = (1, 2, 5, 10, 25, 64)
@@ -193,24 +194,12 @@ def test_pool_switch_without_a_gpu():
         L.GPUMemoryPool_Delete(pool)
 
 
-def _server_script(ns, hops, body):
-    pre = ("import os, sys, ctypes as C; sys.path.insert(0, %r)\n"
-           "os.environ['LEGION_IPC_NO_DEVICE'] = '1'; os.environ['LEGION_IPC_NAMESPACE'] = %r\n") % (ROOT, ns)
-    return pre, pre + ("import numpy as np, subprocess\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
-                       "e = L.NewIPCEnv(1)\n"
-                       "info = K.LegionBuildInfo(); info.partition_count = 1; info.epoch = 1; info.raw_batch_size = 500\n"
-                       "tr, va, te = (np.array([x], np.int32) for x in (3601, 700, 300))\n"
-                       "info.training_set_num, info.validation_set_num, info.testing_set_num = tr.ctypes.data, va.ctypes.data, te.ctypes.data\n"
-                       "L.IPCEnv_Coordinate(e, C.byref(info)); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); L.IPCEnv_SetHops(e, %d); K.check()\n"
-                       % hops) + body + "L.IPCEnv_Finalize(e); print('SERVER_OK')\n"
-
-
 def test_sampling_word_round_trip_without_a_gpu():
     """The word behind agg_norm in the "<name>_ext" object, with the device-free IPC env: a server sets it, a client process reads it (0
     from a server that never set it) and every older word it reads is where it was; in the mapped object the three words are neighbours,
     agg_last_hop, agg_norm, sampling; ipc_service.sampling() names the mode."""
     ns = "cpuipc_samp%d_" % os.getpid()
-    pre, _ = _server_script(ns, 3, "")
+    pre, _ = device_free_server(ns, 3, "")
     client = pre + ("sys.path.insert(0, %r)\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
                     "c = C.c_void_p(L.legion_ipc_client_open(0)); K.check(); assert c.value\n"
                     "s = (C.c_int32 * 3)(); L.legion_ipc_client_steps(c, s)\n"
@@ -234,7 +223,7 @@ def test_sampling_word_round_trip_without_a_gpu():
             "    r = subprocess.run([sys.executable, '-c', %r], capture_output=True, text=True, timeout=120)\n"
             "    print(r.stdout.strip(), r.stderr[-500:]); assert 'CLIENT %%d %%d %%d 3 4321 [7, 2, 1]' %% (samp, norm, agg) in r.stdout\n"
             "    assert 'SERVICE ' + ('distinct' if samp else 'replace') in r.stdout\n") % (ns, client)
-    _, server = _server_script(ns, 3, body)
+    _, server = device_free_server(ns, 3, body)
     r = subprocess.run([sys.executable, "-c", server], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "SERVER_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     assert not [f for f in os.listdir("/dev/shm") if ns in f]

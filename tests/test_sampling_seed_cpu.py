@@ -12,6 +12,7 @@ import distinctref as D
 import pyref
 import seededref as R
 from conftest import ROOT
+from harness import device_free_server
 
 def small_graph(seed, V=300, holes=True):
     """tests/test_sample_distinct_cpu.py's graph: degrees 0..11, four hubs of 90, -1 entries"""
@@ -25,19 +26,6 @@ def small_graph(seed, V=300, holes=True):
     feats = rng.rand(V, 5).astype(np.float32)
     seeds = rng.permutation(V)[:97].astype(np.int32)
     return indptr, indices, feats, labels, seeds
-
-
-def _server_script(ns, hops, body):
-    """(preamble, script) of a device-free IPC server process: one GPU, 3601 / 700 / 300 seeds at batch 500 -> steps [7, 2, 1]"""
-    pre = ("import os, sys, ctypes as C; sys.path.insert(0, %r)\n"
-           "os.environ['LEGION_IPC_NO_DEVICE'] = '1'; os.environ['LEGION_IPC_NAMESPACE'] = %r\n") % (ROOT, ns)
-    return pre, pre + ("import numpy as np, subprocess\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
-                       "e = L.NewIPCEnv(1)\n"
-                       "info = K.LegionBuildInfo(); info.partition_count = 1; info.epoch = 1; info.raw_batch_size = 500\n"
-                       "tr, va, te = (np.array([x], np.int32) for x in (3601, 700, 300))\n"
-                       "info.training_set_num, info.validation_set_num, info.testing_set_num = tr.ctypes.data, va.ctypes.data, te.ctypes.data\n"
-                       "L.IPCEnv_Coordinate(e, C.byref(info)); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); L.IPCEnv_SetHops(e, %d); K.check()\n"
-                       % hops) + body + "L.IPCEnv_Finalize(e); print('SERVER_OK')\n"
 
 
 N_LIST = (1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 203, 256, 257, 1000, 4097, 65537, 100003)
@@ -240,7 +228,7 @@ def test_seed_words_round_trip_without_a_gpu():
     ipc_service.sampling_seed() read them ("off" from a server that never set them, and after they are cleared); every older getter reads
     what it read."""
     ns = "cpuipc_seed%d_" % os.getpid()
-    pre, _ = _server_script(ns, 3, "")
+    pre, _ = device_free_server(ns, 3, "")
     client = pre + ("sys.path.insert(0, %r)\nimport legion1_amd.capi as K\nL = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
                     "c = C.c_void_p(L.legion_ipc_client_open(0)); K.check(); assert c.value\n"
                     "s = (C.c_int32 * 3)(); L.legion_ipc_client_steps(c, s); sd = C.c_uint32(77)\n"
@@ -264,7 +252,7 @@ def test_seed_words_round_trip_without_a_gpu():
             "    print(r.stdout.strip(), r.stderr[-500:])\n"
             "    assert 'CLIENT %%d %%d %%d %%d %%d 3 4321 [7, 2, 1]' %% (on, seed if on else 0, samp, norm, agg) in r.stdout\n"
             "    assert 'SERVICE %%s %%s' %% (repr(seed) if on else 'None', 'distinct' if samp else 'replace') in r.stdout\n") % (ns, client)
-    _, server = _server_script(ns, 3, body)
+    _, server = device_free_server(ns, 3, body)
     r = subprocess.run([sys.executable, "-c", server], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "SERVER_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     assert not [f for f in os.listdir("/dev/shm") if ns in f]
