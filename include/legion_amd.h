@@ -415,6 +415,19 @@ void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed);
 int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed);
 int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* noder, int32_t dev_id, int32_t round);
 int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p);
+/* Drawn link-prediction thirds (extension; INTEGRATION.md "Drawn link-prediction thirds").  With GPUMemoryPool_SetLpDraw(pool, k, graph), k > 0,
+ * a TRAINING batch of the seeded pool is 3 k seeds [src | pos | neg]: the src third comes from the training list -- a [src | pos | neg]
+ * list of batches of 3 k, whose triples GPUMemoryPool_BeginRound shuffles as wholes (noder = NULL: file order) --, and the other two
+ * thirds are drawn inside the seed kernel from the batch's draw word W(S, round, iter): pos is one neighbour of src in `graph` (src itself
+ * for an empty row or a negative entry), read where GPU_Random_Sampling would read that row on this GPU, neg is uniform on [0, V).  The
+ * labels of drawn slots are -1.  Everything behind the seeds is the default mode's; validation and test batches are untouched; k = 0 is
+ * today's behaviour, bit for bit.  The pool keeps `graph` (batch_generator_kernel has the reference's signature) and allocates nothing.
+ * Sticky argument errors, by name: a null pool, k < 0, k > 0 with a null graph, a switch while the pool is being captured; in
+ * batch_generator_kernel a training batch under the mode without a seed (GPUMemoryPool_SetSampleSeed), with batch_size != 3 k or on a
+ * list whose length is not a multiple of 3 k (BeginRound refuses such a list too).  LegionBatchGraph_Launch refuses a graph recorded in
+ * another lp_draw state; a new round or seed needs no new recording. */
+void GPUMemoryPool_SetLpDraw(GPUMemoryPool* p, int32_t triples_per_batch, GPUGraphStorage* graph);
+int32_t GPUMemoryPool_GetLpDraw(const GPUMemoryPool* p);
 /* Owner-computes exchange variant of the feature gather (SURVEY 5 option b; the reference reads peer caches in-kernel over
  * NVLink, Kernels.cu:662-702 -- this is the collective formulation for one process per GPU, the all-to-all itself is RCCL /
  * hipMemcpyPeer in the caller: legion-1_amd/exchange.py).  plan (requester): rows of the batch cached on another clique member are
@@ -650,6 +663,11 @@ void legion_seeded_rng_probe(void* stream, uint32_t seed, int32_t round, int32_t
 void legion_seeded_distinct_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* row, const int32_t* hop, const int32_t* deg,
                                   int32_t f, int32_t* pos_out, int32_t n);
 void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, int32_t* perm_out);
+/* Drawn link-prediction thirds, for the batch (seed, round, iter) and slot i = the array index, by the seed kernel's own device functions:
+ * rho_out[i] = the position of the positive in a row of degree deg[i] of source src[i] (-1 for deg <= 0: the source itself), neg_out[i] =
+ * the negative on [0, V), V >= 1.  All pointers are device memory. */
+void legion_lp_draw_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* src, const int32_t* deg, int32_t V, int32_t* rho_out,
+                          int32_t* neg_out, int32_t n);
 uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter);
 uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round);
 /* compute units of the current device as the sampler's persistent grids count them: a hop of more than 4 x this x 1024 slots makes a

@@ -208,6 +208,8 @@ _SIGS = {
     "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
     "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
     "GPUMemoryPool_BeginRound": (C.c_int, [vp, vp, vp, i32, i32]),
+    "GPUMemoryPool_SetLpDraw": (None, [vp, i32, vp]),
+    "GPUMemoryPool_GetLpDraw": (i32, [vp]),
     "GPUMemoryPool_GetRound": (i32, [vp]),
     "legion_exchange_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "legion_exchange_local": (C.c_int, [vp, vp, vp, vp, i32]),
@@ -282,6 +284,7 @@ _SIGS = {
     "legion_seeded_rng_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32]),
     "legion_seeded_distinct_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32, vp, i32]),
     "legion_perm_probe": (None, [vp, u32, i32, i32, vp]),
+    "legion_lp_draw_probe": (None, [vp, u32, i32, i32, vp, vp, i32, vp, vp, i32]),
     "legion_seeded_draw_word": (u32, [u32, i32, i32]),
     "legion_seeded_shuffle_key": (u32, [u32, i32]),
     "legion_sampler_cu_count": (i32, []),
@@ -489,8 +492,11 @@ class Engine:
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
-                  seed=None, round=0):
-        """seed: None (the reference's draws: the same batch every epoch) or a uint32 (GPUMemoryPool_SetSampleSeed: the batch's draws come
+                  seed=None, round=0, lp_draw=0):
+        """lp_draw: 0, or k > 0 (GPUMemoryPool_SetLpDraw, only under a seed): a training batch is 3 k seeds [src | pos | neg], the src third
+        from the round's triple-shuffled training list, pos and neg drawn for this batch.  Set on every call like `seed`; a change re-runs
+        GPUMemoryPool_BeginRound.
+        seed: None (the reference's draws: the same batch every epoch) or a uint32 (GPUMemoryPool_SetSampleSeed: the batch's draws come
         from W(seed, round, counter) and a training batch reads the round's shuffled list); round: the epoch the batch belongs to.  Like
         `sample`, both SET the pool's state on every call, and GPUMemoryPool_BeginRound runs when the seed, the round or the device's
         training list changed.
@@ -503,7 +509,7 @@ class Engine:
         block 1 (GPUMemoryPool_SetAggNorm); result() additionally returns `out_deg` int32 [n]."""
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
-        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc)
+        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw)
         self._agg[(dev, pipe)] = agg and gather
         self._norm[(dev, pipe)] = norm and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
@@ -528,7 +534,7 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
-    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False):
+    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
@@ -544,27 +550,29 @@ class Engine:
         for mode, want in (("SampleDistinct", int(sample == "distinct")), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
             if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
                 getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
-        self._set_seed(dev, seed, round, stream)
+        self._set_seed(dev, seed, round, stream, lp_draw)
         return agg, bool(norm)
 
-    def _set_seed(self, dev, seed, round, stream):
-        """The pool's seeded state := (seed, round); BeginRound on `stream` when either changed (not callable inside a capture: there the
-        state is what capture_batch set before Begin)."""
+    def _set_seed(self, dev, seed, round, stream, lp_draw=0):
+        """The pool's seeded state := (seed, round, lp_draw); BeginRound on `stream` when any of them changed (not callable inside a capture:
+        there the state is what capture_batch set before Begin)."""
         L, pool = self.L, self.pools[dev]
-        want = (None if seed is None else int(seed) & 0xFFFFFFFF, int(round))
-        if self._seed_state.get(dev, (None, 0)) == want:
+        want = (None if seed is None else int(seed) & 0xFFFFFFFF, int(round), int(lp_draw))
+        if self._seed_state.get(dev, (None, 0, 0)) == want:
             return
         L.GPUMemoryPool_SetSampleSeed(pool, int(seed is not None), want[0] or 0)
+        if L.GPUMemoryPool_GetLpDraw(pool) != want[2]:
+            L.GPUMemoryPool_SetLpDraw(pool, want[2], self.graph)
         L.GPUMemoryPool_BeginRound(stream, pool, self.noder, dev, want[1])
         check()
         self._seed_state[dev] = want
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0):
+                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
-        run_graph(..., seed=, round=)."""
+        run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -572,12 +580,12 @@ class Engine:
                 self.streams[dev] = L.d_stream_create()
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
-        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream)
+        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
-                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round)
+                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -585,13 +593,14 @@ class Engine:
         self._graphs.append(g)
         return (g, stream, dev)
 
-    def run_graph(self, handle, counter, sync=True, seed=False, round=None):
-        """seed / round: leave the pool's seeded state as it is (the defaults), or set it first like run_batch does (seed=None: unseeded)."""
+    def run_graph(self, handle, counter, sync=True, seed=False, round=None, lp_draw=None):
+        """seed / round / lp_draw: leave the pool's seeded state as it is (the defaults), or set it first like run_batch does (seed=None:
+        unseeded)."""
         g, stream, dev = handle
         self.L.SetGPUDevice(dev)
-        if seed is not False or round is not None:
-            cur = self._seed_state.get(dev, (None, 0))
-            self._set_seed(dev, cur[0] if seed is False else seed, cur[1] if round is None else round, stream)
+        if seed is not False or round is not None or lp_draw is not None:
+            cur = self._seed_state.get(dev, (None, 0, 0))
+            self._set_seed(dev, cur[0] if seed is False else seed, cur[1] if round is None else round, stream, cur[2] if lp_draw is None else lp_draw)
         if self.L.LegionBatchGraph_Launch(g, stream, int(counter)) != 0:
             check()
             raise RuntimeError("LegionBatchGraph_Launch failed")

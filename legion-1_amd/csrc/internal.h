@@ -113,11 +113,17 @@ struct ServeModes {
     int32_t sampling = 0;        // $LEGION_SAMPLING: 0 = replace (the reference's stream), 1 = distinct: min(degree, fan-out) distinct neighbours per row
     bool seeded = false;         // $LEGION_SAMPLING_SEED: every batch draws from its own word W(seed, round, counter), the training list is reshuffled
     uint32_t seed = 0;           // ... every round ("Seeded sampling").  Seed 0 is a seed like any other: `seeded` says whether there is one
-    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed; }
+    int32_t lp_draw = 0;         // $LEGION_LP_DRAW=1, only under a seed: k > 0 = a training batch is 3 k seeds whose pos and neg thirds are drawn per batch
+                                 // ("Drawn link-prediction thirds"); from the environment it is 1 until serve_modes_resolve_lp_draw puts k there
+    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw; }
 };
-// The only readers of the four variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
-// unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed.  Host code only, no device is touched.
+// The only readers of the five variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
+// unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed, unknown LEGION_LP_DRAW, LEGION_LP_DRAW without a
+// seed.  Host code only, no device is touched.
 bool serve_modes_from_env(ServeModes& m, std::string& why);
+// LEGION_LP_DRAW against what is served, once the meta line is known: false with the refusal in `why` unless the training lists are
+// link-prediction thirds (meta flag 2) of a batch size divisible by 3; m.lp_draw := raw_batch_size / 3.  Nothing to do with the mode off.
+bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why);
 // the distinct mode's fan-out bound (kDistinctMaxFanout) against a fan-out list: false with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
 // what a trainer reads: the five mode words of the "<name>_ext" object := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
@@ -167,6 +173,7 @@ __host__ __device__ inline uint32_t mix32(uint32_t z)
     return z;
 }
 constexpr uint32_t kShuffleTag = 0x53485546u, kDrawTag = 0x44524157u, kGolden = 0x9E3779B9u;
+constexpr uint32_t kLpPosTag = 0x4C50504Fu, kLpNegTag = 0x4C504E45u;   // drawn link-prediction thirds: Kp = mix32(W ^ "LPPO"), Kn = mix32(W ^ "LPNE")
 __host__ __device__ inline uint32_t seeded_shuffle_key(uint32_t seed, uint32_t round) { return mix32(mix32(seed ^ kShuffleTag) ^ round); }
 __host__ __device__ inline uint32_t seeded_draw_key(uint32_t seed, uint32_t round) { return mix32(mix32(seed ^ kDrawTag) ^ round); }
 __host__ __device__ inline uint32_t seeded_draw_word(uint32_t seeded, uint32_t draw_key, int32_t counter) { return seeded ? mix32(draw_key ^ (uint32_t)counter) : 0u; }
@@ -251,13 +258,22 @@ struct SamplerBuffers {
     unsigned long long* edge_access_time; // pre-sampling only (may be null)
 };
 
+// Drawn link-prediction thirds: what k_seed<.., LP> needs beyond the default mode's arguments, fixed for a recording
+struct LpDrawArgs {
+    int32_t k = 0;                 // triples per batch: the batch is 3 k slots
+    int32_t V = 0;                 // negatives are uniform on [0, V); V <= entries of the position table
+    CsrTables csr = {};            // where the positive's row is read: as the sampler would read it on this GPU
+};
+// lp: null = the default mode (the instantiation that ran before the mode existed)
 void launch_seed(hipStream_t s, int32_t* batch_ids, int32_t* labels, int32_t batch_size, int32_t size, int32_t counter,
                  const int32_t* all_ids, const int32_t* all_labels, int32_t total_cap, pos_t* pos_map,
                  uint32_t epoch, BatchCtl* ctl, bool self_driven, int32_t* nc, int32_t* ec, int32_t* aux_next,
-                 int32_t f_next, int32_t aux_cap, uint32_t seeded = 0, uint32_t draw_key = 0);
+                 int32_t f_next, int32_t aux_cap, uint32_t seeded = 0, uint32_t draw_key = 0, const LpDrawArgs* lp = nullptr);
 void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded = 0, uint32_t draw_key = 0);
 // out_ids[g] = ids[perm(g)], out_labels[g] = labels[perm(g)] for g < n under shuffle key ks (seeded_perm)
 void launch_shuffle_seeds(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, uint32_t ks, int32_t* out_ids, int32_t* out_labels);
+// the same for a [src | pos | neg] list of batches of 3 k (n a multiple of 3 k): whole triples move, under perm on [0, n / 3)
+void launch_shuffle_triples(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, int32_t k, uint32_t ks, int32_t* out_ids, int32_t* out_labels);
 void launch_advance(hipStream_t s, BatchCtl* ctl);
 int sampler_cu_count();       // compute units the persistent grids are sized by (current device)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
@@ -334,6 +350,8 @@ void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop
 void launch_seeded_rng_probe(hipStream_t s, uint32_t w, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n);
 void launch_seeded_distinct_probe(hipStream_t s, uint32_t w, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n);
 void launch_perm_probe(hipStream_t s, uint32_t ks, int32_t n, int32_t* out);
+// drawn link-prediction thirds under draw word w: rho[i] = the positive's position in a row of degree deg[i] (-1: deg <= 0), neg[i] on [0, V)
+void launch_lp_draw_probe(hipStream_t s, uint32_t w, const int32_t* src, const int32_t* deg, int32_t V, int32_t* rho, int32_t* neg, int32_t n);
 // cache construction helpers
 void launch_aggregate_access(hipStream_t s, unsigned long long* agg, const unsigned long long* add, int32_t n);
 void launch_iota(hipStream_t s, int32_t* out, int32_t n);
@@ -407,6 +425,9 @@ struct GPUMemoryPool {
     const int32_t* shuf_src = nullptr;
     bool shuf_valid = false, shuf_file_order = false;
     bool seed_reads_shuffle = false;  // the last batch_generator_kernel (the recording's, inside a capture) read the shuffled copy
+    // Drawn link-prediction thirds (modes.lp_draw = k, GPUMemoryPool_SetLpDraw): the graph the positives are read from -- kept here because
+    // batch_generator_kernel has the reference's signature, without a graph.  Under the mode BeginRound shuffles whole triples into the same copy.
+    GPUGraphStorage* lp_graph = nullptr;
     std::vector<int32_t*> agg_out_deg, agg_chunk_cnt;
     std::vector<float*> agg_wdraw;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
@@ -434,7 +455,8 @@ struct GPUMemoryPool {
 namespace legion {
 // The pool's modes := wanted, once for every mode.  Refused in who's name: a null pool, a pool that is being captured (a recording keeps
 // its modes).  Refused as GPUMemoryPool_SetAggNorm: an unknown norm, and a norm on a pool that does not aggregate the last hop -- unless the
-// pool holds that norm already (it stays set while the aggregated mode is off).  Allocates the aggregated modes' per-pipe buffers when the
+// pool holds that norm already (it stays set while the aggregated mode is off).  Refused as GPUMemoryPool_SetLpDraw: a negative triple count,
+// and a positive one on a pool without a graph (lp_graph).  Allocates the aggregated modes' per-pipe buffers when the
 // pool owns scratch (call it under the scratch's device); another seed invalidates the shuffled copy, another seeded state the graph cursor.
 bool pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who);
 }

@@ -101,7 +101,43 @@ __device__ inline int wave_id() { return threadIdx.x >> 6; }
 // arguments.  Host-driven launches pass both as arguments and publish them for the kernels that follow, and with them the batch's
 // draw word (seeded sampling: BatchCtl::draw, 0 with the mode off).  In training mode under a seed all_ids / all_labels are the pool's
 // shuffled copy of the list (k_shuffle_seeds), read exactly as the file-order list is.
-template <bool SELF>
+// Drawn link-prediction thirds (INTEGRATION.md "Drawn link-prediction thirds"): the positive and the negative of slot i of a batch, pure
+// functions of the batch's draw word, the slot and its source.  u is the distinct mode's hash of (key, slot) with the source folded in, so
+// that two GPUs of one job, which share the draw word, do not draw the same negatives.
+__device__ inline uint32_t lp_u(uint32_t key, uint32_t i, int32_t src) { return mix32(distinct_u(key, i) ^ (uint32_t)src); }
+__device__ inline int32_t lp_rho(uint32_t w, uint32_t i, int32_t src, int32_t d) { return (int32_t)__umulhi(lp_u(mix32(w ^ kLpPosTag), i, src), (uint32_t)d); }   // < d, d > 0
+__device__ inline int32_t lp_neg(uint32_t w, uint32_t i, int32_t src, int32_t V) { return (int32_t)__umulhi(lp_u(mix32(w ^ kLpNegTag), i, src), (uint32_t)V); }   // < V
+// The positive: one neighbour of src, read where k_sample would read that row (the owner's fragment when the topology map names one, else
+// the whole CSR; fragment rows are copies in CSR order), degree as k_sample computes it; src itself for an empty row or a negative entry.
+// The row addressing below restates k_sample's ("owner lookup, chunk tables, int32 degree") rather than sharing a helper with it, on
+// purpose: k_sample interleaves those loads with its tile's other work and its twelve instantiations are kept instruction for
+// instruction.  Whoever changes the fragment layout changes both; the cached-topology test compares this copy with the uncached statement.
+__device__ inline int32_t lp_pos(const CsrTables& c, uint32_t w, uint32_t i, int32_t src)
+{
+    const int64_t* ip = c.indptr + src;
+    const int32_t* rowp;
+    const int8_t owner = c.topo_owner ? c.topo_owner[src] : (int8_t)-1;
+    int64_t start;
+    if (owner >= 0) {
+        const int32_t row = c.topo_row[src];
+        ip = c.frag_indptr[owner * c.ip_nch + (row >> c.row_shift)] + (row & ((1 << c.row_shift) - 1));
+        start = ip[0];
+        rowp = c.frag_indices[owner * c.ix_nch + (int32_t)(start >> c.edge_shift)] + (start & ((1ll << c.edge_shift) - 1));
+    } else {
+        start = ip[0];
+        rowp = c.indices + start;
+    }
+    const int32_t d = (int32_t)(ip[1] - start);
+    if (d <= 0) return src;
+    const int32_t pos = rowp[lp_rho(w, i, src, d)];
+    return pos < 0 ? src : pos;
+}
+
+// LP (GPUMemoryPool_SetLpDraw, training batches only): the batch is 3 k slots, [src | pos | neg].  Every thread reads the source of its
+// slot i = idx % k from the (shuffled) triple list; a thread of the second third then reads the row descriptor and one neighbour, a thread
+// of the last third hashes.  No thread waits for another; what follows the id (claim loop, counters, slot states) is the default mode's.
+// LP = false is the kernel as it was: `lp` is not read.
+template <bool SELF, bool LP>
 __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids, int32_t* __restrict__ labels,
                                                  int32_t batch_size, int32_t size, int32_t counter,
                                                  const int32_t* __restrict__ all_ids,
@@ -109,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
                                                  pos_t* __restrict__ pos_map, uint32_t epoch,
                                                  BatchCtl* __restrict__ ctl, int32_t* __restrict__ nc,
                                                  int32_t* __restrict__ ec, int32_t* __restrict__ aux_next,
-                                                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key)
+                                                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key, LpDrawArgs lp)
 {
     int32_t idx = threadIdx.x + blockDim.x * blockIdx.x;
     if (SELF) {
@@ -131,7 +167,19 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
             batch_ids[idx] = -1;
             labels[idx] = -1;
         } else {
-            int32_t src_id = all_ids[g % total_cap];
+            int32_t src_id, label;
+            if constexpr (LP) {
+                const int32_t q = (idx >= lp.k) + (idx >= 2 * lp.k), i = idx - q * lp.k;   // third, slot; size == 3 k (the launcher checked)
+                const int32_t gs = g - q * lp.k;                                          // the slot's entry of the src third
+                const uint32_t w = SELF ? ctl->draw : seeded_draw_word(seeded, draw_key, counter);
+                src_id = all_ids[gs];
+                label = -1;
+                if (q == 0) label = all_labels[gs];
+                else if (q == 1) src_id = lp_pos(lp.csr, w, (uint32_t)i, src_id);
+                else src_id = lp_neg(w, (uint32_t)i, src_id, lp.V);
+            } else {
+                src_id = all_ids[g % total_cap];
+            }
             batch_ids[idx] = src_id;
             // position_map[src_id] = idx (Kernels.cu:92).  The reference assumes distinct seeds (:67); with
             // duplicates (link-prediction triples) its serial order lets the LAST occurrence win, so do the
@@ -143,7 +191,8 @@ __global__ __launch_bounds__(kBlock) void k_seed(int32_t* __restrict__ batch_ids
                 if (seen == cur) break;
                 cur = seen;
             }
-            labels[idx] = all_labels[g % total_cap];
+            if constexpr (LP) labels[idx] = label;
+            else labels[idx] = all_labels[g % total_cap];
         }
     }
     if (idx < LEGION_COUNTER_WORDS) { // cudaMemsetAsync(counters) + update_counter(op 0), Kernels.cu:220-221,118-127
@@ -186,6 +235,20 @@ __global__ __launch_bounds__(kBlock) void k_shuffle_seeds(const int32_t* __restr
     const uint32_t p = seeded_perm((uint32_t)g, (uint32_t)n, ks);   // < n
     out_ids[g] = ids[p];
     out_labels[g] = labels[p];
+}
+
+// Drawn link-prediction thirds: the round's copy of a [src | pos | neg] list of batches of 3 k, one thread per list index.  Triple t =
+// b k + i (batch b, slot i) takes the place of triple perm(t) on [0, n / 3): a triple moves as a whole, each third to its own third.
+__global__ __launch_bounds__(kBlock) void k_shuffle_triples(const int32_t* __restrict__ ids, const int32_t* __restrict__ labels, int32_t n, int32_t k, uint32_t ks,
+                                                            int32_t* __restrict__ out_ids, int32_t* __restrict__ out_labels)
+{
+    const int32_t g = threadIdx.x + blockDim.x * blockIdx.x;
+    if (g >= n) return;
+    const int32_t b = g / (3 * k), r = g - b * 3 * k, q = r / k, i = r - q * k;
+    const uint32_t t = seeded_perm((uint32_t)(b * k + i), (uint32_t)(n / 3), ks);   // < n / 3
+    const int32_t from = (int32_t)(t / (uint32_t)k) * 3 * k + q * k + (int32_t)(t % (uint32_t)k);   // < n
+    out_ids[g] = ids[from];
+    out_labels[g] = labels[from];
 }
 
 // S7: ClearPosMap (Kernels.cu:750-756) has no kernel here: position-table entries carry the batch epoch
@@ -1265,6 +1328,16 @@ __global__ void k_perm_probe(uint32_t ks, int32_t n, int32_t* out)
     if (g < n) out[g] = (int32_t)seeded_perm((uint32_t)g, (uint32_t)n, ks);
 }
 
+// drawn link-prediction thirds: position of the positive in a row of degree deg[i] (-1: deg <= 0, the source itself) and the negative of
+// slot i with source src[i], by the device functions k_seed<.., LP> runs
+__global__ void k_lp_draw_probe(uint32_t w, const int32_t* src, const int32_t* deg, int32_t V, int32_t* rho, int32_t* neg, int32_t n)
+{
+    const int32_t i = threadIdx.x + blockDim.x * blockIdx.x;
+    if (i >= n) return;
+    rho[i] = deg[i] > 0 ? lp_rho(w, (uint32_t)i, src[i], deg[i]) : -1;
+    neg[i] = lp_neg(w, (uint32_t)i, src[i], V);
+}
+
 // ------------------------------------------------------------------------------------------------
 // cache construction kernels (one-off; S8 / S9)
 // ------------------------------------------------------------------------------------------------
@@ -1459,13 +1532,16 @@ static uint32_t* pow_table()
 void launch_seed(hipStream_t s, int32_t* batch_ids, int32_t* labels, int32_t batch_size, int32_t size, int32_t counter,
                  const int32_t* all_ids, const int32_t* all_labels, int32_t total_cap, pos_t* pos_map,
                  uint32_t epoch, BatchCtl* ctl, bool self_driven, int32_t* nc, int32_t* ec, int32_t* aux_next,
-                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key)
+                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key, const LpDrawArgs* lp)
 {
     const int32_t bound = self_driven ? batch_size : size;
     int blocks = bound > 0 ? (bound - 1) / kBlock + 1 : 1;
     LEGION_AUDIT_LAUNCH(s, "k_seed", LEGION_AW(batch_ids), LEGION_AW(labels), LEGION_AW(pos_map), LEGION_AW(ctl), LEGION_AW(nc), LEGION_AW(ec), LEGION_AW(aux_next), LEGION_AL(all_ids), LEGION_AL(all_labels));
-    if (self_driven) k_seed<true><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key);
-    else k_seed<false><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key);
+    const LpDrawArgs a = lp ? *lp : LpDrawArgs{};
+    if (lp && self_driven) k_seed<true, true><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key, a);
+    else if (lp) k_seed<false, true><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key, a);
+    else if (self_driven) k_seed<true, false><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key, a);
+    else k_seed<false, false><<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key, a);
     HIP_CHECK_LAST();
 }
 void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded, uint32_t draw_key)
@@ -1479,6 +1555,13 @@ void launch_shuffle_seeds(hipStream_t s, const int32_t* ids, const int32_t* labe
     if (n <= 0) return;
     LEGION_AUDIT_LAUNCH(s, "k_shuffle_seeds", LEGION_AW(out_ids), LEGION_AW(out_labels), LEGION_AL(ids), LEGION_AL(labels));
     k_shuffle_seeds<<<(n + kBlock - 1) / kBlock, kBlock, 0, s>>>(ids, labels, n, ks, out_ids, out_labels);
+    HIP_CHECK_LAST();
+}
+void launch_shuffle_triples(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, int32_t k, uint32_t ks, int32_t* out_ids, int32_t* out_labels)
+{
+    if (n <= 0 || k <= 0 || n % (3 * k) != 0) return;   // the callers refuse such a list by name
+    LEGION_AUDIT_LAUNCH(s, "k_shuffle_triples", LEGION_AW(out_ids), LEGION_AW(out_labels), LEGION_AL(ids), LEGION_AL(labels));
+    k_shuffle_triples<<<(n + kBlock - 1) / kBlock, kBlock, 0, s>>>(ids, labels, n, k, ks, out_ids, out_labels);
     HIP_CHECK_LAST();
 }
 void launch_advance(hipStream_t s, BatchCtl* ctl)
@@ -1733,6 +1816,14 @@ void launch_seeded_rng_probe(hipStream_t s, uint32_t w, const int32_t* idx, cons
     if (n <= 0) return;
     LEGION_AUDIT_LAUNCH(s, "k_seeded_rng_probe", LEGION_AW(k), LEGION_AL(idx), LEGION_AL(deg));
     k_seeded_rng_probe<<<(n + 255) / 256, 256, 0, s>>>(w, idx, deg, k, n);
+    HIP_CHECK_LAST();
+}
+void launch_lp_draw_probe(hipStream_t s, uint32_t w, const int32_t* src, const int32_t* deg, int32_t V, int32_t* rho, int32_t* neg, int32_t n)
+{
+    if (n <= 0) return;
+    if (V < 1) { LEGION_ARG_ERROR("legion_lp_draw_probe: V must be at least 1"); return; }
+    LEGION_AUDIT_LAUNCH(s, "k_lp_draw_probe", LEGION_AW(rho), LEGION_AW(neg), LEGION_AL(src), LEGION_AL(deg));
+    k_lp_draw_probe<<<(n + 255) / 256, 256, 0, s>>>(w, src, deg, V, rho, neg, n);
     HIP_CHECK_LAST();
 }
 void launch_perm_probe(hipStream_t s, uint32_t ks, int32_t n, int32_t* out)

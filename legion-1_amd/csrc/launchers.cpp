@@ -3,6 +3,7 @@
 // (src/Operator.h:4-27, Operator.cu:10-124).
 #include "internal.h"
 
+#include <algorithm>
 #include <cstring>
 #include <iostream>
 
@@ -30,13 +31,40 @@ static bool pool_ready(const GPUMemoryPool* p, const char* who)
     return true;
 }
 
+// Where logical GPU `dev` reads adjacency rows from: the whole CSR -- its HBM replica when there is one, else the (pinned host) table --
+// and, with `fragments` (every launch but those of pre-sampling: a pre-sampling hop, a seed launch while the cache is still pre-sampling),
+// the clique's fragments through the topology map, once the cache holds one and every fragment that map can name is readable from here.  The one statement of the rule: the sampler's hops and the positives of
+// the drawn link-prediction thirds read a row from the same place.
+static void csr_tables_of(CsrTables& csr, const GPUGraphStorage* graph, const GPUCache* cache, int dev, bool fragments)
+{
+    const int P = graph->partition_count;
+    csr.partition_count = P;
+    csr.indptr = graph->replica_indptr[dev] ? graph->replica_indptr[dev] : graph->csr_node_index_cpu;
+    csr.indices = graph->replica_indices[dev] ? graph->replica_indices[dev] : graph->csr_dst_node_ids_cpu;
+    csr.frag_indptr = nullptr; csr.frag_indices = nullptr;
+    csr.ip_nch = csr.ix_nch = 1; csr.row_shift = graph->row_shift; csr.edge_shift = graph->edge_shift;
+    csr.topo_owner = nullptr;
+    csr.topo_row = nullptr;
+    if (!fragments || !cache || dev >= cache->device_count || !cache->ctl[dev]->topo_owner || cache->ctl[dev]->edge_capacity <= 0) return;
+    // every fragment the topology map of this GPU can name must be readable from here
+    bool all = graph->d_frag_tab[dev] != nullptr;
+    const int Kg = cache->Kg, K0 = (dev / Kg) * Kg;
+    for (int g = K0; g < K0 + Kg && all; g++) all = graph->view[dev][g] && graph->frag[g].complete;
+    if (all) {
+        csr.frag_indptr = (const int64_t* const*)graph->d_frag_tab[dev];
+        csr.frag_indices = (const int32_t* const*)(graph->d_frag_tab[dev] + (size_t)P * graph->ip_nch);
+        csr.ip_nch = graph->ip_nch; csr.ix_nch = graph->ix_nch;
+        csr.topo_owner = cache->ctl[dev]->topo_owner; csr.topo_row = cache->ctl[dev]->topo_row;
+    }
+}
+
 extern "C" {
 
 // batch_generator_kernel, Kernels.cu:162-232
 void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cache, GPUMemoryPool* memorypool,
                             int32_t batch_size, int32_t counter, int32_t part_id, int32_t dev_id, int32_t mode)
 {
-    (void)cache; (void)part_id;
+    (void)part_id;   // cache: only the drawn link-prediction thirds look at it (the topology map of the positives' rows)
     if (!noder || !pool_ready(memorypool, "batch_generator_kernel")) return;
     hipStream_t s = (hipStream_t)strm_hdl;
     if (mode < 0 || mode >= kModes) log_out() << "invalid mode: " << mode << "\n";
@@ -61,6 +89,21 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         all_labels = p->shuf_labels;
         p->seed_reads_shuffle = true;
     }
+    // Drawn link-prediction thirds: a training batch is 3 k slots, the last two thirds drawn inside k_seed from the batch's draw word
+    LpDrawArgs lp_args;
+    const LpDrawArgs* lp = nullptr;
+    if (p->modes.lp_draw > 0 && mode == LEGION_TRAINMODE) {
+        const int32_t k = p->modes.lp_draw;
+        const GPUGraphStorage* graph = p->lp_graph;
+        if (!p->modes.seeded) { LEGION_ARG_ERROR("batch_generator_kernel: drawn link-prediction thirds (GPUMemoryPool_SetLpDraw) draw from the batch's draw word: seed the pool first (GPUMemoryPool_SetSampleSeed)"); return; }
+        if (batch_size != 3 * k) { LEGION_ARG_ERROR("batch_generator_kernel: drawn link-prediction thirds (GPUMemoryPool_SetLpDraw): the batch size must be three times the pool's triples per batch"); return; }
+        if (total_cap % (3 * k) != 0) { LEGION_ARG_ERROR("batch_generator_kernel: drawn link-prediction thirds (GPUMemoryPool_SetLpDraw): the training list's length is not a multiple of the batch of 3 k ([src | pos | neg] thirds, padded)"); return; }
+        if (!graph || dev_id < 0 || dev_id >= graph->partition_count) { LEGION_ARG_ERROR("batch_generator_kernel: drawn link-prediction thirds (GPUMemoryPool_SetLpDraw): device outside the partition table of the pool's graph"); return; }
+        lp_args.k = k;
+        lp_args.V = std::min(p->V, graph->node_num);
+        csr_tables_of(lp_args.csr, graph, cache, dev_id, cache && !cache->is_presc);   // pre-sampling batches: the whole CSR, like their hops
+        lp = &lp_args;
+    }
     const int q = p->current_pipe;
     if (p->device_id != dev_id && audit::on()) {   // the pool starts serving this GPU: its scratch and its output buffers must live there
         LEGION_AUDIT_OWNER(p->pos_map, dev_id, "batch_generator_kernel: scratch of the memory pool");
@@ -82,7 +125,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         // device, `counter` is ignored, bounds are those of a full batch.
         if (batch_size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
         launch_seed(s, p->sampled_ids[q], p->labels[q], batch_size, batch_size, 0, all_ids, all_labels, total_cap, p->pos_map, 0,
-                    p->ctl, true, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key);
+                    p->ctl, true, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key, lp);
         p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0];
         p->bound_n = batch_size > 0 ? batch_size : 0;
         p->bound_nodes = p->bound_n;
@@ -100,7 +143,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     int32_t size = ((batch_size * (counter + 1)) >= total_cap) ? (total_cap - batch_size * counter) : batch_size;
     if (size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
     launch_seed(s, p->sampled_ids[q], p->labels[q], batch_size, size, counter, all_ids, all_labels, total_cap, p->pos_map, epoch,
-                p->ctl, false, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key);
+                p->ctl, false, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key, lp);
     p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0]; // k_seed prepared the slot states of hop 1
     p->bound_n = size > 0 ? size : 0;
     p->bound_nodes = p->bound_n;
@@ -123,14 +166,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     if (slots <= 0) return;
 
     CsrTables csr;
-    csr.partition_count = P;
-    // the whole CSR -- this GPU's HBM replica when there is one, else the (pinned host) table
-    csr.indptr = graph->replica_indptr[dev] ? graph->replica_indptr[dev] : graph->csr_node_index_cpu;
-    csr.indices = graph->replica_indices[dev] ? graph->replica_indices[dev] : graph->csr_dst_node_ids_cpu;
-    csr.frag_indptr = nullptr; csr.frag_indices = nullptr;
-    csr.ip_nch = csr.ix_nch = 1; csr.row_shift = graph->row_shift; csr.edge_shift = graph->edge_shift;
-    csr.topo_owner = nullptr;
-    csr.topo_row = nullptr;
+    csr_tables_of(csr, graph, cache, dev, !is_presc);   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
     SamplerBuffers b;
     const int q = p->current_pipe;
     b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];
@@ -146,17 +182,6 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
         // kernel_pre_sampler_optimized: host CSR only + topology hotness (Kernels.cu:636-649)
         if (!cache || dev >= cache->device_count || !cache->ctl[dev]->edge_access_time) { LEGION_ARG_ERROR("GPU_Random_Sampling: pre-sampling needs an initialised cache controller"); return; }
         b.edge_access_time = cache->ctl[dev]->edge_access_time;
-    } else if (cache && dev < cache->device_count && cache->ctl[dev]->topo_owner && cache->ctl[dev]->edge_capacity > 0) {
-        // every fragment the topology map of this GPU can name must be readable from here
-        bool all = graph->d_frag_tab[dev] != nullptr;
-        const int Kg = cache->Kg, K0 = (dev / Kg) * Kg;
-        for (int g = K0; g < K0 + Kg && all; g++) all = graph->view[dev][g] && graph->frag[g].complete;
-        if (all) {
-            csr.frag_indptr = (const int64_t* const*)graph->d_frag_tab[dev];
-            csr.frag_indices = (const int32_t* const*)(graph->d_frag_tab[dev] + (size_t)P * graph->ip_nch);
-            csr.ip_nch = graph->ip_nch; csr.ix_nch = graph->ix_nch;
-            csr.topo_owner = cache->ctl[dev]->topo_owner; csr.topo_row = cache->ctl[dev]->topo_row;
-        }
     }
     b.aux_cap = p->max_slots;
     b.ids_cap = p->num_ids;

@@ -54,7 +54,8 @@ struct Runner {
     // behind the last hop instead of the last level's gather; the feature buffers then hold n_in + N rows per batch, not n.
     ServeModes modes;
     // Seeded sampling.  round: the one the pool was last told (GPUMemoryPool_BeginRound), -1 = none yet.  lists_verbatim: the training
-    // lists are served as they are (meta flag 2, link-prediction thirds): never shuffled, draws still seeded.
+    // lists are served as they are (meta flag 2, link-prediction thirds): never shuffled, draws still seeded -- unless modes.lp_draw has
+    // their triples shuffled and the pos / neg thirds drawn per batch.
     int32_t round = -1;
     bool lists_verbatim = false;
     int32_t presc_max_rows = 0;     // largest n_in + N of the pre-sampling epoch (read back per batch: that epoch is not pipelined anyway)
@@ -86,6 +87,7 @@ static bool parse_seed(const char* n, uint32_t& seed)
 
 // LEGION_AGG_LAST_HOP: atoi, so anything non-numeric is off.  LEGION_AGG_NORM: unset / empty = plain sums, "both" only on a server that aggregates
 // the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, or "distinct".  LEGION_SAMPLING_SEED: unset / empty = off.
+// LEGION_LP_DRAW: unset / empty / "0" = off, "1" only under a seed (k is resolved against the meta line: serve_modes_resolve_lp_draw).
 bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
 {
     m = ServeModes();
@@ -107,6 +109,21 @@ bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
         if (!parse_seed(seed, m.seed)) { why = std::string("LEGION_SAMPLING_SEED=") + seed + " is not a sampling seed: a decimal or 0x hex integer in [0, 2^32), or unset (the same batches every epoch)"; return false; }
         m.seeded = true;
     }
+    const char* lp = getenv("LEGION_LP_DRAW");
+    if (lp && lp[0] && strcmp(lp, "0") != 0) {
+        if (strcmp(lp, "1") != 0) { why = std::string("LEGION_LP_DRAW=") + lp + " is not a known setting: `1` (the pos and neg thirds of link-prediction batches are drawn per batch), `0` or unset"; return false; }
+        if (!m.seeded) { why = "LEGION_LP_DRAW=1 needs LEGION_SAMPLING_SEED: the thirds are drawn from the batch's draw word"; return false; }
+        m.lp_draw = 1;
+    }
+    return true;
+}
+
+bool legion::serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why)
+{
+    if (!m.lp_draw) return true;
+    if (!lp_lists) { why = "LEGION_LP_DRAW=1 needs link-prediction training lists (meta flag 2: [src | pos | neg] thirds per batch)"; return false; }
+    if (raw_batch_size < 3 || raw_batch_size % 3 != 0) { why = "LEGION_LP_DRAW=1 needs a batch size divisible by 3 ([src | pos | neg] thirds), the meta line has " + std::to_string(raw_batch_size); return false; }
+    m.lp_draw = raw_batch_size / 3;
     return true;
 }
 
@@ -127,9 +144,12 @@ bool legion::serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, 
 static void begin_round(Runner* r, GPUNodeStorage* noder, int32_t round)
 {
     if (!r->modes.seeded || r->round == round) return;
-    if (r->lists_verbatim && r->round < 0)
+    const bool file_order = r->lists_verbatim && !r->modes.lp_draw;
+    if (r->modes.lp_draw && r->round < 0)
+        log_out() << r->local_dev_id << " Drawn link-prediction thirds: " << r->modes.lp_draw << " triples per batch (LEGION_LP_DRAW=1): the triples reshuffled per epoch, pos and neg drawn per batch\n";
+    else if (file_order && r->round < 0)
         log_out() << r->local_dev_id << " Seeded sampling: the training lists are served verbatim (meta flag 2): not shuffled, the draws are seeded\n";
-    GPUMemoryPool_BeginRound(r->streams[0], r->memorypool, r->lists_verbatim ? nullptr : noder, r->local_dev_id, round);
+    GPUMemoryPool_BeginRound(r->streams[0], r->memorypool, file_order ? nullptr : noder, r->local_dev_id, round);
     r->round = round;
 }
 
@@ -297,10 +317,11 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     std::string why;
     if (!serve_modes_from_env(r->modes, why)) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
     r->local_dev_id = params->device_id;
+    IPCEnv* env = (IPCEnv*)params->env;
+    if (!serve_modes_resolve_lp_draw(r->modes, r->lists_verbatim, r->modes.lp_draw && env ? IPCEnv_GetRawBatchsize(env) : 0, why)) { LEGION_ARG_ERROR(("Runner_Initialize: " + why).c_str()); return; }
     DeviceGuard guard(r->local_dev_id);
     GPUCache* cache = (GPUCache*)params->cache;
     GPUNodeStorage* noder = (GPUNodeStorage*)params->noder;
-    IPCEnv* env = (IPCEnv*)params->env;
     HIP_CHECK(hipStreamCreateWithFlags(&r->streams[0], hipStreamNonBlocking));
     HIP_CHECK(hipStreamCreateWithFlags(&r->streams[1], hipStreamNonBlocking));
     // the pool serves train, validation and test batches: size it for the largest of the three (the per-GPU
@@ -332,6 +353,7 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     GPUMemoryPool_AllocateScratch(r->memorypool, total_num_nodes, batch_size, params->fanout, hop_num);
     // before the pre-sampling epoch (the hotness profile sees what will be served): the pool's modes, their buffers on this runner's GPU; what a trainer reads
     const ServeModes& m = r->modes;
+    r->memorypool->lp_graph = m.lp_draw ? (GPUGraphStorage*)params->graph : nullptr;   // the positives' rows (GPUMemoryPool_SetLpDraw keeps it the same way)
     pool_apply_modes(r->memorypool, m, "Runner_Initialize");
     ipc_env_publish_modes(env, m);
     if (m.agg_last_hop) log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
@@ -953,7 +975,8 @@ void Server_Initialize(Server* s, int global_shard_count)
     if (!refused.empty()) { LEGION_ARG_ERROR(refused.c_str()); return; }
     ServeModes modes;   // checked before any device is touched; every runner parses them for itself
     std::string why;
-    if (!serve_modes_from_env(modes, why) || !serve_modes_fit_fanout(modes, s->fanout.data(), (int32_t)s->fanout.size(), why)) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
+    if (!serve_modes_from_env(modes, why) || !serve_modes_fit_fanout(modes, s->fanout.data(), (int32_t)s->fanout.size(), why) ||
+        !serve_modes_resolve_lp_draw(modes, s->meta.partition == 2, s->meta.raw_batch_size, why)) { LEGION_ARG_ERROR(("Server_Initialize: " + why).c_str()); return; }
     const Meta& m = s->meta;
     // from the first device call on the main thread works on GPU 0 unless a scope below says otherwise (the reference's main thread never
     // leaves device 0); not before the meta line and the synth: source are validated -- a refused configuration touches no device

@@ -247,6 +247,11 @@ void legion_seeded_distinct_probe(void* stream, uint32_t seed, int32_t round, in
 {
     launch_seeded_distinct_probe((hipStream_t)stream, seeded_draw_word(1u, seeded_draw_key(seed, (uint32_t)round), iter), row, hop, deg, f, pos_out, n);
 }
+void legion_lp_draw_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* src, const int32_t* deg, int32_t V, int32_t* rho_out,
+                          int32_t* neg_out, int32_t n)
+{
+    launch_lp_draw_probe((hipStream_t)stream, seeded_draw_word(1u, seeded_draw_key(seed, (uint32_t)round), iter), src, deg, V, rho_out, neg_out, n);
+}
 void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, int32_t* perm_out)
 {
     launch_perm_probe((hipStream_t)stream, seeded_shuffle_key(seed, (uint32_t)round), n, perm_out);

@@ -471,7 +471,10 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
     if (p->capturing) { LEGION_ARG_ERROR((name + ": the pool is being captured").c_str()); return false; }
     if (wanted.agg_norm != 0 && wanted.agg_norm != 1) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: unknown norm (0 = none, 1 = out-degree rsqrt)"); return false; }
     if (wanted.agg_norm && !wanted.agg_last_hop && wanted.agg_norm != p->modes.agg_norm) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return false; }
+    if (wanted.lp_draw < 0) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: negative triples per batch (0 = off, k > 0 = batches of 3 k)"); return false; }
+    if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
+    if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k
     if (wanted.seeded != p->modes.seeded || wanted.seed != p->modes.seed) p->ctl_synced = false;   // ctl holds the other state's draw word: a batch graph must reset the cursor
     p->modes = wanted;
     alloc_mode_buffers(p);
@@ -530,10 +533,12 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
 }
 int32_t GPUMemoryPool_NumIds(const GPUMemoryPool* p) { return p->num_ids; }
 
-// The four mode setters: the pool's modes with one field changed, through pool_apply_modes (internal.h: what is refused, what is
+// The five mode setters: the pool's modes with one field changed, through pool_apply_modes (internal.h: what is refused, what is
 // allocated).  Call them under the device the pool's scratch lives on.  Aggregated last hop: INTEGRATION.md "Aggregated last hop";
 // norm: 0 = plain sums, 1 = out-degree rsqrt ("Normalised sums"); distinct draws: "Sampling without replacement", nothing is allocated;
-// seed: "Seeded sampling", seed 0 is a seed like any other, nothing is allocated here (GPUMemoryPool_BeginRound fills the shuffled copy).
+// seed: "Seeded sampling", seed 0 is a seed like any other, nothing is allocated here (GPUMemoryPool_BeginRound fills the shuffled copy);
+// drawn link-prediction thirds: "Drawn link-prediction thirds", k triples per batch (0 = off) and the graph the positives are read from,
+// which the pool keeps (and forgets when the mode is switched off); nothing is allocated.
 static ServeModes modes_of(const GPUMemoryPool* p) { return p ? p->modes : ServeModes(); }
 void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.agg_last_hop = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetAggLastHop"); }
 void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm) { ServeModes m = modes_of(p); m.agg_norm = norm; pool_apply_modes(p, m, "GPUMemoryPool_SetAggNorm"); }
@@ -544,6 +549,15 @@ void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
     m.seeded = on != 0; m.seed = seed;
     if (pool_apply_modes(p, m, "GPUMemoryPool_SetSampleSeed")) p->ctl_synced = false;   // this call always has the next graph replay reset its cursor
 }
+void GPUMemoryPool_SetLpDraw(GPUMemoryPool* p, int32_t triples_per_batch, GPUGraphStorage* graph)
+{
+    ServeModes m = modes_of(p);
+    m.lp_draw = triples_per_batch;
+    GPUGraphStorage* const before = p ? p->lp_graph : nullptr;
+    if (p && !p->capturing) p->lp_graph = triples_per_batch > 0 ? graph : nullptr;
+    if (!pool_apply_modes(p, m, "GPUMemoryPool_SetLpDraw") && p && !p->capturing) p->lp_graph = before;
+}
+int32_t GPUMemoryPool_GetLpDraw(const GPUMemoryPool* p) { return p ? p->modes.lp_draw : 0; }
 int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->modes.agg_last_hop ? 1 : 0; }
 int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->modes.agg_norm : 0; }
 int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->modes.sampling ? 1 : 0; }
@@ -579,6 +593,8 @@ int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* nod
     if (!p->owns_scratch) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: GPUMemoryPool_AllocateScratch was not called"); return -1; }
     const GPUNodeStorage::SeedSet& set = noder->seed_set(LEGION_TRAINMODE, dev_id);
     if (set.num > 0 && (!set.ids || !set.labels)) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: the training list of this device is not built"); return -1; }
+    const int32_t k = p->modes.lp_draw;   // drawn link-prediction thirds: whole triples move
+    if (k > 0 && set.num % (3 * k) != 0) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: drawn link-prediction thirds (GPUMemoryPool_SetLpDraw): the training list's length is not a multiple of the batch of 3 k ([src | pos | neg] thirds, padded)"); return -1; }
     if (set.num > p->shuf_cap || !p->shuf_ids) {   // first use, or a longer list: batches that read the old copy may still be in flight
         HIP_CHECK(hipDeviceSynchronize());
         if (p->shuf_ids) (void)hipFree(p->shuf_ids);
@@ -589,7 +605,8 @@ int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* nod
         HIP_CHECK(hipMalloc(&p->shuf_labels, (size_t)p->shuf_cap * sizeof(int32_t)));
         if (!p->shuf_ids || !p->shuf_labels) return -1;
     }
-    launch_shuffle_seeds((hipStream_t)stream, set.ids, set.labels, set.num, seeded_shuffle_key(p->modes.seed, p->round), p->shuf_ids, p->shuf_labels);
+    if (k > 0) launch_shuffle_triples((hipStream_t)stream, set.ids, set.labels, set.num, k, seeded_shuffle_key(p->modes.seed, p->round), p->shuf_ids, p->shuf_labels);
+    else launch_shuffle_seeds((hipStream_t)stream, set.ids, set.labels, set.num, seeded_shuffle_key(p->modes.seed, p->round), p->shuf_ids, p->shuf_labels);
     p->shuf_n = set.num;
     p->shuf_src = set.ids;
     p->shuf_valid = true;

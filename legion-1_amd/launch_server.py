@@ -57,6 +57,8 @@ def main(argv=None):
                     "min(degree, fan-out) distinct neighbours per row")
     ap.add_argument("--sampling_seed", type=int, default=None, help="extension: a 32-bit seed (LEGION_SAMPLING_SEED for the server): every batch "
                     "draws afresh and the training list is reshuffled every epoch; without it every epoch is the same epoch, like the reference's")
+    ap.add_argument("--lp_draw", action="store_true", help="extension (LEGION_LP_DRAW=1 for the server; needs --seed_lists and --sampling_seed): "
+                    "the [src | pos | neg] triples are reshuffled every epoch and every batch draws its pos and neg thirds afresh")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
@@ -72,6 +74,8 @@ def main(argv=None):
         env["LEGION_SAMPLING"] = args.sampling
     if args.sampling_seed is not None:
         env["LEGION_SAMPLING_SEED"] = str(args.sampling_seed)
+    if args.lp_draw:
+        env["LEGION_LP_DRAW"] = "1"
     return subprocess.call(cmd, env=env)
 
 
