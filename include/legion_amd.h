@@ -400,6 +400,25 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
  * mode and a switch while the pool is being captured are sticky argument errors.  Nothing is allocated. */
 void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p);
+/* Weighted sampling (extension; INTEGRATION.md "Weighted sampling").  The sampling kind of a pool is an enumeration: 0 = replace (the
+ * reference's stream), 1 = distinct (what GPUMemoryPool_SetSampleDistinct(pool, 1) sets; GetSampleDistinct is `kind == 1`), 2 = weighted:
+ * every GPU_Random_Sampling of the pool, pre-sampling hops included, draws with replacement in proportion to the graph's edge weights,
+ * by Walker's alias method over the table GPUGraphStorage_SetEdgeWeights built: slot j of row i of hop h draws column (uc * d) >> 32 and
+ * keeps its neighbour when ub < the column's threshold, else takes the column's alias id (uc, ub: two hashes of (i, h, j) and the batch's
+ * draw word).  The whole CSR is read, never the fragments.  Everything behind the neighbour id is the default mode's.  An unknown kind,
+ * a switch while the pool is being captured, and a weighted hop over a graph without a table are sticky argument errors.
+ *
+ * GPUGraphStorage_SetEdgeWeights (after GPUGraphStorage_Build): w = float32[E], one weight per CSR entry in indices order, finite and
+ * >= 0, at `location` (LEGION_LOC_*).  A kernel counts the weights that are negative, NaN or infinite: any, and the call is refused with
+ * their number and the earlier table stays.  Else the alias table -- E entries {uint32 thr, int32 alias_id}, 8 E bytes of device memory per
+ * physical device -- is built on the device (deterministic: the same weights give the same bytes) and replaces the earlier one; the
+ * weights themselves are not kept.  w == NULL drops the table.  Returns 0, or -1 with a sticky error.  CopyAliasRows copies entries
+ * [e0, e0 + n) of logical GPU dev_id's table to the host (tests, tools). */
+void GPUMemoryPool_SetSampling(GPUMemoryPool* p, int kind);
+int GPUMemoryPool_GetSampling(const GPUMemoryPool* p);
+int GPUGraphStorage_SetEdgeWeights(GPUGraphStorage* g, const float* w, int32_t location);
+int GPUGraphStorage_HasEdgeWeights(const GPUGraphStorage* g);
+int GPUGraphStorage_CopyAliasRows(const GPUGraphStorage* g, int32_t dev_id, int64_t e0, int64_t n, uint32_t* thr, int32_t* alias_id);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
  * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
  * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list
@@ -515,8 +534,9 @@ int32_t IPCEnv_GetAggLastHop(const IPCEnv* e);
 void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm);
 int32_t IPCEnv_GetAggNorm(const IPCEnv* e);
 /* ... and, in a word appended behind that one, how the server's sampler draws: 0 = with replacement (the reference's stream), 1 = distinct
- * neighbours (GPUMemoryPool_SetSampleDistinct; the runner sets it under LEGION_SAMPLING=distinct).  A client of a server without the
- * word reads 0. */
+ * neighbours (GPUMemoryPool_SetSampleDistinct; the runner sets it under LEGION_SAMPLING=distinct), 2 = with replacement by edge weight
+ * (GPUMemoryPool_SetSampling(pool, 2); LEGION_SAMPLING=weighted).  IPCEnv_SetSampling stores 2 as 2 and any other non-zero value as 1.
+ * A client of a server without the word reads 0. */
 void IPCEnv_SetSampling(IPCEnv* e, int32_t mode);
 int32_t IPCEnv_GetSampling(const IPCEnv* e);
 /* ... and, in two words appended behind that one, seeded sampling (GPUMemoryPool_SetSampleSeed; the runner sets them under
@@ -564,6 +584,8 @@ int32_t legion_ipc_client_hops(LegionIPCClient* c);
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c);
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c);
+/* the server's sampling kind: 0 = replace, 1 = distinct, 2 = weighted.  (A trainer built before the weighted mode existed knows 0 and
+ * non-zero only and reports a weighted server as "distinct".) */
 int32_t legion_ipc_client_sampling(LegionIPCClient* c);
 int32_t legion_ipc_client_sampling_seed(LegionIPCClient* c, uint32_t* seed);
 /* both counter arrays of the current pipe (legion_batch_layout.h draws them word by word) (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
@@ -624,6 +646,9 @@ void legion_synth_features(void* stream, float* out, int64_t v0, int64_t nrows, 
 /* the same values with `pitch` floats between two rows (LegionBuildInfo.float_attr_pitch); pad floats are not written */
 void legion_synth_features_pitched(void* stream, float* out, int64_t v0, int64_t nrows, int32_t F, int32_t pitch);
 void legion_synth_labels(void* stream, int32_t* out, int32_t v0, int32_t n, int32_t classes);
+/* edge weights of CSR entries [e0, e0 + n) for the weighted sampler mode: a closed form of the entry's position -- 0 for about one entry
+ * in eight (whole blocks of 64 entries among them: rows without any weight occur), else an integer in 1..16 (exact in float32); synth.py edge_weights() is the NumPy statement */
+void legion_synth_edge_weights(void* stream, float* out, int64_t e0, int64_t n);
 void legion_synth_seed_ids(void* stream, int32_t* out, int64_t i0, int64_t n, int32_t V, uint32_t M2, uint32_t C2, int32_t stride, int32_t phase);
 /* The generator's parameters for a named shape ("products" | "papers100M" | "uk-union", legion_server.py:6-37), shrunk by
  * `scale` in (0, 1] (V and the seed sets; the mean degree stays): the C statement of synth.py spec_for(), field for field
@@ -668,6 +693,11 @@ void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, in
  * the negative on [0, V), V >= 1.  All pointers are device memory. */
 void legion_lp_draw_probe(void* stream, uint32_t seed, int32_t round, int32_t iter, const int32_t* src, const int32_t* deg, int32_t V, int32_t* rho_out,
                           int32_t* neg_out, int32_t n);
+/* Weighted-mode probe, by k_sample's own device functions: for slot slot[m] of row row[m] of hop hop[m] at degree deg[m] under the draw
+ * word word[m] (0 = unseeded), k_out[m] = the column drawn (< deg[m]; -1 for deg <= 0) and ub_out[m] = the word held against the
+ * column's threshold.  All pointers are device memory. */
+void legion_weighted_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
+                           int32_t* k_out, uint32_t* ub_out, int32_t n);
 uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter);
 uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round);
 /* compute units of the current device as the sampler's persistent grids count them: a hop of more than 4 x this x 1024 slots makes a

@@ -205,6 +205,11 @@ _SIGS = {
     "GPUMemoryPool_GetAggOutDeg": (vp, [vp]),
     "GPUMemoryPool_SetSampleDistinct": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetSampleDistinct": (C.c_int, [vp]),
+    "GPUMemoryPool_SetSampling": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetSampling": (C.c_int, [vp]),
+    "GPUGraphStorage_SetEdgeWeights": (C.c_int, [vp, vp, i32]),
+    "GPUGraphStorage_HasEdgeWeights": (C.c_int, [vp]),
+    "GPUGraphStorage_CopyAliasRows": (C.c_int, [vp, i32, i64, i64, vp, vp]),
     "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
     "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
     "GPUMemoryPool_BeginRound": (C.c_int, [vp, vp, vp, i32, i32]),
@@ -271,6 +276,7 @@ _SIGS = {
     "legion_synth_features": (None, [vp, vp, i64, i64, i32]),
     "legion_synth_features_pitched": (None, [vp, vp, i64, i64, i32, i32]),
     "legion_synth_labels": (None, [vp, vp, i32, i32, i32]),
+    "legion_synth_edge_weights": (None, [vp, vp, i64, i64]),
     "legion_synth_seed_ids": (None, [vp, vp, i64, i64, i32, u32, u32, i32, i32]),
     "legion_synth_spec": (C.c_int, [C.c_char_p, f64, vp]),
     "legion_synth_label_host": (i32, [i32, i32]),
@@ -284,6 +290,7 @@ _SIGS = {
     "legion_seeded_rng_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32]),
     "legion_seeded_distinct_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32, vp, i32]),
     "legion_perm_probe": (None, [vp, u32, i32, i32, vp]),
+    "legion_weighted_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
     "legion_lp_draw_probe": (None, [vp, u32, i32, i32, vp, vp, i32, vp, vp, i32]),
     "legion_seeded_draw_word": (u32, [u32, i32, i32]),
     "legion_seeded_shuffle_key": (u32, [u32, i32]),
@@ -367,12 +374,13 @@ class Engine:
     allocations (or externally supplied pointers) -- no IPC involved.
 
     ``indptr`` / ``indices`` / ``features`` may be numpy arrays (copied to the chosen location)
-    or integer device pointers (``*_location`` = LOC_DEVICE).
+    or integer device pointers (``*_location`` = LOC_DEVICE).  ``edge_weights``: float32[E], one weight per CSR entry
+    (GPUGraphStorage_SetEdgeWeights: the graph's alias table, what sample="weighted" draws from); set_edge_weights() replaces or drops it.
     """
 
     def __init__(self, indptr, indices, features, V, F, seeds, batch_size, fanout, G=1,
                  csr_location=LOC_DEVICE, features_location=LOC_DEVICE, cache_memory=0, train_step=1, epoch=1,
-                 pipeline_depth=1, E=None, local_devs=None, features_pitch=0):
+                 pipeline_depth=1, E=None, local_devs=None, features_pitch=0, edge_weights=None):
         L = lib()
         # one process per GPU: the other members of the clique are remote (legion_set_remote_device)
         self.local_devs = list(range(int(G))) if local_devs is None else list(local_devs)
@@ -446,6 +454,8 @@ class Engine:
         self.cache = L.NewGPUCache()
         L.GPUCache_Initialize(self.cache, int(cache_memory), 0, self.F, int(train_step), self.G)
         check()
+        if edge_weights is not None:
+            self.set_edge_weights(edge_weights)
         self.depth = int(pipeline_depth)
         self.pools, self.out = [None] * self.G, [None] * self.G
         for g in self.local_devs:
@@ -476,6 +486,28 @@ class Engine:
         self._norm = {}     # (dev, pipe) -> ... with normalised sums (run_batch(agg_norm="both"))
         check()
 
+    # ---- weighted sampling: the graph's alias table ------------------------------------------------------
+    def set_edge_weights(self, w):
+        """float32[E] weights in `indices` order -> the graph's alias table (replacing an earlier one); None drops it.  A refused table
+        (a negative, NaN or infinite weight) raises and leaves the earlier one in place."""
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if len(w) != self.E:
+                raise ValueError("edge_weights: one float32 per CSR entry (%d), got %d" % (self.E, len(w)))
+        self.L.GPUGraphStorage_SetEdgeWeights(self.graph, None if w is None else w.ctypes.data, LOC_HOST_PAGEABLE)
+        check()
+
+    def has_edge_weights(self):
+        return bool(self.L.GPUGraphStorage_HasEdgeWeights(self.graph))
+
+    def alias_rows(self, dev=0, e0=0, n=None):
+        """(thr uint32[n], alias_id int32[n]): entries [e0, e0 + n) of logical GPU dev's alias table."""
+        n = self.E - e0 if n is None else int(n)
+        thr, alias = np.empty(n, np.uint32), np.empty(n, np.int32)
+        self.L.GPUGraphStorage_CopyAliasRows(self.graph, dev, int(e0), n, thr.ctypes.data, alias.ctypes.data)
+        check()
+        return thr, alias
+
     # ---- feature buffers ------------------------------------------------------------------------------
     def alloc_features(self, rows=None):
         rows = self.num_ids if rows is None else int(rows)
@@ -501,7 +533,8 @@ class Engine:
         `sample`, both SET the pool's state on every call, and GPUMemoryPool_BeginRound runs when the seed, the round or the device's
         training list changed.
         sample: "replace" (the reference's draws with replacement) or "distinct" (GPUMemoryPool_SetSampleDistinct: min(degree, fan-out)
-        distinct neighbours per row, pre-sampling batches included).  Like agg_last_hop and agg_norm, the argument SETS the pool's mode on
+        distinct neighbours per row, pre-sampling batches included) or "weighted" (GPUMemoryPool_SetSampling(pool, 2): with replacement, in
+        proportion to the Engine's edge_weights; refused without them).  Like agg_last_hop and agg_norm, the argument SETS the pool's mode on
         every call: a mode switched on through GPUMemoryPool_SetSampleDistinct directly is switched back by a run_batch() without sample="distinct".
         agg_last_hop: the aggregated hand-off (get_feature_kernel_agg) -- feature rows of the levels < H (per level behind each hop,
         or all of them inside that call with per_level=False) and the last hop as neighbour sums; result() then returns
@@ -541,13 +574,15 @@ class Engine:
             raise ValueError("agg_norm: None or 'both'")
         if norm and not agg:
             raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
-        if sample not in ("replace", "distinct"):
-            raise ValueError("sample: 'replace' or 'distinct'")
+        if sample not in ("replace", "distinct", "weighted"):
+            raise ValueError("sample: 'replace', 'distinct' or 'weighted'")
+        if sample == "weighted" and not self.has_edge_weights():
+            raise ValueError("sample='weighted' needs the Engine's edge_weights (Engine(edge_weights=...) or set_edge_weights())")
         L, pool = self.L, self.pools[dev]
         L.SetGPUDevice(dev)
         agg = bool(agg) and not is_presc
         norm = int(agg and norm == "both")
-        for mode, want in (("SampleDistinct", int(sample == "distinct")), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
+        for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
             if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
                 getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
         self._set_seed(dev, seed, round, stream, lp_draw)

@@ -97,6 +97,15 @@ constexpr int64_t sampler_max_tiles(int64_t max_slots)
 }
 // Distinct-draw sampler mode: the largest fan-out k_sample<.., DISTINCT> runs (its LDS holds the picks of a tile's rows, TILE + 2 of these)
 constexpr int kDistinctMaxFanout = 64;
+// The sampling kinds of ServeModes::sampling, the `sampling` word a trainer reads and GPUMemoryPool_SetSampling
+constexpr int32_t kSamplingReplace = 0, kSamplingDistinct = 1, kSamplingWeighted = 2;
+// Weighted sampler mode: one entry per CSR entry, beside indices[e] (INTEGRATION.md "Weighted sampling").  Column k of a row is drawn with
+// probability 1 / degree; the draw keeps the column's own neighbour with probability thr / 2^32 and takes alias_id, the ID of another
+// neighbour of the row, otherwise.  Every entry of a row whose weights are all zero is {0, -1}: no edge.
+struct AliasEntry { uint32_t thr; int32_t alias_id; };
+static_assert(sizeof(AliasEntry) == 8, "one 8-byte probe per weighted draw");
+// rows of more neighbours than this are built by a whole wave (k_build_alias_hub), the others by one lane each (k_build_alias)
+constexpr int32_t kAliasHubDegree = 256;
 // k_mark runs one CONTIGUOUS chunk of tiles per workgroup and leaves the chunk totals in GPUMemoryPool::chunk_tot; k_write scans them in
 // LDS, kMaxChunks / kBlock per thread.  One constant for the allocation (storage.cpp), the grid clamp (launch_sample_hop) and the LDS
 // array (k_write): changing one of them alone would let k_mark write past the allocation.
@@ -110,7 +119,8 @@ constexpr int kMaxParts = LEGION_MAX_DEVICE;
 struct ServeModes {
     bool agg_last_hop = false;   // $LEGION_AGG_LAST_HOP=1: the last hop is handed over as neighbour sums (INTEGRATION.md "Aggregated last hop")
     int32_t agg_norm = 0;        // $LEGION_AGG_NORM=both, only with agg_last_hop: 1 = the sums weighted by out-degree^-1/2 inside block 1 ("Normalised sums")
-    int32_t sampling = 0;        // $LEGION_SAMPLING: 0 = replace (the reference's stream), 1 = distinct: min(degree, fan-out) distinct neighbours per row
+    int32_t sampling = 0;        // $LEGION_SAMPLING: 0 = replace (the reference's stream), 1 = distinct: min(degree, fan-out) distinct neighbours per row,
+                                 // 2 = weighted: with replacement, in proportion to the graph's edge weights (GPUGraphStorage_SetEdgeWeights)
     bool seeded = false;         // $LEGION_SAMPLING_SEED: every batch draws from its own word W(seed, round, counter), the training list is reshuffled
     uint32_t seed = 0;           // ... every round ("Seeded sampling").  Seed 0 is a seed like any other: `seeded` says whether there is one
     int32_t lp_draw = 0;         // $LEGION_LP_DRAW=1, only under a seed: k > 0 = a training batch is 3 k seeds whose pos and neg thirds are drawn per batch
@@ -278,7 +288,15 @@ void launch_advance(hipStream_t s, BatchCtl* ctl);
 int sampler_cu_count();       // compute units the persistent grids are sized by (current device)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, bool distinct = false);
+                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling = kSamplingReplace, const AliasEntry* alias = nullptr);
+// Weighted sampler mode, the graph's side (kernels.hip "alias table").  bad := the number of weights that are negative, NaN or infinite
+// (a device word the caller zeroed); the table of every row of the CSR from w, with p = double[E] of scratch.  Deterministic: the same
+// weights give the same bytes.
+void launch_check_weights(hipStream_t s, const float* w, int64_t E, unsigned long long* bad);
+void launch_build_alias(hipStream_t s, const int64_t* indptr, const int32_t* indices, const float* w, int32_t V, int64_t E, double* p, AliasEntry* table);
+// k[m] = the column and ub[m] the keep-or-alias word of slot slot[m] of row row[m] of hop hop[m] at degree deg[m] under draw word word[m]
+void launch_weighted_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
+                           int32_t* k, uint32_t* ub, int32_t n);
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,
                       int32_t op_id, const int32_t* feat_map, int32_t bound);
 void launch_find_topo(hipStream_t s, const int32_t* input_ids, int8_t* part_index, int32_t* part_offset,
@@ -470,6 +488,9 @@ struct GPUGraphStorage {
     // HBM replicas of the whole CSR, one per logical GPU that has one (GPUGraphStorage_ReplicateToDevices)
     std::vector<int64_t*> replica_indptr;
     std::vector<int32_t*> replica_indices;
+    // Weighted sampler mode (GPUGraphStorage_SetEdgeWeights): the alias table of the whole CSR per logical GPU, device memory, one copy per
+    // physical device like the replicas; empty / null = no weights are set
+    std::vector<legion::AliasEntry*> alias;
     int32_t csr_location = LEGION_LOC_HOST_PINNED;
     bool owns_csr = false;
     // CSR fragment of one logical GPU (device memory on that GPU's physical device).  Both arrays are chunk lists

@@ -70,7 +70,7 @@ struct shmExt {
     struct Modes {
         int32_t agg_last_hop;     // 1 = the last hop is handed over as neighbour sums: feature rows [0, n_in) are features, rows [n_in, n_in + N) the sums
         int32_t agg_norm;         // how such a server normalises the sums: 0 = plain sums, 1 = every row scaled by its out-degree^-1/2 inside block 1
-        int32_t sampling;         // how the server's sampler draws: 0 = with replacement (the reference's stream), 1 = distinct neighbours
+        int32_t sampling;         // how the server's sampler draws: 0 = with replacement (the reference's stream), 1 = distinct neighbours, 2 = by edge weight
         int32_t sampling_seeded;  // 0 = the reference's draws, the same batches every epoch; 1 = fresh draws per batch, the training list reshuffled per epoch ...
         uint32_t sampling_seed;   // ... under this seed.  Seed 0 is a seed: the flag says whether there is one
     } modes;
@@ -343,7 +343,7 @@ void legion::ipc_env_publish_modes(IPCEnv* e, const ServeModes& m)
 {
     if (!e || !e->ext) return;
     volatile shmExt::Modes& w = e->ext->modes;
-    w.agg_last_hop = m.agg_last_hop; w.agg_norm = m.agg_norm; w.sampling = m.sampling != 0; w.sampling_seed = m.seeded ? m.seed : 0u; w.sampling_seeded = m.seeded;
+    w.agg_last_hop = m.agg_last_hop; w.agg_norm = m.agg_norm; w.sampling = m.sampling; w.sampling_seed = m.seeded ? m.seed : 0u; w.sampling_seeded = m.seeded;
 }
 
 extern "C" {
@@ -539,7 +539,7 @@ void IPCEnv_SetAggLastHop(IPCEnv* e, int32_t on) { if (e && e->ext) e->ext->mode
 int32_t IPCEnv_GetAggLastHop(const IPCEnv* e) { return (e && e->ext) ? e->ext->modes.agg_last_hop : 0; }
 void IPCEnv_SetAggNorm(IPCEnv* e, int32_t norm) { if (e && e->ext) e->ext->modes.agg_norm = norm; }
 int32_t IPCEnv_GetAggNorm(const IPCEnv* e) { return (e && e->ext) ? e->ext->modes.agg_norm : 0; }
-void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->modes.sampling = mode ? 1 : 0; }
+void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->modes.sampling = mode == kSamplingWeighted ? kSamplingWeighted : mode ? kSamplingDistinct : kSamplingReplace; }
 int32_t IPCEnv_GetSampling(const IPCEnv* e) { return (e && e->ext) ? e->ext->modes.sampling : 0; }
 void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed) { if (e && e->ext) { e->ext->modes.sampling_seed = on ? seed : 0u; e->ext->modes.sampling_seeded = on ? 1 : 0; } }
 int32_t IPCEnv_GetSamplingSeed(const IPCEnv* e, uint32_t* seed)

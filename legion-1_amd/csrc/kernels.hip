@@ -88,6 +88,13 @@ __device__ inline void distinct_resolve(int32_t* p, int32_t d, int32_t f)
     }
 }
 
+// Weighted sampler mode (INTEGRATION.md "Weighted sampling"): slot j of row i of hop h under draw word w draws column (uc * d) >> 32 of its
+// row and keeps the column's own neighbour when ub < the column's threshold, else takes the column's alias; uc, ub = distinct_u(K, 2j),
+// distinct_u(K, 2j + 1) under the mode's own row key K.
+__device__ inline uint32_t weighted_key(uint32_t row, uint32_t hop, uint32_t w) { return mix32(distinct_key(row, hop, w) ^ 0xC2B2AE35u); }
+__device__ inline uint32_t weighted_column(uint32_t key, uint32_t j, int32_t d) { return __umulhi(distinct_u(key, 2u * j), (uint32_t)d); }   // < d, d > 0
+__device__ inline uint32_t weighted_ub(uint32_t key, uint32_t j) { return distinct_u(key, 2u * j + 1u); }
+
 __device__ inline int lane_id() { return threadIdx.x & 63; }
 __device__ inline int wave_id() { return threadIdx.x >> 6; }
 
@@ -277,6 +284,7 @@ struct SampleArgs {
     int32_t op_id;
     int32_t window;            // lanes to look back for a repeated draw of the same row: min(count - 1, 8)
     int32_t prefilter_from_op; // first op_id whose claims are preceded by the pre-filter load (4: hop 2; hop 1 never)
+    const AliasEntry* alias;   // WEIGHTED only: the whole CSR's alias table, entry e beside csr.indices[e] (null in the other modes)
 };
 
 // One slot's probe + claim on the position table.  Returns the slot's state: -1 = claim pending / won, >= 0 = the neighbour's known final
@@ -317,9 +325,16 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
 // The hash is pure, so the workgroup stages distinct_u of EVERY slot of the tile's rows (rows that straddle a tile edge included: both tiles
 // compute the whole row) in LDS beside the row descriptors, one lane per row of degree > f resolves the row's picks in place, and after
 // one more barrier every slot reads its own.  Everything behind the position is the default mode's code.
-template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT>
+// WEIGHTED (GPUMemoryPool_SetSampling(pool, 2), INTEGRATION.md "Weighted sampling"): the slot draws a column of its row and keeps the
+// column's neighbour or takes the column's alias (Walker's method over the graph's alias table, k_build_alias).  Both hashes are the slot's
+// own, so nothing is staged beyond the row descriptors, and the alias entry and the column's neighbour are two loads off the staged row
+// start whose addresses do not depend on each other's result: the slot's dependent chain is as long as the default mode's.  Whole CSR
+// only (PARTITIONED = false): the table lies beside the whole CSR's indices, the fragments have none.
+template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
+    static_assert(!(DISTINCT && WEIGHTED) && !(WEIGHTED && PARTITIONED), "one sampling kind per instantiation; weighted draws read the whole CSR");
+    constexpr bool STREAM = !DISTINCT && !WEIGHTED;   // the minstd stream of the default mode
     __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
     __shared__ int32_t s_deg[TILE + 2];
     __shared__ int32_t s_src[TILE + 2];
@@ -338,9 +353,9 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 
     if ((int32_t)blockIdx.x >= n_tiles) return;
 
-    // per-thread RNG state: x[s] = s_b * 48271^(tile*TILE + tid + 256*s + 1) (the distinct mode draws from the hash: no stream)
+    // per-thread RNG state: x[s] = s_b * 48271^(tile*TILE + tid + 256*s + 1) (the distinct and the weighted mode draw from the hash: no stream)
     uint32_t x[TILE / kBlock];
-    if constexpr (!DISTINCT) {
+    if constexpr (STREAM) {
         // uniform per workgroup; the seeded stream is the unseeded one times the batch's s_b (1 with the mode off: mulmod31(b, 1) == b)
         uint32_t base = mulmod31(powmod31(a.a_tile, (uint64_t)blockIdx.x), seeded_stream_seed(draw));
 #pragma unroll
@@ -407,6 +422,13 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 const int32_t deg = s_deg[r];
                 if (j < deg) { // deg == -1 for padded (-1) sources; Kernels.cu:385,399
                     if constexpr (DISTINCT) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
+                    else if constexpr (WEIGHTED) {
+                        const uint32_t key = weighted_key(i, (uint32_t)a.op_id >> 1, draw);
+                        const int32_t* col = s_row[r] + weighted_column(key, (uint32_t)j, deg);
+                        const AliasEntry e = a.alias[col - a.csr.indices];   // beside the neighbour load, not behind it
+                        const int32_t own = *col;
+                        dst = weighted_ub(key, (uint32_t)j) < e.thr ? own : e.alias_id;
+                    }
                     else dst = s_row[r][sample_index(x[s], deg)];
                     if (dst < 0) dst = -1;
                 }
@@ -444,7 +466,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             for (int w = 0; w < kBlock / 64; w++) t += s_cnt[w];
             a.tile_edge[tile] = t;
         }
-        if constexpr (!DISTINCT) {
+        if constexpr (STREAM) {
 #pragma unroll
             for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(x[s], a.a_step);
         }
@@ -1359,6 +1381,144 @@ __global__ void k_distinct_probe(uint32_t w, const int32_t* row, const int32_t* 
     distinct_resolve(out, d, f);
 }
 
+// The weighted mode's draw of n slots, by the device functions k_sample<.., WEIGHTED> runs: the column k[m] < deg[m] and the word ub[m] that
+// is held against the column's threshold; deg[m] <= 0: k = -1, ub = 0.
+__global__ void k_weighted_probe(const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
+                                 int32_t* k, uint32_t* ub, int32_t n)
+{
+    const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
+    if (m >= n) return;
+    const int32_t d = deg[m];
+    if (d <= 0) { k[m] = -1; ub[m] = 0u; return; }
+    const uint32_t key = weighted_key((uint32_t)row[m], (uint32_t)hop[m], word[m]);
+    k[m] = (int32_t)weighted_column(key, (uint32_t)slot[m], d);
+    ub[m] = weighted_ub(key, (uint32_t)slot[m]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// alias table of the weighted sampler mode (one-off per graph; GPUGraphStorage_SetEdgeWeights)
+// ------------------------------------------------------------------------------------------------
+// Weights that are negative, NaN or infinite.  The sum of the per-wave counts does not depend on the order they are added in.
+__global__ void k_check_weights(const float* __restrict__ w, int64_t E, unsigned long long* bad)
+{
+    unsigned long long c = 0;
+    for (int64_t i = threadIdx.x + (int64_t)blockDim.x * blockIdx.x; i < E; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = w[i];
+        if (!(x >= 0.0f) || x > 3.402823466e+38f) c++;   // NaN fails the first test, +inf the second
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if (lane_id() == 0 && c) atomicAdd(bad, c);
+}
+
+__device__ inline uint32_t alias_thr(double p)   // floor(p * 2^32), saturated: p >= 1 - 2^-32 always keeps
+{
+    const double t = p * 4294967296.0;
+    return t >= 4294967295.0 ? 0xFFFFFFFFu : (t > 0.0 ? (uint32_t)t : 0u);
+}
+// Vose's algorithm over one row, sequential, without work lists: p[k] = w[k] d / W on entry (fp64), out[k] = {always keep, own id} on
+// entry.  `s` walks the columns once for the small ones (p < 1), `l` once for the large ones; the running large column's residual is
+// held in a register, a large column that falls below 1 becomes a small one with its residual in p -- taken up at once when the small
+// walk has passed it, found by that walk otherwise.  The last large column is never demoted: it stays the alias of every small column
+// left (its residual is below 1 by rounding only), so a small column, and with it every zero weight, always gives its whole remainder to
+// a column of positive weight.
+__device__ inline void alias_vose(double* p, const int32_t* ids, AliasEntry* out, int32_t d)
+{
+    int32_t s = 0, l = 0;
+    while (l < d && !(p[l] >= 1.0)) l++;
+    if (l >= d) return;                       // no column above the mean (all equal up to rounding): every column keeps itself
+    double pl = p[l];
+    auto next_small = [&]() -> int32_t {
+        while (s < d && (s == l || p[s] >= 1.0)) s++;
+        return s < d ? s++ : -1;
+    };
+    int32_t cur = next_small();
+    while (cur >= 0) {
+        const double pc = p[cur];
+        AliasEntry e;
+        e.thr = alias_thr(pc); e.alias_id = ids[l];
+        out[cur] = e;
+        pl = (pl + pc) - 1.0;
+        if (pl < 1.0) {
+            int32_t l2 = l + 1;
+            while (l2 < d && !(p[l2] >= 1.0)) l2++;
+            if (l2 < d) {
+                const int32_t demoted = l;
+                p[demoted] = pl;
+                l = l2; pl = p[l];
+                cur = demoted < s ? demoted : next_small();
+                continue;
+            }
+        }
+        cur = next_small();
+    }
+}
+
+// One lane per row of at most kAliasHubDegree neighbours: row sum in column order (fp64), p and the keep-itself entries, then alias_vose.
+__global__ __launch_bounds__(kBlock) void k_build_alias(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const float* __restrict__ w,
+                                                        int32_t V, int64_t E, double* p, AliasEntry* table)
+{
+    const int32_t v = threadIdx.x + blockDim.x * blockIdx.x;
+    if (v >= V) return;
+    const int64_t start = indptr[v];
+    const int32_t d = (int32_t)(indptr[v + 1] - start);   // int32 like the sampler's degree
+    if (d <= 0 || d > kAliasHubDegree || start < 0 || start + d > E) return;
+    double W = 0.0;
+    for (int32_t k = 0; k < d; k++) W += (double)w[start + k];
+    AliasEntry e;
+    if (!(W > 0.0)) {
+        e.thr = 0u; e.alias_id = -1;
+        for (int32_t k = 0; k < d; k++) table[start + k] = e;
+        return;
+    }
+    e.thr = 0xFFFFFFFFu;
+    for (int32_t k = 0; k < d; k++) {
+        p[start + k] = (double)w[start + k] * (double)d / W;
+        e.alias_id = indices[start + k];
+        table[start + k] = e;
+    }
+    alias_vose(p + start, indices + start, table + start, d);
+}
+
+// One wave per row of more than kAliasHubDegree neighbours (a workgroup is one wave): the lanes sum, scale and initialise the row together
+// -- per-lane partial sums in column order, then a fixed butterfly, so the sum does not depend on timing --, lane 0 runs alias_vose.
+__global__ __launch_bounds__(64) void k_build_alias_hub(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const float* __restrict__ w,
+                                                        int32_t V, int64_t E, double* p, AliasEntry* table)
+{
+    const int lane = threadIdx.x;
+    for (int64_t base = (int64_t)blockIdx.x * 64; base < V; base += (int64_t)gridDim.x * 64) {
+        const int64_t v = base + lane;
+        int64_t my_start = 0;
+        int32_t my_d = 0;
+        if (v < V) { my_start = indptr[v]; my_d = (int32_t)(indptr[v + 1] - my_start); }
+        unsigned long long hubs = __ballot(my_d > kAliasHubDegree && my_start >= 0 && my_start + my_d <= E);
+        while (hubs) {
+            const int src = __ffsll((long long)hubs) - 1;
+            hubs &= hubs - 1;
+            const int64_t start = __shfl(my_start, src);
+            const int32_t d = __shfl(my_d, src);
+            double W = 0.0;
+            for (int32_t k = lane; k < d; k += 64) W += (double)w[start + k];
+            for (int o = 32; o > 0; o >>= 1) W += __shfl_xor(W, o);   // a + b == b + a bit for bit: every lane holds the same sum
+            AliasEntry e;
+            if (!(W > 0.0)) {
+                e.thr = 0u; e.alias_id = -1;
+                for (int32_t k = lane; k < d; k += 64) table[start + k] = e;
+                continue;
+            }
+            e.thr = 0xFFFFFFFFu;
+            for (int32_t k = lane; k < d; k += 64) {
+                p[start + k] = (double)w[start + k] * (double)d / W;
+                e.alias_id = indices[start + k];
+                table[start + k] = e;
+            }
+            __threadfence_block();
+            __syncthreads();                  // lane 0 reads what the other lanes wrote
+            if (lane == 0) alias_vose(p + start, indices + start, table + start, d);
+            __syncthreads();
+        }
+    }
+}
+
 __global__ void k_aggregate_access(unsigned long long* agg, const unsigned long long* add, int32_t n)
 {   // GPUCache.cu:44-48
     for (int32_t i = threadIdx.x + blockDim.x * blockIdx.x; i < n; i += gridDim.x * blockDim.x) agg[i] += add[i];
@@ -1575,7 +1735,7 @@ int sampler_cu_count() { return cu_count(); }
 
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, bool distinct)
+                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias)
 {
     const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
@@ -1603,17 +1763,22 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.count = count; a.op_id = op_id;
     a.window = std::min(count - 1, 8);
     a.prefilter_from_op = 4;   // hop 1 goes straight to the atomic (see k_sample; moving the boundary lost: profiles/r04_sampler.md)
+    a.alias = sampling == kSamplingWeighted ? alias : nullptr;
     const bool part = csr.topo_owner != nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
-    LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices));
-    if (distinct) {
-        if (is_presc) k_sample<TILE, true, false, true><<<grid, kBlock, 0, s>>>(a);
-        else if (part) k_sample<TILE, false, true, true><<<grid, kBlock, 0, s>>>(a);
-        else k_sample<TILE, false, false, true><<<grid, kBlock, 0, s>>>(a);
+    LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices), LEGION_AL(a.alias));
+    if (sampling == kSamplingWeighted) {   // the caller passed whole-CSR tables (csr_tables_of(.., fragments = false)): no topology map
+        if (is_presc) k_sample<TILE, true, false, false, true><<<grid, kBlock, 0, s>>>(a);
+        else k_sample<TILE, false, false, false, true><<<grid, kBlock, 0, s>>>(a);
     }
-    else if (is_presc) k_sample<TILE, true, false, false><<<grid, kBlock, 0, s>>>(a);
-    else if (part) k_sample<TILE, false, true, false><<<grid, kBlock, 0, s>>>(a);
-    else k_sample<TILE, false, false, false><<<grid, kBlock, 0, s>>>(a);
+    else if (sampling == kSamplingDistinct) {
+        if (is_presc) k_sample<TILE, true, false, true, false><<<grid, kBlock, 0, s>>>(a);
+        else if (part) k_sample<TILE, false, true, true, false><<<grid, kBlock, 0, s>>>(a);
+        else k_sample<TILE, false, false, true, false><<<grid, kBlock, 0, s>>>(a);
+    }
+    else if (is_presc) k_sample<TILE, true, false, false, false><<<grid, kBlock, 0, s>>>(a);
+    else if (part) k_sample<TILE, false, true, false, false><<<grid, kBlock, 0, s>>>(a);
+    else k_sample<TILE, false, false, false, false><<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
     k_mark<TILE><<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
@@ -1632,13 +1797,15 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
 }
 
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, bool distinct)
+                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias)
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
+    const bool distinct = sampling == kSamplingDistinct;
+    if (sampling == kSamplingWeighted && (!alias || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
     if (distinct && count > kDistinctMaxFanout) { LEGION_ARG_ERROR("GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"); return; }
     // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
-    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, distinct);
-    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, distinct);
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias);
 }
 
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,
@@ -1810,6 +1977,32 @@ void launch_seeded_distinct_probe(hipStream_t s, uint32_t w, const int32_t* row,
 void launch_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
 {
     launch_seeded_distinct_probe(s, 0u, row, hop, deg, f, pos, n);
+}
+void launch_weighted_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
+                           int32_t* k, uint32_t* ub, int32_t n)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_weighted_probe", LEGION_AW(k), LEGION_AW(ub), LEGION_AL(row), LEGION_AL(hop), LEGION_AL(slot), LEGION_AL(deg), LEGION_AL(word));
+    k_weighted_probe<<<(n + 255) / 256, 256, 0, s>>>(row, hop, slot, deg, word, k, ub, n);
+    HIP_CHECK_LAST();
+}
+void launch_check_weights(hipStream_t s, const float* w, int64_t E, unsigned long long* bad)
+{
+    if (E <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_check_weights", LEGION_AW(bad), LEGION_AL(w));
+    k_check_weights<<<grid_for(E, kBlock * 4), kBlock, 0, s>>>(w, E, bad);
+    HIP_CHECK_LAST();
+}
+void launch_build_alias(hipStream_t s, const int64_t* indptr, const int32_t* indices, const float* w, int32_t V, int64_t E, double* p, AliasEntry* table)
+{
+    if (V <= 0 || E <= 0) return;
+    // the CSR may be a peer's / the host's table; the weights' copy, the scratch and the table are this GPU's
+    LEGION_AUDIT_LAUNCH(s, "k_build_alias", LEGION_AW(p), LEGION_AW(table), LEGION_AL(w), LEGION_AR(indptr), LEGION_AR(indices));
+    k_build_alias<<<(V + kBlock - 1) / kBlock, kBlock, 0, s>>>(indptr, indices, w, V, E, p, table);
+    HIP_CHECK_LAST();
+    LEGION_AUDIT_LAUNCH(s, "k_build_alias_hub", LEGION_AW(p), LEGION_AW(table), LEGION_AL(w), LEGION_AR(indptr), LEGION_AR(indices));
+    k_build_alias_hub<<<std::min((V + 63) / 64, cu_count() * 16), 64, 0, s>>>(indptr, indices, w, V, E, p, table);
+    HIP_CHECK_LAST();
 }
 void launch_seeded_rng_probe(hipStream_t s, uint32_t w, const int32_t* idx, const int32_t* deg, int32_t* k, int32_t n)
 {

@@ -165,8 +165,12 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     if (slots > p->max_slots) { LEGION_ARG_ERROR("GPU_Random_Sampling: fan-out exceeds what the pool was sized for"); return; }
     if (slots <= 0) return;
 
+    // weighted draws read the graph's alias table, which lies beside the whole CSR: never the fragments, exactly as pre-sampling
+    const bool weighted = p->modes.sampling == kSamplingWeighted;
+    const AliasEntry* alias = weighted && dev < (int)graph->alias.size() ? graph->alias[dev] : nullptr;
+    if (weighted && !alias) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) over a graph without edge weights on this GPU: call GPUGraphStorage_SetEdgeWeights first"); return; }
     CsrTables csr;
-    csr_tables_of(csr, graph, cache, dev, !is_presc);   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
+    csr_tables_of(csr, graph, cache, dev, !is_presc && !weighted);   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
     SamplerBuffers b;
     const int q = p->current_pipe;
     b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];
@@ -188,7 +192,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.V = p->V;
     b.aux_prepared = p->aux_ready_hop == hop && p->aux_ready_count == count;
     b.next_count = hop < p->hops ? p->fanout[hop] : 0;
-    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->modes.sampling != 0);
+    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->modes.sampling, alias);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint

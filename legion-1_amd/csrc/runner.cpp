@@ -86,7 +86,7 @@ static bool parse_seed(const char* n, uint32_t& seed)
 }
 
 // LEGION_AGG_LAST_HOP: atoi, so anything non-numeric is off.  LEGION_AGG_NORM: unset / empty = plain sums, "both" only on a server that aggregates
-// the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, or "distinct".  LEGION_SAMPLING_SEED: unset / empty = off.
+// the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, "distinct" or "weighted".  LEGION_SAMPLING_SEED: unset / empty = off.
 // LEGION_LP_DRAW: unset / empty / "0" = off, "1" only under a seed (k is resolved against the meta line: serve_modes_resolve_lp_draw).
 bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
 {
@@ -101,8 +101,9 @@ bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
     }
     const char* sampling = getenv("LEGION_SAMPLING");
     if (sampling && sampling[0] && strcmp(sampling, "replace") != 0) {
-        if (strcmp(sampling, "distinct") != 0) { why = std::string("LEGION_SAMPLING=") + sampling + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row)"; return false; }
-        m.sampling = 1;
+        if (strcmp(sampling, "weighted") == 0) m.sampling = kSamplingWeighted;
+        else if (strcmp(sampling, "distinct") == 0) m.sampling = kSamplingDistinct;
+        else { why = std::string("LEGION_SAMPLING=") + sampling + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row), or `weighted` (draws with replacement in proportion to the edge weights)"; return false; }
     }
     const char* seed = getenv("LEGION_SAMPLING_SEED");
     if (seed && seed[0]) {
@@ -358,7 +359,7 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     ipc_env_publish_modes(env, m);
     if (m.agg_last_hop) log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
     if (m.agg_norm) log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
-    log_out() << r->local_dev_id << " Sampling: " << (m.sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
+    log_out() << r->local_dev_id << " Sampling: " << (m.sampling == kSamplingWeighted ? "weighted by edge weight, with replacement, from the graph's alias table (LEGION_SAMPLING=weighted)" : m.sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
     if (m.seeded) log_out() << r->local_dev_id << " Sampling seed: " << m.seed << " (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch\n";
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");
@@ -926,6 +927,36 @@ bool place_tables(Server* s, const LegionSynthSpec& spec)
     return true;
 }
 
+// LEGION_SAMPLING=weighted: the graph's edge weights -- `edge_weights` (float32[E], one per entry of edge_dst) beside the dataset's files,
+// generated on the device for a synth: source -- become the graph's alias table on every GPU of the job (GPUGraphStorage_SetEdgeWeights).
+bool load_edge_weights(Server* s)
+{
+    const Meta& m = s->meta;
+    const int64_t E = m.edge_num;
+    if (s->synth) {
+        DeviceGuard guard(0);
+        float* d_w = nullptr;
+        HIP_CHECK(hipMalloc(&d_w, (size_t)std::max<int64_t>(E, 1) * sizeof(float)));
+        if (!d_w) return false;
+        legion_synth_edge_weights(nullptr, d_w, 0, E);
+        HIP_CHECK(hipDeviceSynchronize());
+        const int rc = GPUGraphStorage_SetEdgeWeights(s->graph, d_w, LEGION_LOC_DEVICE);
+        (void)hipFree(d_w);
+        if (rc != 0) return false;
+    } else {
+        std::vector<float> w((size_t)std::max<int64_t>(E, 1));
+        int64_t got = 0;
+        const std::string path = m.dataset_path + "edge_weights";
+        if (!read_file(path, w.data(), E * 4, &got) || got != E * 4) {
+            LEGION_ARG_ERROR(("Server_Initialize: LEGION_SAMPLING=weighted needs " + path + ": float32[" + std::to_string(E) + "], one weight per entry of edge_dst (missing or short)").c_str());
+            return false;
+        }
+        if (GPUGraphStorage_SetEdgeWeights(s->graph, w.data(), LEGION_LOC_HOST_PAGEABLE) != 0) return false;
+    }
+    log_out() << "Edge weights: alias table built in HBM, " << E * 8 / 1e9 << " GB per GPU\n";
+    return true;
+}
+
 // the cache, then one runner per GPU (GPUServer::Initialize, Server.cu:70-81)
 void start_runners(Server* s)
 {
@@ -1000,6 +1031,7 @@ void Server_Initialize(Server* s, int global_shard_count)
     log_out() << "Finish Partition\n";
     build_storages(s, split);
     if (!place_tables(s, spec)) return;
+    if (modes.sampling == kSamplingWeighted && !load_edge_weights(s)) return;
     start_runners(s);
 }
 

@@ -252,6 +252,12 @@ void legion_lp_draw_probe(void* stream, uint32_t seed, int32_t round, int32_t it
 {
     launch_lp_draw_probe((hipStream_t)stream, seeded_draw_word(1u, seeded_draw_key(seed, (uint32_t)round), iter), src, deg, V, rho_out, neg_out, n);
 }
+void legion_weighted_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
+                           int32_t* k_out, uint32_t* ub_out, int32_t n)
+{
+    if (n > 0 && (!row || !hop || !slot || !deg || !word || !k_out || !ub_out)) { LEGION_ARG_ERROR("legion_weighted_probe: null array"); return; }
+    launch_weighted_probe((hipStream_t)stream, row, hop, slot, deg, word, k_out, ub_out, n);
+}
 void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, int32_t* perm_out)
 {
     launch_perm_probe((hipStream_t)stream, seeded_shuffle_key(seed, (uint32_t)round), n, perm_out);

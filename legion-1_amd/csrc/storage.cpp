@@ -107,6 +107,7 @@ void GPUGraphStorage_Build(GPUGraphStorage* g, const LegionBuildInfo* info)
     g->replica_indices.assign(P, nullptr);
     g->view.assign(P, std::vector<bool>(P, false));
     g->d_frag_tab.assign(P, nullptr);
+    g->alias.assign(P, nullptr);
     // chunk geometry of the fragments: powers of two that fit shard_chunk_bytes()
     g->row_shift = chunk_shift(sizeof(int64_t), 4);
     g->edge_shift = chunk_shift(sizeof(int32_t), 4);
@@ -219,9 +220,106 @@ int64_t GPUGraphStorage_ReplicateToDevices(GPUGraphStorage* g)
     return ((int64_t)g->node_num + 1) * 8 + g->edge_num * 4;
 }
 
+// ---- weighted sampler mode: the graph's edge weights as an alias table (INTEGRATION.md "Weighted sampling") ----
+// The table of the whole CSR on the current device (logical GPU dev), from the weights wherever they lie; null with a sticky error.
+// *bad := the number of refused weights (then nothing is built).  The weights' device copy and the fp64 scratch are freed before returning.
+static AliasEntry* build_alias_here(const GPUGraphStorage* g, int dev, const float* w, unsigned long long* bad)
+{
+    const int64_t E = g->edge_num;
+    float* d_w = nullptr;
+    unsigned long long* d_bad = nullptr;
+    double* d_p = nullptr;
+    AliasEntry* table = nullptr;
+    HIP_CHECK(hipMalloc(&d_w, (size_t)E * sizeof(float)));
+    HIP_CHECK(hipMalloc(&d_bad, sizeof(unsigned long long)));
+    if (d_w && d_bad) {
+        HIP_CHECK(hipMemcpy(d_w, w, (size_t)E * sizeof(float), hipMemcpyDefault));
+        HIP_CHECK(hipMemset(d_bad, 0, sizeof(unsigned long long)));
+        launch_check_weights(nullptr, d_w, E, d_bad);
+        *bad = ~0ull;
+        HIP_CHECK(hipMemcpy(bad, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (*bad == 0 && !error_pending()) {
+            HIP_CHECK(hipMalloc(&d_p, (size_t)E * sizeof(double)));
+            HIP_CHECK(hipMalloc(&table, (size_t)E * sizeof(AliasEntry)));
+            if (d_p && table) {
+                HIP_CHECK(hipMemset(table, 0, (size_t)E * sizeof(AliasEntry)));   // entries past a truncated degree are never drawn; keep them defined
+                launch_build_alias(nullptr, g->replica_indptr[dev] ? g->replica_indptr[dev] : g->csr_node_index_cpu,
+                                   g->replica_indices[dev] ? g->replica_indices[dev] : g->csr_dst_node_ids_cpu, d_w, g->node_num, E, d_p, table);
+                HIP_CHECK(hipDeviceSynchronize());
+            }
+            if (error_pending() && table) { (void)hipFree(table); table = nullptr; }
+        }
+    }
+    if (d_p) (void)hipFree(d_p);
+    if (d_bad) (void)hipFree(d_bad);
+    if (d_w) (void)hipFree(d_w);
+    return table;
+}
+
+int GPUGraphStorage_SetEdgeWeights(GPUGraphStorage* g, const float* w, int32_t location)
+{
+    if (!g || g->alias.empty()) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeWeights: null graph, or GPUGraphStorage_Build was not called"); return -1; }
+    if (w && location != LEGION_LOC_HOST_PINNED && location != LEGION_LOC_DEVICE && location != LEGION_LOC_HOST_PAGEABLE) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeWeights: location must be a LEGION_LOC_* value"); return -1; }
+    const int P = g->partition_count;
+    std::vector<AliasEntry*> fresh(P, nullptr);
+    if (w && g->edge_num > 0) {
+        std::vector<std::pair<int, AliasEntry*>> per_phys;
+        for (int p = 0; p < P; p++) {
+            if (is_remote_device(p)) continue;
+            const int phys = physical_device(p);
+            AliasEntry* have = nullptr;
+            for (auto& e : per_phys) if (e.first == phys) have = e.second;
+            if (!have) {
+                DeviceGuard guard(p);
+                unsigned long long bad = 0;
+                have = build_alias_here(g, p, w, &bad);
+                if (!have) {   // refused or failed: the earlier table stays
+                    if (bad && !error_pending())
+                        LEGION_ARG_ERROR(("GPUGraphStorage_SetEdgeWeights: " + std::to_string(bad) + " of " + std::to_string(g->edge_num) +
+                                          " edge weights are negative, NaN or infinite: weights must be finite and >= 0 (the earlier table, if any, stays)").c_str());
+                    else if (!error_pending()) LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeWeights: building the alias table failed");
+                    free_replicas(fresh);
+                    return -1;
+                }
+                per_phys.emplace_back(phys, have);
+            }
+            LEGION_AUDIT_SHARE(have, p);
+            fresh[p] = have;
+        }
+    }
+    // batches that read the earlier table may still be in flight
+    for (int p = 0; p < P; p++)
+        if (g->alias[p] && !is_remote_device(p)) { DeviceGuard guard(p); HIP_CHECK(hipDeviceSynchronize()); }
+    free_replicas(g->alias);
+    g->alias = fresh;
+    return error_pending() ? -1 : 0;
+}
+int GPUGraphStorage_HasEdgeWeights(const GPUGraphStorage* g)
+{
+    if (!g) return 0;
+    for (const AliasEntry* t : g->alias) if (t) return 1;
+    return 0;
+}
+int GPUGraphStorage_CopyAliasRows(const GPUGraphStorage* g, int32_t dev_id, int64_t e0, int64_t n, uint32_t* thr, int32_t* alias_id)
+{
+    if (!g || dev_id < 0 || dev_id >= (int32_t)g->alias.size() || !g->alias[dev_id]) { LEGION_ARG_ERROR("GPUGraphStorage_CopyAliasRows: this logical GPU holds no alias table (GPUGraphStorage_SetEdgeWeights)"); return -1; }
+    if (e0 < 0 || n < 0 || e0 > g->edge_num - n) { LEGION_ARG_ERROR("GPUGraphStorage_CopyAliasRows: entries outside [0, edge count)"); return -1; }
+    if (n == 0) return 0;
+    if (!thr || !alias_id) { LEGION_ARG_ERROR("GPUGraphStorage_CopyAliasRows: null output"); return -1; }
+    std::vector<AliasEntry> h((size_t)n);
+    {
+        DeviceGuard guard(dev_id);
+        HIP_CHECK(hipMemcpy(h.data(), g->alias[dev_id] + e0, (size_t)n * sizeof(AliasEntry), hipMemcpyDeviceToHost));
+    }
+    if (error_pending()) return -1;
+    for (int64_t i = 0; i < n; i++) { thr[i] = h[(size_t)i].thr; alias_id[i] = h[(size_t)i].alias_id; }
+    return 0;
+}
+
 void GPUGraphStorage_Finalize(GPUGraphStorage* g)
 {
     if (!g) return;
+    free_replicas(g->alias);
     free_replicas(g->replica_indptr);
     free_replicas(g->replica_indices);
     for (size_t i = 0; i < g->frag.size(); i++) {
@@ -471,6 +569,7 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
     if (p->capturing) { LEGION_ARG_ERROR((name + ": the pool is being captured").c_str()); return false; }
     if (wanted.agg_norm != 0 && wanted.agg_norm != 1) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: unknown norm (0 = none, 1 = out-degree rsqrt)"); return false; }
     if (wanted.agg_norm && !wanted.agg_last_hop && wanted.agg_norm != p->modes.agg_norm) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return false; }
+    if (wanted.sampling != kSamplingReplace && wanted.sampling != kSamplingDistinct && wanted.sampling != kSamplingWeighted) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampling: unknown sampling kind (0 = replace, 1 = distinct, 2 = weighted)"); return false; }
     if (wanted.lp_draw < 0) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: negative triples per batch (0 = off, k > 0 = batches of 3 k)"); return false; }
     if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
@@ -543,6 +642,10 @@ static ServeModes modes_of(const GPUMemoryPool* p) { return p ? p->modes : Serve
 void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.agg_last_hop = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetAggLastHop"); }
 void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm) { ServeModes m = modes_of(p); m.agg_norm = norm; pool_apply_modes(p, m, "GPUMemoryPool_SetAggNorm"); }
 void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.sampling = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetSampleDistinct"); }
+// the sampling kind as the enumeration it is: 0 = replace, 1 = distinct (what SetSampleDistinct(1) sets), 2 = weighted ("Weighted sampling":
+// nothing is allocated here, the alias table belongs to the graph: GPUGraphStorage_SetEdgeWeights)
+void GPUMemoryPool_SetSampling(GPUMemoryPool* p, int kind) { ServeModes m = modes_of(p); m.sampling = kind; pool_apply_modes(p, m, "GPUMemoryPool_SetSampling"); }
+int GPUMemoryPool_GetSampling(const GPUMemoryPool* p) { return p ? p->modes.sampling : 0; }
 void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {
     ServeModes m = modes_of(p);
@@ -560,7 +663,7 @@ void GPUMemoryPool_SetLpDraw(GPUMemoryPool* p, int32_t triples_per_batch, GPUGra
 int32_t GPUMemoryPool_GetLpDraw(const GPUMemoryPool* p) { return p ? p->modes.lp_draw : 0; }
 int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->modes.agg_last_hop ? 1 : 0; }
 int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->modes.agg_norm : 0; }
-int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->modes.sampling ? 1 : 0; }
+int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->modes.sampling == kSamplingDistinct ? 1 : 0; }
 int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed)
 {
     if (seed) *seed = p ? p->modes.seed : 0;

@@ -23,6 +23,8 @@ constexpr uint64_t S_DEG = (GEN_SEED << 32) ^ 0x0DE6ull;
 constexpr uint64_t S_NBR = (GEN_SEED << 32) ^ 0x0EB2ull;
 constexpr uint64_t S_FEAT = (GEN_SEED << 32) ^ 0xFEA7ull;
 constexpr uint64_t S_LAB = (GEN_SEED << 32) ^ 0x1AB1ull;
+constexpr uint64_t S_WGT = (GEN_SEED << 32) ^ 0x3E16ull;
+constexpr uint64_t S_WGT_BLOCK = (GEN_SEED << 32) ^ 0xB3E16ull;
 constexpr int NBUCKET = 24;
 
 struct Ladder { int32_t lo[NBUCKET + 2]; };
@@ -64,6 +66,16 @@ __global__ void k_synth_labels(int32_t* out, int32_t v0, int32_t n, int32_t clas
 {
     for (int32_t i = threadIdx.x + blockDim.x * blockIdx.x; i < n; i += gridDim.x * blockDim.x)
         out[i] = (int32_t)(sm64(S_LAB + (uint64_t)(v0 + i)) % (uint64_t)classes);
+}
+
+// edge weight of CSR entry e: 0 when the low four bits of the entry's hash or of the hash of its block of 64 entries are 0 (about one
+// entry in eight, whole blocks among them, so that rows without any weight occur), else 1 + the entry's next four bits
+__global__ void k_synth_edge_weights(float* out, int64_t e0, int64_t n)
+{
+    for (int64_t i = threadIdx.x + (int64_t)blockDim.x * blockIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t e = (uint64_t)(e0 + i), h = sm64(S_WGT + e), hb = sm64(S_WGT_BLOCK + (e >> 6));
+        out[i] = ((h & 15ull) && (hb & 15ull)) ? (float)(1u + (uint32_t)((h >> 4) & 15ull)) : 0.0f;
+    }
 }
 
 // out[k] = (i*M2 + C2) % V for i = i0 + phase + k*stride  (stride/phase: the tid % G split of a
@@ -216,6 +228,14 @@ void legion_synth_features_pitched(void* stream, float* out, int64_t v0, int64_t
     if (pitch < F) { LEGION_ARG_ERROR("legion_synth_features_pitched: pitch < F"); return; }
     LEGION_AUDIT_LAUNCH((hipStream_t)stream, "k_synth_features", LEGION_AW(out));
     k_synth_features<<<big_grid(nrows * F), 256, 0, (hipStream_t)stream>>>(out, v0, nrows, F, pitch);
+    HIP_CHECK_LAST();
+}
+void legion_synth_edge_weights(void* stream, float* out, int64_t e0, int64_t n)
+{
+    if (n <= 0) return;
+    if (!out || e0 < 0) { LEGION_ARG_ERROR("legion_synth_edge_weights: bad arguments"); return; }
+    LEGION_AUDIT_LAUNCH((hipStream_t)stream, "k_synth_edge_weights", LEGION_AW(out));
+    k_synth_edge_weights<<<big_grid(n), 256, 0, (hipStream_t)stream>>>(out, e0, n);
     HIP_CHECK_LAST();
 }
 void legion_synth_labels(void* stream, int32_t* out, int32_t v0, int32_t n, int32_t classes)

@@ -23,7 +23,7 @@ static int32_t g_hops = 2;
 static struct ServerModes {
     bool aggregated = false;   // the last hop is handed over as neighbour sums (LEGION_AGG_LAST_HOP=1)
     int agg_norm = 0;          // ... normalised: 0 = plain sums, 1 = out-degree rsqrt inside block 1 (LEGION_AGG_NORM=both)
-    int sampling = 0;          // how the server's sampler draws: 0 = with replacement, 1 = distinct neighbours (LEGION_SAMPLING=distinct)
+    int sampling = 0;          // how the server's sampler draws: 0 = with replacement, 1 = distinct neighbours (LEGION_SAMPLING=distinct), 2 = by edge weight (LEGION_SAMPLING=weighted)
     bool seeded = false;       // seeded sampling (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch
     uint32_t seed = 0;         // ... the seed (0 is a seed: `seeded` says whether there is one)
 } g_modes;
@@ -108,7 +108,7 @@ std::vector<torch::Tensor> get_next_aggregated(int feature_dim) { return next_ba
 std::vector<torch::Tensor> get_next_aggregated_norm(int feature_dim) { return next_batch(feature_dim, true, 1); }
 bool aggregated() { require_env(); return g_modes.aggregated; }
 int aggregate_norm() { require_env(); return g_modes.agg_norm; }
-const char* sampling() { require_env(); return g_modes.sampling ? "distinct" : "replace"; }
+const char* sampling() { require_env(); return g_modes.sampling == 2 ? "weighted" : g_modes.sampling ? "distinct" : "replace"; }
 pybind11::object sampling_seed() { require_env(); return g_modes.seeded ? pybind11::object(pybind11::int_(g_modes.seed)) : pybind11::object(pybind11::none()); }
 
 // [b1_src_nodes, b1_dst_nodes, b2_src_nodes, b2_dst_nodes, ...] = [nc9, nc7, nc7, nc5] at H = 2
@@ -153,7 +153,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("get_next_aggregated_norm", &get_next_aggregated_norm, "next batch of a server that hands the last hop over as out-degree-normalised neighbour sums (extension)", pybind11::call_guard<pybind11::gil_scoped_release>());
     m.def("aggregated", &aggregated, "whether the server hands the last hop over as neighbour sums (extension)");
     m.def("aggregate_norm", &aggregate_norm, "how the server normalises the neighbour sums: 0 = not, 1 = out-degree rsqrt inside block 1 (extension)");
-    m.def("sampling", &sampling, "how the server's sampler draws: \"replace\" (with replacement, the default) or \"distinct\" (LEGION_SAMPLING=distinct; extension)");
+    m.def("sampling", &sampling, "how the server's sampler draws: \"replace\" (with replacement, the default), \"distinct\" (LEGION_SAMPLING=distinct) or \"weighted\" (LEGION_SAMPLING=weighted: with replacement, by edge weight); extension");
     m.def("sampling_seed", &sampling_seed, "the server's sampling seed (LEGION_SAMPLING_SEED: fresh draws per batch, the training list reshuffled per epoch), or None: the same batches every epoch (extension)");
     m.def("get_block_size", &get_block_size, "get dgl block size");
     m.def("get_steps", &get_steps, "get steps");

@@ -52,9 +52,9 @@ def main(argv=None):
     ap.add_argument("--usenvlink", type=int, default=1, help="1: cliques over the GPU interconnect (xGMI)")
     ap.add_argument("--seed_lists", action="store_true", help="extension (link prediction on several GPUs): every GPU g serves its own "
                     "pre-partitioned list trainingset_<G>_<g> verbatim (meta_config flag 2) instead of a split of `trainingset`")
-    ap.add_argument("--sampling", type=str, default=None, choices=["replace", "distinct"], help="extension: how a row draws its neighbours "
+    ap.add_argument("--sampling", type=str, default=None, choices=["replace", "distinct", "weighted"], help="extension: how a row draws its neighbours "
                     "(LEGION_SAMPLING for the server): replace = with replacement like the reference (the default), distinct = "
-                    "min(degree, fan-out) distinct neighbours per row")
+                    "min(degree, fan-out) distinct neighbours per row, weighted = with replacement in proportion to the dataset's edge_weights file")
     ap.add_argument("--sampling_seed", type=int, default=None, help="extension: a 32-bit seed (LEGION_SAMPLING_SEED for the server): every batch "
                     "draws afresh and the training list is reshuffled every epoch; without it every epoch is the same epoch, like the reference's")
     ap.add_argument("--lp_draw", action="store_true", help="extension (LEGION_LP_DRAW=1 for the server; needs --seed_lists and --sampling_seed): "

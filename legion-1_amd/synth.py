@@ -37,6 +37,8 @@ S_DEG = (GEN_SEED << 32) ^ 0x0DE6
 S_NBR = (GEN_SEED << 32) ^ 0x0EB2
 S_FEAT = (GEN_SEED << 32) ^ 0xFEA7
 S_LAB = (GEN_SEED << 32) ^ 0x1AB1
+S_WGT = (GEN_SEED << 32) ^ 0x3E16
+S_WGT_BLOCK = (GEN_SEED << 32) ^ 0xB3E16
 NBUCKET = 24
 LADDER_RATIO = 1.6
 
@@ -194,6 +196,17 @@ def labels(spec: SynthSpec, ids: np.ndarray | None = None) -> np.ndarray:
     with np.errstate(over="ignore"):
         h = sm64(_U64(S_LAB) + ids)
     return (h % _U64(spec.classes)).astype(np.int32)
+
+
+def edge_weights(E: int, e0: int = 0) -> np.ndarray:
+    """float32[E - e0]: the weights of CSR entries [e0, E) a `synth:` source serves under LEGION_SAMPLING=weighted (legion_synth_edge_weights): a
+    closed form of the entry's position -- 0 when the low four bits of the entry's hash or of the hash of its block of 64 entries are 0
+    (about one entry in eight, whole blocks among them: rows without any weight occur), else an integer in 1..16."""
+    e = np.arange(e0, E, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        h, hb = sm64(_U64(S_WGT) + e), sm64(_U64(S_WGT_BLOCK) + (e >> _U64(6)))
+    w = _U64(1) + ((h >> _U64(4)) & _U64(15))
+    return np.where(((h & _U64(15)) != 0) & ((hb & _U64(15)) != 0), w, _U64(0)).astype(np.float32)
 
 
 def seed_ids(spec: SynthSpec, i0: int, i1: int) -> np.ndarray:
