@@ -520,7 +520,7 @@ void IPCEnv_MirrorCounters(IPCEnv* e, int32_t dev_id, int32_t current_pipe, void
 void IPCEnv_SetMirror(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t nc_fill, int32_t ec_fill);
 /* nc[word] (word < LEGION_COUNTER_WORDS) or ec[word - LEGION_COUNTER_WORDS] of the batch about to be posted, from the mirror IPCEnv_MirrorCounters queued (wait for that copy first); -1: not queued.
  * The runner compares legion_batch_nodes(nc, H) with the rows of its feature buffer: a batch that reached more nodes had rows dropped by the bounded
- * gather (kernels.hip k_gather: "never write past the buffer") and its trainer will refuse it -- the server says so, once, and counts. */
+ * gather (gather.hip k_gather: "never write past the buffer") and its trainer will refuse it -- the server says so, once, and counts. */
 int32_t IPCEnv_MirroredNodeCounter(IPCEnv* e, int32_t dev_id, int32_t current_pipe, int32_t word);
 /* the row capacity of a device's feature buffers as published to its trainer (set by IPCEnv_InitializeFeaturesBuffer) */
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows);

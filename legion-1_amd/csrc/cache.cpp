@@ -12,7 +12,7 @@
 //  * CostModel: when the budget covers all features and all adjacency the reference degenerates
 //    (trans_* stay 0, GPUCache.cu:744-751); we then cache everything.  The Intel-PCM PCIe counter
 //    input is optional: NULL selects an estimate from the edge hotness and the row degrees
-//    (k_topo_transactions in kernels.hip has the per-row weight).
+//    (k_topo_transactions in build_kernels.hip has the per-row weight).
 //  * feature shards use the line-aligned row pitch only when the padded shard fits the budget.
 #include "internal.h"
 

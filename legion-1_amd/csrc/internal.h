@@ -215,7 +215,7 @@ struct FastDiv {
     explicit FastDiv(uint32_t div);
 };
 
-// ---- kernel launch API (kernels.hip) -------------------------------------------------------------
+// ---- kernel launch API (sampler.hip, gather.hip, build_kernels.hip, sort_scan.hip, probes.hip) -------------------------------------------------------------
 struct CsrTables {                 // GPU_Memory_Graph_Storage.cu:45-133: the whole CSR + the clique's fragments
     const int64_t* indptr;         // whole CSR (the reference's slot [P]): HBM replica or pinned host table
     const int32_t* indices;
@@ -285,11 +285,11 @@ void launch_shuffle_seeds(hipStream_t s, const int32_t* ids, const int32_t* labe
 // the same for a [src | pos | neg] list of batches of 3 k (n a multiple of 3 k): whole triples move, under perm on [0, n / 3)
 void launch_shuffle_triples(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, int32_t k, uint32_t ks, int32_t* out_ids, int32_t* out_labels);
 void launch_advance(hipStream_t s, BatchCtl* ctl);
-int sampler_cu_count();       // compute units the persistent grids are sized by (current device)
+int sampler_cu_count();       // compute units every grid is sized by (current device; asked once per process)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
                        int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling = kSamplingReplace, const AliasEntry* alias = nullptr);
-// Weighted sampler mode, the graph's side (kernels.hip "alias table").  bad := the number of weights that are negative, NaN or infinite
+// Weighted sampler mode, the graph's side (build_kernels.hip "alias table").  bad := the number of weights that are negative, NaN or infinite
 // (a device word the caller zeroed); the table of every row of the CSR from w, with p = double[E] of scratch.  Deterministic: the same
 // weights give the same bytes.
 void launch_check_weights(hipStream_t s, const float* w, int64_t E, unsigned long long* bad);
@@ -329,12 +329,12 @@ struct GatherArgs {
     bool row_ptr_ready;                       // row_ptr was filled by the caller (exchange plan): skip the lookup pass
 };
 void launch_gather(hipStream_t s, const GatherArgs& a, int32_t rows_bound);
-// Aggregated last hop (kernels.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
+// Aggregated last hop (gather.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
 // slots, from the draws in cand[slot * f + j], into rows [legion_first_block_dst(nc, hops), + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
 // wdraw (normalised sums): the weight of every draw by slot, as launch_agg_norm_weights left it; null = plain sums.
 void launch_gather_sum(hipStream_t s, const GatherArgs& a, const int32_t* cand, int32_t cand_cap, const int32_t* ec, int32_t hops,
                        int32_t f, int32_t runs_bound, const float* wdraw = nullptr);
-// Normalised last hop (kernels.hip "S5, normalised last hop"): out_deg[p] = out-degree of batch position p inside block 1 (all edges of
+// Normalised last hop (gather.hip "S5, normalised last hop"): out_deg[p] = out-degree of batch position p inside block 1 (all edges of
 // the batch), and wdraw[slot] = 1 / sqrt(max(out_deg[position of the slot's draw], 1)) for every slot of the last hop with a draw.
 // Everything here belongs to the batch's pipe.
 struct AggNormArgs {
@@ -355,7 +355,7 @@ constexpr int kRowsSeenAll = LEGION_MAX_HOPS + 1;      // all rows of the batch 
 constexpr int kRowsSeenAggIn = LEGION_MAX_HOPS + 2;    // rows of the levels < H (get_feature_kernel_agg)
 constexpr int kRowsSeenAggRuns = LEGION_MAX_HOPS + 3;  // input slots of the last hop (get_feature_kernel_agg)
 constexpr int kRowsSeenWords = LEGION_MAX_HOPS + 4;
-// owner-computes exchange variant of the gather (kernels.hip "S5, owner-computes"): counts = int32[2 * kMaxParts] scratch
+// owner-computes exchange variant of the gather (gather.hip "S5, owner-computes"): counts = int32[2 * kMaxParts] scratch
 void launch_exchange_plan(hipStream_t s, const GatherArgs& g, int32_t me, int32_t Kg, int32_t* slot, int32_t* counts,
                           int32_t* req_row, int32_t* req_dst, int32_t rows_bound);
 void launch_exchange_rows(hipStream_t s, bool scatter, const float* const* shard_chunks, int32_t chunk_shift, const int32_t* list,
@@ -408,7 +408,7 @@ struct GPUMemoryPool {
     int32_t fanout[LEGION_MAX_HOPS] = {0};
     int32_t max_slots = 0, max_tiles = 0;
     int32_t feature_rows = 0;         // capacity of the feature buffers in rows (0 = unbounded)
-    legion::pos_t* pos_map = nullptr; // pos_t[V], see kernels.hip "position table"
+    legion::pos_t* pos_map = nullptr; // pos_t[V], see sampler.hip "position table"
     uint32_t batch_serial = 0;        // batches started on this pool; epoch = 0xFFFFFFFF - serial
     legion::BatchCtl* ctl = nullptr;  // device copy of (batch cursor, epoch): what the kernels read
     // Feedback for sizing the gather launches without a host round trip: pinned, device-mapped words the gather

@@ -1,5 +1,5 @@
 // launchers.cpp -- the extern "C" operator launchers of the reference (src/Kernels.cuh:47-93,
-// Kernels.cu:162-232,567-659,706-805) on top of kernels.hip, plus the Operator plugin classes
+// Kernels.cu:162-232,567-659,706-805) on top of the kernels' launch wrappers (sampler.hip, gather.hip), plus the Operator plugin classes
 // (src/Operator.h:4-27, Operator.cu:10-124).
 #include "internal.h"
 
@@ -199,6 +199,15 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     p->bound_nodes += (int32_t)slots;
 }
 
+// Launch-size feedback (launch.h: est_rows): the row count an earlier launch of this kind left in word `slot` of the pool's rows_seen
+// becomes this launch's hint, and this launch leaves its own count in the same word.
+static void rows_seen_feedback(GatherArgs& g, const GPUMemoryPool* p, int slot)
+{
+    if (!p->rows_seen || !p->rows_seen_dev) return;
+    g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
+    g.rows_seen = p->rows_seen_dev + slot;
+}
+
 // Arguments of a gather over the rows (nc[off_idx], nc[size_idx]) of the current pipe; false (sticky error) if it cannot run.
 static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, int32_t dev_id, int off_idx, int size_idx,
                         bool count_hits = true)
@@ -226,11 +235,7 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
     g.dst_rows = p->feature_rows;
     g.rows_seen = nullptr; g.rows_hint = 0;
     g.hit_stats = nullptr;
-    if (p->rows_seen && p->rows_seen_dev) { // slot: level of a per-level gather, or the last one for "all rows of the batch"
-        const int slot = off_idx < 0 ? kRowsSeenAll : legion_idx_level(off_idx);
-        g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
-        g.rows_seen = p->rows_seen_dev + slot;
-    }
+    rows_seen_feedback(g, p, off_idx < 0 ? kRowsSeenAll : legion_idx_level(off_idx));   // level of a per-level gather, or "all rows of the batch"
     if (cache && dev_id >= 0 && dev_id < cache->device_count && cache->ctl[dev_id]->feat_map && cache->ctl[dev_id]->node_capacity > 0 &&
         cache->d_shard_tab[dev_id]) {
         const int Ki = dev_id / cache->Kg;
@@ -261,12 +266,17 @@ static bool gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder
     return true;
 }
 
+static bool peer_gather_is_exchange()
+{
+    const char* e = getenv("LEGION_PEER_GATHER");
+    return e && strcmp(e, "exchange") == 0;
+}
+
 // $LEGION_PEER_GATHER=exchange and a filled clique cache (Kg > 1, every member in this process): the peers' rows travel as bulk
 // copies (peer_exchange.cpp) instead of in-kernel xGMI loads
 static bool use_peer_exchange(const GPUCache* cache, const GPUMemoryPool* p, int32_t dev_id)
 {
-    const char* e = getenv("LEGION_PEER_GATHER");
-    if (!e || strcmp(e, "exchange") != 0 || !cache || p->capturing) return false;
+    if (!peer_gather_is_exchange() || !cache || p->capturing) return false;
     if (cache->Kg <= 1 || dev_id < 0 || dev_id >= cache->device_count || !cache->ctl[dev_id]->feat_map || cache->ctl[dev_id]->node_capacity <= 0) return false;
     const int K0 = (dev_id / cache->Kg) * cache->Kg;
     for (int j = 0; j < cache->Kg; j++) if (is_remote_device(K0 + j)) return false;
@@ -299,10 +309,8 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     GPUMemoryPool* p = memorypool;
     const int H = p->hops, q = p->current_pipe;
     if (!p->modes.agg_last_hop) { LEGION_ARG_ERROR("get_feature_kernel_agg: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop)"); return; }
-    {   // the exchange moves rows between clique members, not sums
-        const char* e = getenv("LEGION_PEER_GATHER");
-        if (e && strcmp(e, "exchange") == 0) { LEGION_ARG_ERROR("get_feature_kernel_agg: LEGION_PEER_GATHER=exchange cannot serve the aggregated last hop (GPUMemoryPool_SetAggLastHop): the exchange moves rows, not sums"); return; }
-    }
+    // the exchange moves rows between clique members, not sums
+    if (peer_gather_is_exchange()) { LEGION_ARG_ERROR("get_feature_kernel_agg: LEGION_PEER_GATHER=exchange cannot serve the aggregated last hop (GPUMemoryPool_SetAggLastHop): the exchange moves rows, not sums"); return; }
     if (p->sampled_hop != H) { LEGION_ARG_ERROR("get_feature_kernel_agg: called before the last hop's GPU_Random_Sampling"); return; }
     if (p->sampled_presc) { LEGION_ARG_ERROR("get_feature_kernel_agg: a pre-sampling batch gathers nothing"); return; }
     if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe draw buffers are missing"); return; }
@@ -312,16 +320,11 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (!in_memory) return;
     GatherArgs g;
     if (!gather_args(g, cache, noder, p, dev_id, -1, legion_idx_level_offset(H), false)) return;   // rows [0, n_in): the levels < H; the hit counter belongs to the default mode's batches
-    auto feedback = [&](int slot) {
-        if (!p->rows_seen || !p->rows_seen_dev) return;
-        g.rows_hint = *(volatile int32_t*)(p->rows_seen + slot);
-        g.rows_seen = p->rows_seen_dev + slot;
-    };
     if ((p->levels_gathered & ((1u << H) - 1u)) != (1u << H) - 1u) {
-        feedback(kRowsSeenAggIn);
+        rows_seen_feedback(g, p, kRowsSeenAggIn);
         launch_gather((hipStream_t)strm_hdl, g, p->num_ids - p->level_bound[H]);
     }
-    feedback(kRowsSeenAggRuns);
+    rows_seen_feedback(g, p, kRowsSeenAggRuns);
     if (norm) {   // the block's out-degrees and every draw's weight, from the pipe's own COO and draws, in front of the weighted sums
         legion::AggNormArgs w;
         w.nc = p->node_counter[q]; w.ec = p->edge_counter[q]; w.hops = H; w.f = p->fanout[H - 1];

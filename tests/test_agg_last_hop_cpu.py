@@ -98,7 +98,7 @@ def test_public_surface_carries_the_new_names():
     import inspect
     assert "agg_last_hop" in inspect.signature(K.Engine.run_batch).parameters
     assert "agg_last_hop" in inspect.signature(K.Engine.capture_batch).parameters
-    assert "k_gather_sum" in open(os.path.join(ROOT, "legion-1_amd", "csrc", "kernels.hip")).read()
+    assert "k_gather_sum" in open(os.path.join(ROOT, "legion-1_amd", "csrc", "gather.hip")).read()
     for name in ("IPCEnv_SetAggLastHop", "IPCEnv_GetAggLastHop", "legion_ipc_client_agg_last_hop"):
         assert re.search(r"\b%s\s*\(" % name, header) and name in K._SIGS, name
     import sys

@@ -143,7 +143,7 @@ def test_public_surface_carries_the_new_names():
         assert name in K._SIGS, name
     for fn in (K.Engine.run_batch, K.Engine.capture_batch):
         assert inspect.signature(fn).parameters["agg_norm"].default is None
-    kernels = open(os.path.join(ROOT, "legion-1_amd", "csrc", "kernels.hip")).read()
+    kernels = open(os.path.join(ROOT, "legion-1_amd", "csrc", "gather.hip")).read()
     for name in ("k_block_out_deg", "k_draw_weights", "k_agg_norm_prep", "fp contract(off)"):
         assert name in kernels, name
     sys.path.insert(0, os.path.join(ROOT, "legion-1_amd", "ipc_service"))
