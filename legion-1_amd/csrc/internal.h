@@ -136,6 +136,7 @@ bool serve_modes_from_env(ServeModes& m, std::string& why);
 bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why);
 // the distinct mode's fan-out bound (kDistinctMaxFanout) against a fan-out list: false with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
+void runner_set_lists_verbatim(Runner* r, bool verbatim);   // before Runner_Initialize: meta flag 2 (Runner::lists_verbatim, runner.cpp)
 // what a trainer reads: the five mode words of the "<name>_ext" object := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
 void ipc_env_publish_modes(IPCEnv* e, const ServeModes& m);
 

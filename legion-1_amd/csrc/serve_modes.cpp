@@ -1,0 +1,76 @@
+// serve_modes.cpp -- the serving modes as the environment states them: the only readers of LEGION_AGG_LAST_HOP, LEGION_AGG_NORM,
+// LEGION_SAMPLING, LEGION_SAMPLING_SEED and LEGION_LP_DRAW (ServeModes, internal.h).  Host code only: no device is touched.
+#include "internal.h"
+
+#include <cctype>
+#include <cstring>
+
+using namespace legion;
+
+// $LEGION_SAMPLING_SEED: a decimal or 0x hex integer in [0, 2^32)
+static bool parse_seed(const char* n, uint32_t& seed)
+{
+    const bool hex = n[0] == '0' && (n[1] == 'x' || n[1] == 'X');
+    const char* digits = hex ? n + 2 : n;
+    bool ok = digits[0] != 0 && strlen(digits) <= 16;
+    for (const char* c = digits; ok && *c; c++) ok = hex ? isxdigit((unsigned char)*c) != 0 : isdigit((unsigned char)*c) != 0;
+    unsigned long long v = 0;
+    if (ok) { v = strtoull(digits, nullptr, hex ? 16 : 10); ok = v <= 0xFFFFFFFFull; }
+    seed = ok ? (uint32_t)v : 0;
+    return ok;
+}
+
+// LEGION_AGG_LAST_HOP: atoi, so anything non-numeric is off.  LEGION_AGG_NORM: unset / empty = plain sums, "both" only on a server that aggregates
+// the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, "distinct" or "weighted".  LEGION_SAMPLING_SEED: unset / empty = off.
+// LEGION_LP_DRAW: unset / empty / "0" = off, "1" only under a seed (k is resolved against the meta line: serve_modes_resolve_lp_draw).
+bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
+{
+    m = ServeModes();
+    const char* agg = getenv("LEGION_AGG_LAST_HOP");
+    m.agg_last_hop = agg && atoi(agg) != 0;
+    const char* norm = getenv("LEGION_AGG_NORM");
+    if (norm && norm[0]) {
+        if (strcmp(norm, "both") != 0) { why = std::string("LEGION_AGG_NORM=") + norm + " is not a known norm: `both` (GraphConv norm='both', out-degree rsqrt inside block 1) or unset"; return false; }
+        if (!m.agg_last_hop) { why = "LEGION_AGG_NORM=both needs LEGION_AGG_LAST_HOP=1: only the last hop's neighbour sums are normalised"; return false; }
+        m.agg_norm = 1;
+    }
+    const char* sampling = getenv("LEGION_SAMPLING");
+    if (sampling && sampling[0] && strcmp(sampling, "replace") != 0) {
+        if (strcmp(sampling, "weighted") == 0) m.sampling = kSamplingWeighted;
+        else if (strcmp(sampling, "distinct") == 0) m.sampling = kSamplingDistinct;
+        else { why = std::string("LEGION_SAMPLING=") + sampling + " is not a known sampling mode: `replace` (the default: draws with replacement) or `distinct` (min(degree, fan-out) distinct neighbours per row), or `weighted` (draws with replacement in proportion to the edge weights)"; return false; }
+    }
+    const char* seed = getenv("LEGION_SAMPLING_SEED");
+    if (seed && seed[0]) {
+        if (!parse_seed(seed, m.seed)) { why = std::string("LEGION_SAMPLING_SEED=") + seed + " is not a sampling seed: a decimal or 0x hex integer in [0, 2^32), or unset (the same batches every epoch)"; return false; }
+        m.seeded = true;
+    }
+    const char* lp = getenv("LEGION_LP_DRAW");
+    if (lp && lp[0] && strcmp(lp, "0") != 0) {
+        if (strcmp(lp, "1") != 0) { why = std::string("LEGION_LP_DRAW=") + lp + " is not a known setting: `1` (the pos and neg thirds of link-prediction batches are drawn per batch), `0` or unset"; return false; }
+        if (!m.seeded) { why = "LEGION_LP_DRAW=1 needs LEGION_SAMPLING_SEED: the thirds are drawn from the batch's draw word"; return false; }
+        m.lp_draw = 1;
+    }
+    return true;
+}
+
+bool legion::serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why)
+{
+    if (!m.lp_draw) return true;
+    if (!lp_lists) { why = "LEGION_LP_DRAW=1 needs link-prediction training lists (meta flag 2: [src | pos | neg] thirds per batch)"; return false; }
+    if (raw_batch_size < 3 || raw_batch_size % 3 != 0) { why = "LEGION_LP_DRAW=1 needs a batch size divisible by 3 ([src | pos | neg] thirds), the meta line has " + std::to_string(raw_batch_size); return false; }
+    m.lp_draw = raw_batch_size / 3;
+    return true;
+}
+
+// the launcher refuses such a hop per batch (launch_sample_hop): a server that booted would fail every batch, the pre-sampling epoch first
+bool legion::serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why)
+{
+    for (int32_t h = 0; m.sampling == 1 && h < hops; h++)
+        if (fanout[h] > kDistinctMaxFanout) {
+            why = "LEGION_SAMPLING=distinct takes fan-outs of at most " + std::to_string(kDistinctMaxFanout) + ", hop " + std::to_string(h + 1) + " has " +
+                  std::to_string(fanout[h]) + ": k_sample stages the picks of a tile's rows in static LDS";
+            return false;
+        }
+    return true;
+}

@@ -365,18 +365,24 @@ def test_rows_times_chunks_beyond_int32_is_refused(K):
 # ---------------------------------------------------------------------------------------------------
 # served: the `legion` binary -> ipc_service.get_next_aggregated
 # ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("fan,graph", [([10, 5], "0"), ([5, 4, 3], "0"), ([10, 5], "1"), ([6], "0")])
-def test_server_binary_serves_aggregated_batches(tmp_path, synth, oracle, fan, graph):
+# (the cases that leave LEGION_RUNNER_GATHER at auto keep the ids they had before the parameter)
+@pytest.mark.parametrize("fan,graph,gather", [
+    pytest.param([10, 5], "0", "auto", id="fan0-0"), pytest.param([5, 4, 3], "0", "auto", id="fan1-0"),
+    pytest.param([10, 5], "1", "auto", id="fan2-1"), pytest.param([6], "0", "auto", id="fan3-0"),
+    pytest.param([10, 5], "0", "level", id="fan0-0-level"), pytest.param([10, 5], "0", "all", id="fan0-0-all")])
+def test_server_binary_serves_aggregated_batches(tmp_path, synth, oracle, fan, graph, gather):
     """LEGION_AGG_LAST_HOP=1: a fresh trainer process sees aggregated() == True, get_next raises there, and every batch of the schedule
     (train + valid + test steps, two epochs) through get_next_aggregated equals the oracle's default batch + the NumPy statement.
     graph = 1: the runner's LEGION_BATCH_GRAPH=1 path (sampler graph on stream 0, the sums by a plain call on stream 1 while the next
-    batch's graph overwrites the shared draw buffer)."""
+    batch's graph overwrites the shared draw buffer).  gather = level / all: LEGION_RUNNER_GATHER pinned, so that both ways of the levels
+    below the last are served -- gathered per level in front of the sums, or inside get_feature_kernel_agg -- whichever `auto` picks here."""
     spec = synth.spec_for("products", scale=0.004)
     ds = synth.generate(spec)
     data = str(tmp_path / "ds") + "/"
     synth.write_legion_files(ds, data)
     B, epochs = 512, 2
-    with served(tmp_path, synth.meta_config_line(ds, data, B, 1 << 40, epochs, 0), fan, env=dict(LEGION_BATCH_GRAPH=graph, LEGION_AGG_LAST_HOP="1")) as srv:
+    env = dict(LEGION_BATCH_GRAPH=graph, LEGION_AGG_LAST_HOP="1", **({} if gather == "auto" else dict(LEGION_RUNNER_GATHER=gather)))
+    with served(tmp_path, synth.meta_config_line(ds, data, B, 1 << 40, epochs, 0), fan, env=env) as srv:
         got, = srv.run_clients("ipc_client_modes.py", ["agg", spec.F, epochs, OUT])
         srv.finish()
     H = len(fan)

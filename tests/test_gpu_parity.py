@@ -441,7 +441,7 @@ def test_a_batch_larger_than_the_feature_buffer_is_refused_by_the_trainer_and_na
                                                       (8, 2, 50000, True), (1, 0, None, False), (4, 1, None, False)])
 def test_presampling_cache_pipeline(K, oracle, small_ds, G, mode, chunk_bytes, pcm, monkeypatch):
     # chunk_bytes: force the cache shards to be split into several chunk allocations (default chunk: 1 GiB)
-    # pcm=False: CostModel without the two Intel-PCM counters (what the `legion` server binary does: runner.cpp passes NULL) --
+    # pcm=False: CostModel without the two Intel-PCM counters (what the `legion` server binary does: server.cpp passes NULL) --
     # the PCM-free transaction estimate of SURVEY section 5, computed on the device from AT / QT / indptr, against the oracle's
     if chunk_bytes is not None:
         monkeypatch.setenv("LEGION_SHARD_CHUNK_BYTES", str(chunk_bytes))
