@@ -419,6 +419,21 @@ int GPUMemoryPool_GetSampling(const GPUMemoryPool* p);
 int GPUGraphStorage_SetEdgeWeights(GPUGraphStorage* g, const float* w, int32_t location);
 int GPUGraphStorage_HasEdgeWeights(const GPUGraphStorage* g);
 int GPUGraphStorage_CopyAliasRows(const GPUGraphStorage* g, int32_t dev_id, int64_t e0, int64_t n, uint32_t* thr, int32_t* alias_id);
+/* Weighted sampling without replacement (extension; INTEGRATION.md "Weighted sampling without replacement").  A flag on top of the
+ * weighted kind, not a fourth kind: GetSampling keeps returning 2, the flag is remembered across kinds and acts only while the kind is 2.
+ * With it every row of every GPU_Random_Sampling of the pool, pre-sampling hops included, takes min(m, f) DISTINCT columns, m = its
+ * columns of weight > 0: all of them for m <= f, else the f columns of smallest (key_c, c), key_c = -log((u_c + 0.5) 2^-32) / w_c in fp64
+ * (u_c: a hash of (row, hop, column) and the batch's draw word) -- Efraimidis-Spirakis: successive sampling in proportion to w -- handed
+ * out in ascending column order.  The alias table is not read; the weights themselves are, so the graph must have kept them:
+ * GPUGraphStorage_RetainEdgeWeights(graph, 1) BEFORE GPUGraphStorage_SetEdgeWeights makes that call keep its float32[E] device copy (4 E
+ * bytes per physical device) next to the table; w == NULL drops both; without the call nothing is kept.  Returns 0, or -1 with a sticky
+ * error for a null or unbuilt graph.  Sticky argument errors of GPU_Random_Sampling under the flag, by name: a graph without retained
+ * weights, a fan-out above 64.  A null pool and a switch while the pool is being captured are refused like every mode switch;
+ * LegionBatchGraph_Launch refuses a graph recorded in the other state of the flag.  Nothing is allocated by the pool. */
+int GPUGraphStorage_RetainEdgeWeights(GPUGraphStorage* g, int on);
+int GPUGraphStorage_HasRetainedEdgeWeights(const GPUGraphStorage* g);
+void GPUMemoryPool_SetWeightedDistinct(GPUMemoryPool* p, int on);
+int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
  * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
  * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list
@@ -698,6 +713,11 @@ void legion_lp_draw_probe(void* stream, uint32_t seed, int32_t round, int32_t it
  * column's threshold.  All pointers are device memory. */
 void legion_weighted_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
                            int32_t* k_out, uint32_t* ub_out, int32_t n);
+/* Probe of weighted sampling without replacement, by k_sample's own device functions: for column col[m] of row row[m] of hop hop[m] under
+ * the draw word word[m] (0 = unseeded) and weight w[m] > 0, u_out[m] = the column's hash and key_out[m] = its fp64 key.  All pointers are
+ * device memory. */
+void legion_weighted_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
+                                    uint32_t* u_out, double* key_out, int32_t n);
 uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter);
 uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round);
 /* compute units of the current device as the sampler's persistent grids count them: a hop of more than 4 x this x 1024 slots makes a

@@ -209,6 +209,10 @@ _SIGS = {
     "GPUMemoryPool_GetSampling": (C.c_int, [vp]),
     "GPUGraphStorage_SetEdgeWeights": (C.c_int, [vp, vp, i32]),
     "GPUGraphStorage_HasEdgeWeights": (C.c_int, [vp]),
+    "GPUGraphStorage_RetainEdgeWeights": (C.c_int, [vp, C.c_int]),
+    "GPUGraphStorage_HasRetainedEdgeWeights": (C.c_int, [vp]),
+    "GPUMemoryPool_SetWeightedDistinct": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetWeightedDistinct": (C.c_int, [vp]),
     "GPUGraphStorage_CopyAliasRows": (C.c_int, [vp, i32, i64, i64, vp, vp]),
     "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
     "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
@@ -291,6 +295,7 @@ _SIGS = {
     "legion_seeded_distinct_probe": (None, [vp, u32, i32, i32, vp, vp, vp, i32, vp, i32]),
     "legion_perm_probe": (None, [vp, u32, i32, i32, vp]),
     "legion_weighted_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
+    "legion_weighted_distinct_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
     "legion_lp_draw_probe": (None, [vp, u32, i32, i32, vp, vp, i32, vp, vp, i32]),
     "legion_seeded_draw_word": (u32, [u32, i32, i32]),
     "legion_seeded_shuffle_key": (u32, [u32, i32]),
@@ -376,11 +381,13 @@ class Engine:
     ``indptr`` / ``indices`` / ``features`` may be numpy arrays (copied to the chosen location)
     or integer device pointers (``*_location`` = LOC_DEVICE).  ``edge_weights``: float32[E], one weight per CSR entry
     (GPUGraphStorage_SetEdgeWeights: the graph's alias table, what sample="weighted" draws from); set_edge_weights() replaces or drops it.
+    ``retain_edge_weights=True`` (GPUGraphStorage_RetainEdgeWeights): every table build keeps the weights on the device beside the
+    table, which run_batch(sample="weighted", weighted_distinct=True) reads.
     """
 
     def __init__(self, indptr, indices, features, V, F, seeds, batch_size, fanout, G=1,
                  csr_location=LOC_DEVICE, features_location=LOC_DEVICE, cache_memory=0, train_step=1, epoch=1,
-                 pipeline_depth=1, E=None, local_devs=None, features_pitch=0, edge_weights=None):
+                 pipeline_depth=1, E=None, local_devs=None, features_pitch=0, edge_weights=None, retain_edge_weights=False):
         L = lib()
         # one process per GPU: the other members of the clique are remote (legion_set_remote_device)
         self.local_devs = list(range(int(G))) if local_devs is None else list(local_devs)
@@ -454,6 +461,9 @@ class Engine:
         self.cache = L.NewGPUCache()
         L.GPUCache_Initialize(self.cache, int(cache_memory), 0, self.F, int(train_step), self.G)
         check()
+        if retain_edge_weights:
+            L.GPUGraphStorage_RetainEdgeWeights(self.graph, 1)
+            check()
         if edge_weights is not None:
             self.set_edge_weights(edge_weights)
         self.depth = int(pipeline_depth)
@@ -500,6 +510,9 @@ class Engine:
     def has_edge_weights(self):
         return bool(self.L.GPUGraphStorage_HasEdgeWeights(self.graph))
 
+    def has_retained_edge_weights(self):
+        return bool(self.L.GPUGraphStorage_HasRetainedEdgeWeights(self.graph))
+
     def alias_rows(self, dev=0, e0=0, n=None):
         """(thr uint32[n], alias_id int32[n]): entries [e0, e0 + n) of logical GPU dev's alias table."""
         n = self.E - e0 if n is None else int(n)
@@ -524,8 +537,11 @@ class Engine:
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
-                  seed=None, round=0, lp_draw=0):
-        """lp_draw: 0, or k > 0 (GPUMemoryPool_SetLpDraw, only under a seed): a training batch is 3 k seeds [src | pos | neg], the src third
+                  seed=None, round=0, lp_draw=0, weighted_distinct=False):
+        """weighted_distinct (GPUMemoryPool_SetWeightedDistinct, only with sample="weighted" on an Engine(retain_edge_weights=True)): the
+        weighted draws are without replacement -- min(columns of weight > 0, fan-out) distinct columns per row, by exponential keys.  Set on
+        every call like `sample`.
+        lp_draw: 0, or k > 0 (GPUMemoryPool_SetLpDraw, only under a seed): a training batch is 3 k seeds [src | pos | neg], the src third
         from the round's triple-shuffled training list, pos and neg drawn for this batch.  Set on every call like `seed`; a change re-runs
         GPUMemoryPool_BeginRound.
         seed: None (the reference's draws: the same batch every epoch) or a uint32 (GPUMemoryPool_SetSampleSeed: the batch's draws come
@@ -542,7 +558,7 @@ class Engine:
         block 1 (GPUMemoryPool_SetAggNorm); result() additionally returns `out_deg` int32 [n]."""
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
-        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw)
+        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct)
         self._agg[(dev, pipe)] = agg and gather
         self._norm[(dev, pipe)] = norm and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
@@ -567,7 +583,7 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
-    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0):
+    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
@@ -576,13 +592,17 @@ class Engine:
             raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
         if sample not in ("replace", "distinct", "weighted"):
             raise ValueError("sample: 'replace', 'distinct' or 'weighted'")
+        if weighted_distinct and sample != "weighted":
+            raise ValueError("weighted_distinct=True needs sample='weighted': the flag turns the weighted draws into draws without replacement")
         if sample == "weighted" and not self.has_edge_weights():
             raise ValueError("sample='weighted' needs the Engine's edge_weights (Engine(edge_weights=...) or set_edge_weights())")
+        if weighted_distinct and not self.has_retained_edge_weights():
+            raise ValueError("weighted_distinct=True needs the weights kept on the device: Engine(..., edge_weights=..., retain_edge_weights=True)")
         L, pool = self.L, self.pools[dev]
         L.SetGPUDevice(dev)
         agg = bool(agg) and not is_presc
         norm = int(agg and norm == "both")
-        for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
+        for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("WeightedDistinct", int(bool(weighted_distinct))), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
             if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
                 getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
         self._set_seed(dev, seed, round, stream, lp_draw)
@@ -604,10 +624,11 @@ class Engine:
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0):
+                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
-        run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in."""
+        run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in, and
+        only in the weighted_distinct state it was recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -615,12 +636,13 @@ class Engine:
                 self.streams[dev] = L.d_stream_create()
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
-        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw)
+        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
-                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw)
+                       stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw,
+                       weighted_distinct=weighted_distinct)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:

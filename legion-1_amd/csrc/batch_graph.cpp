@@ -27,7 +27,8 @@ struct LegionBatchGraph {
     // The serving modes the batch was recorded in (the pool refuses to change them during a recording).  A replay is refused only when the
     // pool's seeded state is another by now: the captured k_seed holds list pointers -- the seed set's, or the pool's shuffled copy (shuf_ids,
     // when the recording read it) --, so the graph only replays in that state; the seed, the round and the counter are not part of it
-    // (k_set_cursor carries them into ctl).  Likewise for lp_draw: the captured k_seed is the instantiation, the k and the row tables of that state.
+    // (k_set_cursor carries them into ctl).  Likewise for lp_draw: the captured k_seed is the instantiation, the k and the row tables of that state;
+    // and for weighted_distinct: the captured k_sample is that state's instantiation, over the alias table or over the retained weights.
     ServeModes modes;
     const int32_t* shuf_ids = nullptr;
 };
@@ -79,6 +80,11 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (g->modes.lp_draw != p->modes.lp_draw) {
         LEGION_ARG_ERROR(g->modes.lp_draw ? "LegionBatchGraph_Launch: the graph was recorded with drawn link-prediction thirds (GPUMemoryPool_SetLpDraw) and the pool is in another lp_draw state now: its k_seed draws the thirds for that k -- record it again"
                                           : "LegionBatchGraph_Launch: the graph was recorded without drawn link-prediction thirds and the pool draws them now (GPUMemoryPool_SetLpDraw): its k_seed reads all three thirds from the list -- record it again");
+        return -1;
+    }
+    if (g->modes.weighted_distinct != p->modes.weighted_distinct) {
+        LEGION_ARG_ERROR(g->modes.weighted_distinct ? "LegionBatchGraph_Launch: the graph was recorded with weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again"
+                                                    : "LegionBatchGraph_Launch: the graph was recorded without weighted sampling without replacement and the pool has the flag on now (GPUMemoryPool_SetWeightedDistinct): its k_sample is another instantiation -- record it again");
         return -1;
     }
     if (g->shuf_ids && (g->shuf_ids != p->shuf_ids || !p->shuf_valid)) {

@@ -49,6 +49,82 @@ __device__ inline uint32_t weighted_ub(uint32_t key, uint32_t j) { return distin
 __device__ inline int lane_id() { return threadIdx.x & 63; }
 __device__ inline int wave_id() { return threadIdx.x >> 6; }
 
+// Weighted sampling without replacement (INTEGRATION.md "Weighted sampling without replacement"): column c of row i of hop h under draw
+// word w gets the exponential key -log(x_c) / w_c, x_c = (u_c + 0.5) 2^-32, u_c = distinct_u(K, c) under the mode's own row key K; the row's
+// picks are the f eligible (w > 0) columns of smallest (key, column), handed out in ascending column order (Efraimidis-Spirakis).  fp64
+// throughout, and no contraction: the log, the negation and the divide round one by one, as the NumPy statement's do.
+__device__ inline uint32_t weighted_distinct_key(uint32_t row, uint32_t hop, uint32_t w) { return mix32(distinct_key(row, hop, w) ^ 0x27D4EB2Fu); }
+__device__ inline uint32_t weighted_distinct_u(uint32_t key, uint32_t c) { return distinct_u(key, c); }
+__device__ inline double weighted_distinct_x(uint32_t u) { return ((double)u + 0.5) * 0x1p-32; }   // exact, in (0, 1)
+__device__ inline double weighted_distinct_keyval(uint32_t u, float w)   // w > 0, finite: the key is finite and > 0
+{
+#pragma clang fp contract(off)
+    const double l = log(weighted_distinct_x(u));
+    return -l / (double)w;
+}
+// A column that cannot enter a best list whose last key is tk, told without the log: -log(x) >= 1 - x, so key_c >= (1 - x) / w up to the
+// few ulp of the log and the divide; 1 - x is exact in fp64 and the 2^-40 margin is a thousand times those ulp.  Where it matters -- a
+// full list on a long row, tk w << 1 -- the bound is tight: the columns it lets through are about the ones that do enter.  tk = +inf
+// (the list is not full yet) excludes nothing.
+__device__ inline bool weighted_distinct_excluded(uint32_t u, float w, double tk)
+{
+#pragma clang fp contract(off)
+    return 1.0 - weighted_distinct_x(u) > (tk * (double)w) * (1.0 + 0x1p-40);
+}
+// One WAVE resolves one row (every lane of the wave calls this with the same arguments): p[0, min(m, f)) := the row's picks in ascending
+// column order, m = the row's eligible columns; returns min(m, f).  wp: the row's d > 0 weights; p is LDS in k_sample.  The lanes stride
+// over the row in chunks of 64 (coalesced weight reads, no single-lane loop).  Pass 1 counts the eligible columns and compacts the first f
+// of them by ballot prefix -- with m <= f that is the result, and no key is formed.  Pass 2 (m > f) keeps the best list sorted in registers,
+// entry l in lane l: a column whose (key, column) lies in front of entry f - 1 is inserted where the ballot of the entries in front of
+// it ends and the tail moves up one lane; at the end the first f entries are ranked by column.  A chunk forms the key (the fp64 log) only
+// of the columns weighted_distinct_excluded lets through against the list's last key at the chunk's start (the key only falls from there).
+__device__ inline int32_t weighted_distinct_resolve(int32_t* p, const float* __restrict__ wp, int32_t d, int32_t f, uint32_t key)
+{
+    const int lane = lane_id();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const uint32_t ud = (uint32_t)d;
+    uint32_t m = 0;
+    for (uint32_t c0 = 0; c0 < ud; c0 += 64u) {   // uint32: d < 2^31, so c0 + 64 does not wrap
+        const uint32_t c = c0 + (uint32_t)lane;
+        const bool elig = c < ud && wp[c] > 0.0f;
+        const unsigned long long b = __ballot(elig);
+        const uint32_t at = m + (uint32_t)__popcll(b & lt);
+        if (elig && at < (uint32_t)f) p[at] = (int32_t)c;
+        m += (uint32_t)__popcll(b);
+    }
+    if (m <= (uint32_t)f) return (int32_t)m;
+    const double inf = __builtin_huge_val();
+    double bk = inf;              // entry `lane` of the best list: (key, column), sorted ascending; +inf = empty
+    int32_t bc = 0x7FFFFFFF;
+    for (uint32_t c0 = 0; c0 < ud; c0 += 64u) {
+        const uint32_t c = c0 + (uint32_t)lane;
+        const float w = c < ud ? wp[c] : 0.0f;
+        const uint32_t u = weighted_distinct_u(key, c);
+        const double tk0 = __shfl(bk, f - 1);   // by the whole wave, in front of the lanes' own tests
+        bool todo = w > 0.0f && !weighted_distinct_excluded(u, w, tk0);
+        const double k = todo ? weighted_distinct_keyval(u, w) : inf;
+        for (;;) {   // at most 64 rounds: every round retires one lane of the chunk
+            const double tk = __shfl(bk, f - 1);
+            const int32_t tc = __shfl(bc, f - 1);
+            const unsigned long long beat = __ballot(todo && (k < tk || (k == tk && (int32_t)c < tc)));
+            if (!beat) break;
+            const int src = __ffsll((long long)beat) - 1;
+            const double nk = __shfl(k, src);
+            const int32_t nc = __shfl((int32_t)c, src);
+            const int at = __popcll(__ballot(bk < nk || (bk == nk && bc < nc)));   // the entries in front are a prefix of the lanes: at < f
+            const double uk = __shfl_up(bk, 1);
+            const int32_t uc = __shfl_up(bc, 1);
+            if (lane == at) { bk = nk; bc = nc; }
+            else if (lane > at) { bk = uk; bc = uc; }
+            if (lane == src) todo = false;
+        }
+    }
+    int32_t rank = 0;
+    for (int32_t t = 0; t < f; t++) rank += __shfl(bc, t) < bc;
+    if (lane < f) p[rank] = bc;
+    return f;
+}
+
 // Drawn link-prediction thirds (INTEGRATION.md "Drawn link-prediction thirds"): the positive and the negative of slot i of a batch, pure
 // functions of the batch's draw word, the slot and its source.  u is the distinct mode's hash of (key, slot) with the source folded in, so
 // that two GPUs of one job, which share the draw word, do not draw the same negatives.

@@ -125,16 +125,20 @@ struct ServeModes {
     uint32_t seed = 0;           // ... every round ("Seeded sampling").  Seed 0 is a seed like any other: `seeded` says whether there is one
     int32_t lp_draw = 0;         // $LEGION_LP_DRAW=1, only under a seed: k > 0 = a training batch is 3 k seeds whose pos and neg thirds are drawn per batch
                                  // ("Drawn link-prediction thirds"); from the environment it is 1 until serve_modes_resolve_lp_draw puts k there
-    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw; }
+    bool weighted_distinct = false;   // $LEGION_WEIGHTED_DISTINCT=1, only with sampling = weighted: the weighted draws are WITHOUT replacement, min(eligible
+                                 // columns, fan-out) distinct columns per row by exponential keys over the graph's retained edge weights ("Weighted sampling
+                                 // without replacement").  A flag on top of the kind: remembered across kinds, acts only while sampling == 2; not published
+    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct; }
 };
-// The only readers of the five variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
+// The only readers of the six variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
 // unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed, unknown LEGION_LP_DRAW, LEGION_LP_DRAW without a
-// seed.  Host code only, no device is touched.
+// seed, unknown LEGION_WEIGHTED_DISTINCT, LEGION_WEIGHTED_DISTINCT without LEGION_SAMPLING=weighted.  Host code only, no device is touched.
 bool serve_modes_from_env(ServeModes& m, std::string& why);
 // LEGION_LP_DRAW against what is served, once the meta line is known: false with the refusal in `why` unless the training lists are
 // link-prediction thirds (meta flag 2) of a batch size divisible by 3; m.lp_draw := raw_batch_size / 3.  Nothing to do with the mode off.
 bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why);
-// the distinct mode's fan-out bound (kDistinctMaxFanout) against a fan-out list: false with the refusal in `why`
+// the fan-out bound of the distinct mode and of weighted sampling without replacement (kDistinctMaxFanout) against a fan-out list: false
+// with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
 void runner_set_lists_verbatim(Runner* r, bool verbatim);   // before Runner_Initialize: meta flag 2 (Runner::lists_verbatim, runner.cpp)
 // what a trainer reads: the five mode words of the "<name>_ext" object := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
@@ -289,7 +293,8 @@ void launch_advance(hipStream_t s, BatchCtl* ctl);
 int sampler_cu_count();       // compute units every grid is sized by (current device; asked once per process)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling = kSamplingReplace, const AliasEntry* alias = nullptr);
+                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling = kSamplingReplace, const AliasEntry* alias = nullptr,
+                       const float* weights = nullptr);   // weights (with the weighted kind): the graph's retained edge weights = sampling without replacement
 // Weighted sampler mode, the graph's side (build_kernels.hip "alias table").  bad := the number of weights that are negative, NaN or infinite
 // (a device word the caller zeroed); the table of every row of the CSR from w, with p = double[E] of scratch.  Deterministic: the same
 // weights give the same bytes.
@@ -298,6 +303,9 @@ void launch_build_alias(hipStream_t s, const int64_t* indptr, const int32_t* ind
 // k[m] = the column and ub[m] the keep-or-alias word of slot slot[m] of row row[m] of hop hop[m] at degree deg[m] under draw word word[m]
 void launch_weighted_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
                            int32_t* k, uint32_t* ub, int32_t n);
+// weighted sampling without replacement: u[m] and key[m] of column col[m] of row row[m] of hop hop[m] under draw word word[m] at weight w[m] > 0
+void launch_weighted_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
+                                    uint32_t* u, double* key, int32_t n);
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,
                       int32_t op_id, const int32_t* feat_map, int32_t bound);
 void launch_find_topo(hipStream_t s, const int32_t* input_ids, int8_t* part_index, int32_t* part_offset,
@@ -492,6 +500,11 @@ struct GPUGraphStorage {
     // Weighted sampler mode (GPUGraphStorage_SetEdgeWeights): the alias table of the whole CSR per logical GPU, device memory, one copy per
     // physical device like the replicas; empty / null = no weights are set
     std::vector<legion::AliasEntry*> alias;
+    // Weighted sampling without replacement reads the weights themselves: with retain_weights set (GPUGraphStorage_RetainEdgeWeights, before
+    // SetEdgeWeights) the float32[E] device copy the table was built from stays next to the table, shared per physical device in the same
+    // way; empty / null = not retained (the copy is freed after the build, as it always was)
+    std::vector<float*> weights;
+    bool retain_weights = false;
     int32_t csr_location = LEGION_LOC_HOST_PINNED;
     bool owns_csr = false;
     // CSR fragment of one logical GPU (device memory on that GPU's physical device).  Both arrays are chunk lists

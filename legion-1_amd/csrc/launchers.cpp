@@ -169,6 +169,10 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     const bool weighted = p->modes.sampling == kSamplingWeighted;
     const AliasEntry* alias = weighted && dev < (int)graph->alias.size() ? graph->alias[dev] : nullptr;
     if (weighted && !alias) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) over a graph without edge weights on this GPU: call GPUGraphStorage_SetEdgeWeights first"); return; }
+    // ... and without replacement (GPUMemoryPool_SetWeightedDistinct) the weights themselves, which the graph keeps only when asked to
+    const bool wdistinct = weighted && p->modes.weighted_distinct;
+    const float* weights = wdistinct && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
+    if (wdistinct && !weights) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) over a graph without retained edge weights on this GPU: call GPUGraphStorage_RetainEdgeWeights before GPUGraphStorage_SetEdgeWeights"); return; }
     CsrTables csr;
     csr_tables_of(csr, graph, cache, dev, !is_presc && !weighted);   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
     SamplerBuffers b;
@@ -192,7 +196,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.V = p->V;
     b.aux_prepared = p->aux_ready_hop == hop && p->aux_ready_count == count;
     b.next_count = hop < p->hops ? p->fanout[hop] : 0;
-    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->modes.sampling, alias);
+    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->modes.sampling, alias, weights);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint

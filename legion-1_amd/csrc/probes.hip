@@ -67,6 +67,25 @@ __global__ void k_weighted_probe(const int32_t* row, const int32_t* hop, const i
     ub[m] = weighted_ub(key, (uint32_t)slot[m]);
 }
 
+// Weighted sampling without replacement: the hash and the fp64 key of n columns, by the device functions k_sample<.., DISTINCT, WEIGHTED> runs
+__global__ void k_weighted_distinct_probe(const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
+                                          uint32_t* u, double* key, int32_t n)
+{
+    const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
+    if (m >= n) return;
+    const uint32_t uc = weighted_distinct_u(weighted_distinct_key((uint32_t)row[m], (uint32_t)hop[m], word[m]), (uint32_t)col[m]);
+    u[m] = uc;
+    key[m] = weighted_distinct_keyval(uc, w[m]);
+}
+
+void launch_weighted_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
+                                    uint32_t* u, double* key, int32_t n)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_weighted_distinct_probe", LEGION_AW(u), LEGION_AW(key), LEGION_AL(row), LEGION_AL(hop), LEGION_AL(col), LEGION_AL(word), LEGION_AL(w));
+    k_weighted_distinct_probe<<<(n + 255) / 256, 256, 0, s>>>(row, hop, col, word, w, u, key, n);
+    HIP_CHECK_LAST();
+}
 void launch_seeded_distinct_probe(hipStream_t s, uint32_t w, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
 {
     if (n <= 0) return;

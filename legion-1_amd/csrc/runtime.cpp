@@ -258,6 +258,12 @@ void legion_weighted_probe(void* stream, const int32_t* row, const int32_t* hop,
     if (n > 0 && (!row || !hop || !slot || !deg || !word || !k_out || !ub_out)) { LEGION_ARG_ERROR("legion_weighted_probe: null array"); return; }
     launch_weighted_probe((hipStream_t)stream, row, hop, slot, deg, word, k_out, ub_out, n);
 }
+void legion_weighted_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
+                                    uint32_t* u_out, double* key_out, int32_t n)
+{
+    if (n > 0 && (!row || !hop || !col || !word || !w || !u_out || !key_out)) { LEGION_ARG_ERROR("legion_weighted_distinct_probe: null array"); return; }
+    launch_weighted_distinct_probe((hipStream_t)stream, row, hop, col, word, w, u_out, key_out, n);
+}
 void legion_perm_probe(void* stream, uint32_t seed, int32_t round, int32_t n, int32_t* perm_out)
 {
     launch_perm_probe((hipStream_t)stream, seeded_shuffle_key(seed, (uint32_t)round), n, perm_out);

@@ -233,7 +233,12 @@ struct SampleArgs {
     int32_t op_id;
     int32_t window;            // lanes to look back for a repeated draw of the same row: min(count - 1, 8)
     int32_t prefilter_from_op; // first op_id whose claims are preceded by the pre-filter load (4: hop 2; hop 1 never)
-    const AliasEntry* alias;   // WEIGHTED only: the whole CSR's alias table, entry e beside csr.indices[e] (null in the other modes)
+    // One table per weighted instantiation, in one word: growing the struct would move the hidden kernel arguments behind it, and with them
+    // one load of every instantiation.
+    union {
+        const AliasEntry* alias;   // WEIGHTED only: the whole CSR's alias table, entry e beside csr.indices[e] (null in the other modes)
+        const float* weights;      // DISTINCT && WEIGHTED only: the graph's retained edge weights, w[e] beside csr.indices[e]; the alias table is not read
+    };
 };
 
 // One slot's probe + claim on the position table.  Returns the slot's state: -1 = claim pending / won, >= 0 = the neighbour's known final
@@ -279,10 +284,14 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
 // own, so nothing is staged beyond the row descriptors, and the alias entry and the column's neighbour are two loads off the staged row
 // start whose addresses do not depend on each other's result: the slot's dependent chain is as long as the default mode's.  Whole CSR
 // only (PARTITIONED = false): the table lies beside the whole CSR's indices, the fragments have none.
+// DISTINCT && WEIGHTED (GPUMemoryPool_SetWeightedDistinct on top of the weighted kind, INTEGRATION.md "Weighted sampling without
+// replacement"): the row's picks are its f eligible columns of smallest exponential key, staged in s_pick like the distinct mode's -- but
+// one WAVE resolves a row, its lanes striding over the row's retained weights (weighted_distinct_resolve, draws.h), since a single lane
+// would walk a hub's weights alone.  The row's staged degree becomes min(eligible columns, f); the alias table is not read.
 template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
-    static_assert(!(DISTINCT && WEIGHTED) && !(WEIGHTED && PARTITIONED), "one sampling kind per instantiation; weighted draws read the whole CSR");
+    static_assert(!(WEIGHTED && PARTITIONED), "weighted draws read the whole CSR");
     constexpr bool STREAM = !DISTINCT && !WEIGHTED;   // the minstd stream of the default mode
     __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
     __shared__ int32_t s_deg[TILE + 2];
@@ -345,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             s_deg[r] = deg;
             s_src[r] = src;
         }
-        if constexpr (DISTINCT) {
+        if constexpr (DISTINCT && !WEIGHTED) {
             const uint32_t hop = (uint32_t)a.op_id >> 1;
             for (int32_t p = tid; p < nrows * f; p += kBlock) {
                 const uint32_t rr = fdiv((uint32_t)p, a.fdiv);
@@ -353,9 +362,20 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             }
         }
         __syncthreads();
-        if constexpr (DISTINCT) {
+        if constexpr (DISTINCT && !WEIGHTED) {
             for (int32_t r = tid; r < nrows; r += kBlock)
                 if (s_deg[r] > f) distinct_resolve(s_pick + r * f, s_deg[r], f);
+            __syncthreads();
+        }
+        if constexpr (DISTINCT && WEIGHTED) {
+            const uint32_t hop = (uint32_t)a.op_id >> 1;
+            for (int32_t r = wave_id(); r < nrows; r += kBlock / 64) {   // one wave per row: r and everything read through it is wave-uniform
+                const int32_t d = s_deg[r];
+                if (d <= 0) continue;
+                const int32_t got = weighted_distinct_resolve(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), d, f,
+                                                              weighted_distinct_key((uint32_t)(i0 + r), hop, draw));
+                if (lane_id() == 0) s_deg[r] = got;   // what the slot test below reads: min(eligible columns, f)
+            }
             __syncthreads();
         }
 
@@ -370,7 +390,8 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 r = (int32_t)i - i0;
                 const int32_t deg = s_deg[r];
                 if (j < deg) { // deg == -1 for padded (-1) sources; Kernels.cu:385,399
-                    if constexpr (DISTINCT) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
+                    if constexpr (DISTINCT && WEIGHTED) dst = s_row[r][s_pick[r * f + j]];
+                    else if constexpr (DISTINCT) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
                     else if constexpr (WEIGHTED) {
                         const uint32_t key = weighted_key(i, (uint32_t)a.op_id >> 1, draw);
                         const int32_t* col = s_row[r] + weighted_column(key, (uint32_t)j, deg);
@@ -846,7 +867,7 @@ void warm_static_tables() { (void)pow_table(); (void)sampler_cu_count(); }
 
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias)
+                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias, const float* weights)
 {
     const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
@@ -874,11 +895,17 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.count = count; a.op_id = op_id;
     a.window = std::min(count - 1, 8);
     a.prefilter_from_op = 4;   // hop 1 goes straight to the atomic (see k_sample; moving the boundary lost: profiles/r04_sampler.md)
+    const bool wdistinct = sampling == kSamplingWeighted && weights;   // weighted sampling without replacement
     a.alias = sampling == kSamplingWeighted ? alias : nullptr;
+    if (wdistinct) a.weights = weights;
     const bool part = csr.topo_owner != nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices), LEGION_AL(a.alias));
-    if (sampling == kSamplingWeighted) {   // the caller passed whole-CSR tables (csr_tables_of(.., fragments = false)): no topology map
+    if (wdistinct) {                       // whole-CSR tables like the weighted kind's
+        if (is_presc) k_sample<TILE, true, false, true, true><<<grid, kBlock, 0, s>>>(a);
+        else k_sample<TILE, false, false, true, true><<<grid, kBlock, 0, s>>>(a);
+    }
+    else if (sampling == kSamplingWeighted) {   // the caller passed whole-CSR tables (csr_tables_of(.., fragments = false)): no topology map
         if (is_presc) k_sample<TILE, true, false, false, true><<<grid, kBlock, 0, s>>>(a);
         else k_sample<TILE, false, false, false, true><<<grid, kBlock, 0, s>>>(a);
     }
@@ -908,15 +935,16 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
 }
 
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias)
+                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias, const float* weights)
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
     const bool distinct = sampling == kSamplingDistinct;
     if (sampling == kSamplingWeighted && (!alias || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
     if (distinct && count > kDistinctMaxFanout) { LEGION_ARG_ERROR("GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"); return; }
+    if (weights && sampling == kSamplingWeighted && count > kDistinctMaxFanout) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"); return; }
     // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
-    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias);
-    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias);
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias, weights);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias, weights);
 }
 
 } // namespace legion

@@ -1,5 +1,5 @@
 // serve_modes.cpp -- the serving modes as the environment states them: the only readers of LEGION_AGG_LAST_HOP, LEGION_AGG_NORM,
-// LEGION_SAMPLING, LEGION_SAMPLING_SEED and LEGION_LP_DRAW (ServeModes, internal.h).  Host code only: no device is touched.
+// LEGION_SAMPLING, LEGION_SAMPLING_SEED, LEGION_LP_DRAW and LEGION_WEIGHTED_DISTINCT (ServeModes, internal.h).  Host code only: no device is touched.
 #include "internal.h"
 
 #include <cctype>
@@ -23,6 +23,7 @@ static bool parse_seed(const char* n, uint32_t& seed)
 // LEGION_AGG_LAST_HOP: atoi, so anything non-numeric is off.  LEGION_AGG_NORM: unset / empty = plain sums, "both" only on a server that aggregates
 // the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, "distinct" or "weighted".  LEGION_SAMPLING_SEED: unset / empty = off.
 // LEGION_LP_DRAW: unset / empty / "0" = off, "1" only under a seed (k is resolved against the meta line: serve_modes_resolve_lp_draw).
+// LEGION_WEIGHTED_DISTINCT: unset / empty / "0" = off, "1" only with LEGION_SAMPLING=weighted.
 bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
 {
     m = ServeModes();
@@ -51,6 +52,12 @@ bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
         if (!m.seeded) { why = "LEGION_LP_DRAW=1 needs LEGION_SAMPLING_SEED: the thirds are drawn from the batch's draw word"; return false; }
         m.lp_draw = 1;
     }
+    const char* wd = getenv("LEGION_WEIGHTED_DISTINCT");
+    if (wd && wd[0] && strcmp(wd, "0") != 0) {
+        if (strcmp(wd, "1") != 0) { why = std::string("LEGION_WEIGHTED_DISTINCT=") + wd + " is not a known setting: `1` (weighted draws without replacement: distinct columns per row, by edge weight), `0` or unset"; return false; }
+        if (m.sampling != kSamplingWeighted) { why = "LEGION_WEIGHTED_DISTINCT=1 needs LEGION_SAMPLING=weighted: the flag turns the weighted draws into draws without replacement"; return false; }
+        m.weighted_distinct = true;
+    }
     return true;
 }
 
@@ -70,6 +77,12 @@ bool legion::serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, 
         if (fanout[h] > kDistinctMaxFanout) {
             why = "LEGION_SAMPLING=distinct takes fan-outs of at most " + std::to_string(kDistinctMaxFanout) + ", hop " + std::to_string(h + 1) + " has " +
                   std::to_string(fanout[h]) + ": k_sample stages the picks of a tile's rows in static LDS";
+            return false;
+        }
+    for (int32_t h = 0; m.sampling == kSamplingWeighted && m.weighted_distinct && h < hops; h++)
+        if (fanout[h] > kDistinctMaxFanout) {
+            why = "LEGION_WEIGHTED_DISTINCT=1 takes fan-outs of at most " + std::to_string(kDistinctMaxFanout) + ", hop " + std::to_string(h + 1) + " has " +
+                  std::to_string(fanout[h]) + ": k_sample keeps a row's best picks one per lane and stages them in static LDS";
             return false;
         }
     return true;

@@ -423,10 +423,12 @@ bool place_tables(Server* s, const LegionSynthSpec& spec)
 
 // LEGION_SAMPLING=weighted: the graph's edge weights -- `edge_weights` (float32[E], one per entry of edge_dst) beside the dataset's files,
 // generated on the device for a synth: source -- become the graph's alias table on every GPU of the job (GPUGraphStorage_SetEdgeWeights).
-bool load_edge_weights(Server* s)
+// retain (LEGION_WEIGHTED_DISTINCT=1): the weights themselves stay on every GPU beside the table (GPUGraphStorage_RetainEdgeWeights).
+bool load_edge_weights(Server* s, bool retain)
 {
     const Meta& m = s->meta;
     const int64_t E = m.edge_num;
+    if (GPUGraphStorage_RetainEdgeWeights(s->graph, retain ? 1 : 0) != 0) return false;
     if (s->synth) {
         DeviceGuard guard(0);
         float* d_w = nullptr;
@@ -448,6 +450,7 @@ bool load_edge_weights(Server* s)
         if (GPUGraphStorage_SetEdgeWeights(s->graph, w.data(), LEGION_LOC_HOST_PAGEABLE) != 0) return false;
     }
     log_out() << "Edge weights: alias table built in HBM, " << E * 8 / 1e9 << " GB per GPU\n";
+    if (retain) log_out() << "Edge weights: kept in HBM beside the table, " << E * 4 / 1e9 << " GB per GPU (LEGION_WEIGHTED_DISTINCT=1)\n";
     return true;
 }
 
@@ -525,7 +528,7 @@ void Server_Initialize(Server* s, int global_shard_count)
     log_out() << "Finish Partition\n";
     build_storages(s, split);
     if (!place_tables(s, spec)) return;
-    if (modes.sampling == kSamplingWeighted && !load_edge_weights(s)) return;
+    if (modes.sampling == kSamplingWeighted && !load_edge_weights(s, modes.weighted_distinct)) return;
     start_runners(s);
 }
 

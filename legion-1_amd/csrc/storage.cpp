@@ -108,6 +108,7 @@ void GPUGraphStorage_Build(GPUGraphStorage* g, const LegionBuildInfo* info)
     g->view.assign(P, std::vector<bool>(P, false));
     g->d_frag_tab.assign(P, nullptr);
     g->alias.assign(P, nullptr);
+    g->weights.assign(P, nullptr);
     // chunk geometry of the fragments: powers of two that fit shard_chunk_bytes()
     g->row_shift = chunk_shift(sizeof(int64_t), 4);
     g->edge_shift = chunk_shift(sizeof(int32_t), 4);
@@ -222,8 +223,9 @@ int64_t GPUGraphStorage_ReplicateToDevices(GPUGraphStorage* g)
 
 // ---- weighted sampler mode: the graph's edge weights as an alias table (INTEGRATION.md "Weighted sampling") ----
 // The table of the whole CSR on the current device (logical GPU dev), from the weights wherever they lie; null with a sticky error.
-// *bad := the number of refused weights (then nothing is built).  The weights' device copy and the fp64 scratch are freed before returning.
-static AliasEntry* build_alias_here(const GPUGraphStorage* g, int dev, const float* w, unsigned long long* bad)
+// *bad := the number of refused weights (then nothing is built).  The fp64 scratch is freed before returning, and so is the weights' device
+// copy -- unless `kept` is given and the table was built: then *kept := the copy (weighted sampling without replacement reads it).
+static AliasEntry* build_alias_here(const GPUGraphStorage* g, int dev, const float* w, unsigned long long* bad, float** kept)
 {
     const int64_t E = g->edge_num;
     float* d_w = nullptr;
@@ -252,6 +254,7 @@ static AliasEntry* build_alias_here(const GPUGraphStorage* g, int dev, const flo
     }
     if (d_p) (void)hipFree(d_p);
     if (d_bad) (void)hipFree(d_bad);
+    if (kept && table) { *kept = d_w; d_w = nullptr; }
     if (d_w) (void)hipFree(d_w);
     return table;
 }
@@ -262,37 +265,59 @@ int GPUGraphStorage_SetEdgeWeights(GPUGraphStorage* g, const float* w, int32_t l
     if (w && location != LEGION_LOC_HOST_PINNED && location != LEGION_LOC_DEVICE && location != LEGION_LOC_HOST_PAGEABLE) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeWeights: location must be a LEGION_LOC_* value"); return -1; }
     const int P = g->partition_count;
     std::vector<AliasEntry*> fresh(P, nullptr);
+    std::vector<float*> fresh_w(P, nullptr);
     if (w && g->edge_num > 0) {
         std::vector<std::pair<int, AliasEntry*>> per_phys;
+        std::vector<float*> per_phys_w;
         for (int p = 0; p < P; p++) {
             if (is_remote_device(p)) continue;
             const int phys = physical_device(p);
             AliasEntry* have = nullptr;
-            for (auto& e : per_phys) if (e.first == phys) have = e.second;
+            float* have_w = nullptr;
+            for (size_t q = 0; q < per_phys.size(); q++) if (per_phys[q].first == phys) { have = per_phys[q].second; have_w = per_phys_w[q]; }
             if (!have) {
                 DeviceGuard guard(p);
                 unsigned long long bad = 0;
-                have = build_alias_here(g, p, w, &bad);
+                have = build_alias_here(g, p, w, &bad, g->retain_weights ? &have_w : nullptr);
                 if (!have) {   // refused or failed: the earlier table stays
                     if (bad && !error_pending())
                         LEGION_ARG_ERROR(("GPUGraphStorage_SetEdgeWeights: " + std::to_string(bad) + " of " + std::to_string(g->edge_num) +
                                           " edge weights are negative, NaN or infinite: weights must be finite and >= 0 (the earlier table, if any, stays)").c_str());
                     else if (!error_pending()) LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeWeights: building the alias table failed");
                     free_replicas(fresh);
+                    free_replicas(fresh_w);
                     return -1;
                 }
                 per_phys.emplace_back(phys, have);
+                per_phys_w.push_back(have_w);
             }
             LEGION_AUDIT_SHARE(have, p);
             fresh[p] = have;
+            if (have_w) { LEGION_AUDIT_SHARE(have_w, p); fresh_w[p] = have_w; }
         }
     }
     // batches that read the earlier table may still be in flight
     for (int p = 0; p < P; p++)
         if (g->alias[p] && !is_remote_device(p)) { DeviceGuard guard(p); HIP_CHECK(hipDeviceSynchronize()); }
     free_replicas(g->alias);
+    free_replicas(g->weights);
     g->alias = fresh;
+    g->weights = fresh_w;
     return error_pending() ? -1 : 0;
+}
+// Before GPUGraphStorage_SetEdgeWeights: that call keeps (on != 0) the weights' float32[E] device copy on every physical device, next to
+// the alias table, for weighted sampling without replacement.  It changes nothing that is already built; dropping the table drops the copy.
+int GPUGraphStorage_RetainEdgeWeights(GPUGraphStorage* g, int on)
+{
+    if (!g || g->alias.empty()) { LEGION_ARG_ERROR("GPUGraphStorage_RetainEdgeWeights: null graph, or GPUGraphStorage_Build was not called"); return -1; }
+    g->retain_weights = on != 0;
+    return 0;
+}
+int GPUGraphStorage_HasRetainedEdgeWeights(const GPUGraphStorage* g)
+{
+    if (!g) return 0;
+    for (const float* t : g->weights) if (t) return 1;
+    return 0;
 }
 int GPUGraphStorage_HasEdgeWeights(const GPUGraphStorage* g)
 {
@@ -320,6 +345,7 @@ void GPUGraphStorage_Finalize(GPUGraphStorage* g)
 {
     if (!g) return;
     free_replicas(g->alias);
+    free_replicas(g->weights);
     free_replicas(g->replica_indptr);
     free_replicas(g->replica_indices);
     for (size_t i = 0; i < g->frag.size(); i++) {
@@ -632,7 +658,7 @@ void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, in
 }
 int32_t GPUMemoryPool_NumIds(const GPUMemoryPool* p) { return p->num_ids; }
 
-// The five mode setters: the pool's modes with one field changed, through pool_apply_modes (internal.h: what is refused, what is
+// The mode setters: the pool's modes with one field changed, through pool_apply_modes (internal.h: what is refused, what is
 // allocated).  Call them under the device the pool's scratch lives on.  Aggregated last hop: INTEGRATION.md "Aggregated last hop";
 // norm: 0 = plain sums, 1 = out-degree rsqrt ("Normalised sums"); distinct draws: "Sampling without replacement", nothing is allocated;
 // seed: "Seeded sampling", seed 0 is a seed like any other, nothing is allocated here (GPUMemoryPool_BeginRound fills the shuffled copy);
@@ -646,6 +672,10 @@ void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on) { ServeModes m = 
 // nothing is allocated here, the alias table belongs to the graph: GPUGraphStorage_SetEdgeWeights)
 void GPUMemoryPool_SetSampling(GPUMemoryPool* p, int kind) { ServeModes m = modes_of(p); m.sampling = kind; pool_apply_modes(p, m, "GPUMemoryPool_SetSampling"); }
 int GPUMemoryPool_GetSampling(const GPUMemoryPool* p) { return p ? p->modes.sampling : 0; }
+// weighted sampling without replacement ("Weighted sampling without replacement"): a flag on top of the weighted kind, remembered across
+// kinds and acting only while the kind is 2; nothing is allocated here, the weights belong to the graph (GPUGraphStorage_RetainEdgeWeights)
+void GPUMemoryPool_SetWeightedDistinct(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.weighted_distinct = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetWeightedDistinct"); }
+int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p) { return p && p->modes.weighted_distinct ? 1 : 0; }
 void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {
     ServeModes m = modes_of(p);

@@ -59,6 +59,9 @@ def main(argv=None):
                     "draws afresh and the training list is reshuffled every epoch; without it every epoch is the same epoch, like the reference's")
     ap.add_argument("--lp_draw", action="store_true", help="extension (LEGION_LP_DRAW=1 for the server; needs --seed_lists and --sampling_seed): "
                     "the [src | pos | neg] triples are reshuffled every epoch and every batch draws its pos and neg thirds afresh")
+    ap.add_argument("--weighted-distinct", "--weighted_distinct", dest="weighted_distinct", action="store_true", help="extension "
+                    "(LEGION_WEIGHTED_DISTINCT=1 for the server; needs --sampling weighted): the weighted draws are without replacement, "
+                    "min(neighbours of weight > 0, fan-out) distinct neighbours per row; the server keeps the weights in HBM beside the alias table")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
@@ -76,6 +79,8 @@ def main(argv=None):
         env["LEGION_SAMPLING_SEED"] = str(args.sampling_seed)
     if args.lp_draw:
         env["LEGION_LP_DRAW"] = "1"
+    if args.weighted_distinct:
+        env["LEGION_WEIGHTED_DISTINCT"] = "1"
     return subprocess.call(cmd, env=env)
 
 
