@@ -130,6 +130,17 @@ struct ServeModes {
                                  // without replacement").  A flag on top of the kind: remembered across kinds, acts only while sampling == 2; not published
     bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct; }
 };
+// The draw rule of a sampler hop: what `sampling` and `weighted_distinct` say together.  draw_rule_of is the one place that reads the two; the
+// launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
+enum class DrawRule { Stream, Distinct, Weighted, WeightedDistinct };
+inline DrawRule draw_rule_of(const ServeModes& m)
+{
+    return m.sampling == kSamplingWeighted ? (m.weighted_distinct ? DrawRule::WeightedDistinct : DrawRule::Weighted) : m.sampling == kSamplingDistinct ? DrawRule::Distinct : DrawRule::Stream;
+}
+// the rule's table (alias table, retained weights) lies beside the whole CSR's indices: never the fragments, exactly as pre-sampling
+constexpr bool draw_rule_whole_csr(DrawRule r) { return r == DrawRule::Weighted || r == DrawRule::WeightedDistinct; }
+// the largest fan-out the rule runs (k_sample<.., DISTINCT, ..> stages a row's picks in static LDS); 0 = no bound
+constexpr int32_t draw_rule_max_fanout(DrawRule r) { return r == DrawRule::Distinct || r == DrawRule::WeightedDistinct ? kDistinctMaxFanout : 0; }
 // The only readers of the six variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
 // unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed, unknown LEGION_LP_DRAW, LEGION_LP_DRAW without a
 // seed, unknown LEGION_WEIGHTED_DISTINCT, LEGION_WEIGHTED_DISTINCT without LEGION_SAMPLING=weighted.  Host code only, no device is touched.
@@ -137,8 +148,7 @@ bool serve_modes_from_env(ServeModes& m, std::string& why);
 // LEGION_LP_DRAW against what is served, once the meta line is known: false with the refusal in `why` unless the training lists are
 // link-prediction thirds (meta flag 2) of a batch size divisible by 3; m.lp_draw := raw_batch_size / 3.  Nothing to do with the mode off.
 bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why);
-// the fan-out bound of the distinct mode and of weighted sampling without replacement (kDistinctMaxFanout) against a fan-out list: false
-// with the refusal in `why`
+// the fan-out bound of the modes' draw rule (draw_rule_max_fanout) against a fan-out list: false with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
 void runner_set_lists_verbatim(Runner* r, bool verbatim);   // before Runner_Initialize: meta flag 2 (Runner::lists_verbatim, runner.cpp)
 // what a trainer reads: the five mode words of the "<name>_ext" object := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
@@ -217,7 +227,15 @@ __host__ __device__ inline uint32_t seeded_perm(uint32_t g, uint32_t n, uint32_t
 struct FastDiv {
     uint32_t d = 1, m = 0, s = 0;
     FastDiv() = default;
-    explicit FastDiv(uint32_t div);
+    __host__ __device__ explicit FastDiv(uint32_t div)
+    {
+        d = div ? div : 1;
+        if (d == 1) { m = 0; s = 0; return; }
+        uint32_t l = 0;
+        while ((1ull << l) < d) l++;
+        m = (uint32_t)(((1ull << (31 + l)) / d) + 1ull);
+        s = 31 + l;
+    }
 };
 
 // ---- kernel launch API (sampler.hip, gather.hip, build_kernels.hip, sort_scan.hip, probes.hip) -------------------------------------------------------------
@@ -279,11 +297,20 @@ struct LpDrawArgs {
     int32_t V = 0;                 // negatives are uniform on [0, V); V <= entries of the position table
     CsrTables csr = {};            // where the positive's row is read: as the sampler would read it on this GPU
 };
-// lp: null = the default mode (the instantiation that ran before the mode existed)
-void launch_seed(hipStream_t s, int32_t* batch_ids, int32_t* labels, int32_t batch_size, int32_t size, int32_t counter,
-                 const int32_t* all_ids, const int32_t* all_labels, int32_t total_cap, pos_t* pos_map,
-                 uint32_t epoch, BatchCtl* ctl, bool self_driven, int32_t* nc, int32_t* ec, int32_t* aux_next,
-                 int32_t f_next, int32_t aux_cap, uint32_t seeded = 0, uint32_t draw_key = 0, const LpDrawArgs* lp = nullptr);
+// k_seed's operands; lp: null = the default mode (the instantiation that ran before the mode existed).  A self-driven launch (a captured batch
+// graph) reads counter and epoch from ctl, computes the clamped size on the device and is sized for a full batch.
+struct SeedArgs {
+    int32_t *batch_ids, *labels;
+    int32_t batch_size, size, counter, total_cap;
+    const int32_t *all_ids, *all_labels;
+    pos_t* pos_map;
+    BatchCtl* ctl;
+    int32_t *nc, *ec, *aux_next;
+    int32_t f_next, aux_cap;
+    uint32_t epoch, seeded, draw_key;
+    const LpDrawArgs* lp;
+};
+void launch_seed(hipStream_t s, const SeedArgs& a, bool self_driven);
 void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded = 0, uint32_t draw_key = 0);
 // out_ids[g] = ids[perm(g)], out_labels[g] = labels[perm(g)] for g < n under shuffle key ks (seeded_perm)
 void launch_shuffle_seeds(hipStream_t s, const int32_t* ids, const int32_t* labels, int32_t n, uint32_t ks, int32_t* out_ids, int32_t* out_labels);
@@ -292,9 +319,11 @@ void launch_shuffle_triples(hipStream_t s, const int32_t* ids, const int32_t* la
 void launch_advance(hipStream_t s, BatchCtl* ctl);
 int sampler_cu_count();       // compute units every grid is sized by (current device; asked once per process)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
+// What a hop draws by: the rule and its tables beside the whole CSR -- the alias table (both weighted rules; Weighted reads it) and the graph's
+// retained edge weights (WeightedDistinct reads them); null under the other rules.  Resolved from (graph, modes, device) in launchers.cpp.
+struct DrawTables { DrawRule rule; const AliasEntry* alias; const float* weights; };
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling = kSamplingReplace, const AliasEntry* alias = nullptr,
-                       const float* weights = nullptr);   // weights (with the weighted kind): the graph's retained edge weights = sampling without replacement
+                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw);
 // Weighted sampler mode, the graph's side (build_kernels.hip "alias table").  bad := the number of weights that are negative, NaN or infinite
 // (a device word the caller zeroed); the table of every row of the CSR from w, with p = double[E] of scratch.  Deterministic: the same
 // weights give the same bytes.

@@ -58,6 +58,19 @@ static void csr_tables_of(CsrTables& csr, const GPUGraphStorage* graph, const GP
     }
 }
 
+// What logical GPU `dev` draws a hop by under `modes`: the rule, and the alias table and -- without replacement, which the graph keeps them
+// for only when asked to -- the weights beside the whole CSR.  False (sticky error): the graph lacks the rule's table on this GPU.
+static bool draw_tables_of(DrawTables& t, const GPUGraphStorage* graph, const ServeModes& modes, int dev)
+{
+    t.rule = draw_rule_of(modes);
+    const bool weighted = draw_rule_whole_csr(t.rule), wdistinct = t.rule == DrawRule::WeightedDistinct;
+    t.alias = weighted && dev < (int)graph->alias.size() ? graph->alias[dev] : nullptr;
+    t.weights = wdistinct && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
+    if (weighted && !t.alias) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) over a graph without edge weights on this GPU: call GPUGraphStorage_SetEdgeWeights first"); return false; }
+    if (wdistinct && !t.weights) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) over a graph without retained edge weights on this GPU: call GPUGraphStorage_RetainEdgeWeights before GPUGraphStorage_SetEdgeWeights"); return false; }
+    return true;
+}
+
 extern "C" {
 
 // batch_generator_kernel, Kernels.cu:162-232
@@ -120,32 +133,31 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     }
     p->device_id = dev_id;
     p->sampled_hop = 0; p->sampled_presc = false; p->levels_gathered = 0;
+    SeedArgs a;
+    a.batch_ids = p->sampled_ids[q]; a.labels = p->labels[q]; a.batch_size = batch_size;
+    a.all_ids = all_ids; a.all_labels = all_labels; a.total_cap = total_cap;
+    a.pos_map = p->pos_map; a.ctl = p->ctl; a.nc = p->node_counter[q]; a.ec = p->edge_counter[q];
+    a.aux_next = p->aux2[1]; a.f_next = p->fanout[0]; a.aux_cap = p->max_slots;
+    a.seeded = seeded; a.draw_key = draw_key; a.lp = lp;
     if (p->capturing) {
         // Recording a batch graph: cursor, epoch and the clamped size (Kernels.cu:224) are read / computed on the
         // device, `counter` is ignored, bounds are those of a full batch.
-        if (batch_size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
-        launch_seed(s, p->sampled_ids[q], p->labels[q], batch_size, batch_size, 0, all_ids, all_labels, total_cap, p->pos_map, 0,
-                    p->ctl, true, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key, lp);
-        p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0];
-        p->bound_n = batch_size > 0 ? batch_size : 0;
-        p->bound_nodes = p->bound_n;
-        return;
+        a.size = batch_size; a.counter = 0; a.epoch = 0;
+    } else {
+        // A new batch = a new epoch of the position table: entries of older batches become stale without
+        // touching them (replaces cudaMemsetAsync(accessed_map) + ClearPosMap, Kernels.cu:216,750-756).
+        if (++p->batch_serial >= kSerialLimit) { // epoch space exhausted: wipe once and start over
+            HIP_CHECK(hipMemsetAsync(p->pos_map, 0xFF, (size_t)p->V * sizeof(pos_t), s));
+            p->batch_serial = 1;
+        }
+        p->ctl_synced = false; // k_seed publishes (counter, epoch) of THIS batch: a batch graph must reset the cursor
+        a.size = ((batch_size * (counter + 1)) >= total_cap) ? (total_cap - batch_size * counter) : batch_size;   // Kernels.cu:224
+        a.counter = counter; a.epoch = kEpochTop - p->batch_serial;
     }
-    // A new batch = a new epoch of the position table: entries of older batches become stale without
-    // touching them (replaces cudaMemsetAsync(accessed_map) + ClearPosMap, Kernels.cu:216,750-756).
-    if (++p->batch_serial >= kSerialLimit) { // epoch space exhausted: wipe once and start over
-        HIP_CHECK(hipMemsetAsync(p->pos_map, 0xFF, (size_t)p->V * sizeof(pos_t), s));
-        p->batch_serial = 1;
-    }
-    const uint32_t epoch = kEpochTop - p->batch_serial;
-    p->ctl_synced = false; // k_seed publishes (counter, epoch) of THIS batch: a batch graph must reset the cursor
-    // Kernels.cu:224
-    int32_t size = ((batch_size * (counter + 1)) >= total_cap) ? (total_cap - batch_size * counter) : batch_size;
-    if (size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
-    launch_seed(s, p->sampled_ids[q], p->labels[q], batch_size, size, counter, all_ids, all_labels, total_cap, p->pos_map, epoch,
-                p->ctl, false, p->node_counter[q], p->edge_counter[q], p->aux2[1], p->fanout[0], p->max_slots, seeded, draw_key, lp);
+    if (a.size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
+    launch_seed(s, a, p->capturing);
     p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0]; // k_seed prepared the slot states of hop 1
-    p->bound_n = size > 0 ? size : 0;
+    p->bound_n = a.size > 0 ? a.size : 0;
     p->bound_nodes = p->bound_n;
 }
 
@@ -165,16 +177,10 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     if (slots > p->max_slots) { LEGION_ARG_ERROR("GPU_Random_Sampling: fan-out exceeds what the pool was sized for"); return; }
     if (slots <= 0) return;
 
-    // weighted draws read the graph's alias table, which lies beside the whole CSR: never the fragments, exactly as pre-sampling
-    const bool weighted = p->modes.sampling == kSamplingWeighted;
-    const AliasEntry* alias = weighted && dev < (int)graph->alias.size() ? graph->alias[dev] : nullptr;
-    if (weighted && !alias) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) over a graph without edge weights on this GPU: call GPUGraphStorage_SetEdgeWeights first"); return; }
-    // ... and without replacement (GPUMemoryPool_SetWeightedDistinct) the weights themselves, which the graph keeps only when asked to
-    const bool wdistinct = weighted && p->modes.weighted_distinct;
-    const float* weights = wdistinct && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
-    if (wdistinct && !weights) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) over a graph without retained edge weights on this GPU: call GPUGraphStorage_RetainEdgeWeights before GPUGraphStorage_SetEdgeWeights"); return; }
+    DrawTables draw;
+    if (!draw_tables_of(draw, graph, p->modes, dev)) return;
     CsrTables csr;
-    csr_tables_of(csr, graph, cache, dev, !is_presc && !weighted);   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
+    csr_tables_of(csr, graph, cache, dev, !is_presc && !draw_rule_whole_csr(draw.rule));   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
     SamplerBuffers b;
     const int q = p->current_pipe;
     b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];
@@ -196,7 +202,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.V = p->V;
     b.aux_prepared = p->aux_ready_hop == hop && p->aux_ready_count == count;
     b.next_count = hop < p->hops ? p->fanout[hop] : 0;
-    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, p->modes.sampling, alias, weights);
+    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, draw);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint

@@ -463,18 +463,6 @@ __device__ inline int32_t win_rank(int32_t v) { return -2 - v - kWinBase; }
 // shared reads per workgroup instead of every tile count: 35-70 KB at 4-9 k tiles, re-read by all 1536 workgroups at once -- one such prefix
 // build cost 6.8 / 16.3 us per launch at the papers100M / products hop 3, profiles/r04_sampler.md) and adds tile_pre[t] of any tile it needs.
 // kMaxChunks (internal.h) >= the largest k_mark grid (256 CUs x 8 workgroups); GPUMemoryPool_AllocateScratch sizes chunk_tot with it.
-__host__ __device__ inline FastDiv make_fastdiv(uint32_t div)
-{
-    FastDiv f;
-    f.d = div ? div : 1;
-    if (f.d == 1) { f.m = 0; f.s = 0; return f; }
-    uint32_t l = 0;
-    while ((1ull << l) < f.d) l++;
-    f.m = (uint32_t)(((1ull << (31 + l)) / f.d) + 1ull);
-    f.s = 31 + l;
-    return f;
-}
-
 template <int TILE>
 __global__ __launch_bounds__(kBlock) void k_mark(const int32_t* __restrict__ nc, const int32_t* __restrict__ ec,
                                                  int32_t count, int32_t* __restrict__ aux, const int32_t* __restrict__ tile_edge,
@@ -658,7 +646,7 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
     if ((int32_t)blockIdx.x >= n_tiles) return;
     const int32_t T = (n_tiles + a.mark_grid - 1) / a.mark_grid;   // tiles per chunk, as k_mark derived it
     if (threadIdx.x == 0) {                                        // one 64-bit divide per workgroup (T is device-side: no host round trip)
-        const FastDiv f = make_fastdiv((uint32_t)T);
+        const FastDiv f((uint32_t)T);
         s_div_t[0] = f.d; s_div_t[1] = f.m; s_div_t[2] = f.s;
     }
     const int32_t n_chunks = (n_tiles + T - 1) / T;                // <= mark_grid <= kMaxChunks
@@ -781,16 +769,6 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
 // ------------------------------------------------------------------------------------------------
 // host side: launch wrappers
 // ------------------------------------------------------------------------------------------------
-FastDiv::FastDiv(uint32_t div)
-{
-    d = div ? div : 1;
-    if (d == 1) { m = 0; s = 0; return; }
-    uint32_t l = 0;
-    while ((1ull << l) < d) l++;
-    m = (uint32_t)(((1ull << (31 + l)) / d) + 1ull);
-    s = 31 + l;
-}
-
 // compute units of the current device, asked once per process (launch.h's grid_for sizes every grid by it)
 int sampler_cu_count()
 {
@@ -824,17 +802,18 @@ static uint32_t* pow_table()
     return tabs[dev];
 }
 
-void launch_seed(hipStream_t s, int32_t* batch_ids, int32_t* labels, int32_t batch_size, int32_t size, int32_t counter,
-                 const int32_t* all_ids, const int32_t* all_labels, int32_t total_cap, pos_t* pos_map,
-                 uint32_t epoch, BatchCtl* ctl, bool self_driven, int32_t* nc, int32_t* ec, int32_t* aux_next,
-                 int32_t f_next, int32_t aux_cap, uint32_t seeded, uint32_t draw_key, const LpDrawArgs* lp)
+void launch_seed(hipStream_t s, const SeedArgs& a, bool self_driven)
 {
-    const int32_t bound = self_driven ? batch_size : size;
+    const int32_t bound = self_driven ? a.batch_size : a.size;
     int blocks = bound > 0 ? (bound - 1) / kBlock + 1 : 1;
+    // the audit names an argument by its expression: the pointers under k_seed's parameter names
+    int32_t *batch_ids = a.batch_ids, *labels = a.labels, *nc = a.nc, *ec = a.ec, *aux_next = a.aux_next;
+    const int32_t *all_ids = a.all_ids, *all_labels = a.all_labels;
+    pos_t* pos_map = a.pos_map; BatchCtl* ctl = a.ctl;
     LEGION_AUDIT_LAUNCH(s, "k_seed", LEGION_AW(batch_ids), LEGION_AW(labels), LEGION_AW(pos_map), LEGION_AW(ctl), LEGION_AW(nc), LEGION_AW(ec), LEGION_AW(aux_next), LEGION_AL(all_ids), LEGION_AL(all_labels));
-    const LpDrawArgs a = lp ? *lp : LpDrawArgs{};
-    auto* k = lp ? (self_driven ? k_seed<true, true> : k_seed<false, true>) : (self_driven ? k_seed<true, false> : k_seed<false, false>);
-    k<<<blocks, kBlock, 0, s>>>(batch_ids, labels, batch_size, size, counter, all_ids, all_labels, total_cap, pos_map, epoch, ctl, nc, ec, aux_next, f_next, aux_cap, seeded, draw_key, a);
+    const LpDrawArgs lp = a.lp ? *a.lp : LpDrawArgs{};
+    auto* k = a.lp ? (self_driven ? k_seed<true, true> : k_seed<false, true>) : (self_driven ? k_seed<true, false> : k_seed<false, false>);
+    k<<<blocks, kBlock, 0, s>>>(batch_ids, labels, a.batch_size, a.size, a.counter, all_ids, all_labels, a.total_cap, pos_map, a.epoch, ctl, nc, ec, aux_next, a.f_next, a.aux_cap, a.seeded, a.draw_key, lp);
     HIP_CHECK_LAST();
 }
 void launch_set_cursor(hipStream_t s, BatchCtl* ctl, int32_t counter, uint32_t epoch, uint32_t seeded, uint32_t draw_key)
@@ -867,7 +846,7 @@ void warm_static_tables() { (void)pow_table(); (void)sampler_cu_count(); }
 
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias, const float* weights)
+                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw)
 {
     const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
@@ -895,28 +874,18 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.count = count; a.op_id = op_id;
     a.window = std::min(count - 1, 8);
     a.prefilter_from_op = 4;   // hop 1 goes straight to the atomic (see k_sample; moving the boundary lost: profiles/r04_sampler.md)
-    const bool wdistinct = sampling == kSamplingWeighted && weights;   // weighted sampling without replacement
-    a.alias = sampling == kSamplingWeighted ? alias : nullptr;
-    if (wdistinct) a.weights = weights;
-    const bool part = csr.topo_owner != nullptr;
+    if (draw.rule == DrawRule::WeightedDistinct) a.weights = draw.weights;
+    else a.alias = draw.rule == DrawRule::Weighted ? draw.alias : nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices), LEGION_AL(a.alias));
-    if (wdistinct) {                       // whole-CSR tables like the weighted kind's
-        if (is_presc) k_sample<TILE, true, false, true, true><<<grid, kBlock, 0, s>>>(a);
-        else k_sample<TILE, false, false, true, true><<<grid, kBlock, 0, s>>>(a);
-    }
-    else if (sampling == kSamplingWeighted) {   // the caller passed whole-CSR tables (csr_tables_of(.., fragments = false)): no topology map
-        if (is_presc) k_sample<TILE, true, false, false, true><<<grid, kBlock, 0, s>>>(a);
-        else k_sample<TILE, false, false, false, true><<<grid, kBlock, 0, s>>>(a);
-    }
-    else if (sampling == kSamplingDistinct) {
-        if (is_presc) k_sample<TILE, true, false, true, false><<<grid, kBlock, 0, s>>>(a);
-        else if (part) k_sample<TILE, false, true, true, false><<<grid, kBlock, 0, s>>>(a);
-        else k_sample<TILE, false, false, true, false><<<grid, kBlock, 0, s>>>(a);
-    }
-    else if (is_presc) k_sample<TILE, true, false, false, false><<<grid, kBlock, 0, s>>>(a);
-    else if (part) k_sample<TILE, false, true, false, false><<<grid, kBlock, 0, s>>>(a);
-    else k_sample<TILE, false, false, false, false><<<grid, kBlock, 0, s>>>(a);
+    // The instantiation by [whole CSR / pre-sampling / the clique's fragments][rule]; the rules that draw from the whole CSR only have no
+    // partitioned one (launch_sample_hop refuses such tables).  A pre-sampling hop gets whole-CSR tables, so it is never partitioned.
+    static constexpr void (*kSample[][4])(SampleArgs) = {
+        {k_sample<TILE, false, false, false, false>, k_sample<TILE, false, false, true, false>, k_sample<TILE, false, false, false, true>, k_sample<TILE, false, false, true, true>},
+        {k_sample<TILE, true, false, false, false>, k_sample<TILE, true, false, true, false>, k_sample<TILE, true, false, false, true>, k_sample<TILE, true, false, true, true>},
+        {k_sample<TILE, false, true, false, false>, k_sample<TILE, false, true, true, false>, nullptr, nullptr}};
+    static_assert((int)DrawRule::Stream == 0 && (int)DrawRule::Distinct == 1 && (int)DrawRule::Weighted == 2 && (int)DrawRule::WeightedDistinct == 3, "kSample's columns");
+    kSample[is_presc ? 1 : csr.topo_owner ? 2 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
     k_mark<TILE><<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
@@ -935,16 +904,20 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
 }
 
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, int32_t sampling, const AliasEntry* alias, const float* weights)
+                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw)
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
-    const bool distinct = sampling == kSamplingDistinct;
-    if (sampling == kSamplingWeighted && (!alias || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
-    if (distinct && count > kDistinctMaxFanout) { LEGION_ARG_ERROR("GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"); return; }
-    if (weights && sampling == kSamplingWeighted && count > kDistinctMaxFanout) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"); return; }
+    // the tables match the rule (launchers.cpp resolved both from the same modes): a kernel never receives a null table, nor fragments without one
+    const void* table = draw.rule == DrawRule::WeightedDistinct ? (const void*)draw.weights : (const void*)draw.alias;
+    if (draw_rule_whole_csr(draw.rule) && (!table || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
+    if (draw_rule_max_fanout(draw.rule) && count > draw_rule_max_fanout(draw.rule)) {
+        LEGION_ARG_ERROR(draw.rule == DrawRule::Distinct ? "GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"
+                                                         : "GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS");
+        return;
+    }
     // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
-    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias, weights);
-    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, sampling, alias, weights);
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw);
 }
 
 } // namespace legion
