@@ -434,6 +434,18 @@ int GPUGraphStorage_RetainEdgeWeights(GPUGraphStorage* g, int on);
 int GPUGraphStorage_HasRetainedEdgeWeights(const GPUGraphStorage* g);
 void GPUMemoryPool_SetWeightedDistinct(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p);
+/* Shared-key sampling (extension; INTEGRATION.md "Shared-key sampling"; layer-neighbour sampling in its fixed-size, bottom-k form).  A
+ * flag on top of the distinct kind, not a fourth kind: GetSampling keeps returning 1, the flag is remembered across kinds and acts only
+ * while the kind is 1.  With it the random number belongs to the NEIGHBOUR NODE, not to the row: under the batch's draw word W (0 on an
+ * unseeded pool) Ks = mix32(W ^ 0x165667B1) and key_c = mix32(nbr[c] ^ Ks); a row of degree d <= f takes every column, a row of d > f its
+ * f columns of smallest (key_c, c), handed out in ascending column order.  Per row that is still a uniform sample of min(d, f) distinct
+ * columns; across rows the picks coincide wherever neighbourhoods overlap, so a batch reaches fewer unique nodes for the same edges.  The
+ * rule reads the row alone: whole CSR, pre-sampling hops and the clique's fragments alike; everything behind the position is the default
+ * mode's.  An unseeded pool is allowed and deterministic: every batch prefers the same nodes (the `legion` server refuses that at boot).
+ * Sticky argument errors, by name: a null pool, a switch while the pool is being captured, a fan-out above 64 under the flag
+ * (GPU_Random_Sampling); LegionBatchGraph_Launch refuses a graph recorded in the other state of the flag.  Nothing is allocated. */
+void GPUMemoryPool_SetSharedDraws(GPUMemoryPool* p, int on);
+int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
  * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
  * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list
@@ -718,6 +730,9 @@ void legion_weighted_probe(void* stream, const int32_t* row, const int32_t* hop,
  * device memory. */
 void legion_weighted_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
                                     uint32_t* u_out, double* key_out, int32_t n);
+/* Probe of shared-key sampling, by k_sample's own device functions: key_out[m] = the node key of neighbour id ids[m] (any int32, keyed by
+ * its bit pattern) under the draw word word[m] (0 = unseeded).  All pointers are device memory. */
+void legion_shared_draw_probe(void* stream, const int32_t* ids, const uint32_t* word, uint32_t* key_out, int32_t n);
 uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter);
 uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round);
 /* compute units of the current device as the sampler's persistent grids count them: a hop of more than 4 x this x 1024 slots makes a

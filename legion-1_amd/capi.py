@@ -213,6 +213,8 @@ _SIGS = {
     "GPUGraphStorage_HasRetainedEdgeWeights": (C.c_int, [vp]),
     "GPUMemoryPool_SetWeightedDistinct": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetWeightedDistinct": (C.c_int, [vp]),
+    "GPUMemoryPool_SetSharedDraws": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetSharedDraws": (C.c_int, [vp]),
     "GPUGraphStorage_CopyAliasRows": (C.c_int, [vp, i32, i64, i64, vp, vp]),
     "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
     "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
@@ -296,6 +298,7 @@ _SIGS = {
     "legion_perm_probe": (None, [vp, u32, i32, i32, vp]),
     "legion_weighted_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
     "legion_weighted_distinct_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
+    "legion_shared_draw_probe": (None, [vp, vp, vp, vp, i32]),
     "legion_lp_draw_probe": (None, [vp, u32, i32, i32, vp, vp, i32, vp, vp, i32]),
     "legion_seeded_draw_word": (u32, [u32, i32, i32]),
     "legion_seeded_shuffle_key": (u32, [u32, i32]),
@@ -537,8 +540,11 @@ class Engine:
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
-                  seed=None, round=0, lp_draw=0, weighted_distinct=False):
-        """weighted_distinct (GPUMemoryPool_SetWeightedDistinct, only with sample="weighted" on an Engine(retain_edge_weights=True)): the
+                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False):
+        """shared_draws (GPUMemoryPool_SetSharedDraws, only with sample="distinct"): the distinct draws are keyed by the neighbour node, so rows
+        that see the same neighbours pick the same ones; seed=None draws under word 0 (the same node keys in every batch).  Set on every call
+        like `sample`.
+        weighted_distinct (GPUMemoryPool_SetWeightedDistinct, only with sample="weighted" on an Engine(retain_edge_weights=True)): the
         weighted draws are without replacement -- min(columns of weight > 0, fan-out) distinct columns per row, by exponential keys.  Set on
         every call like `sample`.
         lp_draw: 0, or k > 0 (GPUMemoryPool_SetLpDraw, only under a seed): a training batch is 3 k seeds [src | pos | neg], the src third
@@ -558,7 +564,8 @@ class Engine:
         block 1 (GPUMemoryPool_SetAggNorm); result() additionally returns `out_deg` int32 [n]."""
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
-        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct)
+        agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct,
+                                     shared_draws=shared_draws)
         self._agg[(dev, pipe)] = agg and gather
         self._norm[(dev, pipe)] = norm and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
@@ -583,7 +590,7 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
-    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False):
+    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
@@ -594,6 +601,8 @@ class Engine:
             raise ValueError("sample: 'replace', 'distinct' or 'weighted'")
         if weighted_distinct and sample != "weighted":
             raise ValueError("weighted_distinct=True needs sample='weighted': the flag turns the weighted draws into draws without replacement")
+        if shared_draws and sample != "distinct":
+            raise ValueError("shared_draws=True needs sample='distinct': the flag keys the distinct draws by the neighbour node")
         if sample == "weighted" and not self.has_edge_weights():
             raise ValueError("sample='weighted' needs the Engine's edge_weights (Engine(edge_weights=...) or set_edge_weights())")
         if weighted_distinct and not self.has_retained_edge_weights():
@@ -602,7 +611,7 @@ class Engine:
         L.SetGPUDevice(dev)
         agg = bool(agg) and not is_presc
         norm = int(agg and norm == "both")
-        for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("WeightedDistinct", int(bool(weighted_distinct))), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
+        for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("WeightedDistinct", int(bool(weighted_distinct))), ("SharedDraws", int(bool(shared_draws))), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
             if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
                 getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
         self._set_seed(dev, seed, round, stream, lp_draw)
@@ -624,11 +633,11 @@ class Engine:
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False):
+                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
         run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in, and
-        only in the weighted_distinct state it was recorded in."""
+        only in the weighted_distinct and the shared_draws state it was recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -636,13 +645,13 @@ class Engine:
                 self.streams[dev] = L.d_stream_create()
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
-        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct)
+        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct, shared_draws=shared_draws)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
                        stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw,
-                       weighted_distinct=weighted_distinct)
+                       weighted_distinct=weighted_distinct, shared_draws=shared_draws)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:

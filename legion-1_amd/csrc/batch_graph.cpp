@@ -28,7 +28,8 @@ struct LegionBatchGraph {
     // pool's seeded state is another by now: the captured k_seed holds list pointers -- the seed set's, or the pool's shuffled copy (shuf_ids,
     // when the recording read it) --, so the graph only replays in that state; the seed, the round and the counter are not part of it
     // (k_set_cursor carries them into ctl).  Likewise for lp_draw: the captured k_seed is the instantiation, the k and the row tables of that state;
-    // and for weighted_distinct: the captured k_sample is that state's instantiation, over the alias table or over the retained weights.
+    // and for weighted_distinct: the captured k_sample is that state's instantiation, over the alias table or over the retained weights;
+    // and for shared_draws: the captured k_sample is that state's instantiation.
     ServeModes modes;
     const int32_t* shuf_ids = nullptr;
 };
@@ -85,6 +86,11 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (g->modes.weighted_distinct != p->modes.weighted_distinct) {
         LEGION_ARG_ERROR(g->modes.weighted_distinct ? "LegionBatchGraph_Launch: the graph was recorded with weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again"
                                                     : "LegionBatchGraph_Launch: the graph was recorded without weighted sampling without replacement and the pool has the flag on now (GPUMemoryPool_SetWeightedDistinct): its k_sample is another instantiation -- record it again");
+        return -1;
+    }
+    if (g->modes.shared_draws != p->modes.shared_draws) {
+        LEGION_ARG_ERROR(g->modes.shared_draws ? "LegionBatchGraph_Launch: the graph was recorded with shared-key sampling (GPUMemoryPool_SetSharedDraws) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again"
+                                               : "LegionBatchGraph_Launch: the graph was recorded without shared-key sampling and the pool has the flag on now (GPUMemoryPool_SetSharedDraws): its k_sample is another instantiation -- record it again");
         return -1;
     }
     if (g->shuf_ids && (g->shuf_ids != p->shuf_ids || !p->shuf_valid)) {

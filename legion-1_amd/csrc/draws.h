@@ -125,6 +125,90 @@ __device__ inline int32_t weighted_distinct_resolve(int32_t* p, const float* __r
     return f;
 }
 
+// Shared-key sampling (INTEGRATION.md "Shared-key sampling", GPUMemoryPool_SetSharedDraws on top of the distinct kind): the random number
+// belongs to the NEIGHBOUR NODE, not to the row.  Ks = mix32(w ^ 0x165667B1) is the batch's node-key salt (no hop, no row), key_c =
+// mix32(nbr[c] ^ Ks); a row of degree d > f takes its f columns of smallest (key, column), handed out in ascending column order; d <= f takes
+// every column and forms no key.  mix32 is a bijection, so only equal ids tie, and the column settles those: (key << 32 | column) is one
+// uint64 compare.  A negative entry is keyed by its bit pattern like any id.
+__device__ inline uint32_t shared_salt(uint32_t w) { return mix32(w ^ 0x165667B1u); }
+__device__ inline uint32_t shared_key(int32_t nbr, uint32_t salt) { return mix32((uint32_t)nbr ^ salt); }
+__device__ inline unsigned long long wave_read64(unsigned long long v, int l)   // lane l's v, l wave-uniform: two v_readlane, no LDS crossbar
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// One WAVE resolves one row of d > f (every lane of the wave calls this with the same arguments): p[0, f) := the row's picks in ascending
+// column order.  rowp: the row's d ids; p is LDS in k_sample.  The lanes stride over the row in chunks of 64 (coalesced 256-byte reads, no
+// single-lane loop).
+//  d <= 64, one chunk, a key per lane: the f-th smallest key T is found by bisection over its 32 bits -- one compare and one ballot per
+//    bit, the rest scalar --, the picks are the lanes of key < T and, of the lanes of key == T (multi-edges), the lowest columns that fill
+//    the f; they are compacted by ballot prefix, which is column order.
+//  d > 64: the best list sits sorted in registers, entry l in lane l, as (key << 32 | column).  The first chunk is ranked by counting (64
+//    uniform lane reads) and each entry moved to the lane of its rank.  The later chunks are fetched four at a time (four independent loads
+//    in flight: a hub's chunks are a chain of round trips otherwise); of a chunk only the entries in front of the list's entry f - 1 at the
+//    chunk's start are candidates (the list's last entry only falls from there); each is inserted where the ballot of the entries in
+//    front of it ends and the tail moves up one lane.  At the end the first f entries are ranked by column.  A lane past the row's end
+//    holds 0xFFFFFFFF'80000000 | lane: behind every column (columns are < 2^31) and distinct, so the first chunk's ranks are a permutation.
+__device__ inline void shared_resolve(int32_t* p, const int32_t* __restrict__ rowp, int32_t d, int32_t f, uint32_t salt)
+{
+    const int lane = lane_id();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const uint32_t ud = (uint32_t)d;
+    if (d <= 64) {
+        const bool valid = lane < d;
+        const uint32_t key = valid ? shared_key(rowp[lane], salt) : 0u;
+        uint32_t T = 0;   // the smallest T with f or more keys <= T: bit by bit from the top, a bit stays 0 if the keys below it suffice
+        for (int bit = 31; bit >= 0; bit--) {
+            const uint32_t trial = T | ((1u << bit) - 1u);
+            if (__popcll(__ballot(valid && key <= trial)) < f) T |= 1u << bit;
+        }
+        const bool less = valid && key < T, eq = valid && key == T;
+        const int need = f - __popcll(__ballot(less));   // >= 1 of the lanes at T
+        const bool in = less || (eq && __popcll(__ballot(eq) & lt) < need);
+        const unsigned long long m = __ballot(in);
+        if (in) p[__popcll(m & lt)] = lane;
+        return;
+    }
+    auto entry = [&](int32_t id, uint32_t c) {
+        return c < ud ? ((unsigned long long)shared_key(id, salt) << 32) | c : 0xFFFFFFFF80000000ull | (unsigned long long)lane;
+    };
+    unsigned long long b = entry(rowp[lane], (uint32_t)lane);   // d > 64: the first chunk is whole
+    int32_t rank = 0;
+    for (int t = 0; t < 64; t++) rank += wave_read64(b, t) < b;
+    {   // entry of rank l to lane l: a push through the LDS crossbar, the ranks are a permutation of 0..63
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_permute(rank << 2, (int)(uint32_t)b), hi = (uint32_t)__builtin_amdgcn_ds_permute(rank << 2, (int)(uint32_t)(b >> 32));
+        b = ((unsigned long long)hi << 32) | lo;
+    }
+    for (uint32_t c0 = 64u; c0 < ud; c0 += 256u) {   // uint32: d < 2^31, so c0 + 319 does not wrap
+        int32_t id[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) {
+            const uint32_t c = c0 + 64u * u + (uint32_t)lane;
+            id[u] = c < ud ? rowp[c] : 0;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) {
+            const unsigned long long k = entry(id[u], c0 + 64u * u + (uint32_t)lane);
+            bool todo = k < wave_read64(b, f - 1);   // by the whole wave, in front of any insertion
+            for (;;) {   // at most 64 rounds: every round retires one lane of the chunk
+                const unsigned long long beat = __ballot(todo && k < wave_read64(b, f - 1));
+                if (!beat) break;
+                const int src = __ffsll((long long)beat) - 1;
+                const unsigned long long nk = wave_read64(k, src);
+                const int at = __popcll(__ballot(b < nk));   // the entries in front are a prefix of the lanes: at < f
+                const unsigned long long up = __shfl_up(b, 1);
+                if (lane == at) b = nk;
+                else if (lane > at) b = up;
+                if (lane == src) todo = false;
+            }
+        }
+    }
+    const int32_t bc = lane < f ? (int32_t)(uint32_t)b : 0x7FFFFFFF;
+    rank = 0;
+    for (int32_t t = 0; t < f; t++) rank += __builtin_amdgcn_readlane(bc, t) < bc;
+    if (lane < f) p[rank] = bc;
+}
+
 // Drawn link-prediction thirds (INTEGRATION.md "Drawn link-prediction thirds"): the positive and the negative of slot i of a batch, pure
 // functions of the batch's draw word, the slot and its source.  u is the distinct mode's hash of (key, slot) with the source folded in, so
 // that two GPUs of one job, which share the draw word, do not draw the same negatives.

@@ -78,6 +78,20 @@ __global__ void k_weighted_distinct_probe(const int32_t* row, const int32_t* hop
     key[m] = weighted_distinct_keyval(uc, w[m]);
 }
 
+// Shared-key sampling: the node key of n neighbour ids, by the device functions k_sample<.., SHARED> forms it with
+__global__ void k_shared_draw_probe(const int32_t* ids, const uint32_t* word, uint32_t* key, int32_t n)
+{
+    const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
+    if (m < n) key[m] = shared_key(ids[m], shared_salt(word[m]));
+}
+
+void launch_shared_draw_probe(hipStream_t s, const int32_t* ids, const uint32_t* word, uint32_t* key, int32_t n)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_shared_draw_probe", LEGION_AW(key), LEGION_AL(ids), LEGION_AL(word));
+    k_shared_draw_probe<<<(n + 255) / 256, 256, 0, s>>>(ids, word, key, n);
+    HIP_CHECK_LAST();
+}
 void launch_weighted_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
                                     uint32_t* u, double* key, int32_t n)
 {

@@ -258,6 +258,11 @@ void legion_weighted_probe(void* stream, const int32_t* row, const int32_t* hop,
     if (n > 0 && (!row || !hop || !slot || !deg || !word || !k_out || !ub_out)) { LEGION_ARG_ERROR("legion_weighted_probe: null array"); return; }
     launch_weighted_probe((hipStream_t)stream, row, hop, slot, deg, word, k_out, ub_out, n);
 }
+void legion_shared_draw_probe(void* stream, const int32_t* ids, const uint32_t* word, uint32_t* key_out, int32_t n)
+{
+    if (n > 0 && (!ids || !word || !key_out)) { LEGION_ARG_ERROR("legion_shared_draw_probe: null array"); return; }
+    launch_shared_draw_probe((hipStream_t)stream, ids, word, key_out, n);
+}
 void legion_weighted_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
                                     uint32_t* u_out, double* key_out, int32_t n)
 {

@@ -59,7 +59,7 @@ namespace legion {
 // The positive of a drawn link-prediction triple (lp_rho, draws.h): one neighbour of src, read where k_sample would read that row (the owner's fragment when the topology map names one, else
 // the whole CSR; fragment rows are copies in CSR order), degree as k_sample computes it; src itself for an empty row or a negative entry.
 // The row addressing below restates k_sample's ("owner lookup, chunk tables, int32 degree") rather than sharing a helper with it, on
-// purpose: k_sample interleaves those loads with its tile's other work and its twelve instantiations are kept instruction for
+// purpose: k_sample interleaves those loads with its tile's other work and its instantiations are kept instruction for
 // instruction.  Whoever changes the fragment layout changes both; the cached-topology test compares this copy with the uncached statement.
 __device__ inline int32_t lp_pos(const CsrTables& c, uint32_t w, uint32_t i, int32_t src)
 {
@@ -288,10 +288,16 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
 // replacement"): the row's picks are its f eligible columns of smallest exponential key, staged in s_pick like the distinct mode's -- but
 // one WAVE resolves a row, its lanes striding over the row's retained weights (weighted_distinct_resolve, draws.h), since a single lane
 // would walk a hub's weights alone.  The row's staged degree becomes min(eligible columns, f); the alias table is not read.
-template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED>
+// DISTINCT && SHARED (GPUMemoryPool_SetSharedDraws on top of the distinct kind, INTEGRATION.md "Shared-key sampling"): the row's picks are
+// its f columns of smallest NODE key, a hash of the neighbour's id and the batch's draw word alone, so rows that see the same neighbours pick
+// the same ones.  Staged in s_pick and read by the slots exactly like the distinct mode's; one WAVE resolves a row of degree > f, its lanes
+// striding over the row's ids (shared_resolve, draws.h).  The rule reads nothing but the row itself, through s_row[r]: whole CSR, pre-sampling
+// and the clique's fragments alike, and no table.
+template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED, bool SHARED>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
     static_assert(!(WEIGHTED && PARTITIONED), "weighted draws read the whole CSR");
+    static_assert(!SHARED || (DISTINCT && !WEIGHTED), "shared keys are a flag on top of the distinct kind");
     constexpr bool STREAM = !DISTINCT && !WEIGHTED;   // the minstd stream of the default mode
     __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
     __shared__ int32_t s_deg[TILE + 2];
@@ -354,7 +360,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             s_deg[r] = deg;
             s_src[r] = src;
         }
-        if constexpr (DISTINCT && !WEIGHTED) {
+        if constexpr (DISTINCT && !WEIGHTED && !SHARED) {
             const uint32_t hop = (uint32_t)a.op_id >> 1;
             for (int32_t p = tid; p < nrows * f; p += kBlock) {
                 const uint32_t rr = fdiv((uint32_t)p, a.fdiv);
@@ -362,9 +368,17 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             }
         }
         __syncthreads();
-        if constexpr (DISTINCT && !WEIGHTED) {
+        if constexpr (DISTINCT && !WEIGHTED && !SHARED) {
             for (int32_t r = tid; r < nrows; r += kBlock)
                 if (s_deg[r] > f) distinct_resolve(s_pick + r * f, s_deg[r], f);
+            __syncthreads();
+        }
+        if constexpr (SHARED) {
+            const uint32_t salt = shared_salt(draw);
+            for (int32_t r = wave_id(); r < nrows; r += kBlock / 64) {   // one wave per row: r and everything read through it is wave-uniform
+                const int32_t d = s_deg[r];
+                if (d > f) shared_resolve(s_pick + r * f, s_row[r], d, f, salt);
+            }
             __syncthreads();
         }
         if constexpr (DISTINCT && WEIGHTED) {
@@ -880,11 +894,12 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices), LEGION_AL(a.alias));
     // The instantiation by [whole CSR / pre-sampling / the clique's fragments][rule]; the rules that draw from the whole CSR only have no
     // partitioned one (launch_sample_hop refuses such tables).  A pre-sampling hop gets whole-CSR tables, so it is never partitioned.
-    static constexpr void (*kSample[][4])(SampleArgs) = {
-        {k_sample<TILE, false, false, false, false>, k_sample<TILE, false, false, true, false>, k_sample<TILE, false, false, false, true>, k_sample<TILE, false, false, true, true>},
-        {k_sample<TILE, true, false, false, false>, k_sample<TILE, true, false, true, false>, k_sample<TILE, true, false, false, true>, k_sample<TILE, true, false, true, true>},
-        {k_sample<TILE, false, true, false, false>, k_sample<TILE, false, true, true, false>, nullptr, nullptr}};
+    static constexpr void (*kSample[][5])(SampleArgs) = {
+        {k_sample<TILE, false, false, false, false, false>, k_sample<TILE, false, false, true, false, false>, k_sample<TILE, false, false, false, true, false>, k_sample<TILE, false, false, true, true, false>, k_sample<TILE, false, false, true, false, true>},
+        {k_sample<TILE, true, false, false, false, false>, k_sample<TILE, true, false, true, false, false>, k_sample<TILE, true, false, false, true, false>, k_sample<TILE, true, false, true, true, false>, k_sample<TILE, true, false, true, false, true>},
+        {k_sample<TILE, false, true, false, false, false>, k_sample<TILE, false, true, true, false, false>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true>}};
     static_assert((int)DrawRule::Stream == 0 && (int)DrawRule::Distinct == 1 && (int)DrawRule::Weighted == 2 && (int)DrawRule::WeightedDistinct == 3, "kSample's columns");
+    static_assert((int)DrawRule::Shared == 4, "kSample's last column");
     kSample[is_presc ? 1 : csr.topo_owner ? 2 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
@@ -912,6 +927,7 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
     if (draw_rule_whole_csr(draw.rule) && (!table || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
     if (draw_rule_max_fanout(draw.rule) && count > draw_rule_max_fanout(draw.rule)) {
         LEGION_ARG_ERROR(draw.rule == DrawRule::Distinct ? "GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"
+                         : draw.rule == DrawRule::Shared ? "GPU_Random_Sampling: shared-key sampling (GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"
                                                          : "GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS");
         return;
     }

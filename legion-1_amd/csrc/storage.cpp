@@ -676,6 +676,10 @@ int GPUMemoryPool_GetSampling(const GPUMemoryPool* p) { return p ? p->modes.samp
 // kinds and acting only while the kind is 2; nothing is allocated here, the weights belong to the graph (GPUGraphStorage_RetainEdgeWeights)
 void GPUMemoryPool_SetWeightedDistinct(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.weighted_distinct = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetWeightedDistinct"); }
 int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p) { return p && p->modes.weighted_distinct ? 1 : 0; }
+// shared-key sampling ("Shared-key sampling"): a flag on top of the distinct kind, remembered across kinds and acting only while the kind
+// is 1; nothing is allocated.  An unseeded pool draws under word 0: deterministic, the same node keys in every batch
+void GPUMemoryPool_SetSharedDraws(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.shared_draws = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetSharedDraws"); }
+int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p) { return p && p->modes.shared_draws ? 1 : 0; }
 void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {
     ServeModes m = modes_of(p);

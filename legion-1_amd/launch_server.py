@@ -62,6 +62,9 @@ def main(argv=None):
     ap.add_argument("--weighted-distinct", "--weighted_distinct", dest="weighted_distinct", action="store_true", help="extension "
                     "(LEGION_WEIGHTED_DISTINCT=1 for the server; needs --sampling weighted): the weighted draws are without replacement, "
                     "min(neighbours of weight > 0, fan-out) distinct neighbours per row; the server keeps the weights in HBM beside the alias table")
+    ap.add_argument("--shared-draws", "--shared_draws", dest="shared_draws", action="store_true", help="extension "
+                    "(LEGION_SHARED_DRAWS=1 for the server; needs --sampling distinct and --sampling_seed): the distinct draws are keyed by the "
+                    "neighbour node, so rows that see the same neighbours pick the same ones and a batch reaches fewer unique nodes")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
@@ -81,6 +84,8 @@ def main(argv=None):
         env["LEGION_LP_DRAW"] = "1"
     if args.weighted_distinct:
         env["LEGION_WEIGHTED_DISTINCT"] = "1"
+    if args.shared_draws:
+        env["LEGION_SHARED_DRAWS"] = "1"
     return subprocess.call(cmd, env=env)
 
 
