@@ -31,6 +31,14 @@ extern "C" {
 #define LEGION_MAX_DEVICE 8      /* CUDA_IPC_Service.cu:14 MAX_DEVICE */
 #define LEGION_PIPELINE_DEPTH 2  /* Server.cu:15, CUDA_IPC_Service.cu:15 */
 #define LEGION_MEMORY_USAGE 7    /* CUDA_IPC_Service.cu:16: buffers per (device, pipe) */
+/* the seven buffers of a (device, pipe): index of memHandle[dev][pipe][.] in the slab, of legion_ipc_client_buffer and of IPCEnv_Get* */
+#define LEGION_BUF_IDS 0          /* int32 node ids of the batch */
+#define LEGION_BUF_FEATURES 1     /* float feature rows (an IPC handle, or a chunk descriptor above the HIP-IPC size limit) */
+#define LEGION_BUF_LABELS 2       /* int32 labels of the seeds */
+#define LEGION_BUF_AGG_SRC 3      /* int32 COO sources of every block */
+#define LEGION_BUF_AGG_DST 4      /* int32 COO destinations */
+#define LEGION_BUF_NODE_COUNTER 5 /* nc: LEGION_COUNTER_WORDS int32 */
+#define LEGION_BUF_EDGE_COUNTER 6 /* ec: LEGION_COUNTER_WORDS int32 */
 /* LEGION_MAX_HOPS (5) and LEGION_COUNTER_WORDS (16) belong to the counter layout: legion_batch_layout.h */
 
 #define LEGION_TRAINMODE 0       /* Kernels.cu:10-12 */

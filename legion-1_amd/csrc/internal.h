@@ -158,7 +158,7 @@ bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch
 // the fan-out bound of the modes' draw rule (draw_rule_max_fanout) against a fan-out list: false with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
 void runner_set_lists_verbatim(Runner* r, bool verbatim);   // before Runner_Initialize: meta flag 2 (Runner::lists_verbatim, runner.cpp)
-// what a trainer reads: the five mode words of the "<name>_ext" object := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
+// what a trainer reads: the five mode words of the "<name>_ext" object (shmExt, ipc_shm.h) := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
 void ipc_env_publish_modes(IPCEnv* e, const ServeModes& m);
 
 // The seed sets are indexed by mode everywhere (LEGION_TRAINMODE, LEGION_VALIDMODE, LEGION_TESTMODE); LegionBuildInfo names their fields
@@ -274,12 +274,12 @@ struct HopState {                  // written by the scan kernel, read by the wr
 };
 
 struct SamplerBuffers {
-    int32_t* sampled_ids;   // IPC buffer 0
+    int32_t* sampled_ids;   // IPC buffer LEGION_BUF_IDS
     int32_t* agg_src_ids;   // per-edge neighbour id == next hop's input list
-    int32_t* agg_src_off;   // IPC buffer 3
-    int32_t* agg_dst_off;   // IPC buffer 4
-    int32_t* nc;            // IPC buffer 5
-    int32_t* ec;            // IPC buffer 6
+    int32_t* agg_src_off;   // IPC buffer LEGION_BUF_AGG_SRC
+    int32_t* agg_dst_off;   // IPC buffer LEGION_BUF_AGG_DST
+    int32_t* nc;            // IPC buffer LEGION_BUF_NODE_COUNTER
+    int32_t* ec;            // IPC buffer LEGION_BUF_EDGE_COUNTER
     pos_t* pos_map;         // pos_t[V]: (epoch << kPosShift) | value
     const BatchCtl* ctl;    // ctl->epoch = 0xFFFFFFFF - batch serial: newer batches compare smaller
     int32_t* cand;          // i32[max slots of a hop]

@@ -87,19 +87,19 @@ static std::vector<torch::Tensor> next_batch(int feature_dim, bool aggregated, i
     const int64_t rows = legion_ipc_client_feature_rows(env);
     TORCH_CHECK(rows <= 0 || n_rows <= rows, "ipc_service: the batch has ", n_rows, aggregated ? " rows (features + neighbour sums)" : " nodes", " but the server's feature buffer holds ", rows,
                 " rows (sized from the pre-sampling epoch; use a training batch size >= the validation / test batch size)");
-    for (int w = 0; w <= 4; w++)    // legion_ipc_client_open refuses a server that has not registered its buffers; never build a tensor on a null one
+    for (int w = LEGION_BUF_IDS; w <= LEGION_BUF_AGG_DST; w++)    // legion_ipc_client_open refuses a server that has not registered its buffers; never build a tensor on a null one
         TORCH_CHECK(legion_ipc_client_buffer(env, w) != nullptr, "ipc_service: hand-off buffer ", w, " of this GPU was never registered by the server");
     std::vector<torch::Tensor> out;
-    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 0), {n_nodes}, i32));
-    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 1), {aggregated ? n_in : n_nodes, (int64_t)feature_dim}, f32));
-    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 2), {(int64_t)legion_nodes_through(h_node_counter, 0)}, i32));
+    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, LEGION_BUF_IDS), {n_nodes}, i32));
+    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, LEGION_BUF_FEATURES), {aggregated ? n_in : n_nodes, (int64_t)feature_dim}, f32));
+    out.push_back(torch::from_blob(legion_ipc_client_buffer(env, LEGION_BUF_LABELS), {(int64_t)legion_nodes_through(h_node_counter, 0)}, i32));
     for (int k = 1; k <= H; k++) {
         const int64_t n_edges = legion_edges_through(h_edge_counter, H - k + 1); // block k: the hops 1..H-k+1 (ec[4], ec[3] at H = 2: ipc_cuda_kernel.cu:198-213)
-        out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 3), {n_edges}, i32));
-        out.push_back(torch::from_blob(legion_ipc_client_buffer(env, 4), {n_edges}, i32));
+        out.push_back(torch::from_blob(legion_ipc_client_buffer(env, LEGION_BUF_AGG_SRC), {n_edges}, i32));
+        out.push_back(torch::from_blob(legion_ipc_client_buffer(env, LEGION_BUF_AGG_DST), {n_edges}, i32));
     }
     if (aggregated)
-        out.push_back(torch::from_blob((float*)legion_ipc_client_buffer(env, 1) + n_in * (int64_t)feature_dim, {n_runs, (int64_t)feature_dim}, f32));
+        out.push_back(torch::from_blob((float*)legion_ipc_client_buffer(env, LEGION_BUF_FEATURES) + n_in * (int64_t)feature_dim, {n_runs, (int64_t)feature_dim}, f32));
     return out;
 }
 

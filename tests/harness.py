@@ -25,8 +25,8 @@ READY = "System is ready for serving"
 
 
 # ---- processes -----------------------------------------------------------------------------------
-# The library builds its names from the namespace: "/<ns>sem_r_<dev>_<pipe>" (sem_name(), csrc/ipc_env.cpp; POSIX: at most NAME_MAX - 4 =
-# 251 characters) and the abstract socket "<ns>legion_vmm_<dev>_<pipe>", which vmm_sock_addr() cuts SILENTLY to 106 bytes -- the tighter
+# The library builds its names from the namespace: "/<ns>sem_r_<dev>_<pipe>" (sem_name(), csrc/ipc_shm.cpp; POSIX: at most NAME_MAX - 4 =
+# 251 characters) and the abstract socket "<ns>legion_vmm_<dev>_<pipe>", which vmm_sock_addr() (csrc/ipc_vmm.cpp) cuts SILENTLY to 106 bytes -- the tighter
 # bound: with two digits each for device and pipe the suffix is 16 characters, so beyond 90 the per-pipe names would collide.
 NS_MAX = 106 - len("legion_vmm_99_99")
 _ns_counter = itertools.count()

@@ -1,6 +1,6 @@
 """The server <-> trainer hand-off protocol WITHOUT a GPU (tests/test_ipc_env_cpu.py; also the workload of the host-sanitizer run,
 `make -C legion-1_amd/csrc asan-host` + profiles/r05_robustness.sh): the shm slab, the named semaphores, the host mirror of the
-counters, the poisoned pipe and the teardown of csrc/ipc_env.cpp, driven through the C ABI by a fake producer (this process:
+counters, the poisoned pipe and the teardown of csrc/ipc_env.cpp (server half) and csrc/ipc_client.cpp (trainer half), driven through the C ABI by a fake producer (this process:
 IPCEnv_*) and one fake consumer process per logical GPU (legion_ipc_client_*).  $LEGION_IPC_NO_DEVICE=1: no hand-off buffer is
 allocated, the handle slots stay zero.
 

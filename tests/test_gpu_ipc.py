@@ -319,7 +319,7 @@ def test_two_gpu_server_link_prediction_lists_keep_their_thirds(tmp_path, synth,
 @pytest.mark.parametrize("client", ["ipc_client.py", "ipc_client_plain.py"])
 def test_chunked_feature_handoff_buffer(tmp_path, synth, oracle, client):
     """A feature hand-off buffer above the HIP-IPC size limit (2^31 bytes under the PyTorch-bundled runtime) is built from
-    chunks, exported as file descriptors and mapped contiguously by the trainer (ipc_env.cpp, VmmDesc).  Forced here with a
+    chunks, exported as file descriptors and mapped contiguously by the trainer (ipc_vmm.cpp, VmmDesc).  Forced here with a
     tiny limit and 1 MiB chunks (a ~3 MB buffer = 3 chunks per pipe); the PyTorch client imports through the bundled ROCm 7.0
     runtime (descriptor by pointer), the plain ctypes client through the system runtime (by value)."""
     spec = synth.spec_for("products", scale=0.004)

@@ -1,4 +1,4 @@
-"""The hand-off protocol of csrc/ipc_env.cpp on the CPU: a fake producer (IPCEnv_*) and one fake consumer process per
+"""The hand-off protocol of csrc/ipc_env.cpp and csrc/ipc_client.cpp on the CPU: a fake producer (IPCEnv_*) and one fake consumer process per
 logical GPU (legion_ipc_client_*) run the slab / semaphore / counter-mirror / poisoned-pipe protocol with $LEGION_IPC_NO_DEVICE=1 -- no GPU
 buffer, zero handle slots.  tests/ipc_env_cpu.py is the workload (its own processes: the no-device switch is read once per process); the same
 script runs under the host-sanitizer build in profiles/r05_robustness.sh."""
@@ -78,6 +78,70 @@ def test_a_stale_extension_object_is_ignored_and_a_killed_servers_leftovers_can_
         r = subprocess.run([sys.executable, "-c", pre + "L.legion_ipc_unlink_namespace(%r.encode(), 8); print('UNLINKED')\n" % ns], capture_output=True, text=True, timeout=60)
         assert "UNLINKED" in r.stdout, r.stdout + r.stderr[-2000:]
         assert not [f for f in os.listdir("/dev/shm") if ns in f]
+    finally:
+        for f in os.listdir("/dev/shm"):
+            if ns in f:
+                os.unlink(os.path.join("/dev/shm", f))
+
+
+# a device-free process with the library loaded and one helper: env(n) = a coordinated NewIPCEnv(n)
+_PRE = ("import os, sys, ctypes as C; sys.path.insert(0, %r)\n"
+        "os.environ['LEGION_IPC_NO_DEVICE'] = '1'; os.environ.pop('LEGION_IPC_NAMESPACE', None)\n"
+        "import numpy as np, legion1_amd.capi as K\n"
+        "L = K.lib(); L.legion_set_error_mode(K.ERR_RETURN)\n"
+        "def env(n):\n"
+        "    e = L.NewIPCEnv(n); K.check(); assert e\n"
+        "    info = K.LegionBuildInfo(); info.partition_count = n; info.epoch = 1; info.raw_batch_size = 500\n"
+        "    tr, va, te = (np.full(n, x, np.int32) for x in (3601, 700, 300))\n"
+        "    info.training_set_num, info.validation_set_num, info.testing_set_num = tr.ctypes.data, va.ctypes.data, te.ctypes.data\n"
+        "    L.IPCEnv_Coordinate(e, C.byref(info)); K.check()\n"
+        "    return e\n"
+        "def left(tag): return sorted(f for f in os.listdir('/dev/shm') if tag in f)\n") % ROOT
+
+
+def test_the_namespace_is_read_at_every_call_and_unlink_spells_the_names_like_create():
+    """One process serves under namespace A, finalizes, then serves under B (legion_ipc_set_namespace, as the in-process runners of the GPU
+    tests do): each env creates exactly the slab, `_ext` and the 2 x 2 semaphores of ITS namespace and Finalize removes exactly those -- a name
+    cached at first use would put B's objects under A.  legion_ipc_unlink_namespace of the emptied namespaces is a no-op without error."""
+    tag = "cpuipc_ns%d" % os.getpid()
+    code = _PRE + ("tag = %r\n"
+                   "for ns in (tag + 'A_', tag + 'B_'):\n"
+                   "    L.legion_ipc_set_namespace(ns.encode())\n"
+                   "    e = env(1); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); K.check()\n"
+                   "    want = sorted([ns + 'simpleIPCshm', ns + 'simpleIPCshm_ext'] + ['sem.' + ns + 'sem_%%s_0_%%d' %% (rw, q) for rw in 'rw' for q in (0, 1)])\n"
+                   "    assert left(tag) == want, (left(tag), want)\n"
+                   "    L.IPCEnv_Finalize(e); K.check()\n"
+                   "    assert left(tag) == [], left(tag)\n"
+                   "for ns in (tag + 'A_', tag + 'B_'):\n"
+                   "    L.legion_ipc_unlink_namespace(ns.encode(), 8); K.check()\n"
+                   "assert left(tag) == []; print('OK')\n") % tag
+    try:
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr[-2000:]
+    finally:
+        for f in os.listdir("/dev/shm"):
+            if tag in f:
+                os.unlink(os.path.join("/dev/shm", f))
+
+
+def test_getters_of_a_partly_built_env_return_null_and_its_teardown_leaves_nothing():
+    """NewIPCEnv(2) with sample buffers for device 0 only.  Every getter answers null -- for the device that was never initialised, for
+    device 0 at pipes 0, 1 and 5 (the wrap; device-free mode registers no buffer), for the device indices -1 and 2 -- without the sticky
+    error, and Finalize tears down the one initialised device and skips the other: nothing is left in /dev/shm."""
+    ns = "cpuipc_part%d_" % os.getpid()
+    code = _PRE + ("ns = %r; L.legion_ipc_set_namespace(ns.encode())\n"
+                   "e = env(2); L.IPCEnv_InitializeSamplesBuffer(e, 500, 1000, 16, 0, 2); K.check()\n"
+                   "assert len(left(ns)) == 2 + 4, left(ns)\n"
+                   "for get in (L.IPCEnv_GetIds, L.IPCEnv_GetFloatFeatures, L.IPCEnv_GetNodeCounter):\n"
+                   "    for dev in (1, 0, -1, 2):\n"
+                   "        for pipe in (0, 1, 5):\n"
+                   "            assert not get(e, dev, pipe), (get.__name__, dev, pipe)\n"
+                   "K.check()\n"
+                   "L.IPCEnv_Finalize(e); K.check()\n"
+                   "assert left(ns) == [], left(ns); print('OK')\n") % ns
+    try:
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr[-2000:]
     finally:
         for f in os.listdir("/dev/shm"):
             if ns in f:
