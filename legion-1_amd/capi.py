@@ -157,6 +157,7 @@ _SIGS = {
     "GPUMemoryPool_GetCacheSearchBuffer": (vp, [vp]),
     "GPUMemoryPool_GetTmpPartIdx": (vp, [vp]),
     "GPUMemoryPool_GetTmpPartOff": (vp, [vp]),
+    "GPUMemoryPool_Finalize": (None, [vp]),
     "GPUMemoryPool_Delete": (None, [vp]),
     "NewGPUCache": (vp, []),
     "GPUCache_Initialize": (None, [vp, i64, i32, i32, i32, i32]),

@@ -14,7 +14,7 @@
 //   * a kernel argument the kernel WRITES, or reads as its own scratch, must be memory of the current logical device (nothing in this
 //     library writes into a peer); a TABLE it reads (CSR, feature rows, rankings, hotness) may also be pinned host memory, an IPC
 //     import, or memory of another logical device if -- and only if -- peer access between the two logical devices was recorded by the
-//     all-pairs enable (storage.cpp enable_p2p); the same rule for the pointers inside device-side pointer tables (shard / fragment
+//     all-pairs enable (chunks.cpp enable_p2p); the same rule for the pointers inside device-side pointer tables (shard / fragment
 //     chunk tables); both ends of a hipMemcpyPeerAsync must live on the physical devices the call names;
 //   * places that fill a per-device slot state the owner they expect (audit::expect_owner).
 // A violation is a sticky error naming the call site, is kept in a process-wide list (legion_audit_*) and counted; the `legion`

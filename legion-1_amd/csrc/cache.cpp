@@ -20,7 +20,7 @@
 #include <cstring>
 #include <iostream>
 
-#include "audit_hooks.h"
+#include "device_mem.h"
 
 using namespace legion;
 
@@ -106,10 +106,9 @@ static void publish_shard_tables(GPUCache* c, int Ki)
 
 static void free_controller_maps(CacheController* k)
 {
-    if (k->feat_map) (void)hipFree(k->feat_map);
-    if (k->topo_owner) (void)hipFree(k->topo_owner);
-    if (k->topo_row) (void)hipFree(k->topo_row);
-    k->feat_map = nullptr; k->topo_owner = nullptr; k->topo_row = nullptr;
+    free_and_null(k->feat_map);
+    free_and_null(k->topo_owner);
+    free_and_null(k->topo_row);
 }
 
 void GPUCache_Finalize(GPUCache* c, int32_t dev_id)
@@ -118,16 +117,14 @@ void GPUCache_Finalize(GPUCache* c, int32_t dev_id)
     CacheController* k = c->ctl[dev_id];
     DeviceGuard guard(dev_id);
     free_controller_maps(k);
-    if (k->node_access_time) (void)hipFree(k->node_access_time);
-    if (k->edge_access_time) (void)hipFree(k->edge_access_time);
-    if (k->d_max_ids) (void)hipFree(k->d_max_ids);
-    if (k->d_global_count) (void)hipFree(k->d_global_count);
+    free_and_null(k->node_access_time);
+    free_and_null(k->edge_access_time);
+    free_and_null(k->d_max_ids);
+    free_and_null(k->d_global_count);
     if (k->hit_stats) { (void)hipHostFree(k->hit_stats); k->hit_stats = nullptr; k->hit_stats_dev = nullptr; }
     for (int q = 0; q < 2; q++) if (k->hit_ev[q]) { (void)hipEventDestroy(k->hit_ev[q]); k->hit_ev[q] = nullptr; k->hit_ev_armed[q] = false; }
-    k->node_access_time = k->edge_access_time = nullptr;
-    k->d_max_ids = k->d_global_count = nullptr;
     c->shards[dev_id].release();
-    if (c->d_shard_tab[dev_id]) { (void)hipFree(c->d_shard_tab[dev_id]); c->d_shard_tab[dev_id] = nullptr; }
+    free_and_null(c->d_shard_tab[dev_id]);
 }
 
 // "Feature Cache Hit" (GPUCache.cu:414-425): every $LEGION_CACHE_HIT_PERIOD-th batch (default 500, the reference's
@@ -322,26 +319,24 @@ HotnessCurves load_curves(const GPUCache* c, int clique, const GPUGraphStorage* 
 {
     HotnessCurves h;
     h.node.resize(V); h.edge.resize(V); h.edge_bytes.resize(V);
-    uint64_t *d_in = nullptr, *d_out = nullptr;
-    HIP_CHECK(hipMalloc(&d_in, (size_t)V * sizeof(uint64_t)));
-    HIP_CHECK(hipMalloc(&d_out, (size_t)V * sizeof(uint64_t)));
+    DeviceTemp<uint64_t> d_out, d_in;   // freed on the way out, d_in first
+    HIP_CHECK(hipMalloc(&d_in.p, (size_t)V * sizeof(uint64_t)));
+    HIP_CHECK(hipMalloc(&d_out.p, (size_t)V * sizeof(uint64_t)));
     auto fetch = [&](const uint64_t* src, std::vector<uint64_t>& dst) {
-        inclusive_scan_u64(nullptr, src, d_out, V);
-        HIP_CHECK(hipMemcpy(dst.data(), d_out, (size_t)V * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        inclusive_scan_u64(nullptr, src, d_out.p, V);
+        HIP_CHECK(hipMemcpy(dst.data(), d_out.p, (size_t)V * sizeof(uint64_t), hipMemcpyDeviceToHost));
     };
     fetch((const uint64_t*)c->AF[clique], h.node);
     fetch((const uint64_t*)c->AT[clique], h.edge);
-    launch_edge_mem(nullptr, c->QT[clique], d_in, V, graph->csr_node_index_cpu);   // GetEdgeMem, GPUCache.cu:35-41
-    fetch(d_in, h.edge_bytes);
+    launch_edge_mem(nullptr, c->QT[clique], d_in.p, V, graph->csr_node_index_cpu);   // GetEdgeMem, GPUCache.cu:35-41
+    fetch(d_in.p, h.edge_bytes);
     if (topo_trans_estimate) {
         // PCM-free input: 64-byte transactions of the pre-sampling epoch's adjacency reads, from our own
         // hotness counters -- deterministic, no MSR access.  See topo_transactions_of() for the per-row weight.
-        launch_topo_transactions(nullptr, c->QT[clique], (const uint64_t*)c->AT[clique], d_in, V, graph->csr_node_index_cpu);
-        inclusive_scan_u64(nullptr, d_in, d_out, V);
-        HIP_CHECK(hipMemcpy(topo_trans_estimate, d_out + (V - 1), sizeof(uint64_t), hipMemcpyDeviceToHost));
+        launch_topo_transactions(nullptr, c->QT[clique], (const uint64_t*)c->AT[clique], d_in.p, V, graph->csr_node_index_cpu);
+        inclusive_scan_u64(nullptr, d_in.p, d_out.p, V);
+        HIP_CHECK(hipMemcpy(topo_trans_estimate, d_out.p + (V - 1), sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
-    HIP_CHECK(hipFree(d_in));
-    HIP_CHECK(hipFree(d_out));
     return h;
 }
 

@@ -60,6 +60,22 @@ struct ChunkList {
 // on `viewer`: audit h, then copy it into `tab` (allocated when null; freed first, after a device sync, when `realloc`; empty h: freed)
 template <typename T> void upload_table(int viewer, const std::vector<T*>& h, T**& tab, bool realloc, const char* what);
 
+// ---- what the three storages share (chunks.cpp; the frees that go with it: device_mem.h); hidden: the library exports what it exported ----
+// all-pairs peer access between the physical devices behind the logical GPUs (GPUGraphStore::EnableP2PAccess, GPUGraphStore.cu:145-168)
+__attribute__((visibility("hidden"))) void enable_p2p(int32_t partition_count);
+// a table the caller handed over: pageable host memory is copied into pinned memory of our own (*owns := true), anything else is used in place
+template <typename T> T* adopt_table(const T* src, int64_t count, int32_t location, bool* owns);
+// "One copy per physical device, shared by its logical GPUs", stated once: leader[p] of the logical GPUs 0..P-1 is the first LOCAL q <= p
+// with physical_device(q) == physical_device(p), -1 for a p another process drives.  The leader (leader[p] == p) builds the copy under
+// its DeviceGuard, the others take array[leader[p]] and record LEGION_AUDIT_SHARE; free_replicas (device_mem.h) is the one free of such
+// an array and goes by pointer identity -- the two belong together.  Host code only, no device is touched.
+__attribute__((visibility("hidden"))) std::vector<int> device_leaders(int P);
+// replica[p] := an HBM copy of `rows` rows of `width` elements of src (src_pitch elements apart) at dst_pitch, for every local logical GPU
+// that holds none, by the rule above.  Equal pitches: one plain copy of rows * dst_pitch elements (a whole CSR array is one such row);
+// otherwise the copy is zeroed and filled row by row.
+template <typename T>
+void replicate_table(const T* src, int64_t rows, int64_t width, int64_t src_pitch, int64_t dst_pitch, std::vector<T*>& replica);
+
 // ---- constants --------------------------------------------------------------------------------
 // Position-table entry: (epoch << kPosShift) | value.  epoch = kEpochTop - batch serial: entries of older batches compare GREATER than
 // anything of the running batch (stale without being touched); value = kProvisional | slot idx while claimed in the running hop, else
@@ -107,7 +123,7 @@ static_assert(sizeof(AliasEntry) == 8, "one 8-byte probe per weighted draw");
 // rows of more neighbours than this are built by a whole wave (k_build_alias_hub), the others by one lane each (k_build_alias)
 constexpr int32_t kAliasHubDegree = 256;
 // k_mark runs one CONTIGUOUS chunk of tiles per workgroup and leaves the chunk totals in GPUMemoryPool::chunk_tot; k_write scans them in
-// LDS, kMaxChunks / kBlock per thread.  One constant for the allocation (storage.cpp), the grid clamp (launch_sample_hop) and the LDS
+// LDS, kMaxChunks / kBlock per thread.  One constant for the allocation (memory_pool.cpp), the grid clamp (launch_sample_hop) and the LDS
 // array (k_write): changing one of them alone would let k_mark write past the allocation.
 constexpr int kMaxChunks = 2048;
 static_assert(kMaxChunks % kBlock == 0 && kMaxChunks >= 256 * 8, "kMaxChunks: a multiple of the workgroup size, >= 256 CUs x 8 workgroups");

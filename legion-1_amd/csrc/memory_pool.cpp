@@ -1,0 +1,281 @@
+// memory_pool.cpp -- host mirror of GPUMemoryPool (GPUMemoryPool.cuh:7-208): the per-batch scratch of one logical GPU, the serving modes
+// it is in and the per-pipe output buffers the caller registered.
+#include "internal.h"
+
+#include <algorithm>
+#include <cstring>
+
+#include "device_mem.h"
+
+using namespace legion;
+
+GPUMemoryPool::GPUMemoryPool(int32_t depth)
+{
+    pipeline_depth = depth > 0 ? depth : 1;
+    float_features.assign(pipeline_depth, nullptr);
+    labels.assign(pipeline_depth, nullptr);
+    node_counter.assign(pipeline_depth, nullptr);
+    edge_counter.assign(pipeline_depth, nullptr);
+    sampled_ids.assign(pipeline_depth, nullptr);
+    agg_src_off.assign(pipeline_depth, nullptr);
+    agg_dst_off.assign(pipeline_depth, nullptr);
+}
+
+// Every device scratch buffer the pool owns, with its size, in allocation order: GPUMemoryPool_AllocateScratch allocates this list and
+// release_scratch frees and forgets it -- a buffer named here is in both.  Sized from V, num_ids, max_slots and max_tiles as they are now.
+struct ScratchBuffer { void** slot; size_t bytes; };
+static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
+{
+    const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots, tiles = (size_t)p->max_tiles + 1;
+    return {{(void**)&p->pos_map, (size_t)p->V * sizeof(pos_t)},
+            {(void**)&p->cand, slots * sizeof(int32_t)},
+            {(void**)&p->aux2[0], slots * sizeof(int32_t)},
+            {(void**)&p->aux2[1], slots * sizeof(int32_t)},
+            {(void**)&p->tile_edge, tiles * sizeof(int32_t)},
+            {(void**)&p->tile_node, tiles * sizeof(int32_t)},
+            {(void**)&p->tile_pre, tiles * sizeof(int2)},
+            {(void**)&p->chunk_tot, (size_t)kMaxChunks * sizeof(int2)},
+            {(void**)&p->hop_state, sizeof(HopState)},
+            {(void**)&p->cache_search_buffer, ids * sizeof(int32_t)},
+            {(void**)&p->row_ptr, ids * sizeof(float*)},
+            {(void**)&p->agg_src_ids, ids * sizeof(int32_t)},
+            {(void**)&p->tmp_part_ind, ids},
+            {(void**)&p->tmp_part_off, ids * sizeof(int32_t)}};
+}
+// The per-pipe buffers of the aggregated modes with their per-pipe sizes, named once in the same way: fn(buffers, bytes per pipe, wanted).
+// The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums, agg_out_deg / agg_wdraw / agg_chunk_cnt.
+template <typename Fn>
+static void for_mode_buffers(GPUMemoryPool* p, Fn fn)
+{
+    const bool agg = p->modes.agg_last_hop, norm = agg && p->modes.agg_norm;
+    fn(p->cand_pipe, (size_t)p->max_slots * sizeof(int32_t), agg);
+    fn(p->agg_out_deg, (size_t)p->num_ids * sizeof(int32_t), norm);
+    fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), norm);
+    fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), norm);
+}
+// on the current device: what the pool's modes want and is missing is allocated, what is there stays
+static void alloc_mode_buffers(GPUMemoryPool* p)
+{
+    if (!p->owns_scratch) return;
+    for_mode_buffers(p, [&](auto& pipes, size_t bytes, bool wanted) {
+        if (!wanted) return;
+        pipes.resize(p->pipeline_depth, nullptr);
+        for (auto& b : pipes)
+            if (!b) HIP_CHECK(hipMalloc(&b, bytes));
+    });
+}
+
+// ---- the releases: each kind of scratch has one, and GPUMemoryPool_Finalize calls them all ----
+static void release_scratch(GPUMemoryPool* p)
+{
+    for (const ScratchBuffer& b : pool_scratch(p)) free_and_null(*b.slot);
+    for_mode_buffers(p, [](auto& pipes, size_t, bool) { for (auto& b : pipes) free_and_null(b); });
+}
+static void release_ctl(GPUMemoryPool* p) { free_and_null(p->ctl); }
+static void release_rows_seen(GPUMemoryPool* p)
+{
+    if (p->rows_seen) (void)hipHostFree(p->rows_seen);
+    p->rows_seen = p->rows_seen_dev = nullptr;
+}
+// the shuffled copy of the training list (GPUMemoryPool_BeginRound allocates it on first use)
+static void release_shuffle(GPUMemoryPool* p)
+{
+    free_and_null(p->shuf_ids);
+    free_and_null(p->shuf_labels);
+    p->shuf_cap = p->shuf_n = 0; p->shuf_src = nullptr; p->shuf_valid = false;
+}
+
+bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who)
+{
+    const std::string name(who);
+    if (!p) { LEGION_ARG_ERROR((name + ": null pool").c_str()); return false; }
+    if (p->capturing) { LEGION_ARG_ERROR((name + ": the pool is being captured").c_str()); return false; }
+    if (wanted.agg_norm != 0 && wanted.agg_norm != 1) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: unknown norm (0 = none, 1 = out-degree rsqrt)"); return false; }
+    if (wanted.agg_norm && !wanted.agg_last_hop && wanted.agg_norm != p->modes.agg_norm) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return false; }
+    if (wanted.sampling != kSamplingReplace && wanted.sampling != kSamplingDistinct && wanted.sampling != kSamplingWeighted) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampling: unknown sampling kind (0 = replace, 1 = distinct, 2 = weighted)"); return false; }
+    if (wanted.lp_draw < 0) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: negative triples per batch (0 = off, k > 0 = batches of 3 k)"); return false; }
+    if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
+    if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
+    if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k
+    if (wanted.seeded != p->modes.seeded || wanted.seed != p->modes.seed) p->ctl_synced = false;   // ctl holds the other state's draw word: a batch graph must reset the cursor
+    p->modes = wanted;
+    alloc_mode_buffers(p);
+    return true;
+}
+
+extern "C" {
+
+GPUMemoryPool* NewGPUMemoryPool(int32_t pipeline_depth) { return new GPUMemoryPool(pipeline_depth); }
+
+// Server.cu:184-196 (num_ids_) and :216-231 (scratch), sized for H hops
+void GPUMemoryPool_AllocateScratch(GPUMemoryPool* p, int32_t total_num_nodes, int32_t batch_size,
+                                   const int32_t* fanout, int32_t hops)
+{
+    if (!p || hops < 1 || hops > LEGION_MAX_HOPS || batch_size < 1 || total_num_nodes < 1) { LEGION_ARG_ERROR("GPUMemoryPool_AllocateScratch: bad arguments"); return; }
+    if (p->owns_scratch) GPUMemoryPool_Finalize(p); // re-sizing an initialised pool: release the old scratch first
+    p->V = total_num_nodes; p->batch_size = batch_size; p->hops = hops;
+    int64_t ids = batch_size, cur = batch_size, max_slots = 0;
+    p->level_bound[0] = batch_size;
+    for (int h = 0; h < hops; h++) {
+        p->fanout[h] = fanout[h];
+        cur *= fanout[h];
+        if (cur > max_slots) max_slots = cur;
+        ids += cur;
+        if (ids >= (1ll << 31)) { LEGION_ARG_ERROR("GPUMemoryPool_AllocateScratch: batch*fanouts exceeds int32"); return; }
+        if (cur >= (1ll << 30)) { LEGION_ARG_ERROR("GPUMemoryPool_AllocateScratch: a hop of 2^30 or more slots exceeds the slot-state encoding"); return; }
+        p->level_bound[h + 1] = (int32_t)cur;
+    }
+    p->num_ids = (int32_t)ids;
+    p->max_slots = (int32_t)max_slots;
+    p->max_tiles = (int32_t)sampler_max_tiles(max_slots);   // the narrow hops run smaller tiles (internal.h)
+    p->owns_scratch = true;
+    for (const ScratchBuffer& b : pool_scratch(p)) HIP_CHECK(hipMalloc(b.slot, b.bytes));
+    HIP_CHECK(hipMemset(p->pos_map, 0xFF, (size_t)total_num_nodes * sizeof(pos_t)));
+    p->batch_serial = 0;
+    HIP_CHECK(hipMalloc(&p->ctl, sizeof(BatchCtl)));
+    { const BatchCtl c{0, kEpochTop}; HIP_CHECK(hipMemcpy(p->ctl, &c, sizeof(c), hipMemcpyHostToDevice)); }
+    p->ctl_synced = false;
+    HIP_CHECK(hipHostMalloc((void**)&p->rows_seen, kRowsSeenWords * sizeof(int32_t), hipHostMallocMapped));
+    memset(p->rows_seen, 0, kRowsSeenWords * sizeof(int32_t));
+    HIP_CHECK(hipHostGetDevicePointer((void**)&p->rows_seen_dev, p->rows_seen, 0));
+    alloc_mode_buffers(p);
+    HIP_CHECK(hipDeviceSynchronize());
+}
+int32_t GPUMemoryPool_NumIds(const GPUMemoryPool* p) { return p->num_ids; }
+
+// The mode setters: the pool's modes with one field changed, through pool_apply_modes (internal.h: what is refused, what is
+// allocated).  Call them under the device the pool's scratch lives on.  Aggregated last hop: INTEGRATION.md "Aggregated last hop";
+// norm: 0 = plain sums, 1 = out-degree rsqrt ("Normalised sums"); distinct draws: "Sampling without replacement", nothing is allocated;
+// seed: "Seeded sampling", seed 0 is a seed like any other, nothing is allocated here (GPUMemoryPool_BeginRound fills the shuffled copy);
+// drawn link-prediction thirds: "Drawn link-prediction thirds", k triples per batch (0 = off) and the graph the positives are read from,
+// which the pool keeps (and forgets when the mode is switched off); nothing is allocated.
+static ServeModes modes_of(const GPUMemoryPool* p) { return p ? p->modes : ServeModes(); }
+void GPUMemoryPool_SetAggLastHop(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.agg_last_hop = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetAggLastHop"); }
+void GPUMemoryPool_SetAggNorm(GPUMemoryPool* p, int norm) { ServeModes m = modes_of(p); m.agg_norm = norm; pool_apply_modes(p, m, "GPUMemoryPool_SetAggNorm"); }
+void GPUMemoryPool_SetSampleDistinct(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.sampling = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetSampleDistinct"); }
+// the sampling kind as the enumeration it is: 0 = replace, 1 = distinct (what SetSampleDistinct(1) sets), 2 = weighted ("Weighted sampling":
+// nothing is allocated here, the alias table belongs to the graph: GPUGraphStorage_SetEdgeWeights)
+void GPUMemoryPool_SetSampling(GPUMemoryPool* p, int kind) { ServeModes m = modes_of(p); m.sampling = kind; pool_apply_modes(p, m, "GPUMemoryPool_SetSampling"); }
+int GPUMemoryPool_GetSampling(const GPUMemoryPool* p) { return p ? p->modes.sampling : 0; }
+// weighted sampling without replacement ("Weighted sampling without replacement"): a flag on top of the weighted kind, remembered across
+// kinds and acting only while the kind is 2; nothing is allocated here, the weights belong to the graph (GPUGraphStorage_RetainEdgeWeights)
+void GPUMemoryPool_SetWeightedDistinct(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.weighted_distinct = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetWeightedDistinct"); }
+int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p) { return p && p->modes.weighted_distinct ? 1 : 0; }
+// shared-key sampling ("Shared-key sampling"): a flag on top of the distinct kind, remembered across kinds and acting only while the kind
+// is 1; nothing is allocated.  An unseeded pool draws under word 0: deterministic, the same node keys in every batch
+void GPUMemoryPool_SetSharedDraws(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.shared_draws = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetSharedDraws"); }
+int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p) { return p && p->modes.shared_draws ? 1 : 0; }
+void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
+{
+    ServeModes m = modes_of(p);
+    m.seeded = on != 0; m.seed = seed;
+    if (pool_apply_modes(p, m, "GPUMemoryPool_SetSampleSeed")) p->ctl_synced = false;   // this call always has the next graph replay reset its cursor
+}
+void GPUMemoryPool_SetLpDraw(GPUMemoryPool* p, int32_t triples_per_batch, GPUGraphStorage* graph)
+{
+    ServeModes m = modes_of(p);
+    m.lp_draw = triples_per_batch;
+    GPUGraphStorage* const before = p ? p->lp_graph : nullptr;
+    if (p && !p->capturing) p->lp_graph = triples_per_batch > 0 ? graph : nullptr;
+    if (!pool_apply_modes(p, m, "GPUMemoryPool_SetLpDraw") && p && !p->capturing) p->lp_graph = before;
+}
+int32_t GPUMemoryPool_GetLpDraw(const GPUMemoryPool* p) { return p ? p->modes.lp_draw : 0; }
+int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->modes.agg_last_hop ? 1 : 0; }
+int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->modes.agg_norm : 0; }
+int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->modes.sampling == kSamplingDistinct ? 1 : 0; }
+int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed)
+{
+    if (seed) *seed = p ? p->modes.seed : 0;
+    return p && p->modes.seeded ? 1 : 0;
+}
+// the current pipe's block out-degrees as the last normalised batch left them (int32[legion_batch_nodes(nc, H)]); null before the mode was set
+int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p)
+{
+    if (!p || p->current_pipe < 0 || p->current_pipe >= (int)p->agg_out_deg.size()) return nullptr;
+    return p->agg_out_deg[p->current_pipe];
+}
+int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p) { return p ? (int32_t)p->round : 0; }
+
+// A new round (the trainer's epoch) begins: the draw words and the shuffle of the batches that follow are those of `round`.  Under a seed the
+// pool's shuffled copy of (noder, dev_id)'s training list is (re)filled on `stream` -- the stream the batch generator runs on, so that the
+// first k_seed of the round is ordered behind it.  noder == null: the training list stays in file order (lists served verbatim, e.g.
+// link-prediction thirds); the draws are seeded all the same.  With the mode off the round is recorded and nothing is launched.
+int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* noder, int32_t dev_id, int32_t round)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: null pool"); return -1; }
+    if (p->capturing) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: the pool is being captured (a round begins between batches, not inside a recording)"); return -1; }
+    if (round < 0) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: negative round"); return -1; }
+    if (p->round != (uint32_t)round) p->shuf_valid = false;   // whatever the mode: the copy holds another round's permutation
+    p->round = (uint32_t)round;
+    p->ctl_synced = false;   // the next replay resets the cursor: k_set_cursor carries the round's draw key
+    if (!p->modes.seeded) return 0;
+    p->shuf_file_order = noder == nullptr;
+    p->shuf_valid = false;
+    if (!noder) return 0;
+    if (!p->owns_scratch) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: GPUMemoryPool_AllocateScratch was not called"); return -1; }
+    const GPUNodeStorage::SeedSet& set = noder->seed_set(LEGION_TRAINMODE, dev_id);
+    if (set.num > 0 && (!set.ids || !set.labels)) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: the training list of this device is not built"); return -1; }
+    const int32_t k = p->modes.lp_draw;   // drawn link-prediction thirds: whole triples move
+    if (k > 0 && set.num % (3 * k) != 0) { LEGION_ARG_ERROR("GPUMemoryPool_BeginRound: drawn link-prediction thirds (GPUMemoryPool_SetLpDraw): the training list's length is not a multiple of the batch of 3 k ([src | pos | neg] thirds, padded)"); return -1; }
+    if (set.num > p->shuf_cap || !p->shuf_ids) {   // first use, or a longer list: batches that read the old copy may still be in flight
+        HIP_CHECK(hipDeviceSynchronize());
+        release_shuffle(p);
+        p->shuf_cap = std::max(set.num, 1);
+        HIP_CHECK(hipMalloc(&p->shuf_ids, (size_t)p->shuf_cap * sizeof(int32_t)));
+        HIP_CHECK(hipMalloc(&p->shuf_labels, (size_t)p->shuf_cap * sizeof(int32_t)));
+        if (!p->shuf_ids || !p->shuf_labels) return -1;
+    }
+    if (k > 0) launch_shuffle_triples((hipStream_t)stream, set.ids, set.labels, set.num, k, seeded_shuffle_key(p->modes.seed, p->round), p->shuf_ids, p->shuf_labels);
+    else launch_shuffle_seeds((hipStream_t)stream, set.ids, set.labels, set.num, seeded_shuffle_key(p->modes.seed, p->round), p->shuf_ids, p->shuf_labels);
+    p->shuf_n = set.num;
+    p->shuf_src = set.ids;
+    p->shuf_valid = true;
+    return error_pending() ? -1 : 0;
+}
+
+#define POOL_PIPE_SETTER(name, field, type) \
+    void GPUMemoryPool_Set##name(GPUMemoryPool* p, type* ptr, int32_t pipe) { \
+        if (pipe < 0 || pipe >= p->pipeline_depth) { LEGION_ARG_ERROR("GPUMemoryPool_Set" #name ": bad pipe"); return; } \
+        p->field[pipe] = ptr; } \
+    type* GPUMemoryPool_Get##name(const GPUMemoryPool* p) { return p->field[p->current_pipe]; }
+POOL_PIPE_SETTER(SampledIds, sampled_ids, int32_t)
+POOL_PIPE_SETTER(FloatFeatures, float_features, float)
+POOL_PIPE_SETTER(Labels, labels, int32_t)
+POOL_PIPE_SETTER(AggSrcOf, agg_src_off, int32_t)
+POOL_PIPE_SETTER(AggDstOf, agg_dst_off, int32_t)
+POOL_PIPE_SETTER(NodeCounter, node_counter, int32_t)
+POOL_PIPE_SETTER(EdgeCounter, edge_counter, int32_t)
+#undef POOL_PIPE_SETTER
+void GPUMemoryPool_SetFeatureRows(GPUMemoryPool* p, int32_t rows) { p->feature_rows = rows; }
+void GPUMemoryPool_SetCurrentPipe(GPUMemoryPool* p, int32_t pipe) { p->current_pipe = pipe % p->pipeline_depth; }
+void GPUMemoryPool_SetCurrentMode(GPUMemoryPool* p, int32_t mode) { p->mode = mode; }
+void GPUMemoryPool_SetIter(GPUMemoryPool* p, int32_t iter) { p->iter = iter; }
+int32_t GPUMemoryPool_GetCurrentMode(const GPUMemoryPool* p) { return p->mode; }
+int32_t GPUMemoryPool_GetIter(const GPUMemoryPool* p) { return p->iter; }
+int32_t* GPUMemoryPool_GetAggSrcId(const GPUMemoryPool* p) { return p->agg_src_ids; }
+int32_t* GPUMemoryPool_GetCacheSearchBuffer(const GPUMemoryPool* p) { return p->cache_search_buffer; }
+char* GPUMemoryPool_GetTmpPartIdx(const GPUMemoryPool* p) { return (char*)p->tmp_part_ind; }
+int32_t* GPUMemoryPool_GetTmpPartOff(const GPUMemoryPool* p) { return p->tmp_part_off; }
+uint64_t* GPUMemoryPool_GetPositionMap(const GPUMemoryPool* p) { return (uint64_t*)p->pos_map; }
+int32_t* GPUMemoryPool_GetCandidateBuffer(const GPUMemoryPool* p) { return p->cand; }
+uint32_t GPUMemoryPool_GetBatchSerial(const GPUMemoryPool* p) { return p->batch_serial; }
+void GPUMemoryPool_SetBatchSerial(GPUMemoryPool* p, uint32_t serial) { p->batch_serial = serial; p->ctl_synced = false; }
+
+void GPUMemoryPool_Finalize(GPUMemoryPool* p)
+{
+    if (!p || !p->owns_scratch) return;
+    GPUMemoryPool_ReleasePeerExchange(p);
+    release_scratch(p);
+    release_ctl(p);
+    release_rows_seen(p);
+    release_shuffle(p);
+    p->owns_scratch = false;
+}
+void GPUMemoryPool_Delete(GPUMemoryPool* p)
+{
+    if (!p) return;
+    GPUMemoryPool_Finalize(p);
+    delete p;
+}
+
+} // extern "C"

@@ -380,25 +380,24 @@ bool place_tables(Server* s, const LegionSynthSpec& spec)
     }
     if (s->synth) {
         // generated in HBM on logical GPU 0; every other physical device of the job gets a copy of its own, generated in place
-        // (the storages free them as replicas)
-        std::vector<int> have{physical_device(0)};
+        // (the storages free them as replicas: device_leaders / free_replicas)
+        const std::vector<int> leader = device_leaders(G);
+        GPUGraphStorage* g = s->graph;
         for (int i = 1; i < G; i++) {
-            const int phys = physical_device(i);
-            int src = -1;
-            for (int j = 1; j < i; j++) if (physical_device(j) == phys && s->graph->replica_indptr[j]) src = j;
-            if (phys == have[0]) {                                 // shares GPU 0's tables
+            if (leader[i] < 0) continue;
+            if (leader[i] == 0) {                                  // shares GPU 0's tables and holds no replica
                 LEGION_AUDIT_SHARE(s->indptr, i); LEGION_AUDIT_SHARE(s->indices, i); LEGION_AUDIT_SHARE(s->feats, i);
                 continue;
             }
-            if (src >= 0) {
-                s->graph->replica_indptr[i] = s->graph->replica_indptr[src]; s->graph->replica_indices[i] = s->graph->replica_indices[src];
-                s->noder->replica_attrs[i] = s->noder->replica_attrs[src];
-                LEGION_AUDIT_SHARE(s->graph->replica_indptr[i], i); LEGION_AUDIT_SHARE(s->graph->replica_indices[i], i); LEGION_AUDIT_SHARE(s->noder->replica_attrs[i], i);
+            if (leader[i] != i) {
+                g->replica_indptr[i] = g->replica_indptr[leader[i]]; g->replica_indices[i] = g->replica_indices[leader[i]];
+                s->noder->replica_attrs[i] = s->noder->replica_attrs[leader[i]];
+                LEGION_AUDIT_SHARE(g->replica_indptr[i], i); LEGION_AUDIT_SHARE(g->replica_indices[i], i); LEGION_AUDIT_SHARE(s->noder->replica_attrs[i], i);
                 continue;
             }
             DeviceGuard guard(i);
             int64_t E2 = 0;
-            if (!synth_tables_here(spec, s->synth_src.skew, s->synth_pitch, &s->graph->replica_indptr[i], &s->graph->replica_indices[i],
+            if (!synth_tables_here(spec, s->synth_src.skew, s->synth_pitch, &g->replica_indptr[i], &g->replica_indices[i],
                                    &s->noder->replica_attrs[i], &E2) || E2 != m.edge_num) {
                 LEGION_ARG_ERROR("Server_Initialize: generating the synth: tables on a further GPU failed");
                 return false;
