@@ -451,7 +451,11 @@ int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p);
  * rule reads the row alone: whole CSR, pre-sampling hops and the clique's fragments alike; everything behind the position is the default
  * mode's.  An unseeded pool is allowed and deterministic: every batch prefers the same nodes (the `legion` server refuses that at boot).
  * Sticky argument errors, by name: a null pool, a switch while the pool is being captured, a fan-out above 64 under the flag
- * (GPU_Random_Sampling); LegionBatchGraph_Launch refuses a graph recorded in the other state of the flag.  Nothing is allocated. */
+ * (GPU_Random_Sampling); LegionBatchGraph_Launch refuses a graph recorded in the other state of the flag.  Nothing is allocated.
+ * Under kind 2 the flag acts only on top of GPUMemoryPool_SetWeightedDistinct (INTEGRATION.md "Weighted shared-key sampling"): the uniform
+ * under a column's exponential key becomes u_c = mix32(nbr[c] ^ mix32(Ks ^ 0x27D4EB2F)), one per NEIGHBOUR NODE and batch, and everything
+ * else is weighted sampling without replacement as it is (retained weights required, whole CSR only, fan-out at most 64).  Under kind 2
+ * without GPUMemoryPool_SetWeightedDistinct the flag is remembered and not read. */
 void GPUMemoryPool_SetSharedDraws(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
@@ -741,6 +745,10 @@ void legion_weighted_distinct_probe(void* stream, const int32_t* row, const int3
 /* Probe of shared-key sampling, by k_sample's own device functions: key_out[m] = the node key of neighbour id ids[m] (any int32, keyed by
  * its bit pattern) under the draw word word[m] (0 = unseeded).  All pointers are device memory. */
 void legion_shared_draw_probe(void* stream, const int32_t* ids, const uint32_t* word, uint32_t* key_out, int32_t n);
+/* Probe of weighted shared-key sampling, by k_sample's own device functions: for neighbour id ids[m] (any int32, keyed by its bit pattern)
+ * under the draw word word[m] (0 = unseeded) and weight w[m] > 0, u_out[m] = the node's hash and key_out[m] = its fp64 key.  All pointers
+ * are device memory. */
+void legion_weighted_shared_probe(void* stream, const int32_t* ids, const uint32_t* word, const float* w, uint32_t* u_out, double* key_out, int32_t n);
 uint32_t legion_seeded_draw_word(uint32_t seed, int32_t round, int32_t iter);
 uint32_t legion_seeded_shuffle_key(uint32_t seed, int32_t round);
 /* compute units of the current device as the sampler's persistent grids count them: a hop of more than 4 x this x 1024 slots makes a

@@ -300,6 +300,7 @@ _SIGS = {
     "legion_weighted_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
     "legion_weighted_distinct_probe": (None, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
     "legion_shared_draw_probe": (None, [vp, vp, vp, vp, i32]),
+    "legion_weighted_shared_probe": (None, [vp, vp, vp, vp, vp, vp, i32]),
     "legion_lp_draw_probe": (None, [vp, u32, i32, i32, vp, vp, i32, vp, vp, i32]),
     "legion_seeded_draw_word": (u32, [u32, i32, i32]),
     "legion_seeded_shuffle_key": (u32, [u32, i32]),
@@ -544,7 +545,8 @@ class Engine:
                   seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False):
         """shared_draws (GPUMemoryPool_SetSharedDraws, only with sample="distinct"): the distinct draws are keyed by the neighbour node, so rows
         that see the same neighbours pick the same ones; seed=None draws under word 0 (the same node keys in every batch).  Set on every call
-        like `sample`.
+        like `sample`.  Also allowed with sample="weighted", weighted_distinct=True: the weighted draws without replacement take their
+        uniforms per neighbour node (INTEGRATION.md "Weighted shared-key sampling").
         weighted_distinct (GPUMemoryPool_SetWeightedDistinct, only with sample="weighted" on an Engine(retain_edge_weights=True)): the
         weighted draws are without replacement -- min(columns of weight > 0, fan-out) distinct columns per row, by exponential keys.  Set on
         every call like `sample`.
@@ -602,7 +604,7 @@ class Engine:
             raise ValueError("sample: 'replace', 'distinct' or 'weighted'")
         if weighted_distinct and sample != "weighted":
             raise ValueError("weighted_distinct=True needs sample='weighted': the flag turns the weighted draws into draws without replacement")
-        if shared_draws and sample != "distinct":
+        if shared_draws and sample != "distinct" and not (sample == "weighted" and weighted_distinct):
             raise ValueError("shared_draws=True needs sample='distinct': the flag keys the distinct draws by the neighbour node")
         if sample == "weighted" and not self.has_edge_weights():
             raise ValueError("sample='weighted' needs the Engine's edge_weights (Engine(edge_weights=...) or set_edge_weights())")

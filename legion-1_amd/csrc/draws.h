@@ -71,6 +71,16 @@ __device__ inline bool weighted_distinct_excluded(uint32_t u, float w, double tk
 #pragma clang fp contract(off)
     return 1.0 - weighted_distinct_x(u) > (tk * (double)w) * (1.0 + 0x1p-40);
 }
+// The node keys of the two shared-key rules ("Shared-key sampling" below states the first): the batch's salt and the hash of a neighbour id under it.
+__device__ inline uint32_t shared_salt(uint32_t w) { return mix32(w ^ 0x165667B1u); }
+__device__ inline uint32_t shared_key(int32_t nbr, uint32_t salt) { return mix32((uint32_t)nbr ^ salt); }
+// Weighted shared-key sampling (INTEGRATION.md "Weighted shared-key sampling", GPUMemoryPool_SetSharedDraws on top of the weighted kind with
+// GPUMemoryPool_SetWeightedDistinct): weighted sampling without replacement whose uniform belongs to the NEIGHBOUR NODE, not to the column.
+// Ksw = mix32(shared_salt(w) ^ 0x27D4EB2F) is the batch's salt (no hop, no row), u_c = mix32(nbr[c] ^ Ksw), and the key is
+// weighted_distinct_keyval(u_c, w_c) as it is: rows that see the same neighbours at the same weights prefer the same ones, and each row still
+// takes its columns in proportion to their weights.  A negative entry is keyed by its bit pattern like any id.
+__device__ inline uint32_t weighted_shared_salt(uint32_t w) { return mix32(shared_salt(w) ^ 0x27D4EB2Fu); }
+__device__ inline uint32_t weighted_shared_u(int32_t nbr, uint32_t salt) { return shared_key(nbr, salt); }
 // One WAVE resolves one row (every lane of the wave calls this with the same arguments): p[0, min(m, f)) := the row's picks in ascending
 // column order, m = the row's eligible columns; returns min(m, f).  wp: the row's d > 0 weights; p is LDS in k_sample.  The lanes stride
 // over the row in chunks of 64 (coalesced weight reads, no single-lane loop).  Pass 1 counts the eligible columns and compacts the first f
@@ -78,7 +88,12 @@ __device__ inline bool weighted_distinct_excluded(uint32_t u, float w, double tk
 // entry l in lane l: a column whose (key, column) lies in front of entry f - 1 is inserted where the ballot of the entries in front of
 // it ends and the tail moves up one lane; at the end the first f entries are ranked by column.  A chunk forms the key (the fp64 log) only
 // of the columns weighted_distinct_excluded lets through against the list's last key at the chunk's start (the key only falls from there).
-__device__ inline int32_t weighted_distinct_resolve(int32_t* p, const float* __restrict__ wp, int32_t d, int32_t f, uint32_t key)
+// NODE (weighted shared-key sampling, below): the uniform of column c is the hash of the column's NEIGHBOUR ID, rowp[c], under the batch's
+// salt `key` instead of the hash of c under the row's key: pass 2 loads rowp[c] beside wp[c] (two independent coalesced loads).  Nothing
+// else differs, since everything else reads (u, w) alone; equal ids of equal weight have bit-equal keys, and the column settles them as
+// the (key, column) compares already do.  NODE = false does not read rowp.
+template <bool NODE>
+__device__ inline int32_t weighted_distinct_resolve(int32_t* p, const float* __restrict__ wp, const int32_t* __restrict__ rowp, int32_t d, int32_t f, uint32_t key)
 {
     const int lane = lane_id();
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -99,7 +114,9 @@ __device__ inline int32_t weighted_distinct_resolve(int32_t* p, const float* __r
     for (uint32_t c0 = 0; c0 < ud; c0 += 64u) {
         const uint32_t c = c0 + (uint32_t)lane;
         const float w = c < ud ? wp[c] : 0.0f;
-        const uint32_t u = weighted_distinct_u(key, c);
+        uint32_t u;
+        if constexpr (NODE) u = weighted_shared_u(c < ud ? rowp[c] : 0, key);
+        else u = weighted_distinct_u(key, c);
         const double tk0 = __shfl(bk, f - 1);   // by the whole wave, in front of the lanes' own tests
         bool todo = w > 0.0f && !weighted_distinct_excluded(u, w, tk0);
         const double k = todo ? weighted_distinct_keyval(u, w) : inf;
@@ -130,8 +147,6 @@ __device__ inline int32_t weighted_distinct_resolve(int32_t* p, const float* __r
 // mix32(nbr[c] ^ Ks); a row of degree d > f takes its f columns of smallest (key, column), handed out in ascending column order; d <= f takes
 // every column and forms no key.  mix32 is a bijection, so only equal ids tie, and the column settles those: (key << 32 | column) is one
 // uint64 compare.  A negative entry is keyed by its bit pattern like any id.
-__device__ inline uint32_t shared_salt(uint32_t w) { return mix32(w ^ 0x165667B1u); }
-__device__ inline uint32_t shared_key(int32_t nbr, uint32_t salt) { return mix32((uint32_t)nbr ^ salt); }
 __device__ inline unsigned long long wave_read64(unsigned long long v, int l)   // lane l's v, l wave-uniform: two v_readlane, no LDS crossbar
 {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);

@@ -147,26 +147,30 @@ struct ServeModes {
     bool shared_draws = false;   // $LEGION_SHARED_DRAWS=1, only with sampling = distinct (and, from the environment, only under a seed): the random number belongs
                                  // to the NEIGHBOUR NODE, not to the row -- every row keeps its min(degree, fan-out) columns of smallest node key, so rows that see
                                  // the same neighbours pick the same ones ("Shared-key sampling").  A flag on top of the kind, like weighted_distinct: remembered
-                                 // across kinds, acts only while sampling == 1; not published
+                                 // across kinds, acts while sampling == 1 and, with weighted_distinct on, while sampling == 2: there the exponential key's uniform
+                                 // belongs to the neighbour node ("Weighted shared-key sampling"); not published
     bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws; }
 };
 // The draw rule of a sampler hop: what `sampling` and the flags `weighted_distinct` and `shared_draws` say together.  draw_rule_of is the one
 // place that reads the three; the launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
-enum class DrawRule { Stream, Distinct, Weighted, WeightedDistinct, Shared };
+enum class DrawRule { Stream, Distinct, Weighted, WeightedDistinct, Shared, WeightedShared };
 inline DrawRule draw_rule_of(const ServeModes& m)
 {
-    if (m.sampling == kSamplingWeighted) return m.weighted_distinct ? DrawRule::WeightedDistinct : DrawRule::Weighted;
+    // shared_draws acts under the weighted kind only on top of weighted_distinct ("Weighted shared-key sampling"): without it the flag is remembered, not read
+    if (m.sampling == kSamplingWeighted) return !m.weighted_distinct ? DrawRule::Weighted : m.shared_draws ? DrawRule::WeightedShared : DrawRule::WeightedDistinct;
     if (m.sampling == kSamplingDistinct) return m.shared_draws ? DrawRule::Shared : DrawRule::Distinct;
     return DrawRule::Stream;
 }
 // the rule's table (alias table, retained weights) lies beside the whole CSR's indices: never the fragments, exactly as pre-sampling
-constexpr bool draw_rule_whole_csr(DrawRule r) { return r == DrawRule::Weighted || r == DrawRule::WeightedDistinct; }
+constexpr bool draw_rule_whole_csr(DrawRule r) { return r == DrawRule::Weighted || r == DrawRule::WeightedDistinct || r == DrawRule::WeightedShared; }
+// the rule reads the graph's retained edge weights, not the alias table
+constexpr bool draw_rule_reads_weights(DrawRule r) { return r == DrawRule::WeightedDistinct || r == DrawRule::WeightedShared; }
 // the largest fan-out the rule runs (k_sample<.., DISTINCT, ..> stages a row's picks in static LDS); 0 = no bound
-constexpr int32_t draw_rule_max_fanout(DrawRule r) { return r == DrawRule::Distinct || r == DrawRule::WeightedDistinct || r == DrawRule::Shared ? kDistinctMaxFanout : 0; }
+constexpr int32_t draw_rule_max_fanout(DrawRule r) { return r == DrawRule::Distinct || r == DrawRule::WeightedDistinct || r == DrawRule::Shared || r == DrawRule::WeightedShared ? kDistinctMaxFanout : 0; }
 // The only readers of the seven variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
 // unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed, unknown LEGION_LP_DRAW, LEGION_LP_DRAW without a
 // seed, unknown LEGION_WEIGHTED_DISTINCT, LEGION_WEIGHTED_DISTINCT without LEGION_SAMPLING=weighted, unknown LEGION_SHARED_DRAWS,
-// LEGION_SHARED_DRAWS without LEGION_SAMPLING=distinct, LEGION_SHARED_DRAWS without a seed.  Host code only, no device is touched.
+// LEGION_SHARED_DRAWS without LEGION_SAMPLING=distinct (or =weighted with LEGION_WEIGHTED_DISTINCT=1), LEGION_SHARED_DRAWS without a seed.  Host code only, no device is touched.
 bool serve_modes_from_env(ServeModes& m, std::string& why);
 // LEGION_LP_DRAW against what is served, once the meta line is known: false with the refusal in `why` unless the training lists are
 // link-prediction thirds (meta flag 2) of a batch size divisible by 3; m.lp_draw := raw_batch_size / 3.  Nothing to do with the mode off.
@@ -343,7 +347,7 @@ void launch_advance(hipStream_t s, BatchCtl* ctl);
 int sampler_cu_count();       // compute units every grid is sized by (current device; asked once per process)
 void warm_static_tables();   // per-device constant tables: must exist before a stream capture starts
 // What a hop draws by: the rule and its tables beside the whole CSR -- the alias table (both weighted rules; Weighted reads it) and the graph's
-// retained edge weights (WeightedDistinct reads them); null under the other rules.  Resolved from (graph, modes, device) in launchers.cpp.
+// retained edge weights (WeightedDistinct and WeightedShared read them); null under the other rules.  Resolved from (graph, modes, device) in launchers.cpp.
 struct DrawTables { DrawRule rule; const AliasEntry* alias; const float* weights; };
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
                        int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw);
@@ -357,6 +361,8 @@ void launch_weighted_probe(hipStream_t s, const int32_t* row, const int32_t* hop
                            int32_t* k, uint32_t* ub, int32_t n);
 // weighted sampling without replacement: u[m] and key[m] of column col[m] of row row[m] of hop hop[m] under draw word word[m] at weight w[m] > 0
 void launch_shared_draw_probe(hipStream_t s, const int32_t* ids, const uint32_t* word, uint32_t* key, int32_t n);
+// weighted shared-key sampling: u[m] and key[m] of neighbour id ids[m] under draw word word[m] at weight w[m] > 0
+void launch_weighted_shared_probe(hipStream_t s, const int32_t* ids, const uint32_t* word, const float* w, uint32_t* u, double* key, int32_t n);
 void launch_weighted_distinct_probe(hipStream_t s, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
                                     uint32_t* u, double* key, int32_t n);
 void launch_find_feat(hipStream_t s, const int32_t* sampled_ids, int32_t* cache_offset, const int32_t* nc,

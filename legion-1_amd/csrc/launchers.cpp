@@ -59,11 +59,11 @@ static void csr_tables_of(CsrTables& csr, const GPUGraphStorage* graph, const GP
 }
 
 // What logical GPU `dev` draws a hop by under `modes`: the rule, and the alias table and -- without replacement, which the graph keeps them
-// for only when asked to -- the weights beside the whole CSR.  False (sticky error): the graph lacks the rule's table on this GPU.
+// for only when asked to -- the weights beside the whole CSR (both rules without replacement: by column key and by node key).  False (sticky error): the graph lacks the rule's table on this GPU.
 static bool draw_tables_of(DrawTables& t, const GPUGraphStorage* graph, const ServeModes& modes, int dev)
 {
     t.rule = draw_rule_of(modes);
-    const bool weighted = draw_rule_whole_csr(t.rule), wdistinct = t.rule == DrawRule::WeightedDistinct;
+    const bool weighted = draw_rule_whole_csr(t.rule), wdistinct = draw_rule_reads_weights(t.rule);
     t.alias = weighted && dev < (int)graph->alias.size() ? graph->alias[dev] : nullptr;
     t.weights = wdistinct && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
     if (weighted && !t.alias) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) over a graph without edge weights on this GPU: call GPUGraphStorage_SetEdgeWeights first"); return false; }

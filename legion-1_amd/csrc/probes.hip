@@ -85,6 +85,23 @@ __global__ void k_shared_draw_probe(const int32_t* ids, const uint32_t* word, ui
     if (m < n) key[m] = shared_key(ids[m], shared_salt(word[m]));
 }
 
+// Weighted shared-key sampling: the node hash and the fp64 key of n (neighbour id, weight) pairs, by the device functions k_sample<.., DISTINCT, WEIGHTED, SHARED> runs
+__global__ void k_weighted_shared_probe(const int32_t* ids, const uint32_t* word, const float* w, uint32_t* u, double* key, int32_t n)
+{
+    const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
+    if (m >= n) return;
+    const uint32_t uc = weighted_shared_u(ids[m], weighted_shared_salt(word[m]));
+    u[m] = uc;
+    key[m] = weighted_distinct_keyval(uc, w[m]);
+}
+
+void launch_weighted_shared_probe(hipStream_t s, const int32_t* ids, const uint32_t* word, const float* w, uint32_t* u, double* key, int32_t n)
+{
+    if (n <= 0) return;
+    LEGION_AUDIT_LAUNCH(s, "k_weighted_shared_probe", LEGION_AW(u), LEGION_AW(key), LEGION_AL(ids), LEGION_AL(word), LEGION_AL(w));
+    k_weighted_shared_probe<<<(n + 255) / 256, 256, 0, s>>>(ids, word, w, u, key, n);
+    HIP_CHECK_LAST();
+}
 void launch_shared_draw_probe(hipStream_t s, const int32_t* ids, const uint32_t* word, uint32_t* key, int32_t n)
 {
     if (n <= 0) return;

@@ -263,6 +263,11 @@ void legion_shared_draw_probe(void* stream, const int32_t* ids, const uint32_t* 
     if (n > 0 && (!ids || !word || !key_out)) { LEGION_ARG_ERROR("legion_shared_draw_probe: null array"); return; }
     launch_shared_draw_probe((hipStream_t)stream, ids, word, key_out, n);
 }
+void legion_weighted_shared_probe(void* stream, const int32_t* ids, const uint32_t* word, const float* w, uint32_t* u_out, double* key_out, int32_t n)
+{
+    if (n > 0 && (!ids || !word || !w || !u_out || !key_out)) { LEGION_ARG_ERROR("legion_weighted_shared_probe: null array"); return; }
+    launch_weighted_shared_probe((hipStream_t)stream, ids, word, w, u_out, key_out, n);
+}
 void legion_weighted_distinct_probe(void* stream, const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
                                     uint32_t* u_out, double* key_out, int32_t n)
 {

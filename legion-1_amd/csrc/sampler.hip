@@ -293,11 +293,15 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
 // the same ones.  Staged in s_pick and read by the slots exactly like the distinct mode's; one WAVE resolves a row of degree > f, its lanes
 // striding over the row's ids (shared_resolve, draws.h).  The rule reads nothing but the row itself, through s_row[r]: whole CSR, pre-sampling
 // and the clique's fragments alike, and no table.
+// DISTINCT && WEIGHTED && SHARED (GPUMemoryPool_SetSharedDraws on top of the weighted kind with GPUMemoryPool_SetWeightedDistinct, INTEGRATION.md
+// "Weighted shared-key sampling"): the weighted rule without replacement with one difference, the uniform under a column's exponential key
+// is the hash of the column's NEIGHBOUR ID and the batch's draw word (weighted_distinct_resolve<true>: it loads the row's ids through s_row[r]
+// beside its weights).  Whole CSR only, like the other weighted rules.
 template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED, bool SHARED>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
     static_assert(!(WEIGHTED && PARTITIONED), "weighted draws read the whole CSR");
-    static_assert(!SHARED || (DISTINCT && !WEIGHTED), "shared keys are a flag on top of the distinct kind");
+    static_assert(!SHARED || DISTINCT, "shared keys are a flag on top of the rules without replacement");
     constexpr bool STREAM = !DISTINCT && !WEIGHTED;   // the minstd stream of the default mode
     __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
     __shared__ int32_t s_deg[TILE + 2];
@@ -373,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 if (s_deg[r] > f) distinct_resolve(s_pick + r * f, s_deg[r], f);
             __syncthreads();
         }
-        if constexpr (SHARED) {
+        if constexpr (SHARED && !WEIGHTED) {
             const uint32_t salt = shared_salt(draw);
             for (int32_t r = wave_id(); r < nrows; r += kBlock / 64) {   // one wave per row: r and everything read through it is wave-uniform
                 const int32_t d = s_deg[r];
@@ -386,8 +390,10 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             for (int32_t r = wave_id(); r < nrows; r += kBlock / 64) {   // one wave per row: r and everything read through it is wave-uniform
                 const int32_t d = s_deg[r];
                 if (d <= 0) continue;
-                const int32_t got = weighted_distinct_resolve(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), d, f,
-                                                              weighted_distinct_key((uint32_t)(i0 + r), hop, draw));
+                int32_t got;
+                if constexpr (SHARED) got = weighted_distinct_resolve<true>(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), s_row[r], d, f, weighted_shared_salt(draw));
+                else got = weighted_distinct_resolve<false>(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), nullptr, d, f,
+                                                            weighted_distinct_key((uint32_t)(i0 + r), hop, draw));
                 if (lane_id() == 0) s_deg[r] = got;   // what the slot test below reads: min(eligible columns, f)
             }
             __syncthreads();
@@ -888,18 +894,18 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.count = count; a.op_id = op_id;
     a.window = std::min(count - 1, 8);
     a.prefilter_from_op = 4;   // hop 1 goes straight to the atomic (see k_sample; moving the boundary lost: profiles/r04_sampler.md)
-    if (draw.rule == DrawRule::WeightedDistinct) a.weights = draw.weights;
+    if (draw_rule_reads_weights(draw.rule)) a.weights = draw.weights;
     else a.alias = draw.rule == DrawRule::Weighted ? draw.alias : nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices), LEGION_AL(a.alias));
     // The instantiation by [whole CSR / pre-sampling / the clique's fragments][rule]; the rules that draw from the whole CSR only have no
     // partitioned one (launch_sample_hop refuses such tables).  A pre-sampling hop gets whole-CSR tables, so it is never partitioned.
-    static constexpr void (*kSample[][5])(SampleArgs) = {
-        {k_sample<TILE, false, false, false, false, false>, k_sample<TILE, false, false, true, false, false>, k_sample<TILE, false, false, false, true, false>, k_sample<TILE, false, false, true, true, false>, k_sample<TILE, false, false, true, false, true>},
-        {k_sample<TILE, true, false, false, false, false>, k_sample<TILE, true, false, true, false, false>, k_sample<TILE, true, false, false, true, false>, k_sample<TILE, true, false, true, true, false>, k_sample<TILE, true, false, true, false, true>},
-        {k_sample<TILE, false, true, false, false, false>, k_sample<TILE, false, true, true, false, false>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true>}};
+    static constexpr void (*kSample[][6])(SampleArgs) = {
+        {k_sample<TILE, false, false, false, false, false>, k_sample<TILE, false, false, true, false, false>, k_sample<TILE, false, false, false, true, false>, k_sample<TILE, false, false, true, true, false>, k_sample<TILE, false, false, true, false, true>, k_sample<TILE, false, false, true, true, true>},
+        {k_sample<TILE, true, false, false, false, false>, k_sample<TILE, true, false, true, false, false>, k_sample<TILE, true, false, false, true, false>, k_sample<TILE, true, false, true, true, false>, k_sample<TILE, true, false, true, false, true>, k_sample<TILE, true, false, true, true, true>},
+        {k_sample<TILE, false, true, false, false, false>, k_sample<TILE, false, true, true, false, false>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true>, nullptr}};
     static_assert((int)DrawRule::Stream == 0 && (int)DrawRule::Distinct == 1 && (int)DrawRule::Weighted == 2 && (int)DrawRule::WeightedDistinct == 3, "kSample's columns");
-    static_assert((int)DrawRule::Shared == 4, "kSample's last column");
+    static_assert((int)DrawRule::Shared == 4 && (int)DrawRule::WeightedShared == 5, "kSample's last columns");
     kSample[is_presc ? 1 : csr.topo_owner ? 2 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
@@ -923,10 +929,11 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
     // the tables match the rule (launchers.cpp resolved both from the same modes): a kernel never receives a null table, nor fragments without one
-    const void* table = draw.rule == DrawRule::WeightedDistinct ? (const void*)draw.weights : (const void*)draw.alias;
+    const void* table = draw_rule_reads_weights(draw.rule) ? (const void*)draw.weights : (const void*)draw.alias;
     if (draw_rule_whole_csr(draw.rule) && (!table || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
     if (draw_rule_max_fanout(draw.rule) && count > draw_rule_max_fanout(draw.rule)) {
         LEGION_ARG_ERROR(draw.rule == DrawRule::Distinct ? "GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"
+                         : draw.rule == DrawRule::WeightedShared ? "GPU_Random_Sampling: weighted shared-key sampling (GPUMemoryPool_SetWeightedDistinct + GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"
                          : draw.rule == DrawRule::Shared ? "GPU_Random_Sampling: shared-key sampling (GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"
                                                          : "GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS");
         return;

@@ -24,7 +24,7 @@ static bool parse_seed(const char* n, uint32_t& seed)
 // the last hop.  LEGION_SAMPLING: unset / empty / "replace" = with replacement, "distinct" or "weighted".  LEGION_SAMPLING_SEED: unset / empty = off.
 // LEGION_LP_DRAW: unset / empty / "0" = off, "1" only under a seed (k is resolved against the meta line: serve_modes_resolve_lp_draw).
 // LEGION_WEIGHTED_DISTINCT: unset / empty / "0" = off, "1" only with LEGION_SAMPLING=weighted.
-// LEGION_SHARED_DRAWS: unset / empty / "0" = off, "1" only with LEGION_SAMPLING=distinct under a seed: unseeded, every batch of every epoch
+// LEGION_SHARED_DRAWS: unset / empty / "0" = off, "1" only with LEGION_SAMPLING=distinct, or =weighted with LEGION_WEIGHTED_DISTINCT=1, under a seed: unseeded, every batch of every epoch
 // would prefer the same nodes (the node key depends on the draw word alone), which a server must not do silently.
 bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
 {
@@ -63,7 +63,7 @@ bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
     const char* sd = getenv("LEGION_SHARED_DRAWS");
     if (sd && sd[0] && strcmp(sd, "0") != 0) {
         if (strcmp(sd, "1") != 0) { why = std::string("LEGION_SHARED_DRAWS=") + sd + " is not a known setting: `1` (distinct draws by a key of the neighbour node: rows that see the same neighbours pick the same ones), `0` or unset"; return false; }
-        if (m.sampling != kSamplingDistinct) { why = "LEGION_SHARED_DRAWS=1 needs LEGION_SAMPLING=distinct: the flag keys the distinct draws by the neighbour node"; return false; }
+        if (m.sampling != kSamplingDistinct && !(m.sampling == kSamplingWeighted && m.weighted_distinct)) { why = "LEGION_SHARED_DRAWS=1 needs LEGION_SAMPLING=distinct: the flag keys the distinct draws by the neighbour node"; return false; }
         if (!m.seeded) { why = "LEGION_SHARED_DRAWS=1 needs LEGION_SAMPLING_SEED: the node keys come from the batch's draw word, and without a seed every batch of every epoch would prefer the same nodes"; return false; }
         m.shared_draws = true;
     }
@@ -86,7 +86,7 @@ bool legion::serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, 
     const int32_t most = draw_rule_max_fanout(rule);
     for (int32_t h = 0; most && h < hops; h++)
         if (fanout[h] > most) {
-            why = std::string(rule == DrawRule::Distinct ? "LEGION_SAMPLING=distinct" : rule == DrawRule::Shared ? "LEGION_SHARED_DRAWS=1" : "LEGION_WEIGHTED_DISTINCT=1") + " takes fan-outs of at most " + std::to_string(most) + ", hop " +
+            why = std::string(rule == DrawRule::Distinct ? "LEGION_SAMPLING=distinct" : rule == DrawRule::Shared ? "LEGION_SHARED_DRAWS=1" : rule == DrawRule::WeightedShared ? "LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1" : "LEGION_WEIGHTED_DISTINCT=1") + " takes fan-outs of at most " + std::to_string(most) + ", hop " +
                   std::to_string(h + 1) + " has " + std::to_string(fanout[h]) +
                   (rule == DrawRule::Distinct ? ": k_sample stages the picks of a tile's rows in static LDS" : ": k_sample keeps a row's best picks one per lane and stages them in static LDS");
             return false;

@@ -64,7 +64,8 @@ def main(argv=None):
                     "min(neighbours of weight > 0, fan-out) distinct neighbours per row; the server keeps the weights in HBM beside the alias table")
     ap.add_argument("--shared-draws", "--shared_draws", dest="shared_draws", action="store_true", help="extension "
                     "(LEGION_SHARED_DRAWS=1 for the server; needs --sampling distinct and --sampling_seed): the distinct draws are keyed by the "
-                    "neighbour node, so rows that see the same neighbours pick the same ones and a batch reaches fewer unique nodes")
+                    "neighbour node, so rows that see the same neighbours pick the same ones and a batch reaches fewer unique nodes; also on top of "
+                    "--sampling weighted --weighted-distinct: the weighted draws without replacement take one uniform per neighbour node")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
