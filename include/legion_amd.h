@@ -261,6 +261,37 @@ uint64_t* GPUMemoryPool_GetPositionMap(const GPUMemoryPool* p);
 /* cand[idx] of the hop that ran last: the neighbour sampler slot idx drew, -1 = no draw (degree < fan-out, padded source); what the
  * duplicate census reads (profiles/dedup_census.py) */
 int32_t* GPUMemoryPool_GetCandidateBuffer(const GPUMemoryPool* p);
+/* What each device buffer of the pool may hold between launches (DESIGN.md "What the pool's scratch may hold between launches"), one
+ * entry per (index, pipe): index 0, 1, .. until the call returns 1 (past the end); -1 + sticky error for a null argument or a pipe the
+ * pool does not have.  Read-only, host state only.  A buffer shared by the pipes reports the same entry for every pipe; a per-pipe buffer
+ * of a mode that was never set reports ptr = NULL.
+ * kind: what an element is.  ID: a node id, a cache slot or a partition index (-1 = none); SLOT_STATE: the sampler's per-slot state (-1
+ * pending, >= 0 known position, <= -2 lost to slot -2 - x or a winner's rank); COUNT / COUNT_PAIR: int32 / int2 counts of edges and nodes;
+ * DEVICE_POINTER: the address of a feature row, NULL = no source; FLOAT; TABLE_ENTRY: (epoch << 32) | value of the position table.
+ * lifetime: when the contents stop meaning anything.  HOP: once the GPU_Random_Sampling that wrote them has returned; BATCH: once the
+ * batch's last op has returned; TABLE: per entry, whenever its epoch field is greater than the running batch's; STATE: never (the batch
+ * cursor: not scratch, listed so that the list is complete). */
+#define LEGION_SCRATCH_ID 0
+#define LEGION_SCRATCH_SLOT_STATE 1
+#define LEGION_SCRATCH_COUNT 2
+#define LEGION_SCRATCH_COUNT_PAIR 3
+#define LEGION_SCRATCH_DEVICE_POINTER 4
+#define LEGION_SCRATCH_FLOAT 5
+#define LEGION_SCRATCH_TABLE_ENTRY 6
+#define LEGION_SCRATCH_HOP 0
+#define LEGION_SCRATCH_BATCH 1
+#define LEGION_SCRATCH_TABLE 2
+#define LEGION_SCRATCH_STATE 3
+typedef struct LegionScratchInfo {
+    const char* name;     /* static string */
+    void* ptr;            /* device pointer, NULL while not allocated */
+    int64_t bytes;
+    int32_t kind;         /* LEGION_SCRATCH_ID .. LEGION_SCRATCH_TABLE_ENTRY */
+    int32_t elem_bytes;
+    int32_t lifetime;     /* LEGION_SCRATCH_HOP .. LEGION_SCRATCH_STATE */
+    int32_t per_pipe;     /* 1: one buffer per pipe */
+} LegionScratchInfo;
+int GPUMemoryPool_ScratchInfo(const GPUMemoryPool* p, int32_t index, int32_t pipe, LegionScratchInfo* out);
 /* batches started on this pool (the table epoch is 0xFFFFFFFF - serial); settable to exercise the wrap-around */
 uint32_t GPUMemoryPool_GetBatchSerial(const GPUMemoryPool* p);
 void GPUMemoryPool_SetBatchSerial(GPUMemoryPool* p, uint32_t serial);

@@ -305,7 +305,31 @@ _SIGS = {
     "legion_seeded_draw_word": (u32, [u32, i32, i32]),
     "legion_seeded_shuffle_key": (u32, [u32, i32]),
     "legion_sampler_cu_count": (i32, []),
+    "GPUMemoryPool_ScratchInfo": (C.c_int, [vp, i32, i32, vp]),
 }
+
+# GPUMemoryPool_ScratchInfo (include/legion_amd.h: LEGION_SCRATCH_*): what an element of a pool buffer is, and when its contents are dead
+SCRATCH_KINDS = ("id", "slot_state", "count", "count_pair", "device_pointer", "float", "table_entry")
+SCRATCH_LIFETIMES = ("hop", "batch", "table", "state")
+
+
+class LegionScratchInfo(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("ptr", vp), ("bytes", i64), ("kind", i32), ("elem_bytes", i32), ("lifetime", i32), ("per_pipe", i32)]
+
+
+def pool_scratch(pool, pipe=0):
+    """The pool's device buffers as GPUMemoryPool_ScratchInfo lists them for `pipe`: [dict(name, ptr, bytes, kind, elem_bytes, lifetime,
+    per_pipe)], kind and lifetime as the words of SCRATCH_KINDS / SCRATCH_LIFETIMES; ptr is None while a buffer is not allocated."""
+    out, info = [], LegionScratchInfo()
+    while True:
+        r = lib().GPUMemoryPool_ScratchInfo(pool, len(out), int(pipe), C.byref(info))
+        if r == 1:
+            return out
+        if r != 0:
+            check()
+            raise RuntimeError("GPUMemoryPool_ScratchInfo failed")
+        out.append(dict(name=info.name.decode(), ptr=info.ptr, bytes=int(info.bytes), kind=SCRATCH_KINDS[info.kind], elem_bytes=int(info.elem_bytes),
+                        lifetime=SCRATCH_LIFETIMES[info.lifetime], per_pipe=bool(info.per_pipe)))
 
 
 def lib():

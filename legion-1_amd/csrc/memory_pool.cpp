@@ -21,43 +21,55 @@ GPUMemoryPool::GPUMemoryPool(int32_t depth)
     agg_dst_off.assign(pipeline_depth, nullptr);
 }
 
-// Every device scratch buffer the pool owns, with its size, in allocation order: GPUMemoryPool_AllocateScratch allocates this list and
-// release_scratch frees and forgets it -- a buffer named here is in both.  Sized from V, num_ids, max_slots and max_tiles as they are now.
-struct ScratchBuffer { void** slot; size_t bytes; };
+// Every device scratch buffer the pool owns, in allocation order, with its size, its name, what an element of it is and how long what it holds
+// means anything (include/legion_amd.h: LEGION_SCRATCH_*; DESIGN.md "What the pool's scratch may hold between launches").
+// GPUMemoryPool_AllocateScratch allocates this list, release_scratch frees and forgets it and GPUMemoryPool_ScratchInfo reports it -- a
+// buffer named here is in all three.  Sized from V, num_ids, max_slots and max_tiles as they are now.
+//   hop:   written and read inside one GPU_Random_Sampling (k_sample, k_mark, k_write of one hop); dead once that call has returned.
+//          cand is read back by callers behind the batch (GPUMemoryPool_GetCandidateBuffer), never by a later launch.
+//   batch: carried from one op of a batch to a later one -- aux2[(h + 1) & 1] (the next hop's slot states, prepared by k_seed / k_write
+//          while aux2[h & 1] is dead as soon as hop h has returned), agg_src_ids (the next hop's input list), row_ptr (exchange plan ->
+//          local gather), cache_search_buffer / tmp_part_* (FindFeat / FindTopo answers the caller carries between two calls) and the per-pipe
+//          buffers of the aggregated modes (last hop -> get_feature_kernel_agg); dead once the batch's last op has returned.
+//   table: pos_map; an entry whose epoch field is greater than the running batch's means nothing.
+struct ScratchBuffer { void** slot; size_t bytes; const char* name; int32_t kind, elem_bytes, lifetime; };
 static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
 {
     const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots, tiles = (size_t)p->max_tiles + 1;
-    return {{(void**)&p->pos_map, (size_t)p->V * sizeof(pos_t)},
-            {(void**)&p->cand, slots * sizeof(int32_t)},
-            {(void**)&p->aux2[0], slots * sizeof(int32_t)},
-            {(void**)&p->aux2[1], slots * sizeof(int32_t)},
-            {(void**)&p->tile_edge, tiles * sizeof(int32_t)},
-            {(void**)&p->tile_node, tiles * sizeof(int32_t)},
-            {(void**)&p->tile_pre, tiles * sizeof(int2)},
-            {(void**)&p->chunk_tot, (size_t)kMaxChunks * sizeof(int2)},
-            {(void**)&p->hop_state, sizeof(HopState)},
-            {(void**)&p->cache_search_buffer, ids * sizeof(int32_t)},
-            {(void**)&p->row_ptr, ids * sizeof(float*)},
-            {(void**)&p->agg_src_ids, ids * sizeof(int32_t)},
-            {(void**)&p->tmp_part_ind, ids},
-            {(void**)&p->tmp_part_off, ids * sizeof(int32_t)}};
+    constexpr int32_t I = sizeof(int32_t), hop = LEGION_SCRATCH_HOP, batch = LEGION_SCRATCH_BATCH;
+    return {{(void**)&p->pos_map, (size_t)p->V * sizeof(pos_t), "pos_map", LEGION_SCRATCH_TABLE_ENTRY, sizeof(pos_t), LEGION_SCRATCH_TABLE},
+            {(void**)&p->cand, slots * sizeof(int32_t), "cand", LEGION_SCRATCH_ID, I, hop},
+            {(void**)&p->aux2[0], slots * sizeof(int32_t), "aux2[0]", LEGION_SCRATCH_SLOT_STATE, I, batch},
+            {(void**)&p->aux2[1], slots * sizeof(int32_t), "aux2[1]", LEGION_SCRATCH_SLOT_STATE, I, batch},
+            {(void**)&p->tile_edge, tiles * sizeof(int32_t), "tile_edge", LEGION_SCRATCH_COUNT, I, hop},
+            {(void**)&p->tile_node, tiles * sizeof(int32_t), "tile_node", LEGION_SCRATCH_COUNT, I, hop},
+            {(void**)&p->tile_pre, tiles * sizeof(int2), "tile_pre", LEGION_SCRATCH_COUNT_PAIR, sizeof(int2), hop},
+            {(void**)&p->chunk_tot, (size_t)kMaxChunks * sizeof(int2), "chunk_tot", LEGION_SCRATCH_COUNT_PAIR, sizeof(int2), hop},
+            {(void**)&p->hop_state, sizeof(HopState), "hop_state", LEGION_SCRATCH_COUNT, I, hop},
+            {(void**)&p->cache_search_buffer, ids * sizeof(int32_t), "cache_search_buffer", LEGION_SCRATCH_ID, I, batch},
+            {(void**)&p->row_ptr, ids * sizeof(float*), "row_ptr", LEGION_SCRATCH_DEVICE_POINTER, sizeof(float*), batch},
+            {(void**)&p->agg_src_ids, ids * sizeof(int32_t), "agg_src_ids", LEGION_SCRATCH_ID, I, batch},
+            {(void**)&p->tmp_part_ind, ids, "tmp_part_ind", LEGION_SCRATCH_ID, 1, batch},
+            {(void**)&p->tmp_part_off, ids * sizeof(int32_t), "tmp_part_off", LEGION_SCRATCH_ID, I, batch}};
 }
-// The per-pipe buffers of the aggregated modes with their per-pipe sizes, named once in the same way: fn(buffers, bytes per pipe, wanted).
-// The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums, agg_out_deg / agg_wdraw / agg_chunk_cnt.
+// The per-pipe buffers of the aggregated modes with their per-pipe sizes, named once in the same way: fn(buffers, bytes per pipe, wanted,
+// description -- a ScratchBuffer without a slot).  The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums,
+// agg_out_deg / agg_wdraw / agg_chunk_cnt.
 template <typename Fn>
 static void for_mode_buffers(GPUMemoryPool* p, Fn fn)
 {
     const bool agg = p->modes.agg_last_hop, norm = agg && p->modes.agg_norm;
-    fn(p->cand_pipe, (size_t)p->max_slots * sizeof(int32_t), agg);
-    fn(p->agg_out_deg, (size_t)p->num_ids * sizeof(int32_t), norm);
-    fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), norm);
-    fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), norm);
+    constexpr int32_t I = sizeof(int32_t), batch = LEGION_SCRATCH_BATCH;
+    fn(p->cand_pipe, (size_t)p->max_slots * sizeof(int32_t), agg, ScratchBuffer{nullptr, 0, "cand_pipe", LEGION_SCRATCH_ID, I, batch});
+    fn(p->agg_out_deg, (size_t)p->num_ids * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_out_deg", LEGION_SCRATCH_COUNT, I, batch});
+    fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), norm, ScratchBuffer{nullptr, 0, "agg_wdraw", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
+    fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch});
 }
 // on the current device: what the pool's modes want and is missing is allocated, what is there stays
 static void alloc_mode_buffers(GPUMemoryPool* p)
 {
     if (!p->owns_scratch) return;
-    for_mode_buffers(p, [&](auto& pipes, size_t bytes, bool wanted) {
+    for_mode_buffers(p, [&](auto& pipes, size_t bytes, bool wanted, const ScratchBuffer&) {
         if (!wanted) return;
         pipes.resize(p->pipeline_depth, nullptr);
         for (auto& b : pipes)
@@ -69,7 +81,7 @@ static void alloc_mode_buffers(GPUMemoryPool* p)
 static void release_scratch(GPUMemoryPool* p)
 {
     for (const ScratchBuffer& b : pool_scratch(p)) free_and_null(*b.slot);
-    for_mode_buffers(p, [](auto& pipes, size_t, bool) { for (auto& b : pipes) free_and_null(b); });
+    for_mode_buffers(p, [](auto& pipes, size_t, bool, const ScratchBuffer&) { for (auto& b : pipes) free_and_null(b); });
 }
 static void release_ctl(GPUMemoryPool* p) { free_and_null(p->ctl); }
 static void release_rows_seen(GPUMemoryPool* p)
@@ -258,6 +270,23 @@ char* GPUMemoryPool_GetTmpPartIdx(const GPUMemoryPool* p) { return (char*)p->tmp
 int32_t* GPUMemoryPool_GetTmpPartOff(const GPUMemoryPool* p) { return p->tmp_part_off; }
 uint64_t* GPUMemoryPool_GetPositionMap(const GPUMemoryPool* p) { return (uint64_t*)p->pos_map; }
 int32_t* GPUMemoryPool_GetCandidateBuffer(const GPUMemoryPool* p) { return p->cand; }
+// The list of pool_scratch() and for_mode_buffers(), then ctl, one entry per call: 0 and *out filled, 1 past the end of the list, -1
+// (sticky error) for a null argument or a pipe the pool does not have.  Reads host state only: no device call, nothing changes.
+int GPUMemoryPool_ScratchInfo(const GPUMemoryPool* pool, int32_t index, int32_t pipe, LegionScratchInfo* out)
+{
+    if (!pool || !out) { LEGION_ARG_ERROR("GPUMemoryPool_ScratchInfo: null argument"); return -1; }
+    if (index < 0 || pipe < 0 || pipe >= pool->pipeline_depth) { LEGION_ARG_ERROR("GPUMemoryPool_ScratchInfo: bad index or pipe"); return -1; }
+    GPUMemoryPool* p = const_cast<GPUMemoryPool*>(pool);   // the two lists take the pool they allocate into; nothing is written through it here
+    std::vector<LegionScratchInfo> all;
+    for (const ScratchBuffer& b : pool_scratch(p)) all.push_back({b.name, *b.slot, (int64_t)b.bytes, b.kind, b.elem_bytes, b.lifetime, 0});
+    for_mode_buffers(p, [&](auto& pipes, size_t bytes, bool, const ScratchBuffer& b) {
+        all.push_back({b.name, pipe < (int)pipes.size() ? (void*)pipes[pipe] : nullptr, (int64_t)bytes, b.kind, b.elem_bytes, b.lifetime, 1});
+    });
+    all.push_back({"ctl", p->ctl, (int64_t)sizeof(BatchCtl), LEGION_SCRATCH_COUNT, (int32_t)sizeof(int32_t), LEGION_SCRATCH_STATE, 0});
+    if (index >= (int32_t)all.size()) return 1;
+    *out = all[index];
+    return 0;
+}
 uint32_t GPUMemoryPool_GetBatchSerial(const GPUMemoryPool* p) { return p->batch_serial; }
 void GPUMemoryPool_SetBatchSerial(GPUMemoryPool* p, uint32_t serial) { p->batch_serial = serial; p->ctl_synced = false; }
 

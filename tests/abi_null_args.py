@@ -26,6 +26,7 @@ calls = [
  ("Runner_Initialize", lambda: L.Runner_Initialize(None, None)),
  ("Server_SetFanout", lambda: L.Server_SetFanout(None, None, 0)),
  ("GPUMemoryPool_ReleasePeerExchange", lambda: L.GPUMemoryPool_ReleasePeerExchange(None)),
+ ("GPUMemoryPool_ScratchInfo", lambda: L.GPUMemoryPool_ScratchInfo(None, 0, 0, None)),
  ("Operator_run", lambda: L.Operator_run(None, None)),
 ]
 for name, fn in calls:
