@@ -489,6 +489,23 @@ int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p);
  * without GPUMemoryPool_SetWeightedDistinct the flag is remembered and not read. */
 void GPUMemoryPool_SetSharedDraws(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p);
+/* Edge ids (extension; INTEGRATION.md "Edge ids").  With GPUMemoryPool_SetEdgeIds(pool, 1) every batch additionally leaves, per pipe,
+ *   edge_ids int64[GPUMemoryPool_NumIds]:   edge_ids[e] = the position in the WHOLE CSR (indptr / indices) of the edge the batch's COO edge e
+ *                                           was drawn from, in the order and at the offsets of agg_src_off / agg_dst_off;
+ *   edge_w   float32[GPUMemoryPool_NumIds]: edge_w[e] = the bits of w[edge_ids[e]], filled when the graph retains its weights
+ *                                           (GPUGraphStorage_RetainEdgeWeights).
+ * Off (the default) every buffer of every batch is what it was and a batch takes the launches it took.  On, a sampler hop runs the k_sample
+ * instantiation that parks each slot's column and one more launch (k_edge_ids) behind its k_write; pre-sampling batches hand nothing over.
+ * Refused by name (sticky error, the pool keeps its modes): a null pool, a pool that is being captured, and the mode together with weighted
+ * sampling WITH replacement (kind 2 without GPUMemoryPool_SetWeightedDistinct: the alias table holds the alias neighbour's id, not its
+ * column) -- whichever of the two is set second.  A LegionBatchGraph replays only in the state it was recorded in.  Call the setter under
+ * the device the pool's scratch lives on: the first switch on allocates.
+ * GPUMemoryPool_GetEdgeIdBuffer / GetEdgeWeightBuffer: the current pipe's buffers; null before the mode was set, and the weights null
+ * unless the pipe's last batch ran over retained weights. */
+void GPUMemoryPool_SetEdgeIds(GPUMemoryPool* p, int on);
+int GPUMemoryPool_GetEdgeIds(const GPUMemoryPool* p);
+int64_t* GPUMemoryPool_GetEdgeIdBuffer(const GPUMemoryPool* p);
+float* GPUMemoryPool_GetEdgeWeightBuffer(const GPUMemoryPool* p);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
  * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
  * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list

@@ -216,6 +216,10 @@ _SIGS = {
     "GPUMemoryPool_GetWeightedDistinct": (C.c_int, [vp]),
     "GPUMemoryPool_SetSharedDraws": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetSharedDraws": (C.c_int, [vp]),
+    "GPUMemoryPool_SetEdgeIds": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetEdgeIds": (C.c_int, [vp]),
+    "GPUMemoryPool_GetEdgeIdBuffer": (vp, [vp]),
+    "GPUMemoryPool_GetEdgeWeightBuffer": (vp, [vp]),
     "GPUGraphStorage_CopyAliasRows": (C.c_int, [vp, i32, i64, i64, vp, vp]),
     "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
     "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
@@ -523,6 +527,7 @@ class Engine:
         self._agg = {}      # (dev, pipe) -> the pipe's last batch was handed over aggregated (run_batch(agg_last_hop=True))
         self._seed_state = {}   # dev -> (seed or None, round) the pool was last put into (run_batch / capture_batch / run_graph)
         self._norm = {}     # (dev, pipe) -> ... with normalised sums (run_batch(agg_norm="both"))
+        self._eid = {}      # (dev, pipe) -> the pipe's last batch left its edge ids (run_batch(edge_ids=True))
         check()
 
     # ---- weighted sampling: the graph's alias table ------------------------------------------------------
@@ -566,8 +571,12 @@ class Engine:
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
-                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False):
-        """shared_draws (GPUMemoryPool_SetSharedDraws, only with sample="distinct"): the distinct draws are keyed by the neighbour node, so rows
+                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False):
+        """edge_ids (GPUMemoryPool_SetEdgeIds): the batch additionally leaves every COO edge's position in the whole CSR in the pipe's buffer, and
+        its weight on an Engine(retain_edge_weights=True); result() then returns `edge_ids` int64 [n_edges] (and `edge_w` float32 [n_edges]).
+        Refused by the library under sample="weighted" without weighted_distinct; a pre-sampling batch hands nothing over.  Set on every call
+        like `sample`.
+        shared_draws (GPUMemoryPool_SetSharedDraws, only with sample="distinct"): the distinct draws are keyed by the neighbour node, so rows
         that see the same neighbours pick the same ones; seed=None draws under word 0 (the same node keys in every batch).  Set on every call
         like `sample`.  Also allowed with sample="weighted", weighted_distinct=True: the weighted draws without replacement take their
         uniforms per neighbour node (INTEGRATION.md "Weighted shared-key sampling").
@@ -592,7 +601,8 @@ class Engine:
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
         agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct,
-                                     shared_draws=shared_draws)
+                                     shared_draws=shared_draws, edge_ids=edge_ids)
+        self._eid[(dev, pipe)] = bool(edge_ids) and not is_presc
         self._agg[(dev, pipe)] = agg and gather
         self._norm[(dev, pipe)] = norm and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
@@ -617,7 +627,7 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
-    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False):
+    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
@@ -638,9 +648,16 @@ class Engine:
         L.SetGPUDevice(dev)
         agg = bool(agg) and not is_presc
         norm = int(agg and norm == "both")
+        # edge ids are refused together with the alias rule, whichever is set second: off in front of a change of the draw rule, on (again) behind it
+        rule = (("replace", "distinct", "weighted").index(sample), int(bool(weighted_distinct)))
+        if L.GPUMemoryPool_GetEdgeIds(pool) and (not edge_ids or rule != (L.GPUMemoryPool_GetSampling(pool), L.GPUMemoryPool_GetWeightedDistinct(pool))):
+            L.GPUMemoryPool_SetEdgeIds(pool, 0)
         for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("WeightedDistinct", int(bool(weighted_distinct))), ("SharedDraws", int(bool(shared_draws))), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
             if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
                 getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
+        if L.GPUMemoryPool_GetEdgeIds(pool) != int(bool(edge_ids)):   # allocates on the first switch on
+            L.GPUMemoryPool_SetEdgeIds(pool, int(bool(edge_ids)))
+            check()
         self._set_seed(dev, seed, round, stream, lp_draw)
         return agg, bool(norm)
 
@@ -660,11 +677,12 @@ class Engine:
 
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
-                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False):
+                      stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False,
+                      edge_ids=False):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
         run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in, and
-        only in the weighted_distinct and the shared_draws state it was recorded in."""
+        only in the weighted_distinct, the shared_draws and the edge_ids state it was recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -672,13 +690,14 @@ class Engine:
                 self.streams[dev] = L.d_stream_create()
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
-        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct, shared_draws=shared_draws)
+        self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct, shared_draws=shared_draws,
+                        edge_ids=edge_ids)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
                        stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw,
-                       weighted_distinct=weighted_distinct, shared_draws=shared_draws)
+                       weighted_distinct=weighted_distinct, shared_draws=shared_draws, edge_ids=edge_ids)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -701,8 +720,10 @@ class Engine:
             self.L.d_stream_sync(stream)
             check()
 
-    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None):
-        """aggregated: how to read the pipe's feature buffer -- None: as run_batch / capture_batch on this engine left it; True / False
+    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None, edge_ids=None):
+        """edge_ids: whether the pipe's edge ids are read (`edge_ids`, and `edge_w` where the batch ran over retained weights) -- None: as
+        run_batch / capture_batch on this engine left it.
+        aggregated: how to read the pipe's feature buffer -- None: as run_batch / capture_batch on this engine left it; True / False
         for a caller that drove the launchers itself.  normalised: likewise, whether the pipe's block out-degrees are read (`out_deg`)."""
         if aggregated is None:
             aggregated = self._agg.get((dev, pipe), False)
@@ -716,6 +737,15 @@ class Engine:
         n_nodes, n_edges = layout.batch_nodes(nc, H), layout.batch_edges(ec, H)
         res = dict(nc=nc, ec=ec, ids=o["ids"].to_numpy(np.int32, n_nodes), labels=o["labels"].to_numpy(np.int32, layout.level_size(nc, 0)),
                    src_off=o["src"].to_numpy(np.int32, n_edges), dst_off=o["dst"].to_numpy(np.int32, n_edges))
+        if self._eid.get((dev, pipe), False) if edge_ids is None else edge_ids:
+            self.L.GPUMemoryPool_SetCurrentPipe(self.pools[dev], pipe)
+            eid, ew = self.L.GPUMemoryPool_GetEdgeIdBuffer(self.pools[dev]), self.L.GPUMemoryPool_GetEdgeWeightBuffer(self.pools[dev])
+            check()
+            if not eid:
+                raise RuntimeError("result(edge_ids=True): the pool has no edge-id buffer (GPUMemoryPool_SetEdgeIds was never on)")
+            res["edge_ids"] = read_dev(eid, np.int64, n_edges)
+            if ew:
+                res["edge_w"] = read_dev(ew, np.float32, n_edges)
         if with_features and o["feat"] is not None and aggregated:
             # aggregated hand-off: rows [0, n_in) are features, rows [n_in, n_in + N) the last hop's neighbour sums per input slot
             n_in, runs = layout.first_block_dst(nc, H), layout.hop_inputs(nc, ec, H)

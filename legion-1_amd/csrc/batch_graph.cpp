@@ -29,7 +29,8 @@ struct LegionBatchGraph {
     // when the recording read it) --, so the graph only replays in that state; the seed, the round and the counter are not part of it
     // (k_set_cursor carries them into ctl).  Likewise for lp_draw: the captured k_seed is the instantiation, the k and the row tables of that state;
     // and for weighted_distinct: the captured k_sample is that state's instantiation, over the alias table or over the retained weights;
-    // and for shared_draws: the captured k_sample is that state's instantiation.
+    // and for shared_draws: the captured k_sample is that state's instantiation; and for edge_ids: the captured hops park their columns and
+    // launch k_edge_ids, or do neither.
     ServeModes modes;
     const int32_t* shuf_ids = nullptr;
 };
@@ -91,6 +92,11 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (g->modes.shared_draws != p->modes.shared_draws) {
         LEGION_ARG_ERROR(g->modes.shared_draws ? "LegionBatchGraph_Launch: the graph was recorded with shared-key sampling (GPUMemoryPool_SetSharedDraws) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again"
                                                : "LegionBatchGraph_Launch: the graph was recorded without shared-key sampling and the pool has the flag on now (GPUMemoryPool_SetSharedDraws): its k_sample is another instantiation -- record it again");
+        return -1;
+    }
+    if (g->modes.edge_ids != p->modes.edge_ids) {
+        LEGION_ARG_ERROR(g->modes.edge_ids ? "LegionBatchGraph_Launch: the graph was recorded with edge ids (GPUMemoryPool_SetEdgeIds) and the pool has the mode off now: its hops park their columns and launch k_edge_ids -- record it again"
+                                           : "LegionBatchGraph_Launch: the graph was recorded without edge ids and the pool has the mode on now (GPUMemoryPool_SetEdgeIds): its hops leave no edge ids behind -- record it again");
         return -1;
     }
     if (g->shuf_ids && (g->shuf_ids != p->shuf_ids || !p->shuf_valid)) {

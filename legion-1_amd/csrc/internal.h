@@ -149,7 +149,10 @@ struct ServeModes {
                                  // the same neighbours pick the same ones ("Shared-key sampling").  A flag on top of the kind, like weighted_distinct: remembered
                                  // across kinds, acts while sampling == 1 and, with weighted_distinct on, while sampling == 2: there the exponential key's uniform
                                  // belongs to the neighbour node ("Weighted shared-key sampling"); not published
-    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws; }
+    bool edge_ids = false;       // GPUMemoryPool_SetEdgeIds (no variable yet): every sampled edge's position in the whole CSR, and its weight where the graph
+                                 // retains them, beside the pipe's COO ("Edge ids").  Refused together with the alias rule (sampling == 2 without
+                                 // weighted_distinct); pre-sampling batches hand nothing over; not published
+    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids; }
 };
 // The draw rule of a sampler hop: what `sampling` and the flags `weighted_distinct` and `shared_draws` say together.  draw_rule_of is the one
 // place that reads the three; the launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
@@ -349,8 +352,19 @@ void warm_static_tables();   // per-device constant tables: must exist before a 
 // What a hop draws by: the rule and its tables beside the whole CSR -- the alias table (both weighted rules; Weighted reads it) and the graph's
 // retained edge weights (WeightedDistinct and WeightedShared read them); null under the other rules.  Resolved from (graph, modes, device) in launchers.cpp.
 struct DrawTables { DrawRule rule; const AliasEntry* alias; const float* weights; };
+// Edge ids (GPUMemoryPool_SetEdgeIds): what a hop needs beyond the sampler's buffers to hand over every edge's position in the whole CSR.
+// k_sample parks the slot's column in cols, k_edge_ids behind k_write stores edge_ids[e] = indptr[src] + column and, with weights, edge_w[e].
+struct EdgeIdOut {
+    int32_t* cols;            // i32[max slots of a hop], the pool's (dead once the hop has returned)
+    int64_t* edge_ids;        // i64[ids_cap], the pipe's
+    float* edge_w;            // f32[ids_cap], the pipe's; filled when `weights` is there
+    const int64_t* indptr;    // the WHOLE CSR's, whatever the hop draws from (a fragment row is the whole row's copy)
+    const float* weights;     // the graph's retained weights on this GPU, or null
+    int64_t E;                // entries of the whole CSR
+};
+// eo: null = the hop as it always was; else the k_sample instantiation that parks the columns, and one more launch, k_edge_ids
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw);
+                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw, const EdgeIdOut* eo = nullptr);
 // Weighted sampler mode, the graph's side (build_kernels.hip "alias table").  bad := the number of weights that are negative, NaN or infinite
 // (a device word the caller zeroed); the table of every row of the CSR from w, with p = double[E] of scratch.  Deterministic: the same
 // weights give the same bytes.
@@ -516,6 +530,13 @@ struct GPUMemoryPool {
     GPUGraphStorage* lp_graph = nullptr;
     std::vector<int32_t*> agg_out_deg, agg_chunk_cnt;
     std::vector<float*> agg_wdraw;
+    // Edge ids (modes.edge_ids, GPUMemoryPool_SetEdgeIds): allocated when the mode is switched on, kept until the scratch is released.  cols:
+    // max_slots words, one buffer (written by k_sample, read by k_edge_ids of the same hop).  edge_ids / edge_w: num_ids elements per pipe,
+    // the batch's, read back by callers.  edge_w_filled[pipe]: the pipe's last batch ran over retained weights (GetEdgeWeightBuffer is null otherwise).
+    int32_t* cols = nullptr;
+    std::vector<int64_t*> edge_ids;
+    std::vector<float*> edge_w;
+    std::vector<char> edge_w_filled;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
     int32_t aux_ready_hop = 0, aux_ready_count = 0; // the launch before prepared aux2[hop & 1] for this fan-out
     int32_t* tile_edge = nullptr;

@@ -125,6 +125,9 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         for (int32_t* c : p->agg_out_deg) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (int32_t* c : p->agg_chunk_cnt) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (float* c : p->agg_wdraw) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        if (p->cols) LEGION_AUDIT_OWNER(p->cols, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (int64_t* c : p->edge_ids) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (float* c : p->edge_w) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (int i = 0; i < p->pipeline_depth; i++) {
             LEGION_AUDIT_OWNER(p->sampled_ids[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
             LEGION_AUDIT_OWNER(p->node_counter[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
@@ -202,7 +205,22 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     b.V = p->V;
     b.aux_prepared = p->aux_ready_hop == hop && p->aux_ready_count == count;
     b.next_count = hop < p->hops ? p->fanout[hop] : 0;
-    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, draw);
+    // Edge ids (GPUMemoryPool_SetEdgeIds): the hop parks its columns and one more launch behind k_write, on this stream, leaves every edge's
+    // position in the WHOLE CSR in the pipe's buffer -- and its weight, where this GPU holds the graph's retained weights.  A pre-sampling
+    // batch hands nothing over: it runs the hop as it always did, whatever the mode says.
+    EdgeIdOut eo_args;
+    const EdgeIdOut* eo = nullptr;
+    if (p->modes.edge_ids && !is_presc) {
+        if ((int)p->edge_ids.size() <= q || !p->edge_ids[q] || !p->edge_w[q] || !p->cols) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) without the pool's buffers (the mode was set before GPUMemoryPool_AllocateScratch failed?)"); return; }
+        CsrTables whole;
+        csr_tables_of(whole, graph, cache, dev, false);
+        eo_args.cols = p->cols; eo_args.edge_ids = p->edge_ids[q]; eo_args.edge_w = p->edge_w[q];
+        eo_args.indptr = whole.indptr; eo_args.E = graph->edge_num;
+        eo_args.weights = graph->retain_weights && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
+        p->edge_w_filled[q] = eo_args.weights != nullptr;
+        eo = &eo_args;
+    }
+    launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, draw, eo);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint

@@ -32,12 +32,16 @@ GPUMemoryPool::GPUMemoryPool(int32_t depth)
 //          local gather), cache_search_buffer / tmp_part_* (FindFeat / FindTopo answers the caller carries between two calls) and the per-pipe
 //          buffers of the aggregated modes (last hop -> get_feature_kernel_agg); dead once the batch's last op has returned.
 //   table: pos_map; an entry whose epoch field is greater than the running batch's means nothing.
+// The buffers of the edge-id mode (GPUMemoryPool_SetEdgeIds) join the list once the pool has been in that mode, behind the others of their
+// kind, and stay until the scratch is released: a pool that never saw the mode lists what it always listed.  cols (hop): k_sample's columns,
+// read by k_edge_ids of the same GPU_Random_Sampling.  edge_ids / edge_w (batch, per pipe): outputs no launch reads, the caller's behind the batch.
+static bool lists_edge_ids(const GPUMemoryPool* p) { return p->modes.edge_ids || p->cols || !p->edge_ids.empty(); }
 struct ScratchBuffer { void** slot; size_t bytes; const char* name; int32_t kind, elem_bytes, lifetime; };
 static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
 {
     const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots, tiles = (size_t)p->max_tiles + 1;
     constexpr int32_t I = sizeof(int32_t), hop = LEGION_SCRATCH_HOP, batch = LEGION_SCRATCH_BATCH;
-    return {{(void**)&p->pos_map, (size_t)p->V * sizeof(pos_t), "pos_map", LEGION_SCRATCH_TABLE_ENTRY, sizeof(pos_t), LEGION_SCRATCH_TABLE},
+    std::vector<ScratchBuffer> all = {{(void**)&p->pos_map, (size_t)p->V * sizeof(pos_t), "pos_map", LEGION_SCRATCH_TABLE_ENTRY, sizeof(pos_t), LEGION_SCRATCH_TABLE},
             {(void**)&p->cand, slots * sizeof(int32_t), "cand", LEGION_SCRATCH_ID, I, hop},
             {(void**)&p->aux2[0], slots * sizeof(int32_t), "aux2[0]", LEGION_SCRATCH_SLOT_STATE, I, batch},
             {(void**)&p->aux2[1], slots * sizeof(int32_t), "aux2[1]", LEGION_SCRATCH_SLOT_STATE, I, batch},
@@ -51,6 +55,8 @@ static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
             {(void**)&p->agg_src_ids, ids * sizeof(int32_t), "agg_src_ids", LEGION_SCRATCH_ID, I, batch},
             {(void**)&p->tmp_part_ind, ids, "tmp_part_ind", LEGION_SCRATCH_ID, 1, batch},
             {(void**)&p->tmp_part_off, ids * sizeof(int32_t), "tmp_part_off", LEGION_SCRATCH_ID, I, batch}};
+    if (lists_edge_ids(p)) all.push_back({(void**)&p->cols, slots * sizeof(int32_t), "cols", LEGION_SCRATCH_COUNT, I, hop});
+    return all;
 }
 // The per-pipe buffers of the aggregated modes with their per-pipe sizes, named once in the same way: fn(buffers, bytes per pipe, wanted,
 // description -- a ScratchBuffer without a slot).  The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums,
@@ -64,6 +70,10 @@ static void for_mode_buffers(GPUMemoryPool* p, Fn fn)
     fn(p->agg_out_deg, (size_t)p->num_ids * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_out_deg", LEGION_SCRATCH_COUNT, I, batch});
     fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), norm, ScratchBuffer{nullptr, 0, "agg_wdraw", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
     fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch});
+    if (!lists_edge_ids(p)) return;
+    // an edge id is one 8-byte word no kernel reads back: any bytes are safe in it, a pair of counts is what the poison's kinds offer
+    fn(p->edge_ids, (size_t)p->num_ids * sizeof(int64_t), p->modes.edge_ids, ScratchBuffer{nullptr, 0, "edge_ids", LEGION_SCRATCH_COUNT_PAIR, sizeof(int64_t), batch});
+    fn(p->edge_w, (size_t)p->num_ids * sizeof(float), p->modes.edge_ids, ScratchBuffer{nullptr, 0, "edge_w", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
 }
 // on the current device: what the pool's modes want and is missing is allocated, what is there stays
 static void alloc_mode_buffers(GPUMemoryPool* p)
@@ -75,6 +85,10 @@ static void alloc_mode_buffers(GPUMemoryPool* p)
         for (auto& b : pipes)
             if (!b) HIP_CHECK(hipMalloc(&b, bytes));
     });
+    if (p->modes.edge_ids) {
+        if (!p->cols) HIP_CHECK(hipMalloc(&p->cols, (size_t)p->max_slots * sizeof(int32_t)));
+        p->edge_w_filled.resize(p->pipeline_depth, 0);
+    }
 }
 
 // ---- the releases: each kind of scratch has one, and GPUMemoryPool_Finalize calls them all ----
@@ -82,6 +96,7 @@ static void release_scratch(GPUMemoryPool* p)
 {
     for (const ScratchBuffer& b : pool_scratch(p)) free_and_null(*b.slot);
     for_mode_buffers(p, [](auto& pipes, size_t, bool, const ScratchBuffer&) { for (auto& b : pipes) free_and_null(b); });
+    p->edge_ids.clear(); p->edge_w.clear(); p->edge_w_filled.clear();   // with cols null again the pool lists them only while the mode is on
 }
 static void release_ctl(GPUMemoryPool* p) { free_and_null(p->ctl); }
 static void release_rows_seen(GPUMemoryPool* p)
@@ -106,6 +121,8 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
     if (wanted.agg_norm && !wanted.agg_last_hop && wanted.agg_norm != p->modes.agg_norm) { LEGION_ARG_ERROR("GPUMemoryPool_SetAggNorm: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are normalised"); return false; }
     if (wanted.sampling != kSamplingReplace && wanted.sampling != kSamplingDistinct && wanted.sampling != kSamplingWeighted) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampling: unknown sampling kind (0 = replace, 1 = distinct, 2 = weighted)"); return false; }
     if (wanted.lp_draw < 0) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: negative triples per batch (0 = off, k > 0 = batches of 3 k)"); return false; }
+    // the alias rule draws a column and may keep the column's ALIAS neighbour, whose id the table holds and whose column it does not (open)
+    if (wanted.edge_ids && draw_rule_of(wanted) == DrawRule::Weighted) { LEGION_ARG_ERROR((name + ": edge ids (GPUMemoryPool_SetEdgeIds) cannot be handed over under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column").c_str()); return false; }
     if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
     if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k
@@ -177,6 +194,23 @@ int GPUMemoryPool_GetWeightedDistinct(const GPUMemoryPool* p) { return p && p->m
 // is 1; nothing is allocated.  An unseeded pool draws under word 0: deterministic, the same node keys in every batch
 void GPUMemoryPool_SetSharedDraws(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.shared_draws = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetSharedDraws"); }
 int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p) { return p && p->modes.shared_draws ? 1 : 0; }
+// edge ids ("Edge ids"): every batch additionally leaves each COO edge's position in the whole CSR, and its weight where the graph retains them,
+// in per-pipe buffers of the pool.  Allocates cols (max_slots words) and edge_ids / edge_w (num_ids elements per pipe) on the first switch on
+void GPUMemoryPool_SetEdgeIds(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.edge_ids = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetEdgeIds"); }
+int GPUMemoryPool_GetEdgeIds(const GPUMemoryPool* p) { return p && p->modes.edge_ids ? 1 : 0; }
+// the current pipe's buffers as the last batch under the mode left them: int64 / float32 [legion_batch_edges(ec, H)], in the order and at the
+// offsets of the COO.  Null before the mode was set; the weights are null unless that batch ran over a graph that retains them
+int64_t* GPUMemoryPool_GetEdgeIdBuffer(const GPUMemoryPool* p)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeIdBuffer: null pool"); return nullptr; }
+    return p->current_pipe >= 0 && p->current_pipe < (int)p->edge_ids.size() ? p->edge_ids[p->current_pipe] : nullptr;
+}
+float* GPUMemoryPool_GetEdgeWeightBuffer(const GPUMemoryPool* p)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeWeightBuffer: null pool"); return nullptr; }
+    const int q = p->current_pipe;
+    return q >= 0 && q < (int)p->edge_w.size() && q < (int)p->edge_w_filled.size() && p->edge_w_filled[q] ? p->edge_w[q] : nullptr;
+}
 void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {
     ServeModes m = modes_of(p);

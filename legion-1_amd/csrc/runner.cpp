@@ -167,7 +167,9 @@ static void enqueue_gather(Runner* r, int l, Gather want, hipEvent_t behind)
 
 // A batch: the seed launch (level 0), hop 1 .. hop H, the planner on `sampler`; behind each level its event (when `record`) and, on the
 // gather stream, what gather_behind says.  The host issues them interleaved, so a level's gather reaches its stream before the next hop
-// reaches the sampler's.  A runner that was never initialised enqueues nothing.
+// reaches the sampler's.  A runner that was never initialised enqueues nothing.  A pool in the edge-id mode (GPUMemoryPool_SetEdgeIds on
+// Runner_GetMemoryPool; no LEGION_* variable yet) has every hop's GPU_Random_Sampling enqueue k_edge_ids behind its k_write, in front of the
+// level's event: in-process runners and recordings leave the pipe's edge ids like the plain calls do.
 static void enqueue_stages(Runner* r, hipStream_t sampler, bool presc, bool record, Gather want)
 {
     GPUMemoryPool* pool = r->memorypool;

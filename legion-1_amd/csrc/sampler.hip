@@ -223,7 +223,12 @@ struct SampleArgs {
     int32_t* cand;
     int32_t* aux;
     int32_t* tile_edge;
-    unsigned long long* edge_access_time;
+    // One word for two pointers no instantiation reads together (like the tables at the end, and for the same reason): the hotness counters
+    // are read under PRESC only, the slot's column is stored under COLS only, and COLS is never instantiated with PRESC.
+    union {
+        unsigned long long* edge_access_time;   // PRESC only
+        int32_t* cols;                          // COLS only (GPUMemoryPool_SetEdgeIds): cols[idx] = the column of slot idx's draw inside its row
+    };
     const BatchCtl* ctl;       // table epoch of the running batch
     const uint32_t* pow_tab;   // pow_tab[m] = 48271^(m+1), m < kTile (a launch with a smaller tile reads its first TILE entries)
     uint32_t a_tile;           // 48271^TILE
@@ -297,9 +302,16 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
 // "Weighted shared-key sampling"): the weighted rule without replacement with one difference, the uniform under a column's exponential key
 // is the hash of the column's NEIGHBOUR ID and the batch's draw word (weighted_distinct_resolve<true>: it loads the row's ids through s_row[r]
 // beside its weights).  Whole CSR only, like the other weighted rules.
-template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED, bool SHARED>
+// COLS (GPUMemoryPool_SetEdgeIds, INTEGRATION.md "Edge ids"): the slot's column -- the position inside its row that the rule above picked, the
+// one place it is known -- is parked in cols[idx] beside cand[idx]; k_edge_ids turns it into the edge's position in the whole CSR.  A fragment
+// row is the whole row's copy in CSR order, so the column means the same there.  Not with PRESC (a pre-sampling batch hands nothing over) and
+// not with the alias rule (WEIGHTED without DISTINCT: the draw may take the alias neighbour, whose id the table holds and whose column it
+// does not).  COLS = false is the kernel as it was, instruction for instruction (profiles/edge_ids.md): `cols` is not read.
+template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED, bool SHARED, bool COLS = false>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
+    static_assert(!(COLS && PRESC), "pre-sampling batches hand no edge ids over (and cols shares edge_access_time's word)");
+    static_assert(!(COLS && WEIGHTED && !DISTINCT), "the alias table holds the alias neighbour's id, not its column");
     static_assert(!(WEIGHTED && PARTITIONED), "weighted draws read the whole CSR");
     static_assert(!SHARED || DISTINCT, "shared keys are a flag on top of the rules without replacement");
     constexpr bool STREAM = !DISTINCT && !WEIGHTED;   // the minstd stream of the default mode
@@ -404,13 +416,20 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
         for (int s = 0; s < TILE / kBlock; s++) {
             const int32_t idx = tile_start + tid + kBlock * s;
             int32_t dst = -1, known = -1, j = 0, r = 0;
+            [[maybe_unused]] int32_t col = 0;
             if (idx < tile_end) {
                 const uint32_t i = fdiv((uint32_t)idx, a.fdiv);
                 j = idx - (int32_t)i * f;
                 r = (int32_t)i - i0;
                 const int32_t deg = s_deg[r];
                 if (j < deg) { // deg == -1 for padded (-1) sources; Kernels.cu:385,399
-                    if constexpr (DISTINCT && WEIGHTED) dst = s_row[r][s_pick[r * f + j]];
+                    if constexpr (COLS) {   // the rule's pick, named; the loads below are the ones of COLS = false
+                        if constexpr (DISTINCT && WEIGHTED) col = s_pick[r * f + j];
+                        else if constexpr (DISTINCT) col = deg <= f ? j : s_pick[r * f + j];
+                        else col = sample_index(x[s], deg);
+                        dst = s_row[r][col];
+                    }
+                    else if constexpr (DISTINCT && WEIGHTED) dst = s_row[r][s_pick[r * f + j]];
                     else if constexpr (DISTINCT) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
                     else if constexpr (WEIGHTED) {
                         const uint32_t key = weighted_key(i, (uint32_t)a.op_id >> 1, draw);
@@ -439,6 +458,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             }
             if (idx < tile_end) {
                 a.cand[idx] = dst;
+                if constexpr (COLS) a.cols[idx] = col;   // read by k_edge_ids for a slot with a draw only
                 // aux[idx] was initialised to -1 ("claim pending") by the previous launch.  A pending slot must not
                 // store here: the slot that replaces its claim writes aux[idx] from another XCD, and two L2s
                 // holding different dirty bytes for one address would be written back in no defined order.
@@ -787,6 +807,119 @@ __global__ __launch_bounds__(kBlock) void k_write(WriteArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
+// Edge ids (GPUMemoryPool_SetEdgeIds): slot -> edge, once more, behind k_write
+// ------------------------------------------------------------------------------------------------
+// edge_ids[e] = indptr[src] + cols[slot] for the COO edge e that k_write made of `slot`: one edge per slot with a draw (cand != -1), in
+// ascending slot order, behind the edges of the earlier hops.  The prefix is re-derived from what k_mark left, as k_write derives it and as
+// k_draw_weights (gather.hip) re-derives the last hop's: the <= kMaxChunks chunk totals scanned per workgroup in LDS, tile_pre[tile] on
+// top, wave ballots and popcount prefixes inside the tile -- no scan launch, no device-scope hand-off, no per-element atomic.  The launch
+// sits on the sampler stream directly behind the hop's k_write, in front of the next hop: cand (cand_pipe on an aggregated last hop), cols,
+// tile_pre, chunk_tot and hop_state are still this hop's.  The live counters are NOT: k_write's last tile applied update_counter, so the
+// hop's sizes and offsets come from the snapshot in hop_state.  indptr is the WHOLE CSR's, whatever the hop drew from.  Nothing here
+// depends on what edge_ids / edge_w held: every edge of the hop is stored, nothing else is.
+struct EdgeIdArgs {
+    const HopState* hs;
+    const int32_t* cand;
+    const int32_t* cols;
+    const int2* tile_pre;
+    const int2* chunk_tot;
+    const int32_t* sampled_ids;
+    const int32_t* agg_src_ids;
+    const int64_t* indptr;     // whole CSR
+    const float* weights;      // WEIGHTS only: the graph's retained weights, w[e] beside indices[e]
+    int64_t* edge_ids;
+    float* edge_w;             // WEIGHTS only
+    int64_t E;                 // entries of the whole CSR: bound of the weight probe
+    FastDiv fdiv;              // / fan-out
+    int32_t op_id;
+    int32_t mark_grid;         // workgroups of the hop's k_mark: T = ceil(tiles / mark_grid)
+    int32_t slots_cap;         // elements of cand / cols
+    int32_t ids_cap;           // elements of edge_ids / edge_w, sampled_ids and agg_src_ids
+};
+
+template <int TILE, bool WEIGHTS>
+__global__ __launch_bounds__(kBlock) void k_edge_ids(EdgeIdArgs a)
+{
+    constexpr int S = TILE / kBlock, W = kBlock / 64, PER = kMaxChunks / kBlock;
+    __shared__ int32_t s_chunk[kMaxChunks];   // edges in front of chunk c of the hop
+    __shared__ int32_t s_scan[W];
+    __shared__ int32_t s_e[S * W];
+    const int lane = lane_id(), wave = wave_id();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const int32_t q0 = (int32_t)threadIdx.x * PER;
+    int32_t v[PER];
+#pragma unroll
+    for (int u = 0; u < PER; u++) v[u] = a.chunk_tot[q0 + u].x;   // kMaxChunks entries are allocated; masked below
+    const HopState h = *a.hs;
+    const int32_t total = min(h.slots, a.slots_cap);
+    const int32_t n_tiles = (total + TILE - 1) / TILE;
+    if ((int32_t)blockIdx.x >= n_tiles) return;
+    const int32_t T = (n_tiles + a.mark_grid - 1) / a.mark_grid;   // tiles per chunk, as k_mark derived it
+    const int32_t n_chunks = (n_tiles + T - 1) / T;                // <= mark_grid <= kMaxChunks
+    {
+        int32_t se = 0;
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            if (q0 + u >= n_chunks) v[u] = 0;
+            se += v[u];
+        }
+        int32_t ie = se;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t ue = __shfl_up(ie, o);
+            if (lane >= o) ie += ue;
+        }
+        if (lane == 63) s_scan[wave] = ie;
+        __syncthreads();
+        int32_t run = ie - se;
+#pragma unroll
+        for (int w = 0; w < W; w++)
+            if (w < wave) run += s_scan[w];
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            if (q0 + u < n_chunks) s_chunk[q0 + u] = run;
+            run += v[u];
+        }
+        __syncthreads();
+    }
+    const int32_t* __restrict__ input = (a.op_id == 2) ? a.sampled_ids : a.agg_src_ids + h.in_off;
+    for (int32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int32_t ebase = h.edge_base + s_chunk[tile / T] + a.tile_pre[tile].x;
+        int32_t col[S], src[S], re[S];
+        bool draw[S];
+#pragma unroll
+        for (int s = 0; s < S; s++) {
+            const int32_t idx = tile * TILE + threadIdx.x + kBlock * s;
+            draw[s] = idx < total && a.cand[idx] != -1;
+            col[s] = 0; src[s] = -1;
+            if (draw[s]) {
+                col[s] = a.cols[idx];
+                const int32_t i = (int32_t)fdiv((uint32_t)idx, a.fdiv);
+                if (i < h.n_in && LEGION_STORE_OK((a.op_id == 2 ? 0 : h.in_off) + i, a.ids_cap)) src[s] = input[i];
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < S; s++) {
+            const unsigned long long be = __ballot(draw[s]);
+            re[s] = __popcll(be & lt);
+            if (lane == 0) s_e[s * W + wave] = __popcll(be);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < S; s++) {
+            if (!draw[s] || src[s] < 0) continue;
+            int32_t pe = 0;
+            for (int q = 0; q < s * W + wave; q++) pe += s_e[q];   // slot order inside a tile: s-major, then wave, then lane
+            const int32_t e = ebase + pe + re[s];
+            if (!LEGION_STORE_OK(e, a.ids_cap)) continue;
+            const int64_t eid = a.indptr[src[s]] + col[s];
+            a.edge_ids[e] = eid;
+            if constexpr (WEIGHTS) a.edge_w[e] = (unsigned long long)eid < (unsigned long long)a.E ? a.weights[eid] : 0.0f;
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side: launch wrappers
 // ------------------------------------------------------------------------------------------------
 // compute units of the current device, asked once per process (launch.h's grid_for sizes every grid by it)
@@ -866,7 +999,7 @@ void warm_static_tables() { (void)pow_table(); (void)sampler_cu_count(); }
 
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw)
+                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw, const EdgeIdOut* eo)
 {
     const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
@@ -885,7 +1018,8 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.csr = csr;
     a.sampled_ids = b.sampled_ids; a.agg_src_ids = b.agg_src_ids; a.nc = b.nc; a.ec = b.ec;
     a.pos_map = b.pos_map; a.cand = b.cand; a.aux = b.aux; a.tile_edge = b.tile_edge;
-    a.edge_access_time = b.edge_access_time;
+    if (eo) a.cols = eo->cols;   // launch_sample_hop refused the pre-sampling hop: the word is free
+    else a.edge_access_time = b.edge_access_time;
     a.ctl = b.ctl;
     a.pow_tab = pow_table();
     a.a_tile = powmod31(kA, TILE);
@@ -906,7 +1040,12 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
         {k_sample<TILE, false, true, false, false, false>, k_sample<TILE, false, true, true, false, false>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true>, nullptr}};
     static_assert((int)DrawRule::Stream == 0 && (int)DrawRule::Distinct == 1 && (int)DrawRule::Weighted == 2 && (int)DrawRule::WeightedDistinct == 3, "kSample's columns");
     static_assert((int)DrawRule::Shared == 4 && (int)DrawRule::WeightedShared == 5, "kSample's last columns");
-    kSample[is_presc ? 1 : csr.topo_owner ? 2 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
+    // ... and the same rules with the slot's column parked for k_edge_ids (GPUMemoryPool_SetEdgeIds): no pre-sampling row, no alias rule
+    static constexpr void (*kSampleCols[][6])(SampleArgs) = {
+        {k_sample<TILE, false, false, false, false, false, true>, k_sample<TILE, false, false, true, false, false, true>, nullptr, k_sample<TILE, false, false, true, true, false, true>, k_sample<TILE, false, false, true, false, true, true>, k_sample<TILE, false, false, true, true, true, true>},
+        {k_sample<TILE, false, true, false, false, false, true>, k_sample<TILE, false, true, true, false, false, true>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true, true>, nullptr}};
+    if (eo) kSampleCols[csr.topo_owner ? 1 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
+    else kSample[is_presc ? 1 : csr.topo_owner ? 2 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
     k_mark<TILE><<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
@@ -922,12 +1061,28 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     LEGION_AUDIT_LAUNCH(s, "k_write", LEGION_AW(w.hs), LEGION_AW(w.nc), LEGION_AW(w.ec), LEGION_AW(w.sampled_ids), LEGION_AW(w.agg_src_ids), LEGION_AW(w.agg_src_off), LEGION_AW(w.agg_dst_off), LEGION_AW(w.pos_map), LEGION_AW(w.aux_next), LEGION_AL(w.cand), LEGION_AL(w.aux), LEGION_AL(w.tile_edge), LEGION_AL(w.tile_node), LEGION_AL(w.tile_pre), LEGION_AL(w.chunk_tot), LEGION_AL(w.ctl));
     k_write<TILE><<<wgrid, kBlock, 0, s>>>(w);
     HIP_CHECK_LAST();
+    if (!eo) return;
+    EdgeIdArgs e;
+    e.hs = b.hop_state; e.cand = b.cand; e.cols = eo->cols; e.tile_pre = b.tile_pre; e.chunk_tot = b.chunk_tot;
+    e.sampled_ids = b.sampled_ids; e.agg_src_ids = b.agg_src_ids; e.indptr = eo->indptr; e.weights = eo->weights;
+    e.edge_ids = eo->edge_ids; e.edge_w = eo->edge_w; e.E = eo->E; e.fdiv = a.fdiv; e.op_id = op_id; e.mark_grid = grid;
+    e.slots_cap = std::min(slots_bound, b.aux_cap); e.ids_cap = b.ids_cap;
+    // the whole CSR's indptr may be a peer's / the host's table, the weights are this GPU's copy; 8 KB of static LDS: the grid of k_write
+    LEGION_AUDIT_LAUNCH(s, "k_edge_ids", LEGION_AW(e.edge_ids), LEGION_AW(e.edge_w), LEGION_AL(e.hs), LEGION_AL(e.cand), LEGION_AL(e.cols), LEGION_AL(e.tile_pre), LEGION_AL(e.chunk_tot), LEGION_AL(e.sampled_ids), LEGION_AL(e.agg_src_ids), LEGION_AR(e.indptr), LEGION_AL(e.weights));
+    if (e.weights && e.edge_w) k_edge_ids<TILE, true><<<wgrid, kBlock, 0, s>>>(e);
+    else k_edge_ids<TILE, false><<<wgrid, kBlock, 0, s>>>(e);
+    HIP_CHECK_LAST();
 }
 
 void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw)
+                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw, const EdgeIdOut* eo)
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
+    if (eo) {   // edge ids (GPUMemoryPool_SetEdgeIds): the caller leaves eo null for a pre-sampling hop, which hands nothing over
+        if (is_presc) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) of a pre-sampling hop: such a batch hands nothing over"); return; }
+        if (draw.rule == DrawRule::Weighted) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column"); return; }
+        if (!eo->cols || !eo->edge_ids || !eo->indptr) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) without the pool's column and edge-id buffers"); return; }
+    }
     // the tables match the rule (launchers.cpp resolved both from the same modes): a kernel never receives a null table, nor fragments without one
     const void* table = draw_rule_reads_weights(draw.rule) ? (const void*)draw.weights : (const void*)draw.alias;
     if (draw_rule_whole_csr(draw.rule) && (!table || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
@@ -939,8 +1094,8 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
         return;
     }
     // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
-    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw);
-    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw);
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw, eo);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw, eo);
 }
 
 } // namespace legion
