@@ -111,7 +111,7 @@ constexpr int64_t sampler_max_tiles(int64_t max_slots)
     const int64_t narrow = (narrow_slots + kTileNarrow - 1) / kTileNarrow;
     return wide > narrow ? wide : narrow;
 }
-// Distinct-draw sampler mode: the largest fan-out k_sample<.., DISTINCT> runs (its LDS holds the picks of a tile's rows, TILE + 2 of these)
+// The rules without replacement: the largest fan-out k_sample runs under a rule that stages picks (its LDS holds the picks of a tile's rows, TILE + 2 of these)
 constexpr int kDistinctMaxFanout = 64;
 // The sampling kinds of ServeModes::sampling, the `sampling` word a trainer reads and GPUMemoryPool_SetSampling
 constexpr int32_t kSamplingReplace = 0, kSamplingDistinct = 1, kSamplingWeighted = 2;
@@ -164,12 +164,35 @@ inline DrawRule draw_rule_of(const ServeModes& m)
     if (m.sampling == kSamplingDistinct) return m.shared_draws ? DrawRule::Shared : DrawRule::Distinct;
     return DrawRule::Stream;
 }
-// the rule's table (alias table, retained weights) lies beside the whole CSR's indices: never the fragments, exactly as pre-sampling
-constexpr bool draw_rule_whole_csr(DrawRule r) { return r == DrawRule::Weighted || r == DrawRule::WeightedDistinct || r == DrawRule::WeightedShared; }
-// the rule reads the graph's retained edge weights, not the alias table
-constexpr bool draw_rule_reads_weights(DrawRule r) { return r == DrawRule::WeightedDistinct || r == DrawRule::WeightedShared; }
-// the largest fan-out the rule runs (k_sample<.., DISTINCT, ..> stages a row's picks in static LDS); 0 = no bound
-constexpr int32_t draw_rule_max_fanout(DrawRule r) { return r == DrawRule::Distinct || r == DrawRule::WeightedDistinct || r == DrawRule::Shared || r == DrawRule::WeightedShared ? kDistinctMaxFanout : 0; }
+// What is true of a rule, once, one row per rule in the enumeration's order (the assertion behind it holds the two together).  The kernel's branches,
+// the launchers' refusals, the fan-out checks and the log line read this table and nothing else; a new rule is a new row.
+//   whole_csr:     the rule's table (alias table, retained weights) lies beside the whole CSR's indices: never the fragments, exactly as pre-sampling
+//   reads_weights: the rule reads the graph's retained edge weights, not the alias table
+//   max_fanout:    the largest fan-out the rule runs, 0 = no bound; a rule has one because k_sample stages a row's picks in static LDS (s_pick): stages_picks()
+//   picks_column:  what the rule picks is a column of the row (the alias rule may take the column's ALIAS neighbour, whose column nobody knows)
+//   fanout_refusal / env_head, env_tail / sentence: the rule's name to a person, as launch_sample_hop refuses a fan-out above the bound, as
+//                  serve_modes_fit_fanout puts its refusal together, and as Runner_Initialize logs what it serves (null where there is no bound)
+struct DrawRuleFacts {
+    DrawRule rule; bool whole_csr, reads_weights; int32_t max_fanout; bool picks_column; const char *fanout_refusal, *env_head, *env_tail, *sentence;
+    constexpr bool stages_picks() const { return max_fanout != 0; }
+};
+constexpr DrawRuleFacts kDrawRuleFacts[] = {
+    {DrawRule::Stream, false, false, 0, true, nullptr, nullptr, nullptr, "with replacement (LEGION_SAMPLING=replace)"},
+    {DrawRule::Distinct, false, false, kDistinctMaxFanout, true, "GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS", "LEGION_SAMPLING=distinct", ": k_sample stages the picks of a tile's rows in static LDS", "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)"},
+    {DrawRule::Weighted, true, false, 0, false, nullptr, nullptr, nullptr, "weighted by edge weight, with replacement, from the graph's alias table (LEGION_SAMPLING=weighted)"},
+    {DrawRule::WeightedDistinct, true, true, kDistinctMaxFanout, true, "GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS", "LEGION_WEIGHTED_DISTINCT=1", ": k_sample keeps a row's best picks one per lane and stages them in static LDS", "weighted by edge weight, without replacement: min(columns of weight > 0, fan-out) distinct columns per row, from the graph's retained weights (LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1)"},
+    {DrawRule::Shared, false, false, kDistinctMaxFanout, true, "GPU_Random_Sampling: shared-key sampling (GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS", "LEGION_SHARED_DRAWS=1", ": k_sample keeps a row's best picks one per lane and stages them in static LDS", "distinct neighbours, min(degree, fan-out) per row, by a key of the neighbour node: rows that see the same neighbours pick the same ones (LEGION_SAMPLING=distinct LEGION_SHARED_DRAWS=1)"},
+    {DrawRule::WeightedShared, true, true, kDistinctMaxFanout, true, "GPU_Random_Sampling: weighted shared-key sampling (GPUMemoryPool_SetWeightedDistinct + GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS", "LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1", ": k_sample keeps a row's best picks one per lane and stages them in static LDS", "weighted by edge weight, without replacement, by a key of the neighbour node: min(columns of weight > 0, fan-out) distinct columns per row, rows that see the same neighbours prefer the same ones (LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1)"}};
+constexpr int kDrawRules = sizeof(kDrawRuleFacts) / sizeof(kDrawRuleFacts[0]);
+constexpr const DrawRuleFacts& draw_rule_facts(DrawRule r) { return kDrawRuleFacts[(int)r]; }
+static_assert([] { for (int i = 0; i < kDrawRules; i++) if ((int)kDrawRuleFacts[i].rule != i) return false; return true; }(), "kDrawRuleFacts: row i states rule i");
+// Where k_sample reads a row: the whole CSR, the whole CSR while counting topology hotness (a pre-sampling hop), or the owner's fragment
+// where the topology map names one.  launch_sample_hop derives it from (is_presc, the tables it was given).
+enum class RowSource { Whole, Presc, Fragments }; constexpr int kRowSources = 3;
+// Which k_sample<TILE, SRC, RULE, COLS> there are, for the kernel's assertion, the dispatch table built from it (sampler.hip) and every host
+// check: no columns (GPUMemoryPool_SetEdgeIds) from a pre-sampling hop, which hands nothing over; none under a rule whose pick is not a
+// column; no fragments under a rule whose table lies beside the whole CSR.
+constexpr bool sample_variant_exists(RowSource s, DrawRule r, bool cols) { return !(cols && (s == RowSource::Presc || !draw_rule_facts(r).picks_column)) && !(s == RowSource::Fragments && draw_rule_facts(r).whole_csr); }
 // The only readers of the seven variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
 // unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed, unknown LEGION_LP_DRAW, LEGION_LP_DRAW without a
 // seed, unknown LEGION_WEIGHTED_DISTINCT, LEGION_WEIGHTED_DISTINCT without LEGION_SAMPLING=weighted, unknown LEGION_SHARED_DRAWS,
@@ -178,7 +201,7 @@ bool serve_modes_from_env(ServeModes& m, std::string& why);
 // LEGION_LP_DRAW against what is served, once the meta line is known: false with the refusal in `why` unless the training lists are
 // link-prediction thirds (meta flag 2) of a batch size divisible by 3; m.lp_draw := raw_batch_size / 3.  Nothing to do with the mode off.
 bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch_size, std::string& why);
-// the fan-out bound of the modes' draw rule (draw_rule_max_fanout) against a fan-out list: false with the refusal in `why`
+// the fan-out bound of the modes' draw rule (DrawRuleFacts::max_fanout) against a fan-out list: false with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
 void runner_set_lists_verbatim(Runner* r, bool verbatim);   // before Runner_Initialize: meta flag 2 (Runner::lists_verbatim, runner.cpp)
 // what a trainer reads: the five mode words of the "<name>_ext" object (shmExt, ipc_shm.h) := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)

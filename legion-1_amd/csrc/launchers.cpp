@@ -63,7 +63,7 @@ static void csr_tables_of(CsrTables& csr, const GPUGraphStorage* graph, const GP
 static bool draw_tables_of(DrawTables& t, const GPUGraphStorage* graph, const ServeModes& modes, int dev)
 {
     t.rule = draw_rule_of(modes);
-    const bool weighted = draw_rule_whole_csr(t.rule), wdistinct = draw_rule_reads_weights(t.rule);
+    const bool weighted = draw_rule_facts(t.rule).whole_csr, wdistinct = draw_rule_facts(t.rule).reads_weights;
     t.alias = weighted && dev < (int)graph->alias.size() ? graph->alias[dev] : nullptr;
     t.weights = wdistinct && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
     if (weighted && !t.alias) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) over a graph without edge weights on this GPU: call GPUGraphStorage_SetEdgeWeights first"); return false; }
@@ -183,7 +183,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     DrawTables draw;
     if (!draw_tables_of(draw, graph, p->modes, dev)) return;
     CsrTables csr;
-    csr_tables_of(csr, graph, cache, dev, !is_presc && !draw_rule_whole_csr(draw.rule));   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
+    csr_tables_of(csr, graph, cache, dev, !is_presc && sample_variant_exists(RowSource::Fragments, draw.rule, false));   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
     SamplerBuffers b;
     const int q = p->current_pipe;
     b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];

@@ -122,7 +122,7 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
     if (wanted.sampling != kSamplingReplace && wanted.sampling != kSamplingDistinct && wanted.sampling != kSamplingWeighted) { LEGION_ARG_ERROR("GPUMemoryPool_SetSampling: unknown sampling kind (0 = replace, 1 = distinct, 2 = weighted)"); return false; }
     if (wanted.lp_draw < 0) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: negative triples per batch (0 = off, k > 0 = batches of 3 k)"); return false; }
     // the alias rule draws a column and may keep the column's ALIAS neighbour, whose id the table holds and whose column it does not (open)
-    if (wanted.edge_ids && draw_rule_of(wanted) == DrawRule::Weighted) { LEGION_ARG_ERROR((name + ": edge ids (GPUMemoryPool_SetEdgeIds) cannot be handed over under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column").c_str()); return false; }
+    if (wanted.edge_ids && !sample_variant_exists(RowSource::Whole, draw_rule_of(wanted), true)) { LEGION_ARG_ERROR((name + ": edge ids (GPUMemoryPool_SetEdgeIds) cannot be handed over under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column").c_str()); return false; }
     if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
     if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k

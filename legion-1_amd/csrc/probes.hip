@@ -35,7 +35,7 @@ __global__ void k_lp_draw_probe(uint32_t w, const int32_t* src, const int32_t* d
     neg[i] = lp_neg(w, (uint32_t)i, src[i], V);
 }
 
-// The distinct mode's positions of n rows, by the device functions k_sample<.., DISTINCT> runs: pos[m * f + j] = neighbour position of slot j
+// The distinct mode's positions of n rows, by the device functions k_sample<.., DrawRule::Distinct> runs: pos[m * f + j] = neighbour position of slot j
 // of row row[m] of hop hop[m] at degree deg[m], -1 = no draw.  One thread per row; the row's f words of pos are its work space.  w: the
 // batch's draw word (legion_seeded_distinct_probe), 0 = the seeded mode off.
 __global__ void k_distinct_probe(uint32_t w, const int32_t* row, const int32_t* hop, const int32_t* deg, int32_t f, int32_t* pos, int32_t n)
@@ -53,7 +53,7 @@ __global__ void k_distinct_probe(uint32_t w, const int32_t* row, const int32_t* 
     distinct_resolve(out, d, f);
 }
 
-// The weighted mode's draw of n slots, by the device functions k_sample<.., WEIGHTED> runs: the column k[m] < deg[m] and the word ub[m] that
+// The weighted mode's draw of n slots, by the device functions k_sample<.., DrawRule::Weighted> runs: the column k[m] < deg[m] and the word ub[m] that
 // is held against the column's threshold; deg[m] <= 0: k = -1, ub = 0.
 __global__ void k_weighted_probe(const int32_t* row, const int32_t* hop, const int32_t* slot, const int32_t* deg, const uint32_t* word,
                                  int32_t* k, uint32_t* ub, int32_t n)
@@ -67,7 +67,7 @@ __global__ void k_weighted_probe(const int32_t* row, const int32_t* hop, const i
     ub[m] = weighted_ub(key, (uint32_t)slot[m]);
 }
 
-// Weighted sampling without replacement: the hash and the fp64 key of n columns, by the device functions k_sample<.., DISTINCT, WEIGHTED> runs
+// Weighted sampling without replacement: the hash and the fp64 key of n columns, by the device functions k_sample<.., DrawRule::WeightedDistinct> runs
 __global__ void k_weighted_distinct_probe(const int32_t* row, const int32_t* hop, const int32_t* col, const uint32_t* word, const float* w,
                                           uint32_t* u, double* key, int32_t n)
 {
@@ -78,14 +78,14 @@ __global__ void k_weighted_distinct_probe(const int32_t* row, const int32_t* hop
     key[m] = weighted_distinct_keyval(uc, w[m]);
 }
 
-// Shared-key sampling: the node key of n neighbour ids, by the device functions k_sample<.., SHARED> forms it with
+// Shared-key sampling: the node key of n neighbour ids, by the device functions k_sample<.., DrawRule::Shared> forms it with
 __global__ void k_shared_draw_probe(const int32_t* ids, const uint32_t* word, uint32_t* key, int32_t n)
 {
     const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;
     if (m < n) key[m] = shared_key(ids[m], shared_salt(word[m]));
 }
 
-// Weighted shared-key sampling: the node hash and the fp64 key of n (neighbour id, weight) pairs, by the device functions k_sample<.., DISTINCT, WEIGHTED, SHARED> runs
+// Weighted shared-key sampling: the node hash and the fp64 key of n (neighbour id, weight) pairs, by the device functions k_sample<.., DrawRule::WeightedShared> runs
 __global__ void k_weighted_shared_probe(const int32_t* ids, const uint32_t* word, const float* w, uint32_t* u, double* key, int32_t n)
 {
     const int32_t m = threadIdx.x + blockDim.x * blockIdx.x;

@@ -284,7 +284,7 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     ipc_env_publish_modes(env, m);
     if (m.agg_last_hop) log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
     if (m.agg_norm) log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
-    log_out() << r->local_dev_id << " Sampling: " << (draw_rule_of(m) == DrawRule::WeightedShared ? "weighted by edge weight, without replacement, by a key of the neighbour node: min(columns of weight > 0, fan-out) distinct columns per row, rows that see the same neighbours prefer the same ones (LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1)" : m.sampling == kSamplingWeighted && m.weighted_distinct ? "weighted by edge weight, without replacement: min(columns of weight > 0, fan-out) distinct columns per row, from the graph's retained weights (LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1)" : m.sampling == kSamplingWeighted ? "weighted by edge weight, with replacement, from the graph's alias table (LEGION_SAMPLING=weighted)" : m.sampling && m.shared_draws ? "distinct neighbours, min(degree, fan-out) per row, by a key of the neighbour node: rows that see the same neighbours pick the same ones (LEGION_SAMPLING=distinct LEGION_SHARED_DRAWS=1)" : m.sampling ? "distinct neighbours, min(degree, fan-out) per row (LEGION_SAMPLING=distinct)" : "with replacement (LEGION_SAMPLING=replace)") << "\n";
+    log_out() << r->local_dev_id << " Sampling: " << draw_rule_facts(draw_rule_of(m)).sentence << "\n";
     if (m.seeded) log_out() << r->local_dev_id << " Sampling seed: " << m.seed << " (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch\n";
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");
     LEGION_AUDIT_STREAM(r->streams[0], r->local_dev_id, "Runner_Initialize: sampler stream");

@@ -5,7 +5,7 @@
 //   S1 batch_generator                Kernels.cu:68-96      -> k_seed
 //   S2 update_counter                 Kernels.cu:112-150    -> folded into k_seed / k_write (last tile)
 //   S3 kernel_random_sampler_2        Kernels.cu:342-448    -> k_sample + k_mark + k_write
-//   S3' kernel_pre_sampler_optimized  Kernels.cu:468-564    -> k_sample<PRESC>
+//   S3' kernel_pre_sampler_optimized  Kernels.cu:468-564    -> k_sample<.., RowSource::Presc, ..>
 //   S4 construct_graph                Kernels.cu:450-463    -> k_write (both sides)
 //   S5 zero_copy_with_aggregated_cache Kernels.cu:662-702   -> k_gather (+ k_row_ptrs in front of a cached gather): gather.hip
 //   S6 FindFeat/FindTopo (BGHT find)  GPUCache.cu:387-461   -> direct-mapped int32/int8[V] tables: gather.hip, build_kernels.hip
@@ -47,6 +47,7 @@
 #include "internal.h"
 #include "draws.h"
 #include "launch.h"
+#include <array>
 #include <mutex>
 
 #include "audit_hooks.h"
@@ -224,9 +225,9 @@ struct SampleArgs {
     int32_t* aux;
     int32_t* tile_edge;
     // One word for two pointers no instantiation reads together (like the tables at the end, and for the same reason): the hotness counters
-    // are read under PRESC only, the slot's column is stored under COLS only, and COLS is never instantiated with PRESC.
+    // are read from RowSource::Presc only, the slot's column is stored under COLS only, and COLS is never instantiated with Presc.
     union {
-        unsigned long long* edge_access_time;   // PRESC only
+        unsigned long long* edge_access_time;   // Presc only
         int32_t* cols;                          // COLS only (GPUMemoryPool_SetEdgeIds): cols[idx] = the column of slot idx's draw inside its row
     };
     const BatchCtl* ctl;       // table epoch of the running batch
@@ -238,11 +239,11 @@ struct SampleArgs {
     int32_t op_id;
     int32_t window;            // lanes to look back for a repeated draw of the same row: min(count - 1, 8)
     int32_t prefilter_from_op; // first op_id whose claims are preceded by the pre-filter load (4: hop 2; hop 1 never)
-    // One table per weighted instantiation, in one word: growing the struct would move the hidden kernel arguments behind it, and with them
+    // One table per weighted rule, in one word: growing the struct would move the hidden kernel arguments behind it, and with them
     // one load of every instantiation.
     union {
-        const AliasEntry* alias;   // WEIGHTED only: the whole CSR's alias table, entry e beside csr.indices[e] (null in the other modes)
-        const float* weights;      // DISTINCT && WEIGHTED only: the graph's retained edge weights, w[e] beside csr.indices[e]; the alias table is not read
+        const AliasEntry* alias;   // Weighted only: the whole CSR's alias table, entry e beside csr.indices[e] (null under the other rules)
+        const float* weights;      // the rules that read weights (WeightedDistinct, WeightedShared): the graph's retained edge weights, w[e] beside csr.indices[e]; the alias table is not read
     };
 };
 
@@ -280,47 +281,50 @@ __device__ inline int32_t claim_slot(const SampleArgs& a, uint32_t epoch, int32_
     return -1;
 }
 
-// DISTINCT (GPUMemoryPool_SetSampleDistinct): the slot's neighbour position comes from the row's distinct picks instead of the minstd stream.
-// The hash is pure, so the workgroup stages distinct_u of EVERY slot of the tile's rows (rows that straddle a tile edge included: both tiles
-// compute the whole row) in LDS beside the row descriptors, one lane per row of degree > f resolves the row's picks in place, and after
-// one more barrier every slot reads its own.  Everything behind the position is the default mode's code.
-// WEIGHTED (GPUMemoryPool_SetSampling(pool, 2), INTEGRATION.md "Weighted sampling"): the slot draws a column of its row and keeps the
-// column's neighbour or takes the column's alias (Walker's method over the graph's alias table, k_build_alias).  Both hashes are the slot's
-// own, so nothing is staged beyond the row descriptors, and the alias entry and the column's neighbour are two loads off the staged row
-// start whose addresses do not depend on each other's result: the slot's dependent chain is as long as the default mode's.  Whole CSR
-// only (PARTITIONED = false): the table lies beside the whole CSR's indices, the fragments have none.
-// DISTINCT && WEIGHTED (GPUMemoryPool_SetWeightedDistinct on top of the weighted kind, INTEGRATION.md "Weighted sampling without
-// replacement"): the row's picks are its f eligible columns of smallest exponential key, staged in s_pick like the distinct mode's -- but
-// one WAVE resolves a row, its lanes striding over the row's retained weights (weighted_distinct_resolve, draws.h), since a single lane
-// would walk a hub's weights alone.  The row's staged degree becomes min(eligible columns, f); the alias table is not read.
-// DISTINCT && SHARED (GPUMemoryPool_SetSharedDraws on top of the distinct kind, INTEGRATION.md "Shared-key sampling"): the row's picks are
-// its f columns of smallest NODE key, a hash of the neighbour's id and the batch's draw word alone, so rows that see the same neighbours pick
-// the same ones.  Staged in s_pick and read by the slots exactly like the distinct mode's; one WAVE resolves a row of degree > f, its lanes
-// striding over the row's ids (shared_resolve, draws.h).  The rule reads nothing but the row itself, through s_row[r]: whole CSR, pre-sampling
-// and the clique's fragments alike, and no table.
-// DISTINCT && WEIGHTED && SHARED (GPUMemoryPool_SetSharedDraws on top of the weighted kind with GPUMemoryPool_SetWeightedDistinct, INTEGRATION.md
-// "Weighted shared-key sampling"): the weighted rule without replacement with one difference, the uniform under a column's exponential key
-// is the hash of the column's NEIGHBOUR ID and the batch's draw word (weighted_distinct_resolve<true>: it loads the row's ids through s_row[r]
-// beside its weights).  Whole CSR only, like the other weighted rules.
-// COLS (GPUMemoryPool_SetEdgeIds, INTEGRATION.md "Edge ids"): the slot's column -- the position inside its row that the rule above picked, the
-// one place it is known -- is parked in cols[idx] beside cand[idx]; k_edge_ids turns it into the edge's position in the whole CSR.  A fragment
-// row is the whole row's copy in CSR order, so the column means the same there.  Not with PRESC (a pre-sampling batch hands nothing over) and
-// not with the alias rule (WEIGHTED without DISTINCT: the draw may take the alias neighbour, whose id the table holds and whose column it
-// does not).  COLS = false is the kernel as it was, instruction for instruction (profiles/edge_ids.md): `cols` is not read.
-template <int TILE, bool PRESC, bool PARTITIONED, bool DISTINCT, bool WEIGHTED, bool SHARED, bool COLS = false>
+// An instantiation is k_sample<TILE, SRC, RULE, COLS>: where a row is read (RowSource), what a slot draws by (DrawRule), and whether the
+// slot's column is handed on.  sample_variant_exists (internal.h) says which of them there are; the dispatch table behind the kernels is
+// built from it.  Branches that belong to one rule test RULE; branches that several rules share test the rule's fact (kDrawRuleFacts).
+// SRC, the row source.  Whole: indptr / indices of the whole CSR.  Presc (S3', a pre-sampling hop): the whole CSR, and every draw counts in
+// edge_access_time[src], the topology hotness.  Fragments: the owner's fragment where the topology map names one (FindTopo fused), else the
+// whole CSR; a fragment row is the whole row's copy in CSR order.  Not under a rule whose table lies beside the whole CSR (whole_csr).
+// RULE, the draw rule:
+//  Stream (the default, the reference's draws): the slot's position in its row comes from the minstd stream, x[s].
+//  Distinct (GPUMemoryPool_SetSampleDistinct): the position comes from the row's distinct picks instead.  The hash is pure, so the workgroup
+//   stages distinct_u of EVERY slot of the tile's rows (rows that straddle a tile edge included: both tiles compute the whole row) in LDS
+//   beside the row descriptors (s_pick: every rule that stages picks has it, and the fan-out bound that goes with it), one lane per row of
+//   degree > f resolves the row's picks in place, and after one more barrier every slot reads its own.  Everything behind the position is
+//   the stream rule's code.
+//  Weighted (GPUMemoryPool_SetSampling(pool, 2), INTEGRATION.md "Weighted sampling"), the alias rule: the slot draws a column of its row and
+//   keeps the column's neighbour or takes the column's alias (Walker's method over the graph's alias table, k_build_alias).  Both hashes are
+//   the slot's own, so nothing is staged beyond the row descriptors, and the alias entry and the column's neighbour are two loads off the
+//   staged row start whose addresses do not depend on each other's result: the slot's dependent chain is as long as the stream rule's.
+//   Whole CSR only: the table lies beside the whole CSR's indices, the fragments have none.  The one rule whose pick is not a column.
+//  WeightedDistinct (GPUMemoryPool_SetWeightedDistinct on top of the weighted kind, INTEGRATION.md "Weighted sampling without replacement"):
+//   the row's picks are its f eligible columns of smallest exponential key, staged in s_pick like the distinct rule's -- but one WAVE
+//   resolves a row, its lanes striding over the row's retained weights (weighted_distinct_resolve, draws.h), since a single lane would walk
+//   a hub's weights alone.  The row's staged degree becomes min(eligible columns, f); reads the weights, not the alias table; whole CSR only.
+//  Shared (GPUMemoryPool_SetSharedDraws on top of the distinct kind, INTEGRATION.md "Shared-key sampling"): the row's picks are its f columns
+//   of smallest NODE key, a hash of the neighbour's id and the batch's draw word alone, so rows that see the same neighbours pick the same
+//   ones.  Staged in s_pick and read by the slots exactly like the distinct rule's; one WAVE resolves a row of degree > f, its lanes striding
+//   over the row's ids (shared_resolve, draws.h).  The rule reads nothing but the row itself, through s_row[r]: every row source, no table.
+//  WeightedShared (GPUMemoryPool_SetSharedDraws on top of the weighted kind with GPUMemoryPool_SetWeightedDistinct, INTEGRATION.md "Weighted
+//   shared-key sampling"): WeightedDistinct with one difference, the uniform under a column's exponential key is the hash of the column's
+//   NEIGHBOUR ID and the batch's draw word (weighted_distinct_resolve<true>: it loads the row's ids through s_row[r] beside its weights).
+// COLS (GPUMemoryPool_SetEdgeIds, INTEGRATION.md "Edge ids"): the slot's column -- the position inside its row that the rule picked, the one
+// place it is known -- is parked in cols[idx] beside cand[idx]; k_edge_ids turns it into the edge's position in the whole CSR.  A fragment
+// row is the whole row's copy, so the column means the same there.  Not from Presc (a pre-sampling batch hands nothing over) and not under
+// the alias rule (the draw may take the alias neighbour, whose id the table holds and whose column it does not).  COLS = false is the
+// kernel as it was, instruction for instruction (profiles/edge_ids.md): `cols` is not read.
+template <int TILE, RowSource SRC, DrawRule RULE, bool COLS = false>
 __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 {
-    static_assert(!(COLS && PRESC), "pre-sampling batches hand no edge ids over (and cols shares edge_access_time's word)");
-    static_assert(!(COLS && WEIGHTED && !DISTINCT), "the alias table holds the alias neighbour's id, not its column");
-    static_assert(!(WEIGHTED && PARTITIONED), "weighted draws read the whole CSR");
-    static_assert(!SHARED || DISTINCT, "shared keys are a flag on top of the rules without replacement");
-    constexpr bool STREAM = !DISTINCT && !WEIGHTED;   // the minstd stream of the default mode
+    static_assert(sample_variant_exists(SRC, RULE, COLS), "no such variant: internal.h says why (and cols shares edge_access_time's word with the pre-sampling counters)");
     __shared__ const int32_t* s_row[TILE + 2]; // pointer to the first neighbour of the staged row
     __shared__ int32_t s_deg[TILE + 2];
     __shared__ int32_t s_src[TILE + 2];
     __shared__ int32_t s_cnt[kBlock / 64];
     // the tile's rows hold at most TILE + 2 (f - 1) slots: the first row may begin f - 1 slots in front of the tile, the last end f - 1 behind it
-    __shared__ int32_t s_pick[DISTINCT ? TILE + 2 * kDistinctMaxFanout : 1];
+    __shared__ int32_t s_pick[draw_rule_facts(RULE).stages_picks() ? TILE + 2 * kDistinctMaxFanout : 1];
 
     const int32_t N = a.nc[LEGION_NC_NEXT_INPUTS];
     const int32_t f = a.count;
@@ -335,7 +339,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
 
     // per-thread RNG state: x[s] = s_b * 48271^(tile*TILE + tid + 256*s + 1) (the distinct and the weighted mode draw from the hash: no stream)
     uint32_t x[TILE / kBlock];
-    if constexpr (STREAM) {
+    if constexpr (RULE == DrawRule::Stream) {
         // uniform per workgroup; the seeded stream is the unseeded one times the batch's s_b (1 with the mode off: mulmod31(b, 1) == b)
         uint32_t base = mulmod31(powmod31(a.a_tile, (uint64_t)blockIdx.x), seeded_stream_seed(draw));
 #pragma unroll
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 const int64_t* ip = a.csr.indptr + src;
                 const int32_t* ix = a.csr.indices;
                 int8_t owner = -1;
-                if (PARTITIONED && !PRESC) owner = a.csr.topo_owner[src]; // FindTopo fused (GPUCache.cu:434-443)
+                if (SRC == RowSource::Fragments) owner = a.csr.topo_owner[src]; // FindTopo fused (GPUCache.cu:434-443)
                 if (owner >= 0) {   // cached row: chunk tables of the owner's fragment (local HBM or xGMI peer)
                     const int32_t row = a.csr.topo_row[src];
                     ip = a.csr.frag_indptr[owner * a.csr.ip_nch + (row >> a.csr.row_shift)] + (row & ((1 << a.csr.row_shift) - 1));
@@ -376,7 +380,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             s_deg[r] = deg;
             s_src[r] = src;
         }
-        if constexpr (DISTINCT && !WEIGHTED && !SHARED) {
+        if constexpr (RULE == DrawRule::Distinct) {
             const uint32_t hop = (uint32_t)a.op_id >> 1;
             for (int32_t p = tid; p < nrows * f; p += kBlock) {
                 const uint32_t rr = fdiv((uint32_t)p, a.fdiv);
@@ -384,12 +388,12 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             }
         }
         __syncthreads();
-        if constexpr (DISTINCT && !WEIGHTED && !SHARED) {
+        if constexpr (RULE == DrawRule::Distinct) {
             for (int32_t r = tid; r < nrows; r += kBlock)
                 if (s_deg[r] > f) distinct_resolve(s_pick + r * f, s_deg[r], f);
             __syncthreads();
         }
-        if constexpr (SHARED && !WEIGHTED) {
+        if constexpr (RULE == DrawRule::Shared) {
             const uint32_t salt = shared_salt(draw);
             for (int32_t r = wave_id(); r < nrows; r += kBlock / 64) {   // one wave per row: r and everything read through it is wave-uniform
                 const int32_t d = s_deg[r];
@@ -397,13 +401,13 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             }
             __syncthreads();
         }
-        if constexpr (DISTINCT && WEIGHTED) {
+        if constexpr (draw_rule_facts(RULE).reads_weights) {
             const uint32_t hop = (uint32_t)a.op_id >> 1;
             for (int32_t r = wave_id(); r < nrows; r += kBlock / 64) {   // one wave per row: r and everything read through it is wave-uniform
                 const int32_t d = s_deg[r];
                 if (d <= 0) continue;
                 int32_t got;
-                if constexpr (SHARED) got = weighted_distinct_resolve<true>(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), s_row[r], d, f, weighted_shared_salt(draw));
+                if constexpr (RULE == DrawRule::WeightedShared) got = weighted_distinct_resolve<true>(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), s_row[r], d, f, weighted_shared_salt(draw));
                 else got = weighted_distinct_resolve<false>(s_pick + r * f, a.weights + (s_row[r] - a.csr.indices), nullptr, d, f,
                                                             weighted_distinct_key((uint32_t)(i0 + r), hop, draw));
                 if (lane_id() == 0) s_deg[r] = got;   // what the slot test below reads: min(eligible columns, f)
@@ -424,14 +428,14 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 const int32_t deg = s_deg[r];
                 if (j < deg) { // deg == -1 for padded (-1) sources; Kernels.cu:385,399
                     if constexpr (COLS) {   // the rule's pick, named; the loads below are the ones of COLS = false
-                        if constexpr (DISTINCT && WEIGHTED) col = s_pick[r * f + j];
-                        else if constexpr (DISTINCT) col = deg <= f ? j : s_pick[r * f + j];
+                        if constexpr (draw_rule_facts(RULE).reads_weights) col = s_pick[r * f + j];
+                        else if constexpr (draw_rule_facts(RULE).stages_picks()) col = deg <= f ? j : s_pick[r * f + j];
                         else col = sample_index(x[s], deg);
                         dst = s_row[r][col];
                     }
-                    else if constexpr (DISTINCT && WEIGHTED) dst = s_row[r][s_pick[r * f + j]];
-                    else if constexpr (DISTINCT) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
-                    else if constexpr (WEIGHTED) {
+                    else if constexpr (draw_rule_facts(RULE).reads_weights) dst = s_row[r][s_pick[r * f + j]];
+                    else if constexpr (draw_rule_facts(RULE).stages_picks()) dst = s_row[r][deg <= f ? j : s_pick[r * f + j]];
+                    else if constexpr (RULE == DrawRule::Weighted) {
                         const uint32_t key = weighted_key(i, (uint32_t)a.op_id >> 1, draw);
                         const int32_t* col = s_row[r] + weighted_column(key, (uint32_t)j, deg);
                         const AliasEntry e = a.alias[col - a.csr.indices];   // beside the neighbour load, not behind it
@@ -451,7 +455,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
                 if (d <= j && d <= lane_id() && o == dst) dup = d; // keeps the earliest match: short chains
             }
             if (dst >= 0) {
-                if (PRESC) atomicAdd(a.edge_access_time + s_src[r], 1ull); // Kernels.cu:525
+                if (SRC == RowSource::Presc) atomicAdd(a.edge_access_time + s_src[r], 1ull); // Kernels.cu:525
                 if (dup) known = -2 - (idx - dup);
                 else known = claim_slot(a, epoch, dst, idx);
                 cnt++;
@@ -476,7 +480,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(SampleArgs a)
             for (int w = 0; w < kBlock / 64; w++) t += s_cnt[w];
             a.tile_edge[tile] = t;
         }
-        if constexpr (STREAM) {
+        if constexpr (RULE == DrawRule::Stream) {
 #pragma unroll
             for (int s = 0; s < TILE / kBlock; s++) x[s] = mulmod31(x[s], a.a_step);
         }
@@ -997,9 +1001,21 @@ void launch_advance(hipStream_t s, BatchCtl* ctl)
 }
 void warm_static_tables() { (void)pow_table(); (void)sampler_cu_count(); }
 
+// The k_sample instantiations of a tile, by (row source, rule, columns): entry sample_variant_index(..) is the variant where
+// sample_variant_exists says there is one -- taking its address here is what instantiates it -- and null where there is none.
+constexpr int sample_variant_index(RowSource src, DrawRule rule, bool cols) { return ((int)src * kDrawRules + (int)rule) * 2 + (cols ? 1 : 0); }
+template <int TILE, RowSource SRC, DrawRule RULE, bool COLS>
+constexpr auto sample_variant() -> void (*)(SampleArgs)
+{
+    if constexpr (sample_variant_exists(SRC, RULE, COLS)) return k_sample<TILE, SRC, RULE, COLS>;
+    else return nullptr;
+}
+template <int TILE, int... I>
+constexpr std::array<void (*)(SampleArgs), sizeof...(I)> sample_variants(std::integer_sequence<int, I...>) { return {{sample_variant<TILE, (RowSource)(I / 2 / kDrawRules), (DrawRule)(I / 2 % kDrawRules), I % 2 != 0>()...}}; }
+
 template <int TILE>
 static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const SamplerBuffers& b, int32_t count, int32_t op_id,
-                       int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw, const EdgeIdOut* eo)
+                       int32_t hops, int32_t slots_bound, RowSource src, const DrawTables& draw, const EdgeIdOut* eo)
 {
     const int max_tiles = (slots_bound + TILE - 1) / TILE;
     // Workgroups per CU of the persistent tile loops.  The memory system is saturated by the scattered probes long before the CUs
@@ -1018,7 +1034,7 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.csr = csr;
     a.sampled_ids = b.sampled_ids; a.agg_src_ids = b.agg_src_ids; a.nc = b.nc; a.ec = b.ec;
     a.pos_map = b.pos_map; a.cand = b.cand; a.aux = b.aux; a.tile_edge = b.tile_edge;
-    if (eo) a.cols = eo->cols;   // launch_sample_hop refused the pre-sampling hop: the word is free
+    if (eo) a.cols = eo->cols;   // no columns from a pre-sampling hop (sample_variant_exists): the word is free
     else a.edge_access_time = b.edge_access_time;
     a.ctl = b.ctl;
     a.pow_tab = pow_table();
@@ -1028,24 +1044,12 @@ static void launch_sample_hop_t(hipStream_t s, const CsrTables& csr, const Sampl
     a.count = count; a.op_id = op_id;
     a.window = std::min(count - 1, 8);
     a.prefilter_from_op = 4;   // hop 1 goes straight to the atomic (see k_sample; moving the boundary lost: profiles/r04_sampler.md)
-    if (draw_rule_reads_weights(draw.rule)) a.weights = draw.weights;
+    if (draw_rule_facts(draw.rule).reads_weights) a.weights = draw.weights;
     else a.alias = draw.rule == DrawRule::Weighted ? draw.alias : nullptr;
     // the whole CSR may be a peer's / the host's table; the fragment chunk tables, the id -> (owner, row) maps and every buffer of the pool are this GPU's
     LEGION_AUDIT_LAUNCH(s, "k_sample", LEGION_AW(a.pos_map), LEGION_AW(a.cand), LEGION_AW(a.aux), LEGION_AW(a.tile_edge), LEGION_AW(a.edge_access_time), LEGION_AL(a.sampled_ids), LEGION_AL(a.agg_src_ids), LEGION_AL(a.nc), LEGION_AL(a.ec), LEGION_AL(a.ctl), LEGION_AL(a.pow_tab), LEGION_AL(csr.frag_indptr), LEGION_AL(csr.frag_indices), LEGION_AL(csr.topo_owner), LEGION_AL(csr.topo_row), LEGION_AR(csr.indptr), LEGION_AR(csr.indices), LEGION_AL(a.alias));
-    // The instantiation by [whole CSR / pre-sampling / the clique's fragments][rule]; the rules that draw from the whole CSR only have no
-    // partitioned one (launch_sample_hop refuses such tables).  A pre-sampling hop gets whole-CSR tables, so it is never partitioned.
-    static constexpr void (*kSample[][6])(SampleArgs) = {
-        {k_sample<TILE, false, false, false, false, false>, k_sample<TILE, false, false, true, false, false>, k_sample<TILE, false, false, false, true, false>, k_sample<TILE, false, false, true, true, false>, k_sample<TILE, false, false, true, false, true>, k_sample<TILE, false, false, true, true, true>},
-        {k_sample<TILE, true, false, false, false, false>, k_sample<TILE, true, false, true, false, false>, k_sample<TILE, true, false, false, true, false>, k_sample<TILE, true, false, true, true, false>, k_sample<TILE, true, false, true, false, true>, k_sample<TILE, true, false, true, true, true>},
-        {k_sample<TILE, false, true, false, false, false>, k_sample<TILE, false, true, true, false, false>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true>, nullptr}};
-    static_assert((int)DrawRule::Stream == 0 && (int)DrawRule::Distinct == 1 && (int)DrawRule::Weighted == 2 && (int)DrawRule::WeightedDistinct == 3, "kSample's columns");
-    static_assert((int)DrawRule::Shared == 4 && (int)DrawRule::WeightedShared == 5, "kSample's last columns");
-    // ... and the same rules with the slot's column parked for k_edge_ids (GPUMemoryPool_SetEdgeIds): no pre-sampling row, no alias rule
-    static constexpr void (*kSampleCols[][6])(SampleArgs) = {
-        {k_sample<TILE, false, false, false, false, false, true>, k_sample<TILE, false, false, true, false, false, true>, nullptr, k_sample<TILE, false, false, true, true, false, true>, k_sample<TILE, false, false, true, false, true, true>, k_sample<TILE, false, false, true, true, true, true>},
-        {k_sample<TILE, false, true, false, false, false, true>, k_sample<TILE, false, true, true, false, false, true>, nullptr, nullptr, k_sample<TILE, false, true, true, false, true, true>, nullptr}};
-    if (eo) kSampleCols[csr.topo_owner ? 1 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
-    else kSample[is_presc ? 1 : csr.topo_owner ? 2 : 0][(int)draw.rule]<<<grid, kBlock, 0, s>>>(a);
+    static constexpr auto variants = sample_variants<TILE>(std::make_integer_sequence<int, kRowSources * kDrawRules * 2>());
+    variants[sample_variant_index(src, draw.rule, eo != nullptr)]<<<grid, kBlock, 0, s>>>(a);   // launch_sample_hop saw that it exists
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_mark", LEGION_AW(b.aux), LEGION_AW(b.tile_node), LEGION_AW(b.tile_pre), LEGION_AW(b.chunk_tot), LEGION_AW(b.hop_state), LEGION_AL(b.nc), LEGION_AL(b.ec), LEGION_AL(b.tile_edge));
     k_mark<TILE><<<grid, kBlock, 0, s>>>(b.nc, b.ec, count, b.aux, b.tile_edge, b.tile_node, b.tile_pre, b.chunk_tot, b.hop_state);
@@ -1078,24 +1082,20 @@ void launch_sample_hop(hipStream_t s, const CsrTables& csr, const SamplerBuffers
                        int32_t hops, int32_t slots_bound, bool is_presc, const DrawTables& draw, const EdgeIdOut* eo)
 {
     if (count <= 0 || slots_bound <= 0) { LEGION_ARG_ERROR("GPU_Random_Sampling: empty hop"); return; }
-    if (eo) {   // edge ids (GPUMemoryPool_SetEdgeIds): the caller leaves eo null for a pre-sampling hop, which hands nothing over
-        if (is_presc) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) of a pre-sampling hop: such a batch hands nothing over"); return; }
-        if (draw.rule == DrawRule::Weighted) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column"); return; }
-        if (!eo->cols || !eo->edge_ids || !eo->indptr) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) without the pool's column and edge-id buffers"); return; }
-    }
-    // the tables match the rule (launchers.cpp resolved both from the same modes): a kernel never receives a null table, nor fragments without one
-    const void* table = draw_rule_reads_weights(draw.rule) ? (const void*)draw.weights : (const void*)draw.alias;
-    if (draw_rule_whole_csr(draw.rule) && (!table || csr.topo_owner)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
-    if (draw_rule_max_fanout(draw.rule) && count > draw_rule_max_fanout(draw.rule)) {
-        LEGION_ARG_ERROR(draw.rule == DrawRule::Distinct ? "GPU_Random_Sampling: distinct sampling (GPUMemoryPool_SetSampleDistinct) takes a fan-out of at most 64: k_sample stages the picks of a tile's rows in static LDS"
-                         : draw.rule == DrawRule::WeightedShared ? "GPU_Random_Sampling: weighted shared-key sampling (GPUMemoryPool_SetWeightedDistinct + GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"
-                         : draw.rule == DrawRule::Shared ? "GPU_Random_Sampling: shared-key sampling (GPUMemoryPool_SetSharedDraws) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS"
-                                                         : "GPU_Random_Sampling: weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) takes a fan-out of at most 64: k_sample keeps a row's best picks one per lane and stages them in static LDS");
-        return;
-    }
+    const RowSource src = is_presc ? RowSource::Presc : csr.topo_owner ? RowSource::Fragments : RowSource::Whole;
+    // what a caller of the C ABI can get wrong, in the order it always was refused in: edge ids (GPUMemoryPool_SetEdgeIds) under the rule whose
+    // pick is no column, edge ids without the pool's buffers, a whole-CSR rule without its table (launchers.cpp resolved rule and tables from
+    // the same modes: a kernel never receives a null table, nor fragments without one), a fan-out above the rule's bound
+    if (eo && !draw_rule_facts(draw.rule).picks_column) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column"); return; }
+    if (eo && (!eo->cols || !eo->edge_ids || !eo->indptr)) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) without the pool's column and edge-id buffers"); return; }
+    const void* table = draw_rule_facts(draw.rule).reads_weights ? (const void*)draw.weights : (const void*)draw.alias;
+    if (draw_rule_facts(draw.rule).whole_csr && (!table || src == RowSource::Fragments)) { LEGION_ARG_ERROR("GPU_Random_Sampling: weighted sampling (GPUMemoryPool_SetSampling) draws from the whole CSR's alias table: the graph has none (GPUGraphStorage_SetEdgeWeights)"); return; }
+    if (draw_rule_facts(draw.rule).max_fanout && count > draw_rule_facts(draw.rule).max_fanout) { LEGION_ARG_ERROR(draw_rule_facts(draw.rule).fanout_refusal); return; }
+    // ... and what none of them can: the dispatch table has no kernel for the rest (GPU_Random_Sampling leaves eo null for a pre-sampling hop)
+    if (!sample_variant_exists(src, draw.rule, eo != nullptr)) { LEGION_ARG_ERROR("launch_sample_hop: no k_sample variant for this row source, draw rule and column hand-over"); return; }
     // one tile size for the three passes of the hop, from its static slot bound (internal.h: kNarrowSlots)
-    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw, eo);
-    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, is_presc, draw, eo);
+    if (sampler_tile_of(slots_bound) == kTileNarrow) launch_sample_hop_t<kTileNarrow>(s, csr, b, count, op_id, hops, slots_bound, src, draw, eo);
+    else launch_sample_hop_t<kTile>(s, csr, b, count, op_id, hops, slots_bound, src, draw, eo);
 }
 
 } // namespace legion

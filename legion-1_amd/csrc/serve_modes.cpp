@@ -82,13 +82,10 @@ bool legion::serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t r
 // the launcher refuses such a hop per batch (launch_sample_hop): a server that booted would fail every batch, the pre-sampling epoch first
 bool legion::serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why)
 {
-    const DrawRule rule = draw_rule_of(m);
-    const int32_t most = draw_rule_max_fanout(rule);
-    for (int32_t h = 0; most && h < hops; h++)
-        if (fanout[h] > most) {
-            why = std::string(rule == DrawRule::Distinct ? "LEGION_SAMPLING=distinct" : rule == DrawRule::Shared ? "LEGION_SHARED_DRAWS=1" : rule == DrawRule::WeightedShared ? "LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1" : "LEGION_WEIGHTED_DISTINCT=1") + " takes fan-outs of at most " + std::to_string(most) + ", hop " +
-                  std::to_string(h + 1) + " has " + std::to_string(fanout[h]) +
-                  (rule == DrawRule::Distinct ? ": k_sample stages the picks of a tile's rows in static LDS" : ": k_sample keeps a row's best picks one per lane and stages them in static LDS");
+    const DrawRuleFacts& rule = draw_rule_facts(draw_rule_of(m));
+    for (int32_t h = 0; rule.max_fanout && h < hops; h++)
+        if (fanout[h] > rule.max_fanout) {
+            why = std::string(rule.env_head) + " takes fan-outs of at most " + std::to_string(rule.max_fanout) + ", hop " + std::to_string(h + 1) + " has " + std::to_string(fanout[h]) + rule.env_tail;
             return false;
         }
     return true;

@@ -2,13 +2,19 @@
 """Hold the gfx950 code of every kernel of a change against the parent's, kernel by kernel.
 
     hipcc <the Makefile's CXXFLAGS> --save-temps -c <unit>.hip        (every unit, once on the parent, once on the change)
-    python3 profiles/isa_diff.py [--symbols REGEX] PARENT.s... -- CHANGE.s...
+    python3 profiles/isa_diff.py [--symbols REGEX] [--rename REGEX=REPLACEMENT]... PARENT.s... -- CHANGE.s...
 
 Each side is any number of `*-hip-amdgcn-amd-amdhsa-gfx950.s` files: a kernel may move between units.  For every kernel whose symbol
 matches REGEX (default `_ZN6legion`) two things are compared: the kernel descriptor's vgpr_count, sgpr_count, group_segment_fixed_size
 (LDS bytes) and private_segment_fixed_size (scratch bytes), and the lines of the function body -- comments, blank lines and directives
 dropped, and the local labels `.LBB<n>_<m>` rewritten to `.LBB_<m>`, since <n> is the function's index in its unit.  Text only: the
-script knows no instruction.  Prints a markdown table; exit code 1 unless every kernel of the parent is in the change and identical."""
+script knows no instruction.  Prints a markdown table; exit code 1 unless every kernel of the parent is in the change and identical.
+
+A change that renames kernels (other template parameters, another namespace) says so with --rename REGEX=REPLACEMENT, any number of times:
+each is a `re.sub` over the PARENT's mangled symbols, applied in the order given before the two sides are matched, so the parent's kernel
+is held against the change's kernel of the new name.  The REGEX ends at its first `=`; the REPLACEMENT may use `\\1`.  Bodies are compared
+as they are: a kernel that names another kernel's symbol in its body differs under a rename.  Two parent kernels that end up under one name
+are an error."""
 import argparse
 import re
 import subprocess
@@ -18,8 +24,8 @@ WORDS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segmen
 LOCAL_LABEL = re.compile(r"\.L([A-Za-z_]+)\d+_(\d+)")
 
 
-def kernels(paths, select):
-    """symbol -> (the four words, [body lines]) of every selected kernel of the files"""
+def kernels(paths, select, renames=()):
+    """symbol -> (the four words, [body lines]) of every selected kernel of the files, under its name after `renames`"""
     out = {}
     for path in paths:
         bodies, words, name, block, functions = {}, {}, None, {}, set()
@@ -47,9 +53,12 @@ def kernels(paths, select):
                 block = {}
         for sym, w in words.items():
             if select.search(sym):
-                if sym in out:
-                    sys.exit("%s: kernel %s is in more than one file of this side" % (path, sym))
-                out[sym] = (w, bodies[sym])
+                new = sym
+                for pattern, replacement in renames:
+                    new = pattern.sub(replacement, new)
+                if new in out:
+                    sys.exit("%s: kernel %s is in more than one file of this side, or two kernels were renamed to it" % (path, new))
+                out[new] = (w, bodies[sym])
     return out
 
 
@@ -79,6 +88,8 @@ def without_parameters(name):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--symbols", default="_ZN6legion", help="regex a kernel's symbol must match (default: %(default)s)")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT",
+                    help="re.sub applied to the parent's symbols before matching; repeatable, applied in order")
     ap.add_argument("files", nargs="+", help="PARENT.s... -- CHANGE.s...")
     argv = sys.argv[1:]
     if "--" not in argv:
@@ -86,7 +97,10 @@ def main():
     cut = argv.index("--")
     a = ap.parse_args(argv[:cut])
     select = re.compile(a.symbols)
-    P, C = kernels(a.files, select), kernels(argv[cut + 1:], select)
+    if any("=" not in r for r in a.rename):
+        ap.error("--rename takes REGEX=REPLACEMENT")
+    renames = [(re.compile(r.split("=", 1)[0]), r.split("=", 1)[1]) for r in a.rename]
+    P, C = kernels(a.files, select, renames), kernels(argv[cut + 1:], select)
     if not P or not C:
         sys.exit("no kernel matches %r on one side" % a.symbols)
     names = demangled(sorted(set(P) | set(C)))

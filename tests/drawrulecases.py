@@ -3,7 +3,8 @@ graph, the two batch shapes that select the sampler's two tiles, and each draw r
 
 The four rules are what `sampling` and `weighted_distinct` say together (DrawRule, csrc/internal.h): stream = the reference's draws with
 replacement, distinct, weighted, wdistinct = weighted without replacement.  Every statement is distinctref.run_batch with the rule's
-`draw`; nothing here restates a rule."""
+`draw`; nothing here restates a rule.  Where the rows are read is k_sample's other parameter (RowSource, csrc/internal.h): plain = Whole,
+presc = Presc, partitioned = Fragments; a (rule, kind) pair below is k_sample<TILE, SRC, RULE> of either tile."""
 import numpy as np
 
 import distinctref
@@ -16,7 +17,7 @@ RULES = ("stream", "distinct", "weighted", "wdistinct")
 ENGINE_ARGS = dict(stream=dict(sample="replace"), distinct=dict(sample="distinct"), weighted=dict(sample="weighted"),
                    wdistinct=dict(sample="weighted", weighted_distinct=True))
 WHOLE_CSR_ONLY = ("weighted", "wdistinct")          # the rules whose table lies beside the whole CSR: no partitioned sampler
-# (rule, where the rows are read): every reachable combination, the k_sample instantiations of one tile
+# (rule, where the rows are read): every combination of these rules that there is (sample_variant_exists), the k_sample<TILE, SRC, RULE> of one tile
 COMBOS = [(r, k) for r in RULES for k in ("plain", "presc", "partitioned") if not (k == "partitioned" and r in WHOLE_CSR_ONLY)]
 
 NARROW_SLOTS, MAX_FANOUT = 256 * 1024, 64           # kNarrowSlots, kDistinctMaxFanout (csrc/internal.h)

@@ -1,4 +1,4 @@
-"""The distinct-draw sampler mode (k_sample<TILE, PRESC, PARTITIONED, DISTINCT>) where the suite's stress tests had never seen it: on both
+"""The distinct-draw sampler mode (k_sample<TILE, SRC, DrawRule::Distinct>) where the suite's stress tests had never seen it: on both
 sides of the tile switch, in the wide pre-sampling and the wide partitioned instantiations behind a chunked cache, at chosen degrees around
 the take-all / Floyd boundary inside whole batches, switched per batch together with the hand-off mode and recorded batch graphs, served
 with the aggregated hand-offs, and refused at boot with a fan-out it cannot run.  Run with `pytest -m gpu`.
@@ -76,7 +76,7 @@ def test_distinct_batches_do_not_depend_on_the_tile_of_a_hop(K, oracle, switch_g
 @pytest.mark.parametrize("chunk_bytes,peer,lookup", [(None, None, "fused"), (None, "exchange", "pass"), (40000, None, "pass"), (40000, "exchange", "fused")])
 def test_wide_presampling_and_partitioned_hops(K, monkeypatch, chunk_bytes, peer, lookup):
     """{25, 10} from 1049 seeds per logical GPU, G = 2 clique on one device: hop 2's bound is 262 250 slots, so its pre-sampling batches run
-    k_sample<1024, PRESC, ., DISTINCT> and, behind the cache, k_sample<1024, ., PARTITIONED, DISTINCT>.  The pre-sampling batches are the
+    k_sample<1024, RowSource::Presc, DrawRule::Distinct> and, behind the cache, k_sample<1024, RowSource::Fragments, DrawRule::Distinct>.  The pre-sampling batches are the
     statement's and edge_access_time its draw counts; then CSR fragments and feature shards in one chunk each or (chunk_bytes) in several;
     peer rows by in-kernel loads or through the exchange; FindFeat as a lookup pass or fused into the gather."""
     L = K.lib()

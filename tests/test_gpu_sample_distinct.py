@@ -1,4 +1,4 @@
-"""The distinct-draw sampler mode on the GPU (GPUMemoryPool_SetSampleDistinct / LEGION_SAMPLING=distinct: k_sample<.., DISTINCT>), through the
+"""The distinct-draw sampler mode on the GPU (GPUMemoryPool_SetSampleDistinct / LEGION_SAMPLING=distinct: k_sample<.., DrawRule::Distinct>), through the
 C ABI and served, against the NumPy statement of tests/distinctref.py.  Every batch check is array_equal on nc, ec, ids, labels, both COO
 arrays and the feature rows; the aggregated hand-offs on top are held bit for bit against tests/aggref.py / tests/gcnref.py fed with the
 statement's batch.  Run with `pytest -m gpu`."""

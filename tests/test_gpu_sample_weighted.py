@@ -1,4 +1,4 @@
-"""The weighted sampler mode on the GPU (GPUMemoryPool_SetSampling(pool, 2) / LEGION_SAMPLING=weighted: k_sample<.., WEIGHTED> over the alias
+"""The weighted sampler mode on the GPU (GPUMemoryPool_SetSampling(pool, 2) / LEGION_SAMPLING=weighted: k_sample<.., DrawRule::Weighted> over the alias
 table k_build_alias made of GPUGraphStorage_SetEdgeWeights' weights), through the C ABI and served, against the NumPy statement of
 tests/weightedref.py fed with the LIBRARY'S OWN table -- which tests/weightedref.py's check_table holds to the weights first.  Every batch
 check is array_equal on nc, ec, ids, labels, both COO arrays and the feature rows, and on the draws the last hop parked.  Run with

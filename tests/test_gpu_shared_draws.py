@@ -1,5 +1,5 @@
 """Shared-key sampling on the GPU (GPUMemoryPool_SetSharedDraws on top of the distinct kind / LEGION_SAMPLING=distinct LEGION_SHARED_DRAWS=1:
-k_sample<.., DISTINCT, .., SHARED> and shared_resolve, csrc/draws.h), through the C ABI and served, against the NumPy statement of
+k_sample<.., DrawRule::Shared> and shared_resolve, csrc/draws.h), through the C ABI and served, against the NumPy statement of
 tests/sharedref.py.  Every check is array_equal: nc, ec, ids, labels, both COO arrays, the feature rows, the draws every hop parked and,
 under pre-sampling, edge_access_time -- every value is an integer or a copied float, so no tolerance applies and no row is left out.
 Run with `pytest -m gpu`."""

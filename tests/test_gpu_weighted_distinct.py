@@ -1,5 +1,5 @@
 """Weighted sampling without replacement on the GPU (GPUMemoryPool_SetWeightedDistinct on top of the weighted kind / LEGION_SAMPLING=weighted
-LEGION_WEIGHTED_DISTINCT=1: k_sample<.., DISTINCT, WEIGHTED> over the graph's retained edge weights), through the C ABI and served, against
+LEGION_WEIGHTED_DISTINCT=1: k_sample<.., DrawRule::WeightedDistinct> over the graph's retained edge weights), through the C ABI and served, against
 the NumPy statement of tests/wdistinctref.py.  Every batch check is array_equal on nc, ec, ids, labels, both COO arrays and the feature
 rows, and on the draws the last hop parked -- after asserting that no row of the compared batches is a near tie (wdistinctref: the cap is
 zero rows).  Run with `pytest -m gpu`."""

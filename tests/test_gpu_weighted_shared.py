@@ -1,5 +1,5 @@
 """Weighted shared-key sampling on the GPU (GPUMemoryPool_SetSharedDraws on top of the weighted kind with GPUMemoryPool_SetWeightedDistinct /
-LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1: k_sample<.., DISTINCT, WEIGHTED, SHARED> and
+LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1 LEGION_SHARED_DRAWS=1: k_sample<.., DrawRule::WeightedShared> and
 weighted_distinct_resolve<true>, csrc/draws.h), through the C ABI and served, against the NumPy statement of tests/wsharedref.py.  Every
 check is array_equal -- nc, ec, ids, labels, both COO arrays, the feature rows, the draws every hop parked and, under pre-sampling,
 edge_access_time -- except the probe's fp64 key, which is held within 4 ulp.  Every compared batch is first asserted free of near ties
