@@ -72,3 +72,20 @@ def run_batch(g, rule, all_ids, all_labels, batch_size, counter, fanout, seed=No
     res["edge_w"] = np.asarray(g["w"], dtype=np.float32)[res["edge_ids"]]
     res["positions"] = log
     return res
+
+
+# ---- a served batch against the statement ----------------------------------------------------------
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_edge_ids(want, got, weights=True):
+    """the engine's batch `got` with its edge ids against run_batch's `want`: the batch word for word, the ids, and the weights by bit pattern"""
+    from conftest import KEYS_NO_FEATURES, assert_batch_equal
+    assert_batch_equal(want, got, keys=KEYS_NO_FEATURES)
+    assert got["edge_ids"].dtype == np.int64
+    assert_batch_equal(want, got, keys=("edge_ids",))               # names the first differing edges
+    if weights:
+        assert_batch_equal(dict(edge_w=bits(want["edge_w"])), dict(edge_w=bits(got["edge_w"])), keys=("edge_w",))
+    else:
+        assert "edge_w" not in got

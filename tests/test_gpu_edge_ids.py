@@ -8,7 +8,8 @@ import pytest
 import drawrulecases as D
 import eidref as R
 import scratchpoison as P
-from conftest import BATCH_KEYS, KEYS_NO_FEATURES, assert_batch_equal
+from conftest import BATCH_KEYS, assert_batch_equal
+from eidref import assert_edge_ids, bits
 from harness import K, make_engine  # noqa: F401  (K: the module-scoped library fixture)
 
 pytestmark = pytest.mark.gpu
@@ -20,19 +21,6 @@ EDGE_BUFFERS = ("cols", "edge_ids", "edge_w")
 @pytest.fixture(scope="module")
 def g():
     return D.graph()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_edge_ids(want, got, weights=True):
-    assert_batch_equal(want, got, keys=KEYS_NO_FEATURES)
-    assert got["edge_ids"].dtype == np.int64 and np.array_equal(want["edge_ids"], got["edge_ids"])
-    if weights:
-        assert np.array_equal(bits(want["edge_w"]), bits(got["edge_w"]))
-    else:
-        assert "edge_w" not in got
 
 
 class Engines:
