@@ -506,6 +506,20 @@ void GPUMemoryPool_SetEdgeIds(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetEdgeIds(const GPUMemoryPool* p);
 int64_t* GPUMemoryPool_GetEdgeIdBuffer(const GPUMemoryPool* p);
 float* GPUMemoryPool_GetEdgeWeightBuffer(const GPUMemoryPool* p);
+/* Edge-weighted sums for GraphConv / GCNConv with edge_weight (extension; INTEGRATION.md "Aggregated last hop", "Edge-weighted sums").  A flag on
+ * top of the aggregated last hop, only with edge ids on and without a norm.  With GPUMemoryPool_SetAggEdgeWeight(pool, 1)
+ * get_feature_kernel_agg writes into rows [n_in, n_in + N)
+ *   S_e[i, :] = ((0.0f + fl(edge_w[e0] * x[c0])) + fl(edge_w[e1] * x[c1])) + ...   (the product and the add rounded separately, no FMA)
+ * where e_j is the COO edge of draw j of run i (the run's draws are a contiguous slice of the last hop's edges, in slot order) and edge_w is
+ * what the edge-id mode hands over.  A weight of 0 is not special-cased (0 * x is +-0, or NaN for a non-finite x).  Everything else is as in
+ * the plain aggregated mode with edge ids.  Sticky argument errors, in the name of whichever setter comes second, the pool's modes kept: the
+ * flag on a pool that does not aggregate the last hop (the flag is remembered while that mode is switched off and on, as the norm is), the
+ * flag without edge ids and GPUMemoryPool_SetEdgeIds(pool, 0) while it is on, the flag together with GPUMemoryPool_SetAggNorm != 0 (the
+ * composed norm='both' with edge_weight is not in this build); and a null pool or one that is being captured.  get_feature_kernel_agg
+ * refuses a batch over a graph that does not retain its weights (GPUGraphStorage_RetainEdgeWeights).  A LegionBatchGraph replays only in
+ * the state it was recorded in.  Setting it allocates per pipe 4 bytes per slot of the largest hop and a few KB on the current device. */
+void GPUMemoryPool_SetAggEdgeWeight(GPUMemoryPool* p, int on);
+int GPUMemoryPool_GetAggEdgeWeight(const GPUMemoryPool* p);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
  * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
  * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list

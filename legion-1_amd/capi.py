@@ -218,6 +218,8 @@ _SIGS = {
     "GPUMemoryPool_GetSharedDraws": (C.c_int, [vp]),
     "GPUMemoryPool_SetEdgeIds": (None, [vp, C.c_int]),
     "GPUMemoryPool_GetEdgeIds": (C.c_int, [vp]),
+    "GPUMemoryPool_SetAggEdgeWeight": (None, [vp, C.c_int]),
+    "GPUMemoryPool_GetAggEdgeWeight": (C.c_int, [vp]),
     "GPUMemoryPool_GetEdgeIdBuffer": (vp, [vp]),
     "GPUMemoryPool_GetEdgeWeightBuffer": (vp, [vp]),
     "GPUGraphStorage_CopyAliasRows": (C.c_int, [vp, i32, i64, i64, vp, vp]),
@@ -571,8 +573,11 @@ class Engine:
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
-                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False):
-        """edge_ids (GPUMemoryPool_SetEdgeIds): the batch additionally leaves every COO edge's position in the whole CSR in the pipe's buffer, and
+                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False, agg_edge_weight=False):
+        """agg_edge_weight (GPUMemoryPool_SetAggEdgeWeight, only with agg_last_hop=True, edge_ids=True and without agg_norm, on an
+        Engine(retain_edge_weights=True)): `nbr_sum` holds the sums with every row scaled by its draw's edge weight, S_e of INTEGRATION.md
+        "Edge-weighted sums".  Set on every call like `agg_norm`.
+        edge_ids (GPUMemoryPool_SetEdgeIds): the batch additionally leaves every COO edge's position in the whole CSR in the pipe's buffer, and
         its weight on an Engine(retain_edge_weights=True); result() then returns `edge_ids` int64 [n_edges] (and `edge_w` float32 [n_edges]).
         Refused by the library under sample="weighted" without weighted_distinct; a pre-sampling batch hands nothing over.  Set on every call
         like `sample`.
@@ -601,7 +606,7 @@ class Engine:
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
         agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct,
-                                     shared_draws=shared_draws, edge_ids=edge_ids)
+                                     shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight)
         self._eid[(dev, pipe)] = bool(edge_ids) and not is_presc
         self._agg[(dev, pipe)] = agg and gather
         self._norm[(dev, pipe)] = norm and gather
@@ -627,13 +632,18 @@ class Engine:
             L.d_stream_sync(stream)
             check()
 
-    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False):
+    def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False,
+                   agg_edge_weight=False):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
             raise ValueError("agg_norm: None or 'both'")
         if norm and not agg:
             raise ValueError("agg_norm needs agg_last_hop=True: only the last hop's neighbour sums are normalised")
+        if agg_edge_weight and not (agg and edge_ids):
+            raise ValueError("agg_edge_weight needs agg_last_hop=True, edge_ids=True: the last hop's neighbour sums are scaled by the edge_w the edge-id mode hands over")
+        if agg_edge_weight and norm:
+            raise ValueError("agg_edge_weight and agg_norm together are not in this build: GraphConv(norm='both', edge_weight=) rounds twice per product")
         if sample not in ("replace", "distinct", "weighted"):
             raise ValueError("sample: 'replace', 'distinct' or 'weighted'")
         if weighted_distinct and sample != "weighted":
@@ -650,13 +660,21 @@ class Engine:
         norm = int(agg and norm == "both")
         # edge ids are refused together with the alias rule, whichever is set second: off in front of a change of the draw rule, on (again) behind it
         rule = (("replace", "distinct", "weighted").index(sample), int(bool(weighted_distinct)))
-        if L.GPUMemoryPool_GetEdgeIds(pool) and (not edge_ids or rule != (L.GPUMemoryPool_GetSampling(pool), L.GPUMemoryPool_GetWeightedDistinct(pool))):
+        # the edge-weighted sums sit on top of the aggregated mode and of edge ids, and exclude a norm: off in front of everything they depend on, on behind it
+        ew = int(bool(agg_edge_weight) and agg)
+        eid_off = L.GPUMemoryPool_GetEdgeIds(pool) and (not edge_ids or rule != (L.GPUMemoryPool_GetSampling(pool), L.GPUMemoryPool_GetWeightedDistinct(pool)))
+        if L.GPUMemoryPool_GetAggEdgeWeight(pool) and (not ew or eid_off):
+            L.GPUMemoryPool_SetAggEdgeWeight(pool, 0)
+        if eid_off:
             L.GPUMemoryPool_SetEdgeIds(pool, 0)
         for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("WeightedDistinct", int(bool(weighted_distinct))), ("SharedDraws", int(bool(shared_draws))), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
             if getattr(L, "GPUMemoryPool_Get" + mode)(pool) != want:
                 getattr(L, "GPUMemoryPool_Set" + mode)(pool, want)
         if L.GPUMemoryPool_GetEdgeIds(pool) != int(bool(edge_ids)):   # allocates on the first switch on
             L.GPUMemoryPool_SetEdgeIds(pool, int(bool(edge_ids)))
+            check()
+        if L.GPUMemoryPool_GetAggEdgeWeight(pool) != ew:   # allocates where the norm has not
+            L.GPUMemoryPool_SetAggEdgeWeight(pool, ew)
             check()
         self._set_seed(dev, seed, round, stream, lp_draw)
         return agg, bool(norm)
@@ -678,11 +696,11 @@ class Engine:
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
                       stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False,
-                      edge_ids=False):
+                      edge_ids=False, agg_edge_weight=False):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
         run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in, and
-        only in the weighted_distinct, the shared_draws and the edge_ids state it was recorded in."""
+        only in the weighted_distinct, the shared_draws, the edge_ids and the agg_edge_weight state it was recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -691,13 +709,13 @@ class Engine:
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
         self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct, shared_draws=shared_draws,
-                        edge_ids=edge_ids)
+                        edge_ids=edge_ids, agg_edge_weight=agg_edge_weight)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
                        stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw,
-                       weighted_distinct=weighted_distinct, shared_draws=shared_draws, edge_ids=edge_ids)
+                       weighted_distinct=weighted_distinct, shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:

@@ -30,7 +30,8 @@ struct LegionBatchGraph {
     // (k_set_cursor carries them into ctl).  Likewise for lp_draw: the captured k_seed is the instantiation, the k and the row tables of that state;
     // and for weighted_distinct: the captured k_sample is that state's instantiation, over the alias table or over the retained weights;
     // and for shared_draws: the captured k_sample is that state's instantiation; and for edge_ids: the captured hops park their columns and
-    // launch k_edge_ids, or do neither.
+    // launch k_edge_ids, or do neither; and for agg_edge_weight: a captured get_feature_kernel_agg ranks the draws' edge weights and sums
+    // with them, or sums plainly.
     ServeModes modes;
     const int32_t* shuf_ids = nullptr;
 };
@@ -97,6 +98,11 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (g->modes.edge_ids != p->modes.edge_ids) {
         LEGION_ARG_ERROR(g->modes.edge_ids ? "LegionBatchGraph_Launch: the graph was recorded with edge ids (GPUMemoryPool_SetEdgeIds) and the pool has the mode off now: its hops park their columns and launch k_edge_ids -- record it again"
                                            : "LegionBatchGraph_Launch: the graph was recorded without edge ids and the pool has the mode on now (GPUMemoryPool_SetEdgeIds): its hops leave no edge ids behind -- record it again");
+        return -1;
+    }
+    if (g->modes.agg_edge_weight != p->modes.agg_edge_weight) {
+        LEGION_ARG_ERROR(g->modes.agg_edge_weight ? "LegionBatchGraph_Launch: the graph was recorded with edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) and the pool has the flag off now: its last hop is summed by k_draw_edge_weights and the weighted k_gather_sum -- record it again"
+                                                  : "LegionBatchGraph_Launch: the graph was recorded without edge-weighted sums and the pool has the flag on now (GPUMemoryPool_SetAggEdgeWeight): its last hop is summed unweighted -- record it again");
         return -1;
     }
     if (g->shuf_ids && (g->shuf_ids != p->shuf_ids || !p->shuf_valid)) {

@@ -411,6 +411,74 @@ __global__ __launch_bounds__(kBlock) void k_draw_weights(AggNormArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
+// S5, edge-weighted last hop (no counterpart in the reference): the sums a GraphConv / GCNConv with edge_weight needs
+// ------------------------------------------------------------------------------------------------
+// S_e[i, :] = ((0.0f + fl(edge_w[e(i, j0)] * x[c(i, j0)])) + fl(edge_w[e(i, j1)] * x[c(i, j1)])) + ...  -- k_gather_sum<WT> as it is, over
+// wdraw[slot] = edge_w[edge of the slot's draw], edge_w being what k_edge_ids left in the pipe's buffer behind the last hop.  The slot -> edge
+// rank is k_draw_weights': the edge of a slot with a draw is (edges of the hops < H) + (draws in front of it).  One kernel, launched twice on
+// one grid: COUNT leaves the draws of every chunk of slots in chunk_cnt (k_agg_norm_prep's count without its zeroing of out_deg, a buffer
+// this mode does not hold); the second pass adds up the chunk counts in front of its chunk in LDS, ranks its slots by ballot and stores the
+// weights.  A rank beyond the batch's (clamped) edges gets 0.0f.  Reads the batch's own pipe only; plain vector stores, no atomics.
+__device__ inline int64_t agg_norm_slots(const AggEdgeWeightArgs& a)
+{
+    return min((int64_t)legion_hop_inputs(a.nc, a.ec, a.hops) * a.f, (int64_t)a.cand_cap);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_draw_edge_weights(AggEdgeWeightArgs a)
+{
+    constexpr int W = kBlock / 64, PER = kMaxChunks / kBlock;
+    __shared__ int32_t s_w[W];
+    __shared__ int32_t s_c[W];
+    const int lane = lane_id(), wave = wave_id();
+    const int64_t total = agg_norm_slots(a);
+    const int64_t len = agg_norm_chunk_len(total, (int32_t)gridDim.x);
+    const int64_t lo = min((int64_t)blockIdx.x * len, total), hi = min(lo + len, total);
+    int32_t mine = 0;
+    if constexpr (COUNT) {
+        for (int64_t idx = lo + threadIdx.x; idx < hi; idx += kBlock) mine += a.cand[idx] != -1;
+    } else {   // draws in front of this workgroup's chunk
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            const int32_t c = (int32_t)threadIdx.x + kBlock * u;
+            if (c < (int32_t)blockIdx.x) mine += a.chunk_cnt[c];
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if (lane == 0) s_w[wave] = mine;
+    __syncthreads();
+    int32_t rank0 = 0;
+#pragma unroll
+    for (int w = 0; w < W; w++) rank0 += s_w[w];
+    if constexpr (COUNT) {
+        if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = rank0;
+    } else {
+        const unsigned long long lt = (1ull << lane) - 1ull;
+        const int32_t e_in = legion_hop_edges_begin(a.ec, a.hops);   // edges of the hops < H
+        const int32_t E = min(legion_batch_edges(a.ec, a.hops), a.ids_cap);
+        for (int64_t s0 = lo; s0 < hi; s0 += kBlock) {
+            const int64_t idx = s0 + threadIdx.x;
+            const bool draw = idx < hi && a.cand[idx] != -1;
+            const unsigned long long b = __ballot(draw);
+            if (lane == 0) s_c[wave] = __popcll(b);
+            __syncthreads();
+            int32_t r = rank0 + __popcll(b & lt), all = 0;
+#pragma unroll
+            for (int w = 0; w < W; w++) {
+                if (w < wave) r += s_c[w];
+                all += s_c[w];
+            }
+            if (draw) {
+                const int32_t e = e_in + r;
+                a.wdraw[idx] = e >= 0 && e < E ? a.edge_w[e] : 0.0f;
+            }
+            rank0 += all;
+            __syncthreads();
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // S5, owner-computes exchange variant (SURVEY 5 option b; one process per GPU): rows whose cache slot lives on another
 // clique member are not read in-kernel over xGMI; the requester lists them per owner, the owners gather them from their
 // own HBM and the rows come back in one all-to-all (RCCL / hipMemcpyPeer).  Everything else is gathered as usual.
@@ -618,6 +686,19 @@ void launch_agg_norm_weights(hipStream_t s, const AggNormArgs& a, int32_t slots_
     HIP_CHECK_LAST();
     LEGION_AUDIT_LAUNCH(s, "k_draw_weights", LEGION_AW(a.wdraw), LEGION_AL(a.out_deg), LEGION_AL(a.chunk_cnt), LEGION_AL(a.cand), LEGION_AL(a.src_off), LEGION_AL(a.nc), LEGION_AL(a.ec));
     k_draw_weights<<<chunks, kBlock, 0, s>>>(a);
+    HIP_CHECK_LAST();
+}
+
+void launch_agg_edge_weights(hipStream_t s, const AggEdgeWeightArgs& a, int32_t slots_bound)
+{
+    if (slots_bound <= 0 || a.f <= 0) return;
+    // every buffer is the pipe's own, on this GPU; the grid from the static bound of the hop, loop bounds from the counters
+    const int chunks = std::min<int64_t>(kMaxChunks, grid_for(slots_bound, kBlock));   // one grid for both passes, launch_agg_norm_weights' rule
+    LEGION_AUDIT_LAUNCH(s, "k_draw_edge_weights<count>", LEGION_AW(a.chunk_cnt), LEGION_AL(a.cand), LEGION_AL(a.nc), LEGION_AL(a.ec));
+    k_draw_edge_weights<true><<<chunks, kBlock, 0, s>>>(a);
+    HIP_CHECK_LAST();
+    LEGION_AUDIT_LAUNCH(s, "k_draw_edge_weights", LEGION_AW(a.wdraw), LEGION_AL(a.chunk_cnt), LEGION_AL(a.cand), LEGION_AL(a.edge_w), LEGION_AL(a.nc), LEGION_AL(a.ec));
+    k_draw_edge_weights<false><<<chunks, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
 }
 

@@ -152,7 +152,10 @@ struct ServeModes {
     bool edge_ids = false;       // GPUMemoryPool_SetEdgeIds (no variable yet): every sampled edge's position in the whole CSR, and its weight where the graph
                                  // retains them, beside the pipe's COO ("Edge ids").  Refused together with the alias rule (sampling == 2 without
                                  // weighted_distinct); pre-sampling batches hand nothing over; not published
-    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids; }
+    bool agg_edge_weight = false;   // GPUMemoryPool_SetAggEdgeWeight (no variable: the edge buffers are not served), only with agg_last_hop and edge_ids and
+                                 // without agg_norm: the sums scale every row by its draw's edge weight, edge_w of the edge-id mode ("Edge-weighted sums").  A flag
+                                 // on top of the aggregated mode: remembered while that mode is off, as the norm is; not published
+    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
 };
 // The draw rule of a sampler hop: what `sampling` and the flags `weighted_distinct` and `shared_draws` say together.  draw_rule_of is the one
 // place that reads the three; the launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
@@ -455,6 +458,20 @@ struct AggNormArgs {
     float* wdraw;
 };
 void launch_agg_norm_weights(hipStream_t s, const AggNormArgs& a, int32_t slots_bound, int32_t edges_bound);
+// Edge-weighted last hop (gather.hip "S5, edge-weighted last hop"): wdraw[slot] = edge_w[edge of the slot's draw] for every slot of the last hop
+// with a draw, edge_w as k_edge_ids left it behind the last hop.  Everything here belongs to the batch's pipe.
+struct AggEdgeWeightArgs {
+    const int32_t* nc;
+    const int32_t* ec;
+    int32_t hops, f;
+    const int32_t* cand;     // the last hop's draws
+    int32_t cand_cap;        // elements of cand and of wdraw
+    const float* edge_w;     // the pipe's edge weights, by COO edge
+    int32_t ids_cap;         // elements of edge_w
+    int32_t* chunk_cnt;      // int32[kMaxChunks]: draws per chunk of slots
+    float* wdraw;
+};
+void launch_agg_edge_weights(hipStream_t s, const AggEdgeWeightArgs& a, int32_t slots_bound);
 // words of GPUMemoryPool::rows_seen: [l] = level-l gather, then one per launch kind below
 constexpr int kRowsSeenAll = LEGION_MAX_HOPS + 1;      // all rows of the batch (get_feature_kernel_all)
 constexpr int kRowsSeenAggIn = LEGION_MAX_HOPS + 2;    // rows of the levels < H (get_feature_kernel_agg)
@@ -536,7 +553,8 @@ struct GPUMemoryPool {
     uint32_t levels_gathered = 0;     // bit l: get_feature_kernel gathered level l of the current batch
     // Normalised sums (modes.agg_norm, only with modes.agg_last_hop): per pipe, allocated when the mode is set (agg_out_deg / agg_wdraw /
     // agg_chunk_cnt below): the degrees (num_ids words), the draws' weights (max_slots floats) and the chunk counts of the slot -> edge
-    // prefix.  The distinct-draw sampler mode (modes.sampling) allocates nothing.
+    // prefix.  The distinct-draw sampler mode (modes.sampling) allocates nothing.  The edge-weighted sums (modes.agg_edge_weight) use agg_wdraw and
+    // agg_chunk_cnt in the same way and no degrees: a pool that only ever saw that flag holds no agg_out_deg.
     // Seeded sampling (modes.seeded / modes.seed, GPUMemoryPool_BeginRound): the training batches read the round's shuffled copy of the
     // training list (shuf_ids / shuf_labels, filled by k_shuffle_seeds in BeginRound; allocated there on first use, never inside a capture).
     // shuf_src: the seed set's list the copy was made of; shuf_valid: it holds the permutation of (seed, round).  shuf_file_order: BeginRound
@@ -585,7 +603,9 @@ struct GPUMemoryPool {
 namespace legion {
 // The pool's modes := wanted, once for every mode.  Refused in who's name: a null pool, a pool that is being captured (a recording keeps
 // its modes).  Refused as GPUMemoryPool_SetAggNorm: an unknown norm, and a norm on a pool that does not aggregate the last hop -- unless the
-// pool holds that norm already (it stays set while the aggregated mode is off).  Refused as GPUMemoryPool_SetLpDraw: a negative triple count,
+// pool holds that norm already (it stays set while the aggregated mode is off).  Refused in who's name, whichever setter comes second: the
+// edge-weighted sums (agg_edge_weight) without the aggregated mode -- unless the pool holds the flag already --, without edge ids, or together
+// with a norm.  Refused as GPUMemoryPool_SetLpDraw: a negative triple count,
 // and a positive one on a pool without a graph (lp_graph).  Allocates the aggregated modes' per-pipe buffers when the
 // pool owns scratch (call it under the scratch's device); another seed invalidates the shuffled copy, another seeded state the graph cursor.
 bool pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who);

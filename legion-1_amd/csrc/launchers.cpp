@@ -345,6 +345,10 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     const bool norm = p->modes.agg_norm != 0;
     if (norm && ((int)p->agg_out_deg.size() <= q || !p->agg_out_deg[q] || !p->agg_wdraw[q] || !p->agg_chunk_cnt[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe buffers of the normalised sums are missing (GPUMemoryPool_SetAggNorm before AllocateScratch failed?)"); return; }
     if (norm && !p->agg_src_off[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the COO buffers of the current pipe are not set"); return; }
+    // Edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight): every draw's weight is the edge_w k_edge_ids left behind the last hop, in the pipe's buffer
+    const bool ew = p->modes.agg_edge_weight;
+    if (ew && ((int)p->agg_wdraw.size() <= q || !p->agg_wdraw[q] || (int)p->agg_chunk_cnt.size() <= q || !p->agg_chunk_cnt[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe buffers of the edge-weighted sums are missing (GPUMemoryPool_SetAggEdgeWeight before AllocateScratch failed?)"); return; }
+    if (ew && (!p->modes.edge_ids || (int)p->edge_w.size() <= q || !p->edge_w[q] || (int)p->edge_w_filled.size() <= q || !p->edge_w_filled[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) over a batch without edge weights: the graph does not retain its weights (GPUGraphStorage_RetainEdgeWeights before GPUGraphStorage_SetEdgeWeights)"); return; }
     if (!in_memory) return;
     GatherArgs g;
     if (!gather_args(g, cache, noder, p, dev_id, -1, legion_idx_level_offset(H), false)) return;   // rows [0, n_in): the levels < H; the hit counter belongs to the default mode's batches
@@ -361,8 +365,16 @@ void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
         const int64_t slots = (int64_t)p->level_bound[H - 1] * p->fanout[H - 1];
         launch_agg_norm_weights((hipStream_t)strm_hdl, w, (int32_t)std::min<int64_t>(slots, p->max_slots), p->num_ids);
     }
+    if (ew) {   // every draw's edge weight by slot, from the pipe's own draws and edge_w, in front of the weighted sums
+        legion::AggEdgeWeightArgs w;
+        w.nc = p->node_counter[q]; w.ec = p->edge_counter[q]; w.hops = H; w.f = p->fanout[H - 1];
+        w.cand = p->cand_pipe[q]; w.cand_cap = p->max_slots; w.edge_w = p->edge_w[q]; w.ids_cap = p->num_ids;
+        w.chunk_cnt = p->agg_chunk_cnt[q]; w.wdraw = p->agg_wdraw[q];
+        const int64_t slots = (int64_t)p->level_bound[H - 1] * p->fanout[H - 1];
+        launch_agg_edge_weights((hipStream_t)strm_hdl, w, (int32_t)std::min<int64_t>(slots, p->max_slots));
+    }
     launch_gather_sum((hipStream_t)strm_hdl, g, p->cand_pipe[q], p->max_slots, p->edge_counter[q], H, p->fanout[H - 1], p->level_bound[H - 1],
-                      norm ? p->agg_wdraw[q] : nullptr);
+                      norm || ew ? p->agg_wdraw[q] : nullptr);
 }
 
 void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,

@@ -60,16 +60,17 @@ static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
 }
 // The per-pipe buffers of the aggregated modes with their per-pipe sizes, named once in the same way: fn(buffers, bytes per pipe, wanted,
 // description -- a ScratchBuffer without a slot).  The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums,
-// agg_out_deg / agg_wdraw / agg_chunk_cnt.
+// agg_out_deg / agg_wdraw / agg_chunk_cnt; the edge-weighted sums want the last two of them.
 template <typename Fn>
 static void for_mode_buffers(GPUMemoryPool* p, Fn fn)
 {
     const bool agg = p->modes.agg_last_hop, norm = agg && p->modes.agg_norm;
+    const bool wdraw = norm || (agg && p->modes.agg_edge_weight);   // the edge-weighted sums rank their draws the same way, without the degrees
     constexpr int32_t I = sizeof(int32_t), batch = LEGION_SCRATCH_BATCH;
     fn(p->cand_pipe, (size_t)p->max_slots * sizeof(int32_t), agg, ScratchBuffer{nullptr, 0, "cand_pipe", LEGION_SCRATCH_ID, I, batch});
     fn(p->agg_out_deg, (size_t)p->num_ids * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_out_deg", LEGION_SCRATCH_COUNT, I, batch});
-    fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), norm, ScratchBuffer{nullptr, 0, "agg_wdraw", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
-    fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch});
+    fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), wdraw, ScratchBuffer{nullptr, 0, "agg_wdraw", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
+    fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), wdraw, ScratchBuffer{nullptr, 0, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch});
     if (!lists_edge_ids(p)) return;
     // an edge id is one 8-byte word no kernel reads back: any bytes are safe in it, a pair of counts is what the poison's kinds offer
     fn(p->edge_ids, (size_t)p->num_ids * sizeof(int64_t), p->modes.edge_ids, ScratchBuffer{nullptr, 0, "edge_ids", LEGION_SCRATCH_COUNT_PAIR, sizeof(int64_t), batch});
@@ -123,6 +124,10 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
     if (wanted.lp_draw < 0) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: negative triples per batch (0 = off, k > 0 = batches of 3 k)"); return false; }
     // the alias rule draws a column and may keep the column's ALIAS neighbour, whose id the table holds and whose column it does not (open)
     if (wanted.edge_ids && !sample_variant_exists(RowSource::Whole, draw_rule_of(wanted), true)) { LEGION_ARG_ERROR((name + ": edge ids (GPUMemoryPool_SetEdgeIds) cannot be handed over under weighted sampling with replacement (GPUMemoryPool_SetSampling(pool, 2) without GPUMemoryPool_SetWeightedDistinct): the alias table holds the alias neighbour's id, not its column").c_str()); return false; }
+    // the edge-weighted sums are a flag on top of the aggregated mode (remembered while it is off, as the norm is) that reads the edge-id mode's edge_w
+    if (wanted.agg_edge_weight && !wanted.agg_last_hop && !p->modes.agg_edge_weight) { LEGION_ARG_ERROR((name + ": edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) on a pool that does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are scaled").c_str()); return false; }
+    if (wanted.agg_edge_weight && !wanted.edge_ids) { LEGION_ARG_ERROR((name + ": edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) need edge ids (GPUMemoryPool_SetEdgeIds first, and not off while the flag is on): the weight of a draw is the edge_w that mode hands over").c_str()); return false; }
+    if (wanted.agg_edge_weight && wanted.agg_norm) { LEGION_ARG_ERROR((name + ": edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) together with a norm (GPUMemoryPool_SetAggNorm): GraphConv(norm='both', edge_weight=) rounds twice per product and has no kernel in this build").c_str()); return false; }
     if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
     if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k
@@ -198,6 +203,10 @@ int GPUMemoryPool_GetSharedDraws(const GPUMemoryPool* p) { return p && p->modes.
 // in per-pipe buffers of the pool.  Allocates cols (max_slots words) and edge_ids / edge_w (num_ids elements per pipe) on the first switch on
 void GPUMemoryPool_SetEdgeIds(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.edge_ids = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetEdgeIds"); }
 int GPUMemoryPool_GetEdgeIds(const GPUMemoryPool* p) { return p && p->modes.edge_ids ? 1 : 0; }
+// edge-weighted sums ("Edge-weighted sums"): a flag on top of the aggregated last hop, only with edge ids on and without a norm; remembered while
+// the aggregated mode is off.  Allocates agg_wdraw / agg_chunk_cnt per pipe where they are missing (no agg_out_deg: the degrees are the norm's)
+void GPUMemoryPool_SetAggEdgeWeight(GPUMemoryPool* p, int on) { ServeModes m = modes_of(p); m.agg_edge_weight = on != 0; pool_apply_modes(p, m, "GPUMemoryPool_SetAggEdgeWeight"); }
+int GPUMemoryPool_GetAggEdgeWeight(const GPUMemoryPool* p) { return p && p->modes.agg_edge_weight ? 1 : 0; }
 // the current pipe's buffers as the last batch under the mode left them: int64 / float32 [legion_batch_edges(ec, H)], in the order and at the
 // offsets of the COO.  Null before the mode was set; the weights are null unless that batch ran over a graph that retains them
 int64_t* GPUMemoryPool_GetEdgeIdBuffer(const GPUMemoryPool* p)
