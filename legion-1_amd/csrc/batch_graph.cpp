@@ -21,9 +21,7 @@ struct LegionBatchGraph {
     hipGraphExec_t exec = nullptr;
     GPUMemoryPool* pool = nullptr;
     // what the recording left in the pool's per-batch host state (launchers called behind a replay decide from it, like behind the plain calls)
-    int32_t sampled_hop = 0;
-    bool sampled_presc = false;
-    uint32_t levels_gathered = 0;
+    GPUMemoryPool::Progress progress;
     // The serving modes the batch was recorded in (the pool refuses to change them during a recording).  A replay is refused only when the
     // pool's seeded state is another by now: the captured k_seed holds list pointers -- the seed set's, or the pool's shuffled copy (shuf_ids,
     // when the recording read it) --, so the graph only replays in that state; the seed, the round and the counter are not part of it
@@ -35,6 +33,16 @@ struct LegionBatchGraph {
     ServeModes modes;
     const int32_t* shuf_ids = nullptr;
 };
+// The replay rule, one row per mode field a recording is bound to (the comment above says why), compared in this order: the field's state, and
+// the refusal when the recording had it on / had it off.  A field without a row (sampling, agg_last_hop, agg_norm, seed) is not compared.
+struct ReplayRule { int32_t (*state)(const ServeModes&); const char *recorded_on, *recorded_off; };
+constexpr ReplayRule kReplayRules[] = {
+    {[](const ServeModes& m) -> int32_t { return m.seeded; }, "LegionBatchGraph_Launch: the graph was recorded under a seed (GPUMemoryPool_SetSampleSeed) and the pool is unseeded now: its k_seed holds the shuffled list's pointers -- record it again", "LegionBatchGraph_Launch: the graph was recorded unseeded and the pool is seeded now (GPUMemoryPool_SetSampleSeed): its k_seed holds the file-order list's pointers -- record it again"},
+    {[](const ServeModes& m) -> int32_t { return m.lp_draw; }, "LegionBatchGraph_Launch: the graph was recorded with drawn link-prediction thirds (GPUMemoryPool_SetLpDraw) and the pool is in another lp_draw state now: its k_seed draws the thirds for that k -- record it again", "LegionBatchGraph_Launch: the graph was recorded without drawn link-prediction thirds and the pool draws them now (GPUMemoryPool_SetLpDraw): its k_seed reads all three thirds from the list -- record it again"},
+    {[](const ServeModes& m) -> int32_t { return m.weighted_distinct; }, "LegionBatchGraph_Launch: the graph was recorded with weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again", "LegionBatchGraph_Launch: the graph was recorded without weighted sampling without replacement and the pool has the flag on now (GPUMemoryPool_SetWeightedDistinct): its k_sample is another instantiation -- record it again"},
+    {[](const ServeModes& m) -> int32_t { return m.shared_draws; }, "LegionBatchGraph_Launch: the graph was recorded with shared-key sampling (GPUMemoryPool_SetSharedDraws) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again", "LegionBatchGraph_Launch: the graph was recorded without shared-key sampling and the pool has the flag on now (GPUMemoryPool_SetSharedDraws): its k_sample is another instantiation -- record it again"},
+    {[](const ServeModes& m) -> int32_t { return m.edge_ids; }, "LegionBatchGraph_Launch: the graph was recorded with edge ids (GPUMemoryPool_SetEdgeIds) and the pool has the mode off now: its hops park their columns and launch k_edge_ids -- record it again", "LegionBatchGraph_Launch: the graph was recorded without edge ids and the pool has the mode on now (GPUMemoryPool_SetEdgeIds): its hops leave no edge ids behind -- record it again"},
+    {[](const ServeModes& m) -> int32_t { return m.agg_edge_weight; }, "LegionBatchGraph_Launch: the graph was recorded with edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) and the pool has the flag off now: its last hop is summed by k_draw_edge_weights and the weighted k_gather_sum -- record it again", "LegionBatchGraph_Launch: the graph was recorded without edge-weighted sums and the pool has the flag on now (GPUMemoryPool_SetAggEdgeWeight): its last hop is summed unweighted -- record it again"}};
 
 extern "C" {
 
@@ -57,7 +65,7 @@ LegionBatchGraph* GPUMemoryPool_EndBatchCapture(GPUMemoryPool* p, void* stream)
     p->capturing = false;
     LegionBatchGraph* g = new LegionBatchGraph();
     g->pool = p;
-    g->sampled_hop = p->sampled_hop; g->sampled_presc = p->sampled_presc; g->levels_gathered = p->levels_gathered;
+    g->progress = p->progress;
     g->modes = p->modes; g->shuf_ids = p->seed_reads_shuffle ? p->shuf_ids : nullptr;
     HIP_CHECK(hipStreamEndCapture((hipStream_t)stream, &g->graph));
     if (g->graph) HIP_CHECK(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
@@ -75,36 +83,8 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (!g || !g->exec || !g->pool || !g->pool->ctl) { LEGION_ARG_ERROR("LegionBatchGraph_Launch: null graph"); return -1; }
     GPUMemoryPool* p = g->pool;
     if (p->capturing) { LEGION_ARG_ERROR("LegionBatchGraph_Launch: pool is being captured"); return -1; }
-    if (g->modes.seeded != p->modes.seeded) {
-        LEGION_ARG_ERROR(g->modes.seeded ? "LegionBatchGraph_Launch: the graph was recorded under a seed (GPUMemoryPool_SetSampleSeed) and the pool is unseeded now: its k_seed holds the shuffled list's pointers -- record it again"
-                                   : "LegionBatchGraph_Launch: the graph was recorded unseeded and the pool is seeded now (GPUMemoryPool_SetSampleSeed): its k_seed holds the file-order list's pointers -- record it again");
-        return -1;
-    }
-    if (g->modes.lp_draw != p->modes.lp_draw) {
-        LEGION_ARG_ERROR(g->modes.lp_draw ? "LegionBatchGraph_Launch: the graph was recorded with drawn link-prediction thirds (GPUMemoryPool_SetLpDraw) and the pool is in another lp_draw state now: its k_seed draws the thirds for that k -- record it again"
-                                          : "LegionBatchGraph_Launch: the graph was recorded without drawn link-prediction thirds and the pool draws them now (GPUMemoryPool_SetLpDraw): its k_seed reads all three thirds from the list -- record it again");
-        return -1;
-    }
-    if (g->modes.weighted_distinct != p->modes.weighted_distinct) {
-        LEGION_ARG_ERROR(g->modes.weighted_distinct ? "LegionBatchGraph_Launch: the graph was recorded with weighted sampling without replacement (GPUMemoryPool_SetWeightedDistinct) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again"
-                                                    : "LegionBatchGraph_Launch: the graph was recorded without weighted sampling without replacement and the pool has the flag on now (GPUMemoryPool_SetWeightedDistinct): its k_sample is another instantiation -- record it again");
-        return -1;
-    }
-    if (g->modes.shared_draws != p->modes.shared_draws) {
-        LEGION_ARG_ERROR(g->modes.shared_draws ? "LegionBatchGraph_Launch: the graph was recorded with shared-key sampling (GPUMemoryPool_SetSharedDraws) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again"
-                                               : "LegionBatchGraph_Launch: the graph was recorded without shared-key sampling and the pool has the flag on now (GPUMemoryPool_SetSharedDraws): its k_sample is another instantiation -- record it again");
-        return -1;
-    }
-    if (g->modes.edge_ids != p->modes.edge_ids) {
-        LEGION_ARG_ERROR(g->modes.edge_ids ? "LegionBatchGraph_Launch: the graph was recorded with edge ids (GPUMemoryPool_SetEdgeIds) and the pool has the mode off now: its hops park their columns and launch k_edge_ids -- record it again"
-                                           : "LegionBatchGraph_Launch: the graph was recorded without edge ids and the pool has the mode on now (GPUMemoryPool_SetEdgeIds): its hops leave no edge ids behind -- record it again");
-        return -1;
-    }
-    if (g->modes.agg_edge_weight != p->modes.agg_edge_weight) {
-        LEGION_ARG_ERROR(g->modes.agg_edge_weight ? "LegionBatchGraph_Launch: the graph was recorded with edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) and the pool has the flag off now: its last hop is summed by k_draw_edge_weights and the weighted k_gather_sum -- record it again"
-                                                  : "LegionBatchGraph_Launch: the graph was recorded without edge-weighted sums and the pool has the flag on now (GPUMemoryPool_SetAggEdgeWeight): its last hop is summed unweighted -- record it again");
-        return -1;
-    }
+    for (const ReplayRule& r : kReplayRules)
+        if (r.state(g->modes) != r.state(p->modes)) { LEGION_ARG_ERROR(r.state(g->modes) ? r.recorded_on : r.recorded_off); return -1; }
     if (g->shuf_ids && (g->shuf_ids != p->shuf_ids || !p->shuf_valid)) {
         LEGION_ARG_ERROR("LegionBatchGraph_Launch: the graph reads the pool's shuffled training list, which GPUMemoryPool_BeginRound has not filled for this seed and round (or has reallocated: record the graph again)");
         return -1;
@@ -118,7 +98,7 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     if (!p->ctl_synced || p->ctl_counter != counter) launch_set_cursor(s, p->ctl, counter, kEpochTop - p->batch_serial, p->modes.seeded ? 1u : 0u, p->modes.seeded ? seeded_draw_key(p->modes.seed, p->round) : 0u);
     HIP_CHECK(hipGraphLaunch(g->exec, s));
     // the batch now in flight is the recorded one: what the launchers behind it (get_feature_kernel_agg) decide from
-    p->sampled_hop = g->sampled_hop; p->sampled_presc = g->sampled_presc; p->levels_gathered = g->levels_gathered;
+    p->progress = g->progress;
     p->ctl_synced = true;     // k_advance left (counter + 1, next epoch) in ctl
     p->ctl_counter = counter + 1;
     return error_pending() ? -1 : 0;

@@ -1,6 +1,7 @@
 // internal.h -- shared declarations of liblegion_amd (not installed).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -544,17 +545,28 @@ struct GPUMemoryPool {
     int32_t* cand = nullptr;
     // The serving modes the pool is in: set through pool_apply_modes only (the public setters change one field each), read by the launchers.
     legion::ServeModes modes;
-    // Aggregated last hop (modes.agg_last_hop): the last hop parks its draws in the PIPE's buffer, because k_gather_sum reads
-    // them on the gather stream while hop 1 of the next batch already overwrites `cand` on the sampler stream.  Allocated when the
-    // mode is switched on (max_slots words per pipe); the other hops and the default mode keep the one shared buffer.
-    std::vector<int32_t*> cand_pipe;
-    int32_t sampled_hop = 0;          // hops of the current batch that GPU_Random_Sampling has queued (0 behind batch_generator_kernel)
-    bool sampled_presc = false;       // ... as pre-sampling hops
-    uint32_t levels_gathered = 0;     // bit l: get_feature_kernel gathered level l of the current batch
-    // Normalised sums (modes.agg_norm, only with modes.agg_last_hop): per pipe, allocated when the mode is set (agg_out_deg / agg_wdraw /
-    // agg_chunk_cnt below): the degrees (num_ids words), the draws' weights (max_slots floats) and the chunk counts of the slot -> edge
-    // prefix.  The distinct-draw sampler mode (modes.sampling) allocates nothing.  The edge-weighted sums (modes.agg_edge_weight) use agg_wdraw and
-    // agg_chunk_cnt in the same way and no degrees: a pool that only ever saw that flag holds no agg_out_deg.
+    // What one launcher of a batch leaves for the next: reset by batch_generator_kernel, stored by a recording, restored by a replay
+    struct Progress {
+        int32_t sampled_hop = 0;      // hops of the current batch that GPU_Random_Sampling has queued (0 behind batch_generator_kernel)
+        bool sampled_presc = false;   // ... as pre-sampling hops
+        uint32_t levels_gathered = 0; // bit l: get_feature_kernel gathered level l of the current batch
+    } progress;
+    // Everything that exists once per pipe.  own[]: the device buffers the POOL owns per pipe, one row of pool_pipe_buffers() each (below) --
+    // allocated when a mode that wants them is set, kept until the scratch is released, null before.  cand_pipe: the aggregated last hop parks
+    // its draws in the PIPE's buffer, because k_gather_sum reads them on the gather stream while hop 1 of the next batch already overwrites
+    // `cand` on the sampler stream.  The normalised sums rank them through agg_out_deg / agg_wdraw / agg_chunk_cnt; the edge-weighted sums use
+    // the last two in the same way and no degrees.  edge_ids / edge_w: the batch's, read back by callers.
+    enum PipeBuf { kCandPipe, kAggOutDeg, kAggWdraw, kAggChunkCnt, kEdgeIds, kEdgeW, kPipeBufs };
+    struct Pipe {
+        float* float_features = nullptr;   // the seven buffers the caller registered (IPC buffers)
+        int32_t *labels = nullptr, *node_counter = nullptr, *edge_counter = nullptr, *sampled_ids = nullptr, *agg_src_off = nullptr, *agg_dst_off = nullptr;
+        void* own[kPipeBufs] = {};
+        bool edge_w_filled = false;        // the pipe's last batch ran over retained weights (GetEdgeWeightBuffer is null otherwise)
+        template <typename T> T* buf(PipeBuf b) const { return (T*)own[b]; }
+    };
+    std::vector<Pipe> pipes;               // pipeline_depth of them from the constructor on, never resized
+    Pipe& pipe() { return pipes[current_pipe]; }
+    const Pipe& pipe() const { return pipes[current_pipe]; }
     // Seeded sampling (modes.seeded / modes.seed, GPUMemoryPool_BeginRound): the training batches read the round's shuffled copy of the
     // training list (shuf_ids / shuf_labels, filled by k_shuffle_seeds in BeginRound; allocated there on first use, never inside a capture).
     // shuf_src: the seed set's list the copy was made of; shuf_valid: it holds the permutation of (seed, round).  shuf_file_order: BeginRound
@@ -569,15 +581,9 @@ struct GPUMemoryPool {
     // Drawn link-prediction thirds (modes.lp_draw = k, GPUMemoryPool_SetLpDraw): the graph the positives are read from -- kept here because
     // batch_generator_kernel has the reference's signature, without a graph.  Under the mode BeginRound shuffles whole triples into the same copy.
     GPUGraphStorage* lp_graph = nullptr;
-    std::vector<int32_t*> agg_out_deg, agg_chunk_cnt;
-    std::vector<float*> agg_wdraw;
-    // Edge ids (modes.edge_ids, GPUMemoryPool_SetEdgeIds): allocated when the mode is switched on, kept until the scratch is released.  cols:
-    // max_slots words, one buffer (written by k_sample, read by k_edge_ids of the same hop).  edge_ids / edge_w: num_ids elements per pipe,
-    // the batch's, read back by callers.  edge_w_filled[pipe]: the pipe's last batch ran over retained weights (GetEdgeWeightBuffer is null otherwise).
+    // Edge ids (modes.edge_ids, GPUMemoryPool_SetEdgeIds): max_slots words, one buffer (written by k_sample, read by k_edge_ids of the same
+    // hop); allocated when the mode is switched on, kept until the scratch is released
     int32_t* cols = nullptr;
-    std::vector<int64_t*> edge_ids;
-    std::vector<float*> edge_w;
-    std::vector<char> edge_w_filled;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
     int32_t aux_ready_hop = 0, aux_ready_count = 0; // the launch before prepared aux2[hop & 1] for this fan-out
     int32_t* tile_edge = nullptr;
@@ -591,9 +597,6 @@ struct GPUMemoryPool {
     int32_t* agg_src_ids = nullptr;
     int8_t* tmp_part_ind = nullptr;
     int32_t* tmp_part_off = nullptr;
-    // per pipe (IPC buffers)
-    std::vector<float*> float_features;
-    std::vector<int32_t*> labels, node_counter, edge_counter, sampled_ids, agg_src_off, agg_dst_off;
     // host-side launch bounds (no device round trips)
     int32_t bound_n = 0;        // upper bound of the next hop's input count
     int32_t bound_nodes = 0;    // upper bound of nodes discovered so far
@@ -609,6 +612,12 @@ namespace legion {
 // and a positive one on a pool without a graph (lp_graph).  Allocates the aggregated modes' per-pipe buffers when the
 // pool owns scratch (call it under the scratch's device); another seed invalidates the shuffled copy, another seeded state the graph cursor.
 bool pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who);
+// The pool's two buffer tables (memory_pool.cpp, where the rules are written down): the scratch it owns once, and the buffers it owns per pipe,
+// one row for every Pipe::own[which].  wanted: the pool's modes ask for it now; listed: GPUMemoryPool_ScratchInfo names it
+struct ScratchBuffer { void** slot; size_t bytes; const char* name; int32_t kind, elem_bytes, lifetime; };
+__attribute__((visibility("hidden"))) std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p);
+struct PipeBuffer { GPUMemoryPool::PipeBuf which; size_t bytes; bool wanted, listed; const char* name; int32_t kind, elem_bytes, lifetime; };
+__attribute__((visibility("hidden"))) std::array<PipeBuffer, GPUMemoryPool::kPipeBufs> pool_pipe_buffers(const GPUMemoryPool* p);
 }
 
 struct GPUGraphStorage {

@@ -20,15 +20,26 @@ static inline int pool_dev(const GPUMemoryPool* p)
     return d;
 }
 
-static bool pool_ready(const GPUMemoryPool* p, const char* who)
+using Pool = GPUMemoryPool;
+using Pipe = Pool::Pipe;
+
+// the pool's current pipe, once the pool owns scratch and the caller registered the pipe's output buffers; null (sticky error) otherwise
+static Pipe* pool_ready(GPUMemoryPool* p, const char* who)
 {
-    if (!p || !p->owns_scratch) { LEGION_ARG_ERROR((std::string(who) + ": GPUMemoryPool_AllocateScratch was not called").c_str()); return false; }
-    const int q = p->current_pipe;
-    if (!p->sampled_ids[q] || !p->labels[q] || !p->agg_src_off[q] || !p->agg_dst_off[q] || !p->node_counter[q] || !p->edge_counter[q]) {
+    if (!p || !p->owns_scratch) { LEGION_ARG_ERROR((std::string(who) + ": GPUMemoryPool_AllocateScratch was not called").c_str()); return nullptr; }
+    Pipe& pipe = p->pipe();
+    if (!pipe.sampled_ids || !pipe.labels || !pipe.agg_src_off || !pipe.agg_dst_off || !pipe.node_counter || !pipe.edge_counter) {
         LEGION_ARG_ERROR((std::string(who) + ": output buffers of the current pipe are not set").c_str());
-        return false;
+        return nullptr;
     }
-    return true;
+    return &pipe;
+}
+// the pipe holds every one of `rows` (pool_pipe_buffers' rows, by Pipe::own[]) -- and `also`, what the caller needs beside them; false with `refusal` as the sticky error
+static bool pipe_holds(const Pipe& pipe, std::initializer_list<Pool::PipeBuf> rows, const char* refusal, bool also = true)
+{
+    for (Pool::PipeBuf b : rows) also = also && pipe.own[b];
+    if (!also) LEGION_ARG_ERROR(refusal);
+    return also;
 }
 
 // Where logical GPU `dev` reads adjacency rows from: the whole CSR -- its HBM replica when there is one, else the (pinned host) table --
@@ -78,7 +89,8 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
                             int32_t batch_size, int32_t counter, int32_t part_id, int32_t dev_id, int32_t mode)
 {
     (void)part_id;   // cache: only the drawn link-prediction thirds look at it (the topology map of the positives' rows)
-    if (!noder || !pool_ready(memorypool, "batch_generator_kernel")) return;
+    const Pipe* pipe = noder ? pool_ready(memorypool, "batch_generator_kernel") : nullptr;
+    if (!pipe) return;
     hipStream_t s = (hipStream_t)strm_hdl;
     if (mode < 0 || mode >= kModes) log_out() << "invalid mode: " << mode << "\n";
     const GPUNodeStorage::SeedSet& set = noder->seed_set(mode, dev_id);   // empty for an invalid mode
@@ -117,29 +129,22 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         csr_tables_of(lp_args.csr, graph, cache, dev_id, cache && !cache->is_presc);   // pre-sampling batches: the whole CSR, like their hops
         lp = &lp_args;
     }
-    const int q = p->current_pipe;
     if (p->device_id != dev_id && audit::on()) {   // the pool starts serving this GPU: its scratch and its output buffers must live there
-        LEGION_AUDIT_OWNER(p->pos_map, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        LEGION_AUDIT_OWNER(p->cand, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (int32_t* c : p->cand_pipe) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (int32_t* c : p->agg_out_deg) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (int32_t* c : p->agg_chunk_cnt) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (float* c : p->agg_wdraw) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        if (p->cols) LEGION_AUDIT_OWNER(p->cols, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (int64_t* c : p->edge_ids) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (float* c : p->edge_w) if (c) LEGION_AUDIT_OWNER(c, dev_id, "batch_generator_kernel: scratch of the memory pool");
-        for (int i = 0; i < p->pipeline_depth; i++) {
-            LEGION_AUDIT_OWNER(p->sampled_ids[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
-            LEGION_AUDIT_OWNER(p->node_counter[i], dev_id, "batch_generator_kernel: output buffers of the memory pool");
+        for (const ScratchBuffer& b : pool_scratch(p)) if (*b.slot) LEGION_AUDIT_OWNER(*b.slot, dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (const PipeBuffer& b : pool_pipe_buffers(p))
+            for (const Pipe& each : p->pipes) if (each.own[b.which]) LEGION_AUDIT_OWNER(each.own[b.which], dev_id, "batch_generator_kernel: scratch of the memory pool");
+        for (const Pipe& each : p->pipes) {
+            LEGION_AUDIT_OWNER(each.sampled_ids, dev_id, "batch_generator_kernel: output buffers of the memory pool");
+            LEGION_AUDIT_OWNER(each.node_counter, dev_id, "batch_generator_kernel: output buffers of the memory pool");
         }
         LEGION_AUDIT_OWNER(all_ids, dev_id, "batch_generator_kernel: seed list");
     }
     p->device_id = dev_id;
-    p->sampled_hop = 0; p->sampled_presc = false; p->levels_gathered = 0;
+    p->progress = {};
     SeedArgs a;
-    a.batch_ids = p->sampled_ids[q]; a.labels = p->labels[q]; a.batch_size = batch_size;
+    a.batch_ids = pipe->sampled_ids; a.labels = pipe->labels; a.batch_size = batch_size;
     a.all_ids = all_ids; a.all_labels = all_labels; a.total_cap = total_cap;
-    a.pos_map = p->pos_map; a.ctl = p->ctl; a.nc = p->node_counter[q]; a.ec = p->edge_counter[q];
+    a.pos_map = p->pos_map; a.ctl = p->ctl; a.nc = pipe->node_counter; a.ec = pipe->edge_counter;
     a.aux_next = p->aux2[1]; a.f_next = p->fanout[0]; a.aux_cap = p->max_slots;
     a.seeded = seeded; a.draw_key = draw_key; a.lp = lp;
     if (p->capturing) {
@@ -169,7 +174,8 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
                          int32_t count, int32_t op_id, int is_presc)
 {
     if (graph == nullptr) { log_out() << "invalid storage ptr\n"; return; }
-    if (!pool_ready(memorypool, "GPU_Random_Sampling")) return;
+    Pipe* pipe = pool_ready(memorypool, "GPU_Random_Sampling");
+    if (!pipe) return;
     GPUMemoryPool* p = memorypool;
     const int hop = op_id / 2;
     if (op_id < 2 || (op_id & 1) || hop > p->hops) { LEGION_ARG_ERROR("GPU_Random_Sampling: op_id must be 2,4,..,2*hops"); return; }
@@ -185,13 +191,12 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     CsrTables csr;
     csr_tables_of(csr, graph, cache, dev, !is_presc && sample_variant_exists(RowSource::Fragments, draw.rule, false));   // pre-sampling: the whole CSR only (kernel_pre_sampler_optimized, Kernels.cu:636-649)
     SamplerBuffers b;
-    const int q = p->current_pipe;
-    b.sampled_ids = p->sampled_ids[q]; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = p->agg_src_off[q];
-    b.agg_dst_off = p->agg_dst_off[q]; b.nc = p->node_counter[q]; b.ec = p->edge_counter[q];
+    b.sampled_ids = pipe->sampled_ids; b.agg_src_ids = p->agg_src_ids; b.agg_src_off = pipe->agg_src_off;
+    b.agg_dst_off = pipe->agg_dst_off; b.nc = pipe->node_counter; b.ec = pipe->edge_counter;
     b.pos_map = p->pos_map; b.ctl = p->ctl; b.cand = p->cand;
     if (p->modes.agg_last_hop && hop == p->hops) {   // k_gather_sum reads the last hop's draws while the next batch samples: the pipe's own buffer
-        if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("GPU_Random_Sampling: aggregated last hop without the per-pipe draw buffers (GPUMemoryPool_SetAggLastHop before AllocateScratch failed?)"); return; }
-        b.cand = p->cand_pipe[q];
+        if (!pipe_holds(*pipe, {Pool::kCandPipe}, "GPU_Random_Sampling: aggregated last hop without the per-pipe draw buffers (GPUMemoryPool_SetAggLastHop before AllocateScratch failed?)")) return;
+        b.cand = pipe->buf<int32_t>(Pool::kCandPipe);
     }
     b.aux = p->aux2[hop & 1]; b.aux_next = p->aux2[(hop + 1) & 1]; b.tile_edge = p->tile_edge; b.tile_node = p->tile_node; b.tile_pre = p->tile_pre; b.chunk_tot = p->chunk_tot;
     b.hop_state = p->hop_state; b.edge_access_time = nullptr;
@@ -211,18 +216,18 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     EdgeIdOut eo_args;
     const EdgeIdOut* eo = nullptr;
     if (p->modes.edge_ids && !is_presc) {
-        if ((int)p->edge_ids.size() <= q || !p->edge_ids[q] || !p->edge_w[q] || !p->cols) { LEGION_ARG_ERROR("GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) without the pool's buffers (the mode was set before GPUMemoryPool_AllocateScratch failed?)"); return; }
+        if (!pipe_holds(*pipe, {Pool::kEdgeIds, Pool::kEdgeW}, "GPU_Random_Sampling: edge ids (GPUMemoryPool_SetEdgeIds) without the pool's buffers (the mode was set before GPUMemoryPool_AllocateScratch failed?)", p->cols != nullptr)) return;
         CsrTables whole;
         csr_tables_of(whole, graph, cache, dev, false);
-        eo_args.cols = p->cols; eo_args.edge_ids = p->edge_ids[q]; eo_args.edge_w = p->edge_w[q];
+        eo_args.cols = p->cols; eo_args.edge_ids = pipe->buf<int64_t>(Pool::kEdgeIds); eo_args.edge_w = pipe->buf<float>(Pool::kEdgeW);
         eo_args.indptr = whole.indptr; eo_args.E = graph->edge_num;
         eo_args.weights = graph->retain_weights && dev < (int)graph->weights.size() ? graph->weights[dev] : nullptr;
-        p->edge_w_filled[q] = eo_args.weights != nullptr;
+        pipe->edge_w_filled = eo_args.weights != nullptr;
         eo = &eo_args;
     }
     launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, draw, eo);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
-    p->sampled_hop = hop; p->sampled_presc = is_presc != 0;
+    p->progress.sampled_hop = hop; p->progress.sampled_presc = is_presc != 0;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint
     p->bound_nodes += (int32_t)slots;
 }
@@ -237,13 +242,12 @@ static void rows_seen_feedback(GatherArgs& g, const GPUMemoryPool* p, int slot)
 }
 
 // Arguments of a gather over the rows (nc[off_idx], nc[size_idx]) of the current pipe; false (sticky error) if it cannot run.
-static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, int32_t dev_id, int off_idx, int size_idx,
+static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, const Pipe& pipe, int32_t dev_id, int off_idx, int size_idx,
                         bool count_hits = true)
 {
     const int32_t F = noder->float_attr_len;
     if (F < 0) log_out() << "error feature len\n"; // Kernels.cu:719-721
-    const int q = p->current_pipe;
-    if (!p->float_features[q]) { LEGION_ARG_ERROR("get_feature_kernel: feature buffer of the current pipe is not set"); return false; }
+    if (!pipe.float_features) { LEGION_ARG_ERROR("get_feature_kernel: feature buffer of the current pipe is not set"); return false; }
     const bool replica = dev_id >= 0 && dev_id < noder->partition_count && noder->replica_attrs[dev_id];
     g.table = replica ? noder->replica_attrs[dev_id] : noder->float_attrs;
     g.table_pitch = replica ? noder->replica_pitch : noder->float_attr_pitch;
@@ -255,9 +259,9 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
     g.cache_capacity = 1;
     g.F = F;
     g.total_num_nodes = noder->total_num_nodes;
-    g.sampled_ids = p->sampled_ids[q];
-    g.nc = p->node_counter[q];
-    g.dst = p->float_features[q];
+    g.sampled_ids = pipe.sampled_ids;
+    g.nc = pipe.node_counter;
+    g.dst = pipe.float_features;
     g.off_idx = off_idx;
     g.size_idx = size_idx;
     g.dst_rows = p->feature_rows;
@@ -282,12 +286,12 @@ static bool gather_args(GatherArgs& g, GPUCache* cache, GPUNodeStorage* noder, G
 }
 
 // false: refused, nothing launched
-static bool gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, int32_t dev_id,
+static bool gather_common(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* p, const Pipe& pipe, int32_t dev_id,
                           int off_idx, int size_idx, int32_t rows_bound)
 {
     GatherArgs g;
     // an aggregated batch never reaches the last level's gather, which closes a hit-rate sample: its level gathers do not open one
-    if (!gather_args(g, cache, noder, p, dev_id, off_idx, size_idx, !p->modes.agg_last_hop)) return false;
+    if (!gather_args(g, cache, noder, p, pipe, dev_id, off_idx, size_idx, !p->modes.agg_last_hop)) return false;
     launch_gather((hipStream_t)strm_hdl, g, rows_bound);
     // last counting launch of a sampled batch: the host may read the pinned {hits, rows} words once this event completes
     if (g.hit_stats && (off_idx < 0 || off_idx == legion_idx_level_offset(p->hops))) GPUCache_HitSamplingDone(cache, dev_id, strm_hdl);
@@ -315,7 +319,8 @@ static bool use_peer_exchange(const GPUCache* cache, const GPUMemoryPool* p, int
 void get_feature_kernel(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                         int32_t dev_id, int32_t op_id, int in_memory)
 {
-    if (!noder || !pool_ready(memorypool, "get_feature_kernel")) return;
+    const Pipe* pipe = noder ? pool_ready(memorypool, "get_feature_kernel") : nullptr;
+    if (!pipe) return;
     const int l = (op_id - 1) / 2;
     if (op_id < 1 || !(op_id & 1) || l > memorypool->hops) { LEGION_ARG_ERROR("get_feature_kernel: op_id must be 1,3,..,2*hops+1"); return; }
     if (!in_memory) return; // the reference only launches the in-memory path (Kernels.cu:737-746)
@@ -323,67 +328,80 @@ void get_feature_kernel(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, 
         if (l == memorypool->hops) legion_peer_exchange_gather(strm_hdl, cache, noder, memorypool, dev_id);
         return;
     }
-    if (gather_common(strm_hdl, cache, noder, memorypool, dev_id, legion_idx_level_offset(l), legion_idx_level_size(l), memorypool->level_bound[l]))
-        memorypool->levels_gathered |= 1u << l;
+    if (gather_common(strm_hdl, cache, noder, memorypool, *pipe, dev_id, legion_idx_level_offset(l), legion_idx_level_size(l), memorypool->level_bound[l]))
+        memorypool->progress.levels_gathered |= 1u << l;
 }
 
 // Aggregated last hop (no counterpart in the reference): behind the last hop's GPU_Random_Sampling of a pool in that mode
 // (GPUMemoryPool_SetAggLastHop).  Feature rows [0, n_in) -- the levels < H -- are gathered here unless get_feature_kernel already
 // gathered each of them, and the neighbour sums of the last hop's N input slots are written behind them, rows [n_in, n_in + N).
+// every reason get_feature_kernel_agg cannot run on the pool's current batch: true with the sticky error
+static bool agg_refusal(const GPUMemoryPool* p, const Pipe& pipe)
+{
+    if (!p->modes.agg_last_hop) { LEGION_ARG_ERROR("get_feature_kernel_agg: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop)"); return true; }
+    // the exchange moves rows between clique members, not sums
+    if (peer_gather_is_exchange()) { LEGION_ARG_ERROR("get_feature_kernel_agg: LEGION_PEER_GATHER=exchange cannot serve the aggregated last hop (GPUMemoryPool_SetAggLastHop): the exchange moves rows, not sums"); return true; }
+    if (p->progress.sampled_hop != p->hops) { LEGION_ARG_ERROR("get_feature_kernel_agg: called before the last hop's GPU_Random_Sampling"); return true; }
+    if (p->progress.sampled_presc) { LEGION_ARG_ERROR("get_feature_kernel_agg: a pre-sampling batch gathers nothing"); return true; }
+    if (!pipe_holds(pipe, {Pool::kCandPipe}, "get_feature_kernel_agg: the per-pipe draw buffers are missing")) return true;
+    if (p->modes.agg_norm && !pipe_holds(pipe, {Pool::kAggOutDeg, Pool::kAggWdraw, Pool::kAggChunkCnt}, "get_feature_kernel_agg: the per-pipe buffers of the normalised sums are missing (GPUMemoryPool_SetAggNorm before AllocateScratch failed?)")) return true;
+    if (p->modes.agg_norm && !pipe.agg_src_off) { LEGION_ARG_ERROR("get_feature_kernel_agg: the COO buffers of the current pipe are not set"); return true; }
+    // Edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight): every draw's weight is the edge_w k_edge_ids left behind the last hop, in the pipe's buffer
+    const bool ew = p->modes.agg_edge_weight;
+    if (ew && !pipe_holds(pipe, {Pool::kAggWdraw, Pool::kAggChunkCnt}, "get_feature_kernel_agg: the per-pipe buffers of the edge-weighted sums are missing (GPUMemoryPool_SetAggEdgeWeight before AllocateScratch failed?)")) return true;
+    if (ew && (!p->modes.edge_ids || !pipe.own[Pool::kEdgeW] || !pipe.edge_w_filled)) { LEGION_ARG_ERROR("get_feature_kernel_agg: edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) over a batch without edge weights: the graph does not retain its weights (GPUGraphStorage_RetainEdgeWeights before GPUGraphStorage_SetEdgeWeights)"); return true; }
+    return false;
+}
+// The weight of every draw of the last hop by slot (agg_wdraw), in front of the weighted sums, from the pipe's own draws: by the block's
+// out-degrees over the pipe's COO (the norm), or the edge_w k_edge_ids left (the edge-weighted sums) -- whichever the modes ask for
+static void launch_draw_weights(hipStream_t s, const GPUMemoryPool* p, const Pipe& pipe)
+{
+    const int H = p->hops;
+    const int32_t slots = (int32_t)std::min<int64_t>((int64_t)p->level_bound[H - 1] * p->fanout[H - 1], p->max_slots);
+    auto common = [&](auto w) {   // what the two passes' arguments share
+        w.nc = pipe.node_counter; w.ec = pipe.edge_counter; w.hops = H; w.f = p->fanout[H - 1];
+        w.cand = pipe.buf<int32_t>(Pool::kCandPipe); w.cand_cap = p->max_slots; w.ids_cap = p->num_ids;
+        w.chunk_cnt = pipe.buf<int32_t>(Pool::kAggChunkCnt); w.wdraw = pipe.buf<float>(Pool::kAggWdraw);
+        return w;
+    };
+    if (p->modes.agg_norm) {
+        AggNormArgs w = common(AggNormArgs{});
+        w.src_off = pipe.agg_src_off; w.out_deg = pipe.buf<int32_t>(Pool::kAggOutDeg);
+        launch_agg_norm_weights(s, w, slots, p->num_ids);
+    }
+    if (p->modes.agg_edge_weight) {
+        AggEdgeWeightArgs w = common(AggEdgeWeightArgs{});
+        w.edge_w = pipe.buf<float>(Pool::kEdgeW);
+        launch_agg_edge_weights(s, w, slots);
+    }
+}
+
 void get_feature_kernel_agg(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                             int32_t dev_id, int in_memory)
 {
-    if (!noder || !pool_ready(memorypool, "get_feature_kernel_agg")) return;
+    const Pipe* pipe = noder ? pool_ready(memorypool, "get_feature_kernel_agg") : nullptr;
     GPUMemoryPool* p = memorypool;
-    const int H = p->hops, q = p->current_pipe;
-    if (!p->modes.agg_last_hop) { LEGION_ARG_ERROR("get_feature_kernel_agg: the pool does not aggregate the last hop (GPUMemoryPool_SetAggLastHop)"); return; }
-    // the exchange moves rows between clique members, not sums
-    if (peer_gather_is_exchange()) { LEGION_ARG_ERROR("get_feature_kernel_agg: LEGION_PEER_GATHER=exchange cannot serve the aggregated last hop (GPUMemoryPool_SetAggLastHop): the exchange moves rows, not sums"); return; }
-    if (p->sampled_hop != H) { LEGION_ARG_ERROR("get_feature_kernel_agg: called before the last hop's GPU_Random_Sampling"); return; }
-    if (p->sampled_presc) { LEGION_ARG_ERROR("get_feature_kernel_agg: a pre-sampling batch gathers nothing"); return; }
-    if ((int)p->cand_pipe.size() <= q || !p->cand_pipe[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe draw buffers are missing"); return; }
-    const bool norm = p->modes.agg_norm != 0;
-    if (norm && ((int)p->agg_out_deg.size() <= q || !p->agg_out_deg[q] || !p->agg_wdraw[q] || !p->agg_chunk_cnt[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe buffers of the normalised sums are missing (GPUMemoryPool_SetAggNorm before AllocateScratch failed?)"); return; }
-    if (norm && !p->agg_src_off[q]) { LEGION_ARG_ERROR("get_feature_kernel_agg: the COO buffers of the current pipe are not set"); return; }
-    // Edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight): every draw's weight is the edge_w k_edge_ids left behind the last hop, in the pipe's buffer
-    const bool ew = p->modes.agg_edge_weight;
-    if (ew && ((int)p->agg_wdraw.size() <= q || !p->agg_wdraw[q] || (int)p->agg_chunk_cnt.size() <= q || !p->agg_chunk_cnt[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: the per-pipe buffers of the edge-weighted sums are missing (GPUMemoryPool_SetAggEdgeWeight before AllocateScratch failed?)"); return; }
-    if (ew && (!p->modes.edge_ids || (int)p->edge_w.size() <= q || !p->edge_w[q] || (int)p->edge_w_filled.size() <= q || !p->edge_w_filled[q])) { LEGION_ARG_ERROR("get_feature_kernel_agg: edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) over a batch without edge weights: the graph does not retain its weights (GPUGraphStorage_RetainEdgeWeights before GPUGraphStorage_SetEdgeWeights)"); return; }
-    if (!in_memory) return;
+    if (!pipe || agg_refusal(p, *pipe) || !in_memory) return;
+    const int H = p->hops;
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, -1, legion_idx_level_offset(H), false)) return;   // rows [0, n_in): the levels < H; the hit counter belongs to the default mode's batches
-    if ((p->levels_gathered & ((1u << H) - 1u)) != (1u << H) - 1u) {
+    if (!gather_args(g, cache, noder, p, *pipe, dev_id, -1, legion_idx_level_offset(H), false)) return;   // rows [0, n_in): the levels < H; the hit counter belongs to the default mode's batches
+    if ((p->progress.levels_gathered & ((1u << H) - 1u)) != (1u << H) - 1u) {
         rows_seen_feedback(g, p, kRowsSeenAggIn);
         launch_gather((hipStream_t)strm_hdl, g, p->num_ids - p->level_bound[H]);
     }
     rows_seen_feedback(g, p, kRowsSeenAggRuns);
-    if (norm) {   // the block's out-degrees and every draw's weight, from the pipe's own COO and draws, in front of the weighted sums
-        legion::AggNormArgs w;
-        w.nc = p->node_counter[q]; w.ec = p->edge_counter[q]; w.hops = H; w.f = p->fanout[H - 1];
-        w.cand = p->cand_pipe[q]; w.cand_cap = p->max_slots; w.src_off = p->agg_src_off[q]; w.ids_cap = p->num_ids;
-        w.out_deg = p->agg_out_deg[q]; w.chunk_cnt = p->agg_chunk_cnt[q]; w.wdraw = p->agg_wdraw[q];
-        const int64_t slots = (int64_t)p->level_bound[H - 1] * p->fanout[H - 1];
-        launch_agg_norm_weights((hipStream_t)strm_hdl, w, (int32_t)std::min<int64_t>(slots, p->max_slots), p->num_ids);
-    }
-    if (ew) {   // every draw's edge weight by slot, from the pipe's own draws and edge_w, in front of the weighted sums
-        legion::AggEdgeWeightArgs w;
-        w.nc = p->node_counter[q]; w.ec = p->edge_counter[q]; w.hops = H; w.f = p->fanout[H - 1];
-        w.cand = p->cand_pipe[q]; w.cand_cap = p->max_slots; w.edge_w = p->edge_w[q]; w.ids_cap = p->num_ids;
-        w.chunk_cnt = p->agg_chunk_cnt[q]; w.wdraw = p->agg_wdraw[q];
-        const int64_t slots = (int64_t)p->level_bound[H - 1] * p->fanout[H - 1];
-        launch_agg_edge_weights((hipStream_t)strm_hdl, w, (int32_t)std::min<int64_t>(slots, p->max_slots));
-    }
-    launch_gather_sum((hipStream_t)strm_hdl, g, p->cand_pipe[q], p->max_slots, p->edge_counter[q], H, p->fanout[H - 1], p->level_bound[H - 1],
-                      norm || ew ? p->agg_wdraw[q] : nullptr);
+    launch_draw_weights((hipStream_t)strm_hdl, p, *pipe);
+    launch_gather_sum((hipStream_t)strm_hdl, g, pipe->buf<int32_t>(Pool::kCandPipe), p->max_slots, pipe->edge_counter, H, p->fanout[H - 1], p->level_bound[H - 1],
+                      p->modes.agg_norm || p->modes.agg_edge_weight ? pipe->buf<float>(Pool::kAggWdraw) : nullptr);
 }
 
 void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool,
                             int32_t dev_id, int in_memory)
 {
-    if (!noder || !pool_ready(memorypool, "get_feature_kernel_all")) return;
-    if (!in_memory) return;
+    const Pipe* pipe = noder ? pool_ready(memorypool, "get_feature_kernel_all") : nullptr;
+    if (!pipe || !in_memory) return;
     if (use_peer_exchange(cache, memorypool, dev_id)) { legion_peer_exchange_gather(strm_hdl, cache, noder, memorypool, dev_id); return; }
-    gather_common(strm_hdl, cache, noder, memorypool, dev_id, -1, LEGION_NC_TOTAL, memorypool->num_ids); // every row of the batch
+    gather_common(strm_hdl, cache, noder, memorypool, *pipe, dev_id, -1, LEGION_NC_TOTAL, memorypool->num_ids); // every row of the batch
 }
 
 // ---- owner-computes exchange variant of the gather (SURVEY 5 option b), one process per GPU ---------------------------------
@@ -394,10 +412,11 @@ void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
 int legion_exchange_plan(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool, int32_t dev_id,
                          int32_t* req_row, int32_t* req_dst, int32_t* counts)
 {
-    if (!noder || !cache || !req_row || !req_dst || !counts || !pool_ready(memorypool, "legion_exchange_plan")) return -1;
+    const Pipe* pipe = noder && cache && req_row && req_dst && counts ? pool_ready(memorypool, "legion_exchange_plan") : nullptr;
+    if (!pipe) return -1;
     GPUMemoryPool* p = memorypool;
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, -1, LEGION_NC_TOTAL, false)) return -1;      // the hit counter belongs to the lookup pass of k_row_ptrs
+    if (!gather_args(g, cache, noder, p, *pipe, dev_id, -1, LEGION_NC_TOTAL, false)) return -1;      // the hit counter belongs to the lookup pass of k_row_ptrs
     if (!g.feat_map || !g.row_ptr || !p->cache_search_buffer) { LEGION_ARG_ERROR("legion_exchange_plan: needs a filled unified cache"); return -1; }
     launch_exchange_plan((hipStream_t)strm_hdl, g, dev_id % cache->Kg, cache->Kg, p->cache_search_buffer, counts, req_row, req_dst, p->num_ids);
     return error_pending() ? -1 : 0;
@@ -406,10 +425,11 @@ int legion_exchange_plan(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder,
 // have no source and are skipped -- legion_exchange_scatter fills them in.
 int legion_exchange_local(void* strm_hdl, GPUCache* cache, GPUNodeStorage* noder, GPUMemoryPool* memorypool, int32_t dev_id)
 {
-    if (!noder || !cache || !pool_ready(memorypool, "legion_exchange_local")) return -1;
+    const Pipe* pipe = noder && cache ? pool_ready(memorypool, "legion_exchange_local") : nullptr;
+    if (!pipe) return -1;
     GPUMemoryPool* p = memorypool;
     GatherArgs g;
-    if (!gather_args(g, cache, noder, p, dev_id, -1, LEGION_NC_TOTAL, false)) return -1;
+    if (!gather_args(g, cache, noder, p, *pipe, dev_id, -1, LEGION_NC_TOTAL, false)) return -1;
     if (!g.row_ptr) { LEGION_ARG_ERROR("legion_exchange_local: needs a filled unified cache"); return -1; }
     g.row_ptr_ready = true;   // k_exch_fill resolved the local rows (and left the peers' rows without a source)
     launch_gather((hipStream_t)strm_hdl, g, p->num_ids);
@@ -426,8 +446,9 @@ void legion_exchange_serve(void* strm_hdl, GPUCache* cache, int32_t dev_id, cons
 // Step 3 on the requester: rows[k] (as the owners returned them, in request order) -> feature row req_dst[k] of the current pipe.
 void legion_exchange_scatter(void* strm_hdl, GPUMemoryPool* memorypool, const float* rows, const int32_t* req_dst, int32_t n, int32_t F)
 {
-    if (!pool_ready(memorypool, "legion_exchange_scatter")) return;
-    float* dst = memorypool->float_features[memorypool->current_pipe];
+    const Pipe* pipe = pool_ready(memorypool, "legion_exchange_scatter");
+    if (!pipe) return;
+    float* dst = pipe->float_features;
     if (!dst || (n > 0 && (!rows || !req_dst))) { LEGION_ARG_ERROR("legion_exchange_scatter: bad arguments"); return; }
     launch_exchange_rows((hipStream_t)strm_hdl, true, nullptr, 0, req_dst, n, F, F, rows, dst, memorypool->feature_rows);
 }
@@ -437,12 +458,11 @@ void make_update_plan(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache, G
                       int32_t dev_id, int32_t mode)
 {
     (void)graph;
-    if (!pool_ready(memorypool, "make_update_plan")) return;
-    GPUMemoryPool* p = memorypool;
-    const int q = p->current_pipe;
+    const Pipe* pipe = pool_ready(memorypool, "make_update_plan");
+    if (!pipe) return;
     hipStream_t s = (hipStream_t)strm_hdl;
     if (mode == LEGION_TRAINMODE && cache) // CacheProfiling: HotnessMeasure during pre-sampling
-        GPUCache_CacheProfiling(cache, p->sampled_ids[q], p->node_counter[q], strm_hdl, dev_id);
+        GPUCache_CacheProfiling(cache, pipe->sampled_ids, pipe->node_counter, strm_hdl, dev_id);
     // ClearPosMap (Kernels.cu:780) needs no launch: the next batch starts a new table epoch.
     (void)s;
 }

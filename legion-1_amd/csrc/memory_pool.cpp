@@ -9,22 +9,14 @@
 
 using namespace legion;
 
-GPUMemoryPool::GPUMemoryPool(int32_t depth)
-{
-    pipeline_depth = depth > 0 ? depth : 1;
-    float_features.assign(pipeline_depth, nullptr);
-    labels.assign(pipeline_depth, nullptr);
-    node_counter.assign(pipeline_depth, nullptr);
-    edge_counter.assign(pipeline_depth, nullptr);
-    sampled_ids.assign(pipeline_depth, nullptr);
-    agg_src_off.assign(pipeline_depth, nullptr);
-    agg_dst_off.assign(pipeline_depth, nullptr);
-}
+GPUMemoryPool::GPUMemoryPool(int32_t depth) : pipeline_depth(depth > 0 ? depth : 1), pipes(pipeline_depth) {}
 
 // Every device scratch buffer the pool owns, in allocation order, with its size, its name, what an element of it is and how long what it holds
-// means anything (include/legion_amd.h: LEGION_SCRATCH_*; DESIGN.md "What the pool's scratch may hold between launches").
-// GPUMemoryPool_AllocateScratch allocates this list, release_scratch frees and forgets it and GPUMemoryPool_ScratchInfo reports it -- a
-// buffer named here is in all three.  Sized from V, num_ids, max_slots and max_tiles as they are now.
+// means anything (include/legion_amd.h: LEGION_SCRATCH_*; DESIGN.md "What the pool's scratch may hold between launches"): pool_scratch() for
+// what exists once, pool_pipe_buffers() behind it for what exists once per pipe (Pipe::own[]).  GPUMemoryPool_AllocateScratch and
+// alloc_mode_buffers allocate the two tables, release_scratch frees and forgets them, GPUMemoryPool_ScratchInfo reports them and
+// batch_generator_kernel audits their owner -- a buffer named here is in all of them, and a launcher asks for a pipe's buffer by its row
+// (pipe_holds, launchers.cpp).  Sized from V, num_ids, max_slots and max_tiles as they are now.
 //   hop:   written and read inside one GPU_Random_Sampling (k_sample, k_mark, k_write of one hop); dead once that call has returned.
 //          cand is read back by callers behind the batch (GPUMemoryPool_GetCandidateBuffer), never by a later launch.
 //   batch: carried from one op of a batch to a later one -- aux2[(h + 1) & 1] (the next hop's slot states, prepared by k_seed / k_write
@@ -35,9 +27,10 @@ GPUMemoryPool::GPUMemoryPool(int32_t depth)
 // The buffers of the edge-id mode (GPUMemoryPool_SetEdgeIds) join the list once the pool has been in that mode, behind the others of their
 // kind, and stay until the scratch is released: a pool that never saw the mode lists what it always listed.  cols (hop): k_sample's columns,
 // read by k_edge_ids of the same GPU_Random_Sampling.  edge_ids / edge_w (batch, per pipe): outputs no launch reads, the caller's behind the batch.
-static bool lists_edge_ids(const GPUMemoryPool* p) { return p->modes.edge_ids || p->cols || !p->edge_ids.empty(); }
-struct ScratchBuffer { void** slot; size_t bytes; const char* name; int32_t kind, elem_bytes, lifetime; };
-static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
+// "Has been in the mode", once: the mode is on, or cols is there -- the one allocation every switch on makes on a pool that owns scratch and
+// only release_scratch takes back.  (A pool without a device allocates nothing, so it lists the buffers exactly while the mode is on.)
+static bool lists_edge_ids(const GPUMemoryPool* p) { return p->modes.edge_ids || p->cols; }
+std::vector<ScratchBuffer> legion::pool_scratch(GPUMemoryPool* p)
 {
     const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots, tiles = (size_t)p->max_tiles + 1;
     constexpr int32_t I = sizeof(int32_t), hop = LEGION_SCRATCH_HOP, batch = LEGION_SCRATCH_BATCH;
@@ -58,46 +51,40 @@ static std::vector<ScratchBuffer> pool_scratch(GPUMemoryPool* p)
     if (lists_edge_ids(p)) all.push_back({(void**)&p->cols, slots * sizeof(int32_t), "cols", LEGION_SCRATCH_COUNT, I, hop});
     return all;
 }
-// The per-pipe buffers of the aggregated modes with their per-pipe sizes, named once in the same way: fn(buffers, bytes per pipe, wanted,
-// description -- a ScratchBuffer without a slot).  The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums,
-// agg_out_deg / agg_wdraw / agg_chunk_cnt; the edge-weighted sums want the last two of them.
-template <typename Fn>
-static void for_mode_buffers(GPUMemoryPool* p, Fn fn)
+// The buffers the pool owns once per pipe, named once in the same way: which Pipe::own[], bytes per pipe, whether the modes want it now, whether
+// it is listed, and its description.  The draw buffers of the aggregated last hop (cand_pipe) and, for the normalised sums, agg_out_deg /
+// agg_wdraw / agg_chunk_cnt; the edge-weighted sums want the last two of them.  A new per-pipe buffer is one row here (and its PipeBuf name).
+std::array<PipeBuffer, GPUMemoryPool::kPipeBufs> legion::pool_pipe_buffers(const GPUMemoryPool* p)
 {
-    const bool agg = p->modes.agg_last_hop, norm = agg && p->modes.agg_norm;
+    using Pool = GPUMemoryPool;
+    const bool agg = p->modes.agg_last_hop, norm = agg && p->modes.agg_norm, eid = p->modes.edge_ids, eid_listed = lists_edge_ids(p);
     const bool wdraw = norm || (agg && p->modes.agg_edge_weight);   // the edge-weighted sums rank their draws the same way, without the degrees
+    const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots;
     constexpr int32_t I = sizeof(int32_t), batch = LEGION_SCRATCH_BATCH;
-    fn(p->cand_pipe, (size_t)p->max_slots * sizeof(int32_t), agg, ScratchBuffer{nullptr, 0, "cand_pipe", LEGION_SCRATCH_ID, I, batch});
-    fn(p->agg_out_deg, (size_t)p->num_ids * sizeof(int32_t), norm, ScratchBuffer{nullptr, 0, "agg_out_deg", LEGION_SCRATCH_COUNT, I, batch});
-    fn(p->agg_wdraw, (size_t)p->max_slots * sizeof(float), wdraw, ScratchBuffer{nullptr, 0, "agg_wdraw", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
-    fn(p->agg_chunk_cnt, (size_t)kMaxChunks * sizeof(int32_t), wdraw, ScratchBuffer{nullptr, 0, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch});
-    if (!lists_edge_ids(p)) return;
-    // an edge id is one 8-byte word no kernel reads back: any bytes are safe in it, a pair of counts is what the poison's kinds offer
-    fn(p->edge_ids, (size_t)p->num_ids * sizeof(int64_t), p->modes.edge_ids, ScratchBuffer{nullptr, 0, "edge_ids", LEGION_SCRATCH_COUNT_PAIR, sizeof(int64_t), batch});
-    fn(p->edge_w, (size_t)p->num_ids * sizeof(float), p->modes.edge_ids, ScratchBuffer{nullptr, 0, "edge_w", LEGION_SCRATCH_FLOAT, sizeof(float), batch});
+    return {{{Pool::kCandPipe, slots * sizeof(int32_t), agg, true, "cand_pipe", LEGION_SCRATCH_ID, I, batch},
+             {Pool::kAggOutDeg, ids * sizeof(int32_t), norm, true, "agg_out_deg", LEGION_SCRATCH_COUNT, I, batch},
+             {Pool::kAggWdraw, slots * sizeof(float), wdraw, true, "agg_wdraw", LEGION_SCRATCH_FLOAT, sizeof(float), batch},
+             {Pool::kAggChunkCnt, (size_t)kMaxChunks * sizeof(int32_t), wdraw, true, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch},
+             // an edge id is one 8-byte word no kernel reads back: any bytes are safe in it, a pair of counts is what the poison's kinds offer
+             {Pool::kEdgeIds, ids * sizeof(int64_t), eid, eid_listed, "edge_ids", LEGION_SCRATCH_COUNT_PAIR, sizeof(int64_t), batch},
+             {Pool::kEdgeW, ids * sizeof(float), eid, eid_listed, "edge_w", LEGION_SCRATCH_FLOAT, sizeof(float), batch}}};
 }
 // on the current device: what the pool's modes want and is missing is allocated, what is there stays
 static void alloc_mode_buffers(GPUMemoryPool* p)
 {
     if (!p->owns_scratch) return;
-    for_mode_buffers(p, [&](auto& pipes, size_t bytes, bool wanted, const ScratchBuffer&) {
-        if (!wanted) return;
-        pipes.resize(p->pipeline_depth, nullptr);
-        for (auto& b : pipes)
-            if (!b) HIP_CHECK(hipMalloc(&b, bytes));
-    });
-    if (p->modes.edge_ids) {
-        if (!p->cols) HIP_CHECK(hipMalloc(&p->cols, (size_t)p->max_slots * sizeof(int32_t)));
-        p->edge_w_filled.resize(p->pipeline_depth, 0);
-    }
+    for (const PipeBuffer& b : pool_pipe_buffers(p))
+        for (GPUMemoryPool::Pipe& pipe : p->pipes)
+            if (b.wanted && !pipe.own[b.which]) HIP_CHECK(hipMalloc(&pipe.own[b.which], b.bytes));
+    if (p->modes.edge_ids && !p->cols) HIP_CHECK(hipMalloc(&p->cols, (size_t)p->max_slots * sizeof(int32_t)));
 }
 
 // ---- the releases: each kind of scratch has one, and GPUMemoryPool_Finalize calls them all ----
 static void release_scratch(GPUMemoryPool* p)
 {
     for (const ScratchBuffer& b : pool_scratch(p)) free_and_null(*b.slot);
-    for_mode_buffers(p, [](auto& pipes, size_t, bool, const ScratchBuffer&) { for (auto& b : pipes) free_and_null(b); });
-    p->edge_ids.clear(); p->edge_w.clear(); p->edge_w_filled.clear();   // with cols null again the pool lists them only while the mode is on
+    for (const PipeBuffer& b : pool_pipe_buffers(p))   // every row, listed or not: with cols null again the pool lists the edge-id rows only while the mode is on
+        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[b.which]); pipe.edge_w_filled = false; }
 }
 static void release_ctl(GPUMemoryPool* p) { free_and_null(p->ctl); }
 static void release_rows_seen(GPUMemoryPool* p)
@@ -212,13 +199,12 @@ int GPUMemoryPool_GetAggEdgeWeight(const GPUMemoryPool* p) { return p && p->mode
 int64_t* GPUMemoryPool_GetEdgeIdBuffer(const GPUMemoryPool* p)
 {
     if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeIdBuffer: null pool"); return nullptr; }
-    return p->current_pipe >= 0 && p->current_pipe < (int)p->edge_ids.size() ? p->edge_ids[p->current_pipe] : nullptr;
+    return p->pipe().buf<int64_t>(GPUMemoryPool::kEdgeIds);
 }
 float* GPUMemoryPool_GetEdgeWeightBuffer(const GPUMemoryPool* p)
 {
     if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeWeightBuffer: null pool"); return nullptr; }
-    const int q = p->current_pipe;
-    return q >= 0 && q < (int)p->edge_w.size() && q < (int)p->edge_w_filled.size() && p->edge_w_filled[q] ? p->edge_w[q] : nullptr;
+    return p->pipe().edge_w_filled ? p->pipe().buf<float>(GPUMemoryPool::kEdgeW) : nullptr;
 }
 void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {
@@ -246,8 +232,7 @@ int GPUMemoryPool_GetSampleSeed(const GPUMemoryPool* p, uint32_t* seed)
 // the current pipe's block out-degrees as the last normalised batch left them (int32[legion_batch_nodes(nc, H)]); null before the mode was set
 int32_t* GPUMemoryPool_GetAggOutDeg(const GPUMemoryPool* p)
 {
-    if (!p || p->current_pipe < 0 || p->current_pipe >= (int)p->agg_out_deg.size()) return nullptr;
-    return p->agg_out_deg[p->current_pipe];
+    return p ? p->pipe().buf<int32_t>(GPUMemoryPool::kAggOutDeg) : nullptr;
 }
 int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p) { return p ? (int32_t)p->round : 0; }
 
@@ -291,8 +276,8 @@ int GPUMemoryPool_BeginRound(void* stream, GPUMemoryPool* p, GPUNodeStorage* nod
 #define POOL_PIPE_SETTER(name, field, type) \
     void GPUMemoryPool_Set##name(GPUMemoryPool* p, type* ptr, int32_t pipe) { \
         if (pipe < 0 || pipe >= p->pipeline_depth) { LEGION_ARG_ERROR("GPUMemoryPool_Set" #name ": bad pipe"); return; } \
-        p->field[pipe] = ptr; } \
-    type* GPUMemoryPool_Get##name(const GPUMemoryPool* p) { return p->field[p->current_pipe]; }
+        p->pipes[pipe].field = ptr; } \
+    type* GPUMemoryPool_Get##name(const GPUMemoryPool* p) { return p->pipe().field; }
 POOL_PIPE_SETTER(SampledIds, sampled_ids, int32_t)
 POOL_PIPE_SETTER(FloatFeatures, float_features, float)
 POOL_PIPE_SETTER(Labels, labels, int32_t)
@@ -313,18 +298,17 @@ char* GPUMemoryPool_GetTmpPartIdx(const GPUMemoryPool* p) { return (char*)p->tmp
 int32_t* GPUMemoryPool_GetTmpPartOff(const GPUMemoryPool* p) { return p->tmp_part_off; }
 uint64_t* GPUMemoryPool_GetPositionMap(const GPUMemoryPool* p) { return (uint64_t*)p->pos_map; }
 int32_t* GPUMemoryPool_GetCandidateBuffer(const GPUMemoryPool* p) { return p->cand; }
-// The list of pool_scratch() and for_mode_buffers(), then ctl, one entry per call: 0 and *out filled, 1 past the end of the list, -1
+// The list of pool_scratch() and the listed rows of pool_pipe_buffers(), then ctl, one entry per call: 0 and *out filled, 1 past the end of the list, -1
 // (sticky error) for a null argument or a pipe the pool does not have.  Reads host state only: no device call, nothing changes.
 int GPUMemoryPool_ScratchInfo(const GPUMemoryPool* pool, int32_t index, int32_t pipe, LegionScratchInfo* out)
 {
     if (!pool || !out) { LEGION_ARG_ERROR("GPUMemoryPool_ScratchInfo: null argument"); return -1; }
     if (index < 0 || pipe < 0 || pipe >= pool->pipeline_depth) { LEGION_ARG_ERROR("GPUMemoryPool_ScratchInfo: bad index or pipe"); return -1; }
-    GPUMemoryPool* p = const_cast<GPUMemoryPool*>(pool);   // the two lists take the pool they allocate into; nothing is written through it here
+    GPUMemoryPool* p = const_cast<GPUMemoryPool*>(pool);   // pool_scratch takes the pool it allocates into; nothing is written through it here
     std::vector<LegionScratchInfo> all;
     for (const ScratchBuffer& b : pool_scratch(p)) all.push_back({b.name, *b.slot, (int64_t)b.bytes, b.kind, b.elem_bytes, b.lifetime, 0});
-    for_mode_buffers(p, [&](auto& pipes, size_t bytes, bool, const ScratchBuffer& b) {
-        all.push_back({b.name, pipe < (int)pipes.size() ? (void*)pipes[pipe] : nullptr, (int64_t)bytes, b.kind, b.elem_bytes, b.lifetime, 1});
-    });
+    for (const PipeBuffer& b : pool_pipe_buffers(p))
+        if (b.listed) all.push_back({b.name, p->pipes[pipe].own[b.which], (int64_t)b.bytes, b.kind, b.elem_bytes, b.lifetime, 1});
     all.push_back({"ctl", p->ctl, (int64_t)sizeof(BatchCtl), LEGION_SCRATCH_COUNT, (int32_t)sizeof(int32_t), LEGION_SCRATCH_STATE, 0});
     if (index >= (int32_t)all.size()) return 1;
     *out = all[index];

@@ -346,8 +346,8 @@ void Runner_RunPreSc(Runner* r, RunnerParams* params)
     if (r->modes.agg_last_hop) {   // ... except that sizing the buffer for max(n_in + N) needs both counter arrays of every batch
         int32_t nc[LEGION_COUNTER_WORDS] = {0}, ec[LEGION_COUNTER_WORDS] = {0};
         HIP_CHECK(hipStreamSynchronize(r->streams[0]));
-        HIP_CHECK(hipMemcpy(nc, r->memorypool->node_counter[r->memorypool->current_pipe], sizeof(nc), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(ec, r->memorypool->edge_counter[r->memorypool->current_pipe], sizeof(ec), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(nc, r->memorypool->pipe().node_counter, sizeof(nc), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ec, r->memorypool->pipe().edge_counter, sizeof(ec), hipMemcpyDeviceToHost));
         r->presc_max_rows = std::max(r->presc_max_rows, legion_agg_rows(nc, ec, r->hops));
     }
 }

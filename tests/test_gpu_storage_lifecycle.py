@@ -204,7 +204,10 @@ def test_build_and_close_cycles_leave_the_device_memory_where_it_was(K):
     """V = 2^20, F = 4, 4 edges per node, tables in pinned host memory: indptr 8 MiB, indices 16 MiB, features 16 MiB (their replica, at
     the line-aligned pitch of 32 floats, 128 MiB), position table 8 MiB, alias table 32 MiB, retained weights 16 MiB.  A single one of
     them leaked once per cycle costs >= 3 x 8 MiB over the three measured cycles; the bound is 4 MiB (allocator granularity and the
-    runtime's own pools are far below it)."""
+    runtime's own pools are far below it).  The cycle then runs once more inside the measured window with the aggregated last hop, the
+    norm and edge ids on, on a pool of 2 048 x [32, 32] (2 097 152 slots, 2 164 736 ids; the 64 seeds make a small batch of it): cand_pipe,
+    agg_out_deg, agg_wdraw and edge_w are 8 MiB and more per pipe, edge_ids 16 MiB and cols 8 MiB, so that one of them leaked in that one
+    cycle is above the same bound (agg_chunk_cnt, 8 KiB, is below it: the list tests of tests/test_gpu_pool_pipes.py see it go)."""
     import torch
     L = K.lib()
     V, F, D = 1 << 20, 4, 4
@@ -216,25 +219,31 @@ def test_build_and_close_cycles_leave_the_device_memory_where_it_was(K):
     seeds = np.arange(64, dtype=np.int32)
     labels = np.zeros(64, np.int32)
 
-    def cycle():
-        eng = make_engine(K, (V, F, indptr, indices, feats), 32, [3, 2], seeds=dict(train=[(seeds, labels)]), retain_edge_weights=True,
+    def cycle(B=32, fan=(3, 2), **modes):
+        eng = make_engine(K, (V, F, indptr, indices, feats), B, list(fan), seeds=dict(train=[(seeds, labels)]), retain_edge_weights=True,
                           csr_location=K.LOC_HOST_PINNED, features_location=K.LOC_HOST_PINNED)
         assert L.GPUGraphStorage_ReplicateToDevices(eng.graph) == (V + 1) * 8 + V * D * 4
         assert L.GPUNodeStorage_ReplicateToDevices(eng.noder) == V * L.legion_row_pitch(F) * 4
         eng.set_edge_weights(w)
-        eng.run_batch(0, 0, sample="weighted", weighted_distinct=True)
+        eng.run_batch(0, 0, sample="weighted", weighted_distinct=True, **modes)
         assert layout.batch_edges(eng.result(0)["ec"], 2) > 0
+        if modes:
+            assert {b["name"]: b["bytes"] for b in K.pool_scratch(eng.pools[0]) if b["per_pipe"] and b["ptr"]} == dict(
+                cand_pipe=8 << 20, agg_out_deg=2164736 * 4, agg_wdraw=8 << 20, agg_chunk_cnt=8192, edge_ids=2164736 * 8, edge_w=2164736 * 4)
         eng.close()
         K.check()
 
+    modes = dict(B=2048, fan=(32, 32), agg_last_hop=True, agg_norm="both", edge_ids=True)
     cycle()      # warm-up: whatever the runtime keeps for itself it has now
+    cycle(**modes)
     L.SetGPUDevice(0)
     L.d_stream_sync(None)
     free_before = torch.cuda.mem_get_info(0)[0]
     for _ in range(3):
         cycle()
+    cycle(**modes)
     L.SetGPUDevice(0)
     L.d_stream_sync(None)
     free_after = torch.cuda.mem_get_info(0)[0]
-    print("free device memory: %d bytes before, %d after three cycles (%d lost)" % (free_before, free_after, free_before - free_after))
+    print("free device memory: %d bytes before, %d after four cycles (%d lost)" % (free_before, free_after, free_before - free_after))
     assert free_before - free_after <= 4 << 20, (free_before, free_after)

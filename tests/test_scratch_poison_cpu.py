@@ -1,10 +1,12 @@
-"""tests/scratchpoison.py held to its rules for every kind, GPUMemoryPool_ScratchInfo's list against a literal copy, and the near-tie cap
+"""tests/scratchpoison.py held to its rules for every kind, GPUMemoryPool_ScratchInfo's list against a literal copy (fresh, and through the
+modes' life cycle of tests/poolpipes.py), and the near-tie cap
 of zero rows on the exact batches tests/test_gpu_scratch_poison.py compares for the two weighted rules without replacement.  No device."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import poolpipes as W
 import scratchpoison as P
 import wsharedcases
 
@@ -37,6 +39,79 @@ def test_the_enumerator_lists_every_buffer_with_a_lifetime():
             assert L.GPUMemoryPool_ScratchInfo(*args) == -1
             assert b"GPUMemoryPool_ScratchInfo" in (L.legion_last_error() or b"")
             L.legion_clear_error()
+    finally:
+        L.legion_clear_error()
+        L.GPUMemoryPool_Delete(pool)
+
+
+# GPUMemoryPool_ScratchInfo's list of a pool that never saw a device, with its bytes (V, num_ids, max_slots and max_tiles are all 0), recorded
+# from the library before the per-pipe buffers became one table: while the edge-id mode is off ...
+LISTED = [
+    ("pos_map", "table_entry", 8, "table", False, 0),
+    ("cand", "id", 4, "hop", False, 0),
+    ("aux2[0]", "slot_state", 4, "batch", False, 0),
+    ("aux2[1]", "slot_state", 4, "batch", False, 0),
+    ("tile_edge", "count", 4, "hop", False, 4),
+    ("tile_node", "count", 4, "hop", False, 4),
+    ("tile_pre", "count_pair", 8, "hop", False, 8),
+    ("chunk_tot", "count_pair", 8, "hop", False, 16384),
+    ("hop_state", "count", 4, "hop", False, 32),
+    ("cache_search_buffer", "id", 4, "batch", False, 0),
+    ("row_ptr", "device_pointer", 8, "batch", False, 0),
+    ("agg_src_ids", "id", 4, "batch", False, 0),
+    ("tmp_part_ind", "id", 1, "batch", False, 0),
+    ("tmp_part_off", "id", 4, "batch", False, 0),
+    ("cand_pipe", "id", 4, "batch", True, 0),
+    ("agg_out_deg", "count", 4, "batch", True, 0),
+    ("agg_wdraw", "float", 4, "batch", True, 0),
+    ("agg_chunk_cnt", "count", 4, "batch", True, 8192),
+    ("ctl", "count", 4, "state", False, 20),
+]
+# ... and while it is on: cols behind tmp_part_off, edge_ids and edge_w behind agg_chunk_cnt
+LISTED_EDGE_IDS = [
+    ("pos_map", "table_entry", 8, "table", False, 0),
+    ("cand", "id", 4, "hop", False, 0),
+    ("aux2[0]", "slot_state", 4, "batch", False, 0),
+    ("aux2[1]", "slot_state", 4, "batch", False, 0),
+    ("tile_edge", "count", 4, "hop", False, 4),
+    ("tile_node", "count", 4, "hop", False, 4),
+    ("tile_pre", "count_pair", 8, "hop", False, 8),
+    ("chunk_tot", "count_pair", 8, "hop", False, 16384),
+    ("hop_state", "count", 4, "hop", False, 32),
+    ("cache_search_buffer", "id", 4, "batch", False, 0),
+    ("row_ptr", "device_pointer", 8, "batch", False, 0),
+    ("agg_src_ids", "id", 4, "batch", False, 0),
+    ("tmp_part_ind", "id", 1, "batch", False, 0),
+    ("tmp_part_off", "id", 4, "batch", False, 0),
+    ("cols", "count", 4, "hop", False, 0),
+    ("cand_pipe", "id", 4, "batch", True, 0),
+    ("agg_out_deg", "count", 4, "batch", True, 0),
+    ("agg_wdraw", "float", 4, "batch", True, 0),
+    ("agg_chunk_cnt", "count", 4, "batch", True, 8192),
+    ("edge_ids", "count_pair", 8, "batch", True, 0),
+    ("edge_w", "float", 4, "batch", True, 0),
+    ("ctl", "count", 4, "state", False, 20),
+]
+LISTED_AT = {"fresh": LISTED, "edge ids on": LISTED_EDGE_IDS, "edge ids off": LISTED, "aggregated last hop": LISTED, "norm": LISTED,
+             "edge-weighted sums": LISTED_EDGE_IDS, "everything off": LISTED}
+
+
+def test_the_list_through_the_modes_life_cycle_without_a_device():
+    """A pool of depth 2 that never saw a device allocates nothing, whatever mode is set: every pointer stays null, and the list is the literal
+    table except while the edge-id mode is on -- without cols there is nothing that remembers the mode once it is off again.  No setter
+    leaves an error (poolpipes.walk asserts it behind each)."""
+    import legion1_amd.capi as K
+    L = K.lib()
+    L.legion_set_error_mode(K.ERR_RETURN)
+    assert [t[:5] for t in LISTED] == P.EXPECTED_TABLE and [s[0] for s in W.STEPS] == list(LISTED_AT)
+    pool = L.NewGPUMemoryPool(2)
+    try:
+        for step in W.walk(K, pool):
+            for pipe in (0, 1):
+                rows, ptrs = W.listed(K, pool, pipe)
+                assert rows == LISTED_AT[step], (step, pipe)
+                assert all(v is None for v in ptrs.values()), (step, pipe, ptrs)
+            assert not L.legion_last_error()
     finally:
         L.legion_clear_error()
         L.GPUMemoryPool_Delete(pool)
