@@ -110,6 +110,37 @@ class GraphConvBothFused(GraphConvBoth):
         return self.fc(agg * in_deg.rsqrt().unsqueeze(1))
 
 
+class GraphConvEdgeWeight(nn.Module):
+    """DGL GraphConv(norm='none', allow_zero_in_degree=True) with edge_weight=w, PyG GCNConv(normalize=False) with edge_weight:
+    h_dst = (sum_{e = (s,d)} w_e h_s) W + b.  block = (src, dst, num_src, num_dst, w), w[e] the weight of COO edge e as the server hands
+    it over (LEGION_EDGE_IDS=1 LEGION_EDGE_WEIGHTS=1, ipc_service.get_edge_weights(); INTEGRATION.md "Edge ids"); duplicate edges count twice."""
+
+    def __init__(self, in_feats, out_feats):
+        super().__init__()
+        self.fc = nn.Linear(in_feats, out_feats, bias=True)
+
+    def forward(self, block, h):
+        src, dst, num_src, num_dst, w = block
+        assert h.shape[0] == num_src and w.shape[0] == src.shape[0]
+        m = h.index_select(0, src) * w.to(h.dtype).unsqueeze(1)
+        return self.fc(torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, dst, m))
+
+
+class GraphConvEdgeWeightFused(GraphConvEdgeWeight):
+    """First layer behind a server that hands the last hop over as edge-weighted neighbour sums (LEGION_AGG_EDGE_WEIGHT=1,
+    ipc_service.get_next_aggregated_edge_weight; INTEGRATION.md "Edge-weighted sums").  h = x_in[n_in, F].  The edges of the hops < H (the
+    first e_in of block 1) are scaled by their served weights and aggregated as GraphConvEdgeWeight does; the last hop arrives as one row
+    per input slot, sum_e w_e x[src_e], to be added into node run_dst[i].  Same parameters, same result up to fp32 summation order."""
+
+    def forward(self, block, h):
+        src, dst, num_src, num_dst, e_in, run_dst, nbr_sum, w = block
+        assert h.shape[0] == num_dst
+        m = h.index_select(0, src[:e_in]) * w[:e_in].to(h.dtype).unsqueeze(1)
+        agg = torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, dst[:e_in], m)
+        agg += torch.zeros(num_dst, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, run_dst, nbr_sum)
+        return self.fc(agg)
+
+
 class SAGE(nn.Module):
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, conv=SageMean, first=None):
         super().__init__()
@@ -126,18 +157,25 @@ class SAGE(nn.Module):
         return h
 
 
-def getter(ipc_service, aggregated, norm):
-    """the ipc_service call for the server's hand-off mode: rows, neighbour sums, or out-degree-normalised neighbour sums"""
+def getter(ipc_service, aggregated, norm, edge_weight=False):
+    """the ipc_service call for the server's hand-off mode: rows, neighbour sums, or the sums normalised by out-degree or scaled by edge weight"""
+    if aggregated and edge_weight:
+        return ipc_service.get_next_aggregated_edge_weight
     return ipc_service.get_next_aggregated_norm if aggregated and norm else ipc_service.get_next_aggregated if aggregated else ipc_service.get_next
 
 
-def next_batch(ipc_service, feat_len, hops, aggregated=False, norm=0):
-    out = getter(ipc_service, aggregated, norm)(feat_len)   # zero-copy views of server-owned device memory
+def next_batch(ipc_service, feat_len, hops, aggregated=False, norm=0, edge_weight=False):
+    """edge_weight: every block carries its edges' served weights (ipc_service.get_edge_weights(): block k's is a view of the same length
+    as its src / dst); behind an aggregating server block 1 takes the served edge-weighted sums for the last hop."""
+    out = getter(ipc_service, aggregated, norm, edge_weight)(feat_len)   # zero-copy views of server-owned device memory
     sizes = ipc_service.get_block_size()
     features, labels = out[1], out[2]
     blocks = [(out[3 + 2 * k].long(), out[4 + 2 * k].long(), sizes[2 * k], sizes[2 * k + 1]) for k in range(hops)]
+    edges = [len(b[0]) for b in blocks]
     if aggregated:                                  # features = x_in[n_in, F]; out[-1] = the last hop's neighbour sums per input slot
-        blocks[0] = fused_first_block(*blocks[0], [len(b[0]) for b in blocks], out[3 + 2 * hops])
+        blocks[0] = fused_first_block(*blocks[0], edges, out[3 + 2 * hops])
+    if edge_weight:
+        blocks = [b + (w,) for b, w in zip(blocks, ipc_service.get_edge_weights())]
     return features, labels.long(), blocks
 
 
@@ -162,13 +200,22 @@ def worker(rank, world, args):
     if served_agg != bool(args.aggregated):
         raise SystemExit("--aggregated must match the server: it %s the last hop (LEGION_AGG_LAST_HOP)" % ("aggregates" if served_agg else "does not aggregate"))
     served_norm = int(ipc_service.aggregate_norm()) if hasattr(ipc_service, "aggregate_norm") else 0
-    if served_agg and (served_norm != 0) != (args.model == "gcn"):      # the sums must be the ones the first layer adds up
+    if served_agg and not args.edge_weight and (served_norm != 0) != (args.model == "gcn"):      # the sums must be the ones the first layer adds up
         raise SystemExit("--model %s --aggregated needs a server that %s the neighbour sums (LEGION_AGG_NORM%s): GraphConvBoth adds rows scaled by "
                          "out-degree^-1/2, SageMean the rows themselves" % (args.model, "normalises" if args.model == "gcn" else "does not normalise",
                                                                           "=both" if args.model == "gcn" else " unset"))
     fused = (GraphConvBothFused if args.model == "gcn" else SageMeanFused) if served_agg else None
-    model = SAGE(args.features_num, args.hidden_dim, args.class_num, hops, args.drop_rate,
-                 conv=GraphConvBoth if args.model == "gcn" else SageMean, first=fused).to(device)
+    conv = GraphConvBoth if args.model == "gcn" else SageMean
+    served_ew = bool(ipc_service.aggregate_edge_weight()) if hasattr(ipc_service, "aggregate_edge_weight") else False
+    if args.edge_weight:                 # sum_e w_e h[src_e] per dst: the weights of blocks 2..H are the served edge_w, block 1 takes the served sums
+        if not (hasattr(ipc_service, "edge_weights") and ipc_service.edge_weights()):
+            raise SystemExit("--edge_weight needs a server that serves edge weights (LEGION_EDGE_IDS=1 LEGION_EDGE_WEIGHTS=1)")
+        if served_agg and not served_ew:
+            raise SystemExit("--edge_weight --aggregated needs a server whose neighbour sums are scaled by edge weight (LEGION_AGG_EDGE_WEIGHT=1)")
+        conv, fused = GraphConvEdgeWeight, GraphConvEdgeWeightFused if served_agg else None
+    elif served_ew:
+        raise SystemExit("the server scales its neighbour sums by edge weight (LEGION_AGG_EDGE_WEIGHT=1): run with --edge_weight --aggregated")
+    model = SAGE(args.features_num, args.hidden_dim, args.class_num, hops, args.drop_rate, conv=conv, first=fused).to(device)
     if world > 1:
         model = DDP(model, device_ids=[rank])
     opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate)
@@ -179,7 +226,7 @@ def worker(rank, world, args):
         model.eval()
         with torch.no_grad():
             for _ in range(steps):
-                x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg, served_norm)
+                x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg, served_norm, args.edge_weight)
                 ok = y >= 0                                  # -1 padded seeds of a short batch
                 pred = model(blocks, x).argmax(1)
                 hit += int((pred[ok] == y[ok]).sum())
@@ -194,7 +241,7 @@ def worker(rank, world, args):
 
     def drain(steps):
         for _ in range(steps):
-            getter(ipc_service, served_agg, served_norm)(args.features_num)
+            getter(ipc_service, served_agg, served_norm, args.edge_weight)(args.features_num)
             ipc_service.synchronize()
         return float("nan")
 
@@ -208,7 +255,7 @@ def worker(rank, world, args):
         model.train()
         t0, last = time.time(), float("nan")
         for _ in range(train_steps):
-            x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg, served_norm)
+            x, y, blocks = next_batch(ipc_service, args.features_num, hops, served_agg, served_norm, args.edge_weight)
             loss = lp_loss(model(blocks, x)) if args.task == "lp" else loss_fn(model(blocks, x), y)
             opt.zero_grad()
             loss.backward()
@@ -242,6 +289,9 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed (weights, dropout)")
     ap.add_argument("--aggregated", action="store_true", help="the server runs with LEGION_AGG_LAST_HOP=1: first layer = SageMeanFused over get_next_aggregated; "
                                                               "with --model gcn the server also runs with LEGION_AGG_NORM=both: GraphConvBothFused over get_next_aggregated_norm")
+    ap.add_argument("--edge_weight", action="store_true", help="the server runs with LEGION_EDGE_IDS=1 LEGION_EDGE_WEIGHTS=1: every layer is GraphConvEdgeWeight "
+                                                               "(sum_e w_e h[src_e] per dst) over get_edge_weights(); with --aggregated the server also runs with "
+                                                               "LEGION_AGG_EDGE_WEIGHT=1: first layer = GraphConvEdgeWeightFused over get_next_aggregated_edge_weight")
     a = ap.parse_args()
     if a.gpu_num == 1:
         worker(0, 1, a)

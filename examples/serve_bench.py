@@ -2,6 +2,7 @@
 """Throughput of the `legion` server process as a trainer sees it: a null consumer (wait -> read counters -> post), or with
 --consumer aggregate a PyTorch consumer that computes the first layer's mean aggregate in both hand-off modes (rows / neighbour sums),
 --consumer aggregate-gcn the same for GraphConv(norm='both')'s first-layer aggregate (rows / out-degree-normalised neighbour sums),
+--consumer edges a PyTorch consumer that reads block 1's COO and, where the server serves them, its edge ids and weights,
 drains every batch of the schedule through the C-ABI IPC client, for the two RunOnce variants of the runner:
 
     (default)                  enqueue batch i, then wait for batch i-1 and post it (sampler i || gathers i-1)
@@ -9,6 +10,8 @@ drains every batch of the schedule through the C-ABI IPC client, for the two Run
 (the reference's synchronous loop and the whole-batch graphs lost at every shape: profiles/r01_server_loop.md, r04_graph_trace.md)
 
     python examples/serve_bench.py [--workload products --scale 0.3 --batch 8000 --fanout 25,10 --epochs 3]
+--edge-ids serves every variant three times -- as it is, with LEGION_EDGE_IDS=1, with LEGION_EDGE_IDS=1 LEGION_EDGE_WEIGHTS=1 -- for the cost
+of the served edge buffers (profiles/served_edges.md), under the null consumer or --consumer edges.
 """
 import argparse
 import ctypes as C
@@ -124,6 +127,37 @@ def consume_aggregating_gcn(epochs, feat_dim):
     print(total, dt, edges)
 
 
+def consume_edges(epochs, feat_dim):
+    """A consumer that reads every edge of block 1 once: the sums of src and dst in every mode and, where the server serves them
+    (LEGION_EDGE_IDS=1, LEGION_EDGE_WEIGHTS=1), of the edge ids and the edge weights -- one pass over each served buffer per batch."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "legion-1_amd", "ipc_service"))
+    import ipc_service
+    torch.cuda.set_device(0)
+    ipc_service.initialize()
+    steps = ipc_service.get_steps()
+    ids_on, w_on = ipc_service.edge_ids(), ipc_service.edge_weights()
+    total = (steps[0] + steps[1]) * epochs + steps[2]
+    edges = 0
+    acc = torch.zeros(4, dtype=torch.float64, device="cuda")
+    t0 = time.perf_counter()
+    for _ in range(total):
+        out = ipc_service.get_next(feat_dim)
+        acc[0] += out[3].sum()
+        acc[1] += out[4].sum()
+        if ids_on:
+            acc[2] += ipc_service.get_edge_ids()[0].sum()
+        if w_on:
+            acc[3] += ipc_service.get_edge_weights()[0].sum()
+        edges += int(out[3].numel())
+        torch.cuda.synchronize()
+        ipc_service.synchronize()
+    dt = time.perf_counter() - t0
+    ipc_service.finalize()
+    print("sums of src, dst, edge ids, edge weights: %s (edge ids %s, weights %s)" % (acc.tolist(), "served" if ids_on else "off", "served" if w_on else "off"))
+    print(total, dt, edges)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--consume", type=int, default=0, help="internal: run the null consumer for this many epochs")
@@ -133,10 +167,12 @@ def main():
     ap.add_argument("--fanout", default="25,10")
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--variants", default="all", help="comma list of: pipelined,graph + gather")
-    ap.add_argument("--consumer", default="null", choices=["null", "aggregate", "aggregate-gcn"],
+    ap.add_argument("--consumer", default="null", choices=["null", "aggregate", "aggregate-gcn", "edges"],
                     help="null: wait -> read counters -> post.  aggregate: a PyTorch consumer that computes the first layer's mean aggregate [n_in, F] "
                          "of every batch; each variant is then served twice, default hand-off and LEGION_AGG_LAST_HOP=1.  aggregate-gcn: the same for "
                          "GraphConv(norm='both')'s aggregate, default hand-off and LEGION_AGG_LAST_HOP=1 LEGION_AGG_NORM=both")
+    ap.add_argument("--edge-ids", action="store_true", help="serve every variant three times: as it is, with LEGION_EDGE_IDS=1, and with LEGION_EDGE_IDS=1 "
+                    "LEGION_EDGE_WEIGHTS=1 (consumers null and edges; --source files gets an edge_weights file of the synth: source's weights)")
     ap.add_argument("--features", type=int, default=0, help="internal: feature width for --consume with --consumer aggregate")
     ap.add_argument("--full-eval", action="store_true", help="keep the full validation / test sets (512-seed batches)")
     ap.add_argument("--source", default="files", choices=["files", "synth"],
@@ -146,6 +182,8 @@ def main():
     if a.consume:
         if a.consumer == "aggregate-gcn":
             return consume_aggregating_gcn(a.consume, a.features)
+        if a.consumer == "edges":
+            return consume_edges(a.consume, a.features)
         return consume_aggregating(a.consume, a.features) if a.consumer == "aggregate" else consume(a.consume, len(a.fanout.split(",")))
     import legion1_amd.synth as S
     if a.source == "synth":
@@ -165,6 +203,8 @@ def main():
     tmp = tempfile.mkdtemp(prefix="legion_serve_")
     data = os.path.join(tmp, "ds") + "/"
     S.write_legion_files(ds, data)
+    if a.edge_ids:
+        S.edge_weights(ds.E).astype("<f4").tofile(os.path.join(data, "edge_weights"))
     meta = os.path.join(tmp, "meta_config")
     with open(meta, "w") as f:
         f.write(S.meta_config_line(ds, data, a.batch, 1 << 40, a.epochs, 0))
@@ -180,8 +220,11 @@ def serve_variants(a, tmp, meta, F):
         variants = [(n + m, dict(e, **x)) for n, e in variants for m, x in ((", rows", {}), (", neighbour sums", {"LEGION_AGG_LAST_HOP": "1"}))]
     if a.consumer == "aggregate-gcn":
         variants = [(n + m, dict(e, **x)) for n, e in variants for m, x in ((", rows", {}), (", normalised sums", {"LEGION_AGG_LAST_HOP": "1", "LEGION_AGG_NORM": "both"}))]
+    if a.edge_ids:                   # every variant with the mode off, with the ids, with ids and weights, alternating
+        variants = [(n + m, dict(e, **x)) for n, e in variants for m, x in ((", edge ids off", {}), (", edge ids", {"LEGION_EDGE_IDS": "1"}),
+                                                                            (", edge ids + weights", {"LEGION_EDGE_IDS": "1", "LEGION_EDGE_WEIGHTS": "1"}))]
     for name, extra in variants:
-        ns = "sb%d_%s%s%s_" % (os.getpid(), name[:3], extra.get("LEGION_BATCH_GRAPH", ""), extra.get("LEGION_AGG_LAST_HOP", ""))
+        ns = "sb%d_%s%s%s%s%s_" % (os.getpid(), name[:3], extra.get("LEGION_BATCH_GRAPH", ""), extra.get("LEGION_AGG_LAST_HOP", ""), extra.get("LEGION_EDGE_IDS", ""), extra.get("LEGION_EDGE_WEIGHTS", ""))
         env = dict(os.environ, LEGION_IPC_NAMESPACE=ns, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra)
         log = open(os.path.join(tmp, "server_%s.log" % name[:3]), "w")
         proc = subprocess.Popen([server, "1", "0", a.fanout, meta], stdout=log, stderr=subprocess.STDOUT, env=env, cwd=tmp)

@@ -645,6 +645,29 @@ int32_t IPCEnv_GetSampling(const IPCEnv* e);
  * server without the words reads "off". */
 void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed);
 int32_t IPCEnv_GetSamplingSeed(const IPCEnv* e, uint32_t* seed);
+/* The words that no longer fit the "<name>_ext" object live in a third one, "<name>_ext2" (DESIGN.md 3.15), which a server creates only
+ * when one of them is on: the first setter of a word that is ON creates the object, a 0 on an env without it creates nothing, and a
+ * client of a server without the object reads 0 in every word.  LpDraw: k, the triples per batch the server draws (LEGION_LP_DRAW=1; 0 =
+ * off).  WeightedDistinct / SharedDraws: LEGION_WEIGHTED_DISTINCT / LEGION_SHARED_DRAWS.  EdgeIds: every sampled edge's CSR position is
+ * served (LEGION_EDGE_IDS=1).  EdgeWeights: edge_w is filled, the graph retains its weights (LEGION_EDGE_WEIGHTS=1, or weighted-distinct
+ * sampling).  AggEdgeWeight: the last hop's sums are scaled by each edge's weight (LEGION_AGG_EDGE_WEIGHT=1). */
+void IPCEnv_SetLpDraw(IPCEnv* e, int32_t triples_per_batch);
+int32_t IPCEnv_GetLpDraw(const IPCEnv* e);
+void IPCEnv_SetWeightedDistinct(IPCEnv* e, int32_t on);
+int32_t IPCEnv_GetWeightedDistinct(const IPCEnv* e);
+void IPCEnv_SetSharedDraws(IPCEnv* e, int32_t on);
+int32_t IPCEnv_GetSharedDraws(const IPCEnv* e);
+void IPCEnv_SetEdgeIds(IPCEnv* e, int32_t on);
+int32_t IPCEnv_GetEdgeIds(const IPCEnv* e);
+void IPCEnv_SetEdgeWeights(IPCEnv* e, int32_t on);
+int32_t IPCEnv_GetEdgeWeights(const IPCEnv* e);
+void IPCEnv_SetAggEdgeWeight(IPCEnv* e, int32_t on);
+int32_t IPCEnv_GetAggEdgeWeight(const IPCEnv* e);
+/* Export the edge buffers of (device, pipe) -- the memory pool's, which stays their owner (GPUMemoryPool_GetEdgeIdBuffer /
+ * GPUMemoryPool_GetEdgeWeightBuffer's) -- to the trainers of that device: their IPC handles go into "<name>_ext2", `elems` (elements each
+ * holds, GPUMemoryPool_NumIds) into its edge_elems word.  A buffer above the HIP-IPC size limit is refused by name. */
+void IPCEnv_RegisterEdgeBuffers(IPCEnv* e, int32_t device_id, int32_t pipe, int64_t* ids, float* w, int32_t elems);
+int32_t IPCEnv_GetEdgeElems(const IPCEnv* e, int32_t device_id);
 int IPCEnv_SlabPinned(IPCEnv* e);   /* 1: the slab is page-locked (hipHostRegister), IPCEnv_MirrorCounters queues real asynchronous copies */
 void IPCEnv_IPCPost(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
 void IPCEnv_IPCWait(IPCEnv* e, int32_t dev_id, int32_t current_pipe);
@@ -660,7 +683,7 @@ void IPCEnv_SetHops(IPCEnv* e, int32_t hops);
 /* Namespace for the POSIX shm / semaphore names ("" = the reference's literal names
  * "simpleIPCshm", "sem_r_D_P", "sem_w_D_P").  Also read from $LEGION_IPC_NAMESPACE. */
 void legion_ipc_set_namespace(const char* ns);
-/* Remove what a KILLED server of namespace `ns` left in /dev/shm -- the slab, its extension object, the 2 x depth named semaphores of
+/* Remove what a KILLED server of namespace `ns` left in /dev/shm -- the slab, its extension objects (_ext, _ext2), the 2 x depth named semaphores of
  * each of `devices` GPUs (the reference only unlinks in Finalize, CUDA_IPC_Service.cu:319-320).  Harmless when nothing is there. */
 void legion_ipc_unlink_namespace(const char* ns, int32_t devices);
 
@@ -689,6 +712,17 @@ int32_t legion_ipc_client_agg_norm(LegionIPCClient* c);
  * non-zero only and reports a weighted server as "distinct".) */
 int32_t legion_ipc_client_sampling(LegionIPCClient* c);
 int32_t legion_ipc_client_sampling_seed(LegionIPCClient* c, uint32_t* seed);
+/* the words of the server's "<name>_ext2" object (IPCEnv_SetLpDraw ...); 0 when the server has none */
+int32_t legion_ipc_client_lp_draw(LegionIPCClient* c);
+int32_t legion_ipc_client_weighted_distinct(LegionIPCClient* c);
+int32_t legion_ipc_client_shared_draws(LegionIPCClient* c);
+int32_t legion_ipc_client_edge_ids(LegionIPCClient* c);
+int32_t legion_ipc_client_edge_weights(LegionIPCClient* c);
+int32_t legion_ipc_client_agg_edge_weight(LegionIPCClient* c);
+/* The edge buffers of the current pipe: which = 0, int64 edge ids (each COO edge's position in the whole CSR), which = 1, float32 edge
+ * weights; both in the order of the pipe's COO.  NULL when the server does not serve them (which = 1: when its edge_weights word is 0). */
+void* legion_ipc_client_edge_buffer(LegionIPCClient* c, int32_t which);
+int32_t legion_ipc_client_edge_elems(LegionIPCClient* c);     /* elements each edge buffer of this device holds; 0 = none */
 /* both counter arrays of the current pipe (legion_batch_layout.h draws them word by word) (ipc_cuda_kernel.cu:195-196): from the server's host mirror when it maintains one, else by
  * a blocking device copy like the reference */
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[LEGION_COUNTER_WORDS], int32_t h_edge_counter[LEGION_COUNTER_WORDS]);

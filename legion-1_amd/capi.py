@@ -269,6 +269,15 @@ _SIGS = {
     "IPCEnv_SetAggNorm": (None, [vp, i32]), "IPCEnv_GetAggNorm": (i32, [vp]), "legion_ipc_client_agg_norm": (i32, [vp]),
     "IPCEnv_SetSampling": (None, [vp, i32]), "IPCEnv_GetSampling": (i32, [vp]), "legion_ipc_client_sampling": (i32, [vp]),
     "IPCEnv_SetSamplingSeed": (None, [vp, i32, u32]), "IPCEnv_GetSamplingSeed": (i32, [vp, vp]), "legion_ipc_client_sampling_seed": (i32, [vp, vp]),
+    # the words of the "<name>_ext2" object (created only when one of them is on) and the served edge buffers
+    "IPCEnv_SetLpDraw": (None, [vp, i32]), "IPCEnv_GetLpDraw": (i32, [vp]), "legion_ipc_client_lp_draw": (i32, [vp]),
+    "IPCEnv_SetWeightedDistinct": (None, [vp, i32]), "IPCEnv_GetWeightedDistinct": (i32, [vp]), "legion_ipc_client_weighted_distinct": (i32, [vp]),
+    "IPCEnv_SetSharedDraws": (None, [vp, i32]), "IPCEnv_GetSharedDraws": (i32, [vp]), "legion_ipc_client_shared_draws": (i32, [vp]),
+    "IPCEnv_SetEdgeIds": (None, [vp, i32]), "IPCEnv_GetEdgeIds": (i32, [vp]), "legion_ipc_client_edge_ids": (i32, [vp]),
+    "IPCEnv_SetEdgeWeights": (None, [vp, i32]), "IPCEnv_GetEdgeWeights": (i32, [vp]), "legion_ipc_client_edge_weights": (i32, [vp]),
+    "IPCEnv_SetAggEdgeWeight": (None, [vp, i32]), "IPCEnv_GetAggEdgeWeight": (i32, [vp]), "legion_ipc_client_agg_edge_weight": (i32, [vp]),
+    "IPCEnv_RegisterEdgeBuffers": (None, [vp, i32, i32, vp, vp, i32]), "IPCEnv_GetEdgeElems": (i32, [vp, i32]),
+    "legion_ipc_client_edge_buffer": (vp, [vp, i32]), "legion_ipc_client_edge_elems": (i32, [vp]),
     "legion_ipc_client_open": (vp, [i32]), "legion_ipc_client_wait": (None, [vp]),
     "legion_ipc_client_post": (None, [vp]), "legion_ipc_client_post_nosync": (None, [vp]), "legion_ipc_client_buffer": (vp, [vp, i32]),
     "legion_ipc_client_steps": (None, [vp, vp]), "legion_ipc_client_hops": (i32, [vp]), "legion_ipc_client_feature_rows": (i32, [vp]),

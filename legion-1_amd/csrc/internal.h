@@ -144,19 +144,21 @@ struct ServeModes {
                                  // ("Drawn link-prediction thirds"); from the environment it is 1 until serve_modes_resolve_lp_draw puts k there
     bool weighted_distinct = false;   // $LEGION_WEIGHTED_DISTINCT=1, only with sampling = weighted: the weighted draws are WITHOUT replacement, min(eligible
                                  // columns, fan-out) distinct columns per row by exponential keys over the graph's retained edge weights ("Weighted sampling
-                                 // without replacement").  A flag on top of the kind: remembered across kinds, acts only while sampling == 2; not published
+                                 // without replacement").  A flag on top of the kind: remembered across kinds, acts only while sampling == 2
     bool shared_draws = false;   // $LEGION_SHARED_DRAWS=1, only with sampling = distinct (and, from the environment, only under a seed): the random number belongs
                                  // to the NEIGHBOUR NODE, not to the row -- every row keeps its min(degree, fan-out) columns of smallest node key, so rows that see
                                  // the same neighbours pick the same ones ("Shared-key sampling").  A flag on top of the kind, like weighted_distinct: remembered
                                  // across kinds, acts while sampling == 1 and, with weighted_distinct on, while sampling == 2: there the exponential key's uniform
-                                 // belongs to the neighbour node ("Weighted shared-key sampling"); not published
-    bool edge_ids = false;       // GPUMemoryPool_SetEdgeIds (no variable yet): every sampled edge's position in the whole CSR, and its weight where the graph
+                                 // belongs to the neighbour node ("Weighted shared-key sampling")
+    bool edge_ids = false;       // $LEGION_EDGE_IDS=1 / GPUMemoryPool_SetEdgeIds: every sampled edge's position in the whole CSR, and its weight where the graph
                                  // retains them, beside the pipe's COO ("Edge ids").  Refused together with the alias rule (sampling == 2 without
-                                 // weighted_distinct); pre-sampling batches hand nothing over; not published
-    bool agg_edge_weight = false;   // GPUMemoryPool_SetAggEdgeWeight (no variable: the edge buffers are not served), only with agg_last_hop and edge_ids and
+                                 // weighted_distinct); pre-sampling batches hand nothing over
+    bool edge_weights = false;   // $LEGION_EDGE_WEIGHTS=1, only with edge_ids: the SERVER loads the graph's weights and retains them whatever the sampling
+                                 // kind, so edge_w is filled.  Nothing of the pool's: it fills edge_w wherever the graph retains weights (serve_modes_edge_w_filled)
+    bool agg_edge_weight = false;   // $LEGION_AGG_EDGE_WEIGHT=1 / GPUMemoryPool_SetAggEdgeWeight, only with agg_last_hop and edge_ids and
                                  // without agg_norm: the sums scale every row by its draw's edge weight, edge_w of the edge-id mode ("Edge-weighted sums").  A flag
-                                 // on top of the aggregated mode: remembered while that mode is off, as the norm is; not published
-    bool operator==(const ServeModes& o) const { return agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
+                                 // on top of the aggregated mode: remembered while that mode is off, as the norm is
+    bool operator==(const ServeModes& o) const { return edge_weights == o.edge_weights && agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
 };
 // The draw rule of a sampler hop: what `sampling` and the flags `weighted_distinct` and `shared_draws` say together.  draw_rule_of is the one
 // place that reads the three; the launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
@@ -197,10 +199,15 @@ enum class RowSource { Whole, Presc, Fragments }; constexpr int kRowSources = 3;
 // check: no columns (GPUMemoryPool_SetEdgeIds) from a pre-sampling hop, which hands nothing over; none under a rule whose pick is not a
 // column; no fragments under a rule whose table lies beside the whole CSR.
 constexpr bool sample_variant_exists(RowSource s, DrawRule r, bool cols) { return !(cols && (s == RowSource::Presc || !draw_rule_facts(r).picks_column)) && !(s == RowSource::Fragments && draw_rule_facts(r).whole_csr); }
-// The only readers of the seven variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
+// whether a server of these modes retains the graph's edge weights (load_edge_weights(s, retain), server.cpp), and whether it serves edge_w filled
+inline bool serve_modes_retain_weights(const ServeModes& m) { return m.edge_weights || (m.sampling == kSamplingWeighted && m.weighted_distinct); }
+inline bool serve_modes_edge_w_filled(const ServeModes& m) { return m.edge_ids && serve_modes_retain_weights(m); }
+// The only readers of the ten variables.  False with the refusal in `why` (the caller puts its name in front); tested in this order:
 // unknown norm, norm without the aggregated mode, unknown sampling mode, malformed seed, unknown LEGION_LP_DRAW, LEGION_LP_DRAW without a
 // seed, unknown LEGION_WEIGHTED_DISTINCT, LEGION_WEIGHTED_DISTINCT without LEGION_SAMPLING=weighted, unknown LEGION_SHARED_DRAWS,
-// LEGION_SHARED_DRAWS without LEGION_SAMPLING=distinct (or =weighted with LEGION_WEIGHTED_DISTINCT=1), LEGION_SHARED_DRAWS without a seed.  Host code only, no device is touched.
+// LEGION_SHARED_DRAWS without LEGION_SAMPLING=distinct (or =weighted with LEGION_WEIGHTED_DISTINCT=1), LEGION_SHARED_DRAWS without a seed; then unknown
+// LEGION_EDGE_IDS, LEGION_EDGE_IDS under the alias rule, unknown LEGION_EDGE_WEIGHTS, LEGION_EDGE_WEIGHTS without LEGION_EDGE_IDS, unknown LEGION_AGG_EDGE_WEIGHT, and
+// LEGION_AGG_EDGE_WEIGHT with every condition it misses named in one refusal.  Host code only, no device is touched.
 bool serve_modes_from_env(ServeModes& m, std::string& why);
 // LEGION_LP_DRAW against what is served, once the meta line is known: false with the refusal in `why` unless the training lists are
 // link-prediction thirds (meta flag 2) of a batch size divisible by 3; m.lp_draw := raw_batch_size / 3.  Nothing to do with the mode off.
@@ -208,7 +215,8 @@ bool serve_modes_resolve_lp_draw(ServeModes& m, bool lp_lists, int32_t raw_batch
 // the fan-out bound of the modes' draw rule (DrawRuleFacts::max_fanout) against a fan-out list: false with the refusal in `why`
 bool serve_modes_fit_fanout(const ServeModes& m, const int32_t* fanout, int32_t hops, std::string& why);
 void runner_set_lists_verbatim(Runner* r, bool verbatim);   // before Runner_Initialize: meta flag 2 (Runner::lists_verbatim, runner.cpp)
-// what a trainer reads: the five mode words of the "<name>_ext" object (shmExt, ipc_shm.h) := m (ipc_env.cpp; the IPCEnv_Set* calls write one mode each)
+// what a trainer reads: the five mode words of the "<name>_ext" object and the six of "<name>_ext2" (shmExt, shmExt2, ipc_shm.h) := m (ipc_env.cpp; the
+// IPCEnv_Set* calls write one mode each).  The second object appears only when one of its words is on.
 void ipc_env_publish_modes(IPCEnv* e, const ServeModes& m);
 
 // The seed sets are indexed by mode everywhere (LEGION_TRAINMODE, LEGION_VALIDMODE, LEGION_TESTMODE); LegionBuildInfo names their fields

@@ -14,6 +14,9 @@ struct LegionIPCClient {
     int shm_fd = -1;
     volatile shmExt* ext = nullptr;    // null: the server has no extension object (a reference server): hops = 2, counters by device copy
     int ext_fd = -1;
+    volatile shmExt2* ext2 = nullptr;  // null: the server has no "_ext2" object (none of its words is on, or an older server), or a stale one: every word reads 0
+    int ext2_fd = -1;
+    void* edge[LEGION_PIPELINE_DEPTH][2] = {};   // the served edge buffers: [0] = edge_ids int64, [1] = edge_w float32; null = not served
     int device = 0;
     void* buf[LEGION_PIPELINE_DEPTH][LEGION_MEMORY_USAGE] = {};   // the last index: LEGION_BUF_*
     sem_t* semr[LEGION_PIPELINE_DEPTH] = {};
@@ -25,6 +28,15 @@ struct LegionIPCClient {
 };
 
 static const volatile shmExt* ext_of(const LegionIPCClient* c) { return c ? c->ext : nullptr; }
+static const volatile shmExt2* ext2_of(const LegionIPCClient* c) { return c ? c->ext2 : nullptr; }
+// why a client is refused: close what was opened, post nothing, and let `msg` be the error the caller reads
+static LegionIPCClient* refuse(LegionIPCClient* c, const char* msg)
+{
+    legion_ipc_client_close(c);
+    legion_clear_error();
+    LEGION_ARG_ERROR(msg);
+    return nullptr;
+}
 
 extern "C" {
 
@@ -53,6 +65,13 @@ LegionIPCClient* legion_ipc_client_open(int32_t device_id)
         c->ext = nullptr; c->ext_fd = -1;
     }
     c->hops = (c->ext && c->ext->hops > 0) ? c->ext->hops : 2;
+    // the second extension object, likewise never created here and likewise ignored unless it belongs to this slab
+    c->ext2 = (volatile shmExt2*)shm_map(sizeof(shmExt2), &c->ext2_fd, ext2_name(), false);
+    if (c->ext2 && !ext2_tied(c->ext2, c->shm, c->device)) {
+        munmap((void*)c->ext2, sizeof(shmExt2));
+        close(c->ext2_fd);
+        c->ext2 = nullptr; c->ext2_fd = -1;
+    }
     // feature buffers that arrive as chunk descriptors first: they need the server's socket, the one step that depends on a second party
     for (int i = 0; i < LEGION_PIPELINE_DEPTH; i++) {
         hipIpcMemHandle_t h;
@@ -80,13 +99,26 @@ LegionIPCClient* legion_ipc_client_open(int32_t device_id)
                 char msg[256];
                 snprintf(msg, sizeof(msg), "legion_ipc_client_open: the server has not registered buffer %d of pipe %d of GPU %d yet "
                          "(start the trainer after \"System is ready for serving\")", w, i, c->device);
-                legion_ipc_client_close(c);
-                legion_clear_error();   // this is why the client is refused: let it be the error the caller reads
-                LEGION_ARG_ERROR(msg);
-                return nullptr;
+                return refuse(c, msg);
             }
             HIP_CHECK(hipIpcOpenMemHandle(&c->buf[i][w], h, hipIpcMemLazyEnablePeerAccess));
         }
+    }
+    // the served edge buffers of this device (LEGION_EDGE_IDS=1): a server that says so has registered them before it is ready for serving
+    if (ext2_edge_ids(c->ext2) && !no_device()) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "legion_ipc_client_open: the server serves edge ids (LEGION_EDGE_IDS=1) but registered no edge buffers for GPU %d "
+                 "(IPCEnv_RegisterEdgeBuffers; start the trainer after \"System is ready for serving\")", c->device);
+        if (ext2_edge_elems(c->ext2, c->device) <= 0) return refuse(c, msg);
+        for (int i = 0; i < LEGION_PIPELINE_DEPTH; i++)
+            for (int w = 0; w < 2; w++) {
+                hipIpcMemHandle_t h;
+                if (!ext2_edge_handle(c->ext2, c->device, i, w, &h)) {
+                    if (w == 0) return refuse(c, msg);
+                    continue;      // no weights buffer: edge ids alone
+                }
+                HIP_CHECK(hipIpcOpenMemHandle(&c->edge[i][w], h, hipIpcMemLazyEnablePeerAccess));
+            }
     }
     log_out() << "HIP: " << c->device << " IPC shared memory opened\n";
     for (int i = 0; i < LEGION_PIPELINE_DEPTH; i++) {
@@ -132,6 +164,18 @@ int32_t legion_ipc_client_agg_last_hop(LegionIPCClient* c) { return ext_agg_last
 int32_t legion_ipc_client_agg_norm(LegionIPCClient* c) { return ext_agg_norm(ext_of(c)); }
 int32_t legion_ipc_client_sampling(LegionIPCClient* c) { return ext_sampling(ext_of(c)); }
 int32_t legion_ipc_client_sampling_seed(LegionIPCClient* c, uint32_t* seed) { return ext_sampling_seed(ext_of(c), seed); }
+int32_t legion_ipc_client_lp_draw(LegionIPCClient* c) { return ext2_lp_draw(ext2_of(c)); }
+int32_t legion_ipc_client_weighted_distinct(LegionIPCClient* c) { return ext2_weighted_distinct(ext2_of(c)); }
+int32_t legion_ipc_client_shared_draws(LegionIPCClient* c) { return ext2_shared_draws(ext2_of(c)); }
+int32_t legion_ipc_client_edge_ids(LegionIPCClient* c) { return ext2_edge_ids(ext2_of(c)); }
+int32_t legion_ipc_client_edge_weights(LegionIPCClient* c) { return ext2_edge_weights(ext2_of(c)); }
+int32_t legion_ipc_client_agg_edge_weight(LegionIPCClient* c) { return ext2_agg_edge_weight(ext2_of(c)); }
+void* legion_ipc_client_edge_buffer(LegionIPCClient* c, int32_t which)
+{
+    if (!c || which < 0 || which > 1 || !ext2_edge_ids(c->ext2) || (which == 1 && !ext2_edge_weights(c->ext2))) return nullptr;
+    return c->edge[c->current_pipe][which];
+}
+int32_t legion_ipc_client_edge_elems(LegionIPCClient* c) { return c ? ext2_edge_elems(c->ext2, c->device) : 0; }
 int32_t legion_ipc_client_feature_rows(LegionIPCClient* c) { return (c && c->ext) ? c->ext->feature_rows[c->device] : 0; }
 void legion_ipc_client_read_counters(LegionIPCClient* c, int32_t h_node_counter[LEGION_COUNTER_WORDS], int32_t h_edge_counter[LEGION_COUNTER_WORDS])
 {
@@ -153,10 +197,12 @@ void legion_ipc_client_close(LegionIPCClient* c)
             if (c->mapped[i].va == c->buf[i][w]) vmm_unmap(c->mapped[i]);
             else (void)hipIpcCloseMemHandle(c->buf[i][w]);
         }
+        for (void*& p : c->edge[i]) { if (p) (void)hipIpcCloseMemHandle(p); p = nullptr; }
         if (!sem_pair_close(c->semr[i], c->semw[i])) log_out() << "close sem " << i << " failed\n";
     }
     if (c->shm) { munmap((void*)c->shm, sizeof(shmStruct)); close(c->shm_fd); }
     if (c->ext) { munmap((void*)c->ext, sizeof(shmExt)); close(c->ext_fd); }
+    if (c->ext2) { munmap((void*)c->ext2, sizeof(shmExt2)); close(c->ext2_fd); }
     delete c;
 }
 

@@ -5,6 +5,7 @@
 #include <cerrno>
 #include <cstring>
 #include <ctime>
+#include <mutex>
 #include <sys/mman.h>
 #include <unistd.h>
 
@@ -17,6 +18,8 @@ struct IPCEnv {
     int shm_fd = -1;
     volatile shmExt* ext = nullptr;    // the extension object ("<name>_ext"); never null once NewIPCEnv succeeded
     int ext_fd = -1;
+    volatile shmExt2* ext2 = nullptr;  // "<name>_ext2": null until something it carries is on (ext2_of creates it)
+    int ext2_fd = -1;
     int32_t device_count = 0;
     void* buf[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH][LEGION_MEMORY_USAGE] = {};   // the slab's indices; null: not registered
     sem_t* semr[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH] = {};
@@ -31,11 +34,36 @@ struct IPCEnv {
     int32_t* mirror_stage[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH] = {};  // slab not page-locked: queued copies land in pinned staging words
 };
 
+// The _ext2 object of an env: created (and tied to the slab as it stands) by the first caller that has something to put there, i.e. `create`.
+// The runners of one server initialise on their own threads, hence the lock.
+static void tie_ext2(IPCEnv* e)
+{
+    if (!e->ext2 || !e->ext) return;
+    for (int i = 0; i < 3; i++) e->ext2->steps_copy[i] = e->ext->steps_copy[i];
+    for (int d = 0; d < LEGION_MAX_DEVICE; d++) e->ext2->handle_sum[d] = e->ext->handle_sum[d];
+}
+static volatile shmExt2* ext2_of(IPCEnv* e, bool create)
+{
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!e || !e->shm || e->ext2 || !create) return e ? e->ext2 : nullptr;
+    e->ext2 = (volatile shmExt2*)shm_map(sizeof(shmExt2), &e->ext2_fd, ext2_name());
+    if (!e->ext2) { LEGION_ARG_ERROR("IPCEnv: shm_open/mmap of the second extension object (_ext2) failed"); return nullptr; }
+    memset((void*)e->ext2, 0, sizeof(shmExt2));
+    e->ext2->bytes = (uint32_t)sizeof(shmExt2);
+    tie_ext2(e);
+    e->ext2->magic = kExt2Magic;
+    return e->ext2;
+}
+static const volatile shmExt2* ext2_of(const IPCEnv* e) { return e ? e->ext2 : nullptr; }
+
 void legion::ipc_env_publish_modes(IPCEnv* e, const ServeModes& m)
 {
     if (!e || !e->ext) return;
     volatile shmExt::Modes& w = e->ext->modes;
     w.agg_last_hop = m.agg_last_hop; w.agg_norm = m.agg_norm; w.sampling = m.sampling; w.sampling_seed = m.seeded ? m.seed : 0u; w.sampling_seeded = m.seeded;
+    IPCEnv_SetLpDraw(e, m.lp_draw); IPCEnv_SetWeightedDistinct(e, m.weighted_distinct); IPCEnv_SetSharedDraws(e, m.shared_draws);
+    IPCEnv_SetEdgeIds(e, m.edge_ids); IPCEnv_SetEdgeWeights(e, serve_modes_edge_w_filled(m)); IPCEnv_SetAggEdgeWeight(e, m.agg_edge_weight);
 }
 
 static const volatile shmExt* ext_of(const IPCEnv* e) { return e ? e->ext : nullptr; }
@@ -72,6 +100,7 @@ IPCEnv* NewIPCEnv(int32_t device_count)
     log_out() << "Shared Memory Opened\n";
     memset((void*)e->shm, 0, sizeof(shmStruct));     // ADVICE.md, open: a second server of the namespace wipes a live server's table here
     memset((void*)e->ext, 0, sizeof(shmExt));
+    shm_unlink(ext2_name().c_str());                 // a fresh server must not inherit a dead server's words; its own appears with the first word that is on
     e->device_count = device_count;
     pin_slab(e);
     return e;
@@ -129,6 +158,7 @@ void IPCEnv_Coordinate(IPCEnv* e, const LegionBuildInfo* info)
     e->shm->steps[1] = e->valid_step;
     e->shm->steps[2] = e->test_step;
     if (e->ext) for (int i = 0; i < 3; i++) e->ext->steps_copy[i] = e->shm->steps[i];
+    tie_ext2(e);
 }
 
 int32_t IPCEnv_GetMaxStep(IPCEnv* e) { return ((e->train_step + e->valid_step) * e->epoch) + e->test_step; }
@@ -163,7 +193,7 @@ void IPCEnv_InitializeSamplesBuffer(IPCEnv* e, int32_t batch_size, int32_t num_i
         void** buf = e->buf[device_id][i];
         e->pipes[device_id] = i + 1;
         for (const auto& b : sized) buf[b.slot] = ipc_alloc(e->shm, device_id, i, b.slot, b.count * sizeof(int32_t));
-        if (i == 0 && e->ext) e->ext->handle_sum[device_id] = handle_checksum(&e->shm->memHandle[device_id][0][LEGION_BUF_IDS]);
+        if (i == 0 && e->ext) { e->ext->handle_sum[device_id] = handle_checksum(&e->shm->memHandle[device_id][0][LEGION_BUF_IDS]); tie_ext2(e); }
         for (int slot : {LEGION_BUF_NODE_COUNTER, LEGION_BUF_EDGE_COUNTER})
             if (buf[slot]) HIP_CHECK(hipMemset(buf[slot], 0, kCounterBytes));
         // memory lock
@@ -212,6 +242,40 @@ void IPCEnv_SetSampling(IPCEnv* e, int32_t mode) { if (e && e->ext) e->ext->mode
 int32_t IPCEnv_GetSampling(const IPCEnv* e) { return ext_sampling(ext_of(e)); }
 void IPCEnv_SetSamplingSeed(IPCEnv* e, int32_t on, uint32_t seed) { if (e && e->ext) { e->ext->modes.sampling_seed = on ? seed : 0u; e->ext->modes.sampling_seeded = on ? 1 : 0; } }
 int32_t IPCEnv_GetSamplingSeed(const IPCEnv* e, uint32_t* seed) { return ext_sampling_seed(ext_of(e), seed); }
+// ... and the words of the _ext2 object: the first setter of a word that is ON creates the object, a 0 on an env without it creates nothing
+#define ENV_EXT2_WORD(Name, word, value) \
+    void IPCEnv_Set##Name(IPCEnv* e, int32_t v) { if (volatile shmExt2* x = ext2_of(e, (value) != 0)) x->modes.word = (value); } \
+    int32_t IPCEnv_Get##Name(const IPCEnv* e) { return ext2_##word(ext2_of(e)); }
+ENV_EXT2_WORD(LpDraw, lp_draw, v > 0 ? v : 0)
+ENV_EXT2_WORD(WeightedDistinct, weighted_distinct, v ? 1 : 0)
+ENV_EXT2_WORD(SharedDraws, shared_draws, v ? 1 : 0)
+ENV_EXT2_WORD(EdgeIds, edge_ids, v ? 1 : 0)
+ENV_EXT2_WORD(EdgeWeights, edge_weights, v ? 1 : 0)
+ENV_EXT2_WORD(AggEdgeWeight, agg_edge_weight, v ? 1 : 0)
+#undef ENV_EXT2_WORD
+// The edge buffers of a (device, pipe) -- the POOL's, which stays their owner: the env exports their handles into _ext2 and records how many
+// elements each holds.  A buffer above the HIP-IPC size limit is refused by name, as ipc_alloc refuses one (the chunked path is the feature buffer's).
+void IPCEnv_RegisterEdgeBuffers(IPCEnv* e, int32_t device_id, int32_t pipe, int64_t* ids, float* w, int32_t elems)
+{
+    if (!e || device_id < 0 || device_id >= e->device_count || pipe < 0 || pipe >= LEGION_PIPELINE_DEPTH || elems < 1) { LEGION_ARG_ERROR("IPCEnv_RegisterEdgeBuffers: bad arguments"); return; }
+    if (!no_device()) {
+        if (!ids) { LEGION_ARG_ERROR("IPCEnv_RegisterEdgeBuffers: null edge_ids buffer (GPUMemoryPool_SetEdgeIds first)"); return; }
+        if (!ipc_size_ok((int64_t)elems * (int64_t)sizeof(int64_t), "IPCEnv_RegisterEdgeBuffers (edge_ids: 8 bytes per edge slot of one pipe)")) {
+            if (!error_is_fatal()) return;
+            fflush(stderr);
+            exit(EXIT_FAILURE);
+        }
+    }
+    volatile shmExt2* x = ext2_of(e, true);
+    if (!x) return;
+    if (!no_device()) {     // device-free: the handle slots stay zero
+        LEGION_DEVICE_GUARD(device_id);
+        HIP_CHECK(hipIpcGetMemHandle((hipIpcMemHandle_t*)&x->edge_handle[device_id][pipe][0], ids));
+        if (w) HIP_CHECK(hipIpcGetMemHandle((hipIpcMemHandle_t*)&x->edge_handle[device_id][pipe][1], w));
+    }
+    x->edge_elems[device_id] = elems;
+}
+int32_t IPCEnv_GetEdgeElems(const IPCEnv* e, int32_t device_id) { return ext2_edge_elems(ext2_of(e), device_id); }
 // the row capacity published to the trainers of a device (a server that re-sizes its feature buffers; tests)
 void IPCEnv_SetFeatureRows(IPCEnv* e, int32_t device_id, int32_t rows)
 {
@@ -376,6 +440,8 @@ void IPCEnv_Finalize(IPCEnv* e)
         shm_unlink(shm_name().c_str());
         e->shm = nullptr;
         if (e->ext) { munmap((void*)e->ext, sizeof(shmExt)); close(e->ext_fd); shm_unlink(ext_name().c_str()); e->ext = nullptr; }
+        if (e->ext2) { munmap((void*)e->ext2, sizeof(shmExt2)); close(e->ext2_fd); e->ext2 = nullptr; }
+        shm_unlink(ext2_name().c_str());
     }
 }
 

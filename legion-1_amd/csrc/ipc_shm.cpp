@@ -2,6 +2,7 @@
 #include "ipc_shm.h"
 
 #include <cerrno>
+#include <cstring>
 #include <ctime>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -16,6 +17,20 @@ uint32_t handle_checksum(const volatile void* h)
     const volatile unsigned char* b = (const volatile unsigned char*)h;
     for (size_t i = 0; i < sizeof(hipIpcMemHandle_t); i++) { x ^= b[i]; x *= 16777619u; }
     return x ? x : 1u;
+}
+
+bool ext2_tied(const volatile shmExt2* x, const volatile shmStruct* shm, int dev)
+{
+    if (!x || !shm || dev < 0 || dev >= LEGION_MAX_DEVICE || x->magic != kExt2Magic || x->bytes < offsetof(shmExt2, modes)) return false;
+    for (int i = 0; i < 3; i++) if (x->steps_copy[i] != shm->steps[i]) return false;
+    return x->handle_sum[dev] == handle_checksum(&shm->memHandle[dev][0][LEGION_BUF_IDS]);
+}
+bool ext2_edge_handle(const volatile shmExt2* x, int dev, int pipe, int which, hipIpcMemHandle_t* h)
+{
+    if (!x || x->bytes < sizeof(shmExt2) || dev < 0 || dev >= LEGION_MAX_DEVICE || pipe < 0 || pipe >= LEGION_PIPELINE_DEPTH || which < 0 || which > 1) return false;
+    static const hipIpcMemHandle_t zero{};
+    memcpy(h, (const void*)&x->edge_handle[dev][pipe][which], sizeof(*h));
+    return memcmp(h, &zero, sizeof(*h)) != 0;
 }
 
 bool no_device()
@@ -37,6 +52,7 @@ const std::string& ipc_ns()
 }
 std::string shm_name(const std::string& ns) { return "/" + ns + "simpleIPCshm"; }
 std::string ext_name(const std::string& ns) { return shm_name(ns) + "_ext"; }
+std::string ext2_name(const std::string& ns) { return shm_name(ns) + "_ext2"; }
 std::string sem_name(const char* rw, int dev, int pipe, const std::string& ns)
 {
     return "/" + ns + "sem_" + rw + "_" + std::to_string(dev) + "_" + std::to_string(pipe);
@@ -116,13 +132,14 @@ void legion_ipc_set_namespace(const char* ns)
     g_namespace = ns ? ns : "";
     g_ns_init = true;
 }
-// Remove what a server of namespace `ns` that was KILLED left in /dev/shm (IPCEnv_Finalize never ran): the slab, its extension object and
+// Remove what a server of namespace `ns` that was KILLED left in /dev/shm (IPCEnv_Finalize never ran): the slab, its extension objects and
 // the 2 x depth named semaphores of each of `devices` GPUs.  Safe to call when nothing is there.
 void legion_ipc_unlink_namespace(const char* ns, int32_t devices)
 {
     const std::string p = ns ? ns : "";
     shm_unlink(shm_name(p).c_str());
     shm_unlink(ext_name(p).c_str());
+    shm_unlink(ext2_name(p).c_str());
     for (int d = 0; d < devices && d < LEGION_MAX_DEVICE; d++)
         for (int q = 0; q < LEGION_PIPELINE_DEPTH; q++) sem_pair_unlink(d, q, p);
 }

@@ -1,5 +1,5 @@
-// ipc_shm.h -- what the two halves of the server <-> trainer hand-off must agree on, and nothing else: the two shared-memory
-// objects, their names, the semaphore pair of a (device, pipe) and the chunk descriptor of a buffer above the HIP-IPC size limit.
+// ipc_shm.h -- what the two halves of the server <-> trainer hand-off must agree on, and nothing else: the shared-memory
+// objects (the slab, "_ext" and, only when a server has something to put there, "_ext2"), their names, the semaphore pair of a (device, pipe) and the chunk descriptor of a buffer above the HIP-IPC size limit.
 //   server half : ipc_env.cpp     CUDAIPCEnv            src/CUDA_IPC_Service.cu:39-360
 //   trainer half: ipc_client.cpp  GPUIPCEnv             pytorch_extension/ipc_cuda_kernel.cu:36-176
 //   shm helpers : ipc_shm.cpp     helper_multiprocess   src/helper_multiprocess.cpp:5-100
@@ -84,6 +84,47 @@ inline int32_t ext_sampling_seed(const volatile shmExt* x, uint32_t* seed)
     return on ? 1 : 0;
 }
 
+// What came after the _ext object was full and pinned: a THIRD object, "<name>_ext2".  The server creates it only when
+// something it carries is on -- one of the six mode words below, or registered edge buffers --, so a server with none of them leaves exactly
+// the slab, _ext and the semaphores.  A client never creates it; absent, every word reads 0, which is how a client of an older server behaves.
+// It only ever grows at the end: `bytes` is the WRITER's sizeof(shmExt2), and a reader trusts only the words below it.
+struct shmExt2 {
+    uint32_t magic;           // kExt2Magic
+    uint32_t bytes;           // sizeof(shmExt2) of the build that wrote it
+    int32_t steps_copy[3];    // the tie to the live slab, as in shmExt: a client ignores an object whose copies do not match the slab it
+    uint32_t handle_sum[LEGION_MAX_DEVICE];   // attached to (a killed server's object under a later server that has none)
+    struct Modes {
+        int32_t lp_draw;            // k > 0 = a training batch is 3 k seeds whose pos and neg thirds the server draws per batch; 0 = off
+        int32_t weighted_distinct;  // 1 = the weighted draws are without replacement (`sampling` in _ext stays 2)
+        int32_t shared_draws;       // 1 = the distinct draws go by a key of the neighbour node
+        int32_t edge_ids;           // 1 = every sampled edge's position in the whole CSR is served in edge_handle[..][0]
+        int32_t edge_weights;       // 1 = edge_w is filled (the graph retains its weights), served in edge_handle[..][1]
+        int32_t agg_edge_weight;    // 1 = the last hop's sums scale every row by its draw's edge weight
+    } modes;
+    int32_t edge_elems[LEGION_MAX_DEVICE];    // elements each edge buffer of a device holds (GPUMemoryPool_NumIds); 0 = none registered
+    hipIpcMemHandle_t edge_handle[LEGION_MAX_DEVICE][LEGION_PIPELINE_DEPTH][2];   // [..][0] = edge_ids int64, [..][1] = edge_w float32
+};
+static_assert(offsetof(shmExt2, magic) == 0 && offsetof(shmExt2, bytes) == 4 && offsetof(shmExt2, steps_copy) == 8 && offsetof(shmExt2, handle_sum) == 20 &&
+              offsetof(shmExt2, modes.lp_draw) == 52 && offsetof(shmExt2, modes.weighted_distinct) == 56 && offsetof(shmExt2, modes.shared_draws) == 60 &&
+              offsetof(shmExt2, modes.edge_ids) == 64 && offsetof(shmExt2, modes.edge_weights) == 68 && offsetof(shmExt2, modes.agg_edge_weight) == 72 &&
+              offsetof(shmExt2, edge_elems) == 76 && offsetof(shmExt2, edge_handle) == 108 && sizeof(shmExt2) == 108 + 8 * 2 * 2 * 64,
+              "a field of the _ext2 object moved");
+constexpr uint32_t kExt2Magic = 0x4C474E32u;   // "LGN2"
+// whether the object belongs to the slab a peer attached to (and was written by a build that knows the tie)
+bool ext2_tied(const volatile shmExt2* x, const volatile shmStruct* shm, int dev);
+// The one reader of each word, beside ext_*: no object, or a writer that ended before the word, reads 0
+#define LEGION_EXT2_WORD(name) \
+    inline int32_t ext2_##name(const volatile shmExt2* x) { return x && x->bytes >= offsetof(shmExt2, modes.name) + sizeof(int32_t) ? x->modes.name : 0; }
+LEGION_EXT2_WORD(lp_draw) LEGION_EXT2_WORD(weighted_distinct) LEGION_EXT2_WORD(shared_draws)
+LEGION_EXT2_WORD(edge_ids) LEGION_EXT2_WORD(edge_weights) LEGION_EXT2_WORD(agg_edge_weight)
+#undef LEGION_EXT2_WORD
+inline int32_t ext2_edge_elems(const volatile shmExt2* x, int dev)
+{
+    return x && dev >= 0 && dev < LEGION_MAX_DEVICE && x->bytes >= offsetof(shmExt2, edge_elems) + sizeof(x->edge_elems) ? x->edge_elems[dev] : 0;
+}
+// the handle of (dev, pipe, which) into *h; false when the writer ended before the table or the slot is all zero ("no buffer")
+bool ext2_edge_handle(const volatile shmExt2* x, int dev, int pipe, int which, hipIpcMemHandle_t* h);
+
 // $LEGION_IPC_NO_DEVICE=1 (test hook: build containers without a GPU, the host-sanitizer run of tests/test_ipc_env_cpu.py): the slab,
 // the named semaphores, the counter mirror and the poisoned-pipe protocol with no device call at all -- no hand-off buffer is
 // allocated, the handle slots stay zero (a client takes an all-zero handle as "no buffer"), nothing is page-locked.
@@ -91,10 +132,11 @@ bool no_device();
 #define LEGION_DEVICE_GUARD(dev) std::optional<::legion::DeviceGuard> guard_; if (!::legion::no_device()) guard_.emplace(dev)
 
 // The names of a namespace (a prefix; default: the process's, $LEGION_IPC_NAMESPACE or legion_ipc_set_namespace), read at every call:
-// tests switch the namespace inside one process.  "/<ns>simpleIPCshm", "/<ns>simpleIPCshm_ext", "/<ns>sem_<r|w>_<dev>_<pipe>".
+// tests switch the namespace inside one process.  "/<ns>simpleIPCshm", "/<ns>simpleIPCshm_ext", "/<ns>simpleIPCshm_ext2", "/<ns>sem_<r|w>_<dev>_<pipe>".
 const std::string& ipc_ns();
 std::string shm_name(const std::string& ns = ipc_ns());
 std::string ext_name(const std::string& ns = ipc_ns());
+std::string ext2_name(const std::string& ns = ipc_ns());
 std::string sem_name(const char* rw, int dev, int pipe, const std::string& ns = ipc_ns());
 // sharedMemoryCreate (helper_multiprocess.cpp:5-47): shm_open(O_RDWR|O_CREAT) + ftruncate + mmap
 void* shm_map(size_t sz, int* fd_out, const std::string& name = shm_name(), bool create = true);

@@ -167,8 +167,8 @@ static void enqueue_gather(Runner* r, int l, Gather want, hipEvent_t behind)
 
 // A batch: the seed launch (level 0), hop 1 .. hop H, the planner on `sampler`; behind each level its event (when `record`) and, on the
 // gather stream, what gather_behind says.  The host issues them interleaved, so a level's gather reaches its stream before the next hop
-// reaches the sampler's.  A runner that was never initialised enqueues nothing.  A pool in the edge-id mode (GPUMemoryPool_SetEdgeIds on
-// Runner_GetMemoryPool; no LEGION_* variable yet) has every hop's GPU_Random_Sampling enqueue k_edge_ids behind its k_write, in front of the
+// reaches the sampler's.  A runner that was never initialised enqueues nothing.  A pool in the edge-id mode (LEGION_EDGE_IDS=1, or
+// GPUMemoryPool_SetEdgeIds on Runner_GetMemoryPool) has every hop's GPU_Random_Sampling enqueue k_edge_ids behind its k_write, in front of the
 // level's event: in-process runners and recordings leave the pipe's edge ids like the plain calls do.
 static void enqueue_stages(Runner* r, hipStream_t sampler, bool presc, bool record, Gather want)
 {
@@ -284,6 +284,17 @@ void Runner_Initialize(Runner* r, RunnerParams* params)
     ipc_env_publish_modes(env, m);
     if (m.agg_last_hop) log_out() << r->local_dev_id << " Hand-off: the last hop as neighbour sums (LEGION_AGG_LAST_HOP=1)\n";
     if (m.agg_norm) log_out() << r->local_dev_id << " Hand-off: the sums normalised by out-degree^-1/2 inside block 1 (LEGION_AGG_NORM=both)\n";
+    if (m.agg_edge_weight) log_out() << r->local_dev_id << " Hand-off: the sums scaled by each edge's weight (LEGION_AGG_EDGE_WEIGHT=1)\n";
+    if (m.edge_ids) {
+        // the pool's per-pipe edge buffers go to the trainers as they are: the pool stays their owner, the env exports their handles.  A pipe
+        // is posted behind done_ev, which stream 1 records behind plan_ev / the last level's event -- both behind the last hop's k_edge_ids
+        for (int i = 0; i < r->pipeline_depth; i++) {
+            const GPUMemoryPool::Pipe& pipe = r->memorypool->pipes[i];
+            IPCEnv_RegisterEdgeBuffers(env, r->local_dev_id, i, pipe.buf<int64_t>(GPUMemoryPool::kEdgeIds), pipe.buf<float>(GPUMemoryPool::kEdgeW), GPUMemoryPool_NumIds(r->memorypool));
+        }
+        log_out() << r->local_dev_id << " Hand-off: every sampled edge's position in the whole CSR, " << GPUMemoryPool_NumIds(r->memorypool) << " per pipe (LEGION_EDGE_IDS=1)\n";
+        if (serve_modes_edge_w_filled(m)) log_out() << r->local_dev_id << " Hand-off: every sampled edge's weight beside its id (" << (m.edge_weights ? "LEGION_EDGE_WEIGHTS=1" : "LEGION_WEIGHTED_DISTINCT=1") << ")\n";
+    }
     log_out() << r->local_dev_id << " Sampling: " << draw_rule_facts(draw_rule_of(m)).sentence << "\n";
     if (m.seeded) log_out() << r->local_dev_id << " Sampling seed: " << m.seed << " (LEGION_SAMPLING_SEED): fresh draws per batch, the training list reshuffled per epoch\n";
     LEGION_AUDIT_OWNER(r->memorypool->pos_map, r->local_dev_id, "Runner_Initialize: scratch of the memory pool");

@@ -1,5 +1,5 @@
 // serve_modes.cpp -- the serving modes as the environment states them: the only readers of LEGION_AGG_LAST_HOP, LEGION_AGG_NORM,
-// LEGION_SAMPLING, LEGION_SAMPLING_SEED, LEGION_LP_DRAW, LEGION_WEIGHTED_DISTINCT and LEGION_SHARED_DRAWS (ServeModes, internal.h).  Host code only: no device is touched.
+// LEGION_SAMPLING, LEGION_SAMPLING_SEED, LEGION_LP_DRAW, LEGION_WEIGHTED_DISTINCT, LEGION_SHARED_DRAWS, LEGION_EDGE_IDS, LEGION_EDGE_WEIGHTS and LEGION_AGG_EDGE_WEIGHT (ServeModes, internal.h).  Host code only: no device is touched.
 #include "internal.h"
 
 #include <cctype>
@@ -26,6 +26,17 @@ static bool parse_seed(const char* n, uint32_t& seed)
 // LEGION_WEIGHTED_DISTINCT: unset / empty / "0" = off, "1" only with LEGION_SAMPLING=weighted.
 // LEGION_SHARED_DRAWS: unset / empty / "0" = off, "1" only with LEGION_SAMPLING=distinct, or =weighted with LEGION_WEIGHTED_DISTINCT=1, under a seed: unseeded, every batch of every epoch
 // would prefer the same nodes (the node key depends on the draw word alone), which a server must not do silently.
+// LEGION_EDGE_IDS, LEGION_EDGE_WEIGHTS, LEGION_AGG_EDGE_WEIGHT: unset / empty / "0" = off, "1" = on.  Edge ids not under the alias rule (pool_apply_modes'
+// reason); edge weights only with edge ids; the edge-weighted sums only with the aggregated mode, edge ids and retained weights, and without a norm.
+// A switch: false with the refusal when the value is neither; `what`: what "1" means, for the refusal
+static bool parse_switch(const char* var, const char* what, bool& on, std::string& why)
+{
+    const char* v = getenv(var);
+    on = v && strcmp(v, "1") == 0;
+    if (on || !v || !v[0] || strcmp(v, "0") == 0) return true;
+    why = std::string(var) + "=" + v + " is not a known setting: `1` (" + what + "), `0` or unset";
+    return false;
+}
 bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
 {
     m = ServeModes();
@@ -66,6 +77,19 @@ bool legion::serve_modes_from_env(ServeModes& m, std::string& why)
         if (m.sampling != kSamplingDistinct && !(m.sampling == kSamplingWeighted && m.weighted_distinct)) { why = "LEGION_SHARED_DRAWS=1 needs LEGION_SAMPLING=distinct: the flag keys the distinct draws by the neighbour node"; return false; }
         if (!m.seeded) { why = "LEGION_SHARED_DRAWS=1 needs LEGION_SAMPLING_SEED: the node keys come from the batch's draw word, and without a seed every batch of every epoch would prefer the same nodes"; return false; }
         m.shared_draws = true;
+    }
+    if (!parse_switch("LEGION_EDGE_IDS", "every sampled edge's position in the whole CSR is served beside the COO", m.edge_ids, why)) return false;
+    if (m.edge_ids && !draw_rule_facts(draw_rule_of(m)).picks_column) { why = "LEGION_EDGE_IDS=1 cannot be served under LEGION_SAMPLING=weighted without LEGION_WEIGHTED_DISTINCT=1: the alias table holds the alias neighbour's id, not its column"; return false; }
+    if (!parse_switch("LEGION_EDGE_WEIGHTS", "the graph's edge weights are retained and every sampled edge's weight is served beside its id", m.edge_weights, why)) return false;
+    if (m.edge_weights && !m.edge_ids) { why = "LEGION_EDGE_WEIGHTS=1 needs LEGION_EDGE_IDS=1: an edge's weight is served beside its id"; return false; }
+    if (!parse_switch("LEGION_AGG_EDGE_WEIGHT", "the last hop's neighbour sums scale every row by its edge's weight", m.agg_edge_weight, why)) return false;
+    if (m.agg_edge_weight) {
+        std::string missing;
+        if (!m.agg_last_hop) missing += " needs LEGION_AGG_LAST_HOP=1 (only neighbour sums are scaled);";
+        if (!m.edge_ids) missing += " needs LEGION_EDGE_IDS=1 (the weight of a draw is the edge_w that mode hands over);";
+        if (!serve_modes_retain_weights(m)) missing += " needs retained edge weights (LEGION_EDGE_WEIGHTS=1, or LEGION_SAMPLING=weighted LEGION_WEIGHTED_DISTINCT=1);";
+        if (m.agg_norm) missing += " must not be combined with LEGION_AGG_NORM (GraphConv(norm='both', edge_weight=) has no kernel in this build);";
+        if (!missing.empty()) { missing.pop_back(); why = "LEGION_AGG_EDGE_WEIGHT=1" + missing; return false; }
     }
     return true;
 }

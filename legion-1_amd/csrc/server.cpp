@@ -422,8 +422,10 @@ bool place_tables(Server* s, const LegionSynthSpec& spec)
 
 // LEGION_SAMPLING=weighted: the graph's edge weights -- `edge_weights` (float32[E], one per entry of edge_dst) beside the dataset's files,
 // generated on the device for a synth: source -- become the graph's alias table on every GPU of the job (GPUGraphStorage_SetEdgeWeights).
-// retain (LEGION_WEIGHTED_DISTINCT=1): the weights themselves stay on every GPU beside the table (GPUGraphStorage_RetainEdgeWeights).
-bool load_edge_weights(Server* s, bool retain)
+// retain (LEGION_WEIGHTED_DISTINCT=1, LEGION_EDGE_WEIGHTS=1): the weights themselves stay on every GPU beside the table (GPUGraphStorage_RetainEdgeWeights).
+// LEGION_EDGE_WEIGHTS=1 takes this path under every sampling kind: under a kind that is not weighted the 8 E-byte table is built and never read.
+// who: the setting that asked, for the refusal and the log
+bool load_edge_weights(Server* s, bool retain, const char* who)
 {
     const Meta& m = s->meta;
     const int64_t E = m.edge_num;
@@ -443,13 +445,13 @@ bool load_edge_weights(Server* s, bool retain)
         int64_t got = 0;
         const std::string path = m.dataset_path + "edge_weights";
         if (!read_file(path, w.data(), E * 4, &got) || got != E * 4) {
-            LEGION_ARG_ERROR(("Server_Initialize: LEGION_SAMPLING=weighted needs " + path + ": float32[" + std::to_string(E) + "], one weight per entry of edge_dst (missing or short)").c_str());
+            LEGION_ARG_ERROR((std::string("Server_Initialize: ") + who + " needs " + path + ": float32[" + std::to_string(E) + "], one weight per entry of edge_dst (missing or short)").c_str());
             return false;
         }
         if (GPUGraphStorage_SetEdgeWeights(s->graph, w.data(), LEGION_LOC_HOST_PAGEABLE) != 0) return false;
     }
     log_out() << "Edge weights: alias table built in HBM, " << E * 8 / 1e9 << " GB per GPU\n";
-    if (retain) log_out() << "Edge weights: kept in HBM beside the table, " << E * 4 / 1e9 << " GB per GPU (LEGION_WEIGHTED_DISTINCT=1)\n";
+    if (retain) log_out() << "Edge weights: kept in HBM beside the table, " << E * 4 / 1e9 << " GB per GPU (" << (strcmp(who, "LEGION_EDGE_WEIGHTS=1") == 0 ? who : "LEGION_WEIGHTED_DISTINCT=1") << ")\n";
     return true;
 }
 
@@ -527,7 +529,7 @@ void Server_Initialize(Server* s, int global_shard_count)
     log_out() << "Finish Partition\n";
     build_storages(s, split);
     if (!place_tables(s, spec)) return;
-    if (modes.sampling == kSamplingWeighted && !load_edge_weights(s, modes.weighted_distinct)) return;
+    if ((modes.sampling == kSamplingWeighted || modes.edge_weights) && !load_edge_weights(s, serve_modes_retain_weights(modes), modes.sampling == kSamplingWeighted ? "LEGION_SAMPLING=weighted" : "LEGION_EDGE_WEIGHTS=1")) return;
     start_runners(s);
 }
 

@@ -66,6 +66,15 @@ def main(argv=None):
                     "(LEGION_SHARED_DRAWS=1 for the server; needs --sampling distinct and --sampling_seed): the distinct draws are keyed by the "
                     "neighbour node, so rows that see the same neighbours pick the same ones and a batch reaches fewer unique nodes; also on top of "
                     "--sampling weighted --weighted-distinct: the weighted draws without replacement take one uniform per neighbour node")
+    ap.add_argument("--edge-ids", "--edge_ids", dest="edge_ids", action="store_true", help="extension (LEGION_EDGE_IDS=1 for the server): every "
+                    "sampled edge's position in the dataset's edge_dst is served beside the blocks (ipc_service.get_edge_ids(); DGL's edata[dgl.EID], "
+                    "PyG's e_id); not under --sampling weighted without --weighted-distinct")
+    ap.add_argument("--edge-weights", "--edge_weights", dest="edge_weights", action="store_true", help="extension (LEGION_EDGE_WEIGHTS=1 for the "
+                    "server; needs --edge-ids): the server keeps the dataset's edge_weights in HBM under every sampling kind and serves every "
+                    "sampled edge's weight (ipc_service.get_edge_weights())")
+    ap.add_argument("--agg-edge-weight", "--agg_edge_weight", dest="agg_edge_weight", action="store_true", help="extension "
+                    "(LEGION_AGG_EDGE_WEIGHT=1 for the server; needs LEGION_AGG_LAST_HOP=1, --edge-ids and --edge-weights): the last hop's "
+                    "neighbour sums scale every row by its edge's weight (ipc_service.get_next_aggregated_edge_weight())")
     ap.add_argument("--dry_run", action="store_true", help="write meta_config and print the command only")
     args = ap.parse_args(argv)
     fan = [int(x) for x in args.nbrs_num.replace("[", "").replace("]", "").split(",") if x.strip()]
@@ -87,6 +96,12 @@ def main(argv=None):
         env["LEGION_WEIGHTED_DISTINCT"] = "1"
     if args.shared_draws:
         env["LEGION_SHARED_DRAWS"] = "1"
+    if args.edge_ids:
+        env["LEGION_EDGE_IDS"] = "1"
+    if args.edge_weights:
+        env["LEGION_EDGE_WEIGHTS"] = "1"
+    if args.agg_edge_weight:
+        env["LEGION_AGG_EDGE_WEIGHT"] = "1"
     return subprocess.call(cmd, env=env)
 
 
