@@ -520,6 +520,35 @@ float* GPUMemoryPool_GetEdgeWeightBuffer(const GPUMemoryPool* p);
  * the state it was recorded in.  Setting it allocates per pipe 4 bytes per slot of the largest hop and a few KB on the current device. */
 void GPUMemoryPool_SetAggEdgeWeight(GPUMemoryPool* p, int on);
 int GPUMemoryPool_GetAggEdgeWeight(const GPUMemoryPool* p);
+/* Edge features (extension; INTEGRATION.md "Edge features"): a per-edge table gathered by edge id into every batch,
+ *   edge_feat float32[GPUMemoryPool_NumIds, dim]:   edge_feat[e, :] = X[edge_ids[e], :]   for the batch's COO edge e,
+ * the missing counterpart of get_feature_kernel for edges.  Opt-in; a pool that never asks for it is what it was.
+ * The graph's side.  GPUGraphStorage_SetEdgeFeatures (after GPUGraphStorage_Build): x = float32 [E, dim], dense, row e beside indices[e],
+ * at `location` (LEGION_LOC_*); copied once per physical device (4 E dim bytes each), replacing an earlier table.  x == NULL drops the table.
+ * Returns 0, or -1 with a sticky error that names the call -- a null or unbuilt graph, dim < 1, a dim whose table size overflows -- and a
+ * failed replacement keeps the earlier table.  Record a LegionBatchGraph again after replacing the table.  GetEdgeFeatureDim: the table's
+ * dim, 0 when there is none.  CopyEdgeFeatureRows copies rows [e0, e0 + n) of logical GPU dev_id's table to the host (tests, tools).
+ * The pool's side.  GPUMemoryPool_SetEdgeFeatures(pool, dim): dim > 0 switches the mode on at that row width, 0 switches it off.  Only on
+ * top of edge ids.  Refused in the name of whichever setter comes second, the pool's modes kept: the mode without edge ids and
+ * GPUMemoryPool_SetEdgeIds(pool, 0) while it is on; dim < 0; a dim for which NumIds * dim * 4 overflows or NumIds * chunks per row (dim / 4
+ * where dim % 4 == 0, else dim) reaches 2^31; a null pool; a pool that is being captured.  Call it under the device the pool's scratch lives
+ * on: it allocates edge_feat per pipe, and another dim reallocates it.
+ * The launchers, behind the hop's GPU_Random_Sampling, on any stream ordered behind it (they read the batch's pipe and the graph's table
+ * only): get_edge_feature_kernel gathers the edges of the hop whose sampling op is op_id (2, 4, .., 2 * hops), get_edge_feature_kernel_all
+ * all edges [0, legion_batch_edges) in one launch -- the same bytes.  An id outside [0, E), which no correct batch holds, gives a row of
+ * zeros.  Sticky argument errors, by name: a pool that is not in the mode, a graph without a table on this GPU, a table whose dim differs
+ * from the pool's, a pipe whose batch left no edge ids for the hop (a pre-sampling batch, ids off, the hop not sampled yet), an op_id that
+ * is no sampling op.  Both work inside a LegionBatchGraph recording; LegionBatchGraph_Launch refuses a graph recorded under another dim.
+ * GPUMemoryPool_GetEdgeFeatureBuffer: the current pipe's buffer; null unless the pipe's last batch was gathered.
+ * Not served: no LEGION_* variable and no IPC hand-off carry the mode yet. */
+int GPUGraphStorage_SetEdgeFeatures(GPUGraphStorage* g, const float* x, int32_t dim, int32_t location);
+int32_t GPUGraphStorage_GetEdgeFeatureDim(const GPUGraphStorage* g);
+int GPUGraphStorage_CopyEdgeFeatureRows(const GPUGraphStorage* g, int32_t dev_id, int64_t e0, int64_t n, float* out);
+void GPUMemoryPool_SetEdgeFeatures(GPUMemoryPool* p, int32_t dim);
+int32_t GPUMemoryPool_GetEdgeFeatures(const GPUMemoryPool* p);
+float* GPUMemoryPool_GetEdgeFeatureBuffer(const GPUMemoryPool* p);
+void get_edge_feature_kernel(void* strm_hdl, GPUGraphStorage* graph, GPUMemoryPool* memorypool, int32_t dev_id, int32_t op_id);
+void get_edge_feature_kernel_all(void* strm_hdl, GPUGraphStorage* graph, GPUMemoryPool* memorypool, int32_t dev_id);
 /* Seeded sampling (extension; INTEGRATION.md "Seeded sampling").  With GPUMemoryPool_SetSampleSeed(pool, 1, S) every batch of the pool draws
  * from its own word W(S, round, iter): the with-replacement stream becomes thrust::minstd_rand(1 + W % 2147483646) after discard(idx), the
  * distinct mode XORs W into its row key, and a TRAINING batch takes its seeds from the round's shuffled copy of the training list
@@ -784,6 +813,9 @@ void legion_synth_labels(void* stream, int32_t* out, int32_t v0, int32_t n, int3
 /* edge weights of CSR entries [e0, e0 + n) for the weighted sampler mode: a closed form of the entry's position -- 0 for about one entry
  * in eight (whole blocks of 64 entries among them: rows without any weight occur), else an integer in 1..16 (exact in float32); synth.py edge_weights() is the NumPy statement */
 void legion_synth_edge_weights(void* stream, float* out, int64_t e0, int64_t n);
+/* out[(e - e0) * dim + c] = the edge feature of CSR entry e in [e0, e0 + n), column c < dim: a closed form of (e, c), an integer in [0, 2^24)
+ * (exact in float32) from a 32-bit mix of both, so a wrong row and a wrong column are both visible; synth.py edge_features() is the NumPy statement */
+void legion_synth_edge_features(void* stream, float* out, int64_t e0, int64_t n, int32_t dim);
 void legion_synth_seed_ids(void* stream, int32_t* out, int64_t i0, int64_t n, int32_t V, uint32_t M2, uint32_t C2, int32_t stride, int32_t phase);
 /* The generator's parameters for a named shape ("products" | "papers100M" | "uk-union", legion_server.py:6-37), shrunk by
  * `scale` in (0, 1] (V and the seed sets; the mean degree stays): the C statement of synth.py spec_for(), field for field

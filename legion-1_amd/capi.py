@@ -223,6 +223,14 @@ _SIGS = {
     "GPUMemoryPool_GetEdgeIdBuffer": (vp, [vp]),
     "GPUMemoryPool_GetEdgeWeightBuffer": (vp, [vp]),
     "GPUGraphStorage_CopyAliasRows": (C.c_int, [vp, i32, i64, i64, vp, vp]),
+    "GPUGraphStorage_SetEdgeFeatures": (C.c_int, [vp, vp, i32, i32]),
+    "GPUGraphStorage_GetEdgeFeatureDim": (i32, [vp]),
+    "GPUGraphStorage_CopyEdgeFeatureRows": (C.c_int, [vp, i32, i64, i64, vp]),
+    "GPUMemoryPool_SetEdgeFeatures": (None, [vp, i32]),
+    "GPUMemoryPool_GetEdgeFeatures": (i32, [vp]),
+    "GPUMemoryPool_GetEdgeFeatureBuffer": (vp, [vp]),
+    "get_edge_feature_kernel": (None, [vp, vp, vp, i32, i32]),
+    "get_edge_feature_kernel_all": (None, [vp, vp, vp, i32]),
     "GPUMemoryPool_SetSampleSeed": (None, [vp, C.c_int, u32]),
     "GPUMemoryPool_GetSampleSeed": (C.c_int, [vp, vp]),
     "GPUMemoryPool_BeginRound": (C.c_int, [vp, vp, vp, i32, i32]),
@@ -299,6 +307,7 @@ _SIGS = {
     "legion_synth_features_pitched": (None, [vp, vp, i64, i64, i32, i32]),
     "legion_synth_labels": (None, [vp, vp, i32, i32, i32]),
     "legion_synth_edge_weights": (None, [vp, vp, i64, i64]),
+    "legion_synth_edge_features": (None, [vp, vp, i64, i64, i32]),
     "legion_synth_seed_ids": (None, [vp, vp, i64, i64, i32, u32, u32, i32, i32]),
     "legion_synth_spec": (C.c_int, [C.c_char_p, f64, vp]),
     "legion_synth_label_host": (i32, [i32, i32]),
@@ -427,11 +436,15 @@ class Engine:
     (GPUGraphStorage_SetEdgeWeights: the graph's alias table, what sample="weighted" draws from); set_edge_weights() replaces or drops it.
     ``retain_edge_weights=True`` (GPUGraphStorage_RetainEdgeWeights): every table build keeps the weights on the device beside the
     table, which run_batch(sample="weighted", weighted_distinct=True) reads.
+    ``edge_features``: float32 [E, dim], one row per CSR entry (GPUGraphStorage_SetEdgeFeatures), what run_batch(edge_ids=True,
+    edge_features=True) gathers by edge id; a numpy array, or an integer device pointer together with ``edge_feature_dim``.
+    set_edge_features() replaces or drops it.
     """
 
     def __init__(self, indptr, indices, features, V, F, seeds, batch_size, fanout, G=1,
                  csr_location=LOC_DEVICE, features_location=LOC_DEVICE, cache_memory=0, train_step=1, epoch=1,
-                 pipeline_depth=1, E=None, local_devs=None, features_pitch=0, edge_weights=None, retain_edge_weights=False):
+                 pipeline_depth=1, E=None, local_devs=None, features_pitch=0, edge_weights=None, retain_edge_weights=False,
+                 edge_features=None, edge_feature_dim=None):
         L = lib()
         # one process per GPU: the other members of the clique are remote (legion_set_remote_device)
         self.local_devs = list(range(int(G))) if local_devs is None else list(local_devs)
@@ -510,6 +523,11 @@ class Engine:
             check()
         if edge_weights is not None:
             self.set_edge_weights(edge_weights)
+        self.edge_feature_dim = 0
+        if edge_features is not None:
+            self.set_edge_features(edge_features, edge_feature_dim)
+        elif edge_feature_dim is not None:
+            raise ValueError("edge_feature_dim without edge_features: the width belongs to a table")
         self.depth = int(pipeline_depth)
         self.pools, self.out = [None] * self.G, [None] * self.G
         for g in self.local_devs:
@@ -539,6 +557,7 @@ class Engine:
         self._seed_state = {}   # dev -> (seed or None, round) the pool was last put into (run_batch / capture_batch / run_graph)
         self._norm = {}     # (dev, pipe) -> ... with normalised sums (run_batch(agg_norm="both"))
         self._eid = {}      # (dev, pipe) -> the pipe's last batch left its edge ids (run_batch(edge_ids=True))
+        self._efeat = {}    # (dev, pipe) -> the row width the pipe's last batch had its edge rows gathered at (run_batch(edge_features=True)), 0: not
         check()
 
     # ---- weighted sampling: the graph's alias table ------------------------------------------------------
@@ -551,6 +570,38 @@ class Engine:
                 raise ValueError("edge_weights: one float32 per CSR entry (%d), got %d" % (self.E, len(w)))
         self.L.GPUGraphStorage_SetEdgeWeights(self.graph, None if w is None else w.ctypes.data, LOC_HOST_PAGEABLE)
         check()
+
+    # ---- edge features: the graph's per-edge table --------------------------------------------------------
+    def set_edge_features(self, x, dim=None, location=None):
+        """float32 [E, dim] rows in `indices` order -> the graph's edge-feature table (replacing an earlier one); None drops it.  x: a numpy
+        array (dim is its second axis; a flat array needs dim) or an integer device pointer with dim (location: LOC_DEVICE)."""
+        if x is None:
+            self.L.GPUGraphStorage_SetEdgeFeatures(self.graph, None, 0, LOC_HOST_PAGEABLE)
+            check()
+            self.edge_feature_dim = 0
+            return
+        if isinstance(x, (int, np.integer)):
+            if dim is None or int(dim) < 1:
+                raise ValueError("edge_features: a device pointer needs edge_feature_dim >= 1")
+            ptr, dim, location = int(x), int(dim), LOC_DEVICE if location is None else location
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            if x.ndim == 2 and dim is None:
+                dim = x.shape[1]
+            if dim is None or int(dim) < 1 or x.size != self.E * int(dim) or (x.ndim == 2 and x.shape != (self.E, int(dim))):
+                raise ValueError("edge_features: float32 [E, dim] with one row per CSR entry (%d), got shape %s and dim %s" % (self.E, x.shape, dim))
+            ptr, dim, location = x.ctypes.data, int(dim), LOC_HOST_PAGEABLE
+        self.L.GPUGraphStorage_SetEdgeFeatures(self.graph, ptr, dim, location)
+        check()
+        self.edge_feature_dim = int(self.L.GPUGraphStorage_GetEdgeFeatureDim(self.graph))
+
+    def edge_feature_rows(self, dev=0, e0=0, n=None):
+        """float32 [n, dim]: rows [e0, e0 + n) of logical GPU dev's edge-feature table."""
+        n = self.E - e0 if n is None else int(n)
+        out = np.empty((n, self.edge_feature_dim), np.float32)
+        self.L.GPUGraphStorage_CopyEdgeFeatureRows(self.graph, dev, int(e0), n, out.ctypes.data)
+        check()
+        return out
 
     def has_edge_weights(self):
         return bool(self.L.GPUGraphStorage_HasEdgeWeights(self.graph))
@@ -582,8 +633,13 @@ class Engine:
     # ---- one batch through the reference's launcher API -----------------------------------------------------
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
-                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False, agg_edge_weight=False):
-        """agg_edge_weight (GPUMemoryPool_SetAggEdgeWeight, only with agg_last_hop=True, edge_ids=True and without agg_norm, on an
+                  seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False, agg_edge_weight=False,
+                  edge_features=False):
+        """edge_features (GPUMemoryPool_SetEdgeFeatures, only with edge_ids=True on an Engine with an edge-feature table): the batch additionally
+        leaves edge_feat[e, :] = X[edge_ids[e], :] in the pipe's buffer -- gathered per hop (get_edge_feature_kernel) where the node rows are
+        gathered per level, else in one launch behind the last hop (get_edge_feature_kernel_all); result() then returns `edge_feat` float32
+        [n_edges, dim].  A pre-sampling batch gathers nothing.  Set on every call like `edge_ids`.
+        agg_edge_weight (GPUMemoryPool_SetAggEdgeWeight, only with agg_last_hop=True, edge_ids=True and without agg_norm, on an
         Engine(retain_edge_weights=True)): `nbr_sum` holds the sums with every row scaled by its draw's edge weight, S_e of INTEGRATION.md
         "Edge-weighted sums".  Set on every call like `agg_norm`.
         edge_ids (GPUMemoryPool_SetEdgeIds): the batch additionally leaves every COO edge's position in the whole CSR in the pipe's buffer, and
@@ -615,8 +671,11 @@ class Engine:
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
         agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct,
-                                     shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight)
+                                     shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight, edge_features=edge_features)
+        efeat = bool(edge_features) and not is_presc
+        ef_per_hop = efeat and gather and per_level
         self._eid[(dev, pipe)] = bool(edge_ids) and not is_presc
+        self._efeat[(dev, pipe)] = self.edge_feature_dim if efeat else 0
         self._agg[(dev, pipe)] = agg and gather
         self._norm[(dev, pipe)] = norm and gather
         L.GPUMemoryPool_SetCurrentPipe(pool, pipe)
@@ -628,12 +687,16 @@ class Engine:
             L.get_feature_kernel(stream, self.cache, self.noder, pool, dev, 1, 1)
         for h in range(self.hops):
             L.GPU_Random_Sampling(stream, self.graph, self.cache, pool, int(self.fanout[h]), 2 * h + 2, int(is_presc))
+            if ef_per_hop:
+                L.get_edge_feature_kernel(stream, self.graph, pool, dev, 2 * h + 2)
             if gather and not is_presc and per_level and not (agg and h == self.hops - 1):
                 L.get_feature_kernel(stream, self.cache, self.noder, pool, dev, 2 * h + 3, 1)
         if agg and gather:
             L.get_feature_kernel_agg(stream, self.cache, self.noder, pool, dev, 1)
         elif gather and not is_presc and not per_level:
             L.get_feature_kernel_all(stream, self.cache, self.noder, pool, dev, 1)
+        if efeat and not ef_per_hop:
+            L.get_edge_feature_kernel_all(stream, self.graph, pool, dev)
         if plan:
             L.make_update_plan(stream, self.graph, self.cache, pool, dev, mode)
             L.update_cache(stream, self.cache, self.noder, pool, dev, mode)
@@ -642,7 +705,7 @@ class Engine:
             check()
 
     def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False,
-                   agg_edge_weight=False):
+                   agg_edge_weight=False, edge_features=False):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
@@ -653,6 +716,10 @@ class Engine:
             raise ValueError("agg_edge_weight needs agg_last_hop=True, edge_ids=True: the last hop's neighbour sums are scaled by the edge_w the edge-id mode hands over")
         if agg_edge_weight and norm:
             raise ValueError("agg_edge_weight and agg_norm together are not in this build: GraphConv(norm='both', edge_weight=) rounds twice per product")
+        if edge_features and not edge_ids:
+            raise ValueError("edge_features=True needs edge_ids=True: a row is gathered by the id the edge-id mode hands over")
+        if edge_features and not self.edge_feature_dim:
+            raise ValueError("edge_features=True needs the Engine's edge-feature table (Engine(edge_features=...) or set_edge_features())")
         if sample not in ("replace", "distinct", "weighted"):
             raise ValueError("sample: 'replace', 'distinct' or 'weighted'")
         if weighted_distinct and sample != "weighted":
@@ -674,6 +741,10 @@ class Engine:
         eid_off = L.GPUMemoryPool_GetEdgeIds(pool) and (not edge_ids or rule != (L.GPUMemoryPool_GetSampling(pool), L.GPUMemoryPool_GetWeightedDistinct(pool)))
         if L.GPUMemoryPool_GetAggEdgeWeight(pool) and (not ew or eid_off):
             L.GPUMemoryPool_SetAggEdgeWeight(pool, 0)
+        # edge features sit on top of edge ids: off in front of them, on (at the table's width; a pre-sampling batch gathers nothing) behind them
+        ef = self.edge_feature_dim if edge_features and not is_presc else 0
+        if L.GPUMemoryPool_GetEdgeFeatures(pool) and (not ef or eid_off):
+            L.GPUMemoryPool_SetEdgeFeatures(pool, 0)
         if eid_off:
             L.GPUMemoryPool_SetEdgeIds(pool, 0)
         for mode, want in (("Sampling", ("replace", "distinct", "weighted").index(sample)), ("WeightedDistinct", int(bool(weighted_distinct))), ("SharedDraws", int(bool(shared_draws))), ("AggLastHop", int(agg)), ("AggNorm", norm)):   # the last two allocate
@@ -684,6 +755,9 @@ class Engine:
             check()
         if L.GPUMemoryPool_GetAggEdgeWeight(pool) != ew:   # allocates where the norm has not
             L.GPUMemoryPool_SetAggEdgeWeight(pool, ew)
+            check()
+        if L.GPUMemoryPool_GetEdgeFeatures(pool) != ef:   # allocates on the first switch on, reallocates at another width
+            L.GPUMemoryPool_SetEdgeFeatures(pool, ef)
             check()
         self._set_seed(dev, seed, round, stream, lp_draw)
         return agg, bool(norm)
@@ -705,11 +779,12 @@ class Engine:
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
                       stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False,
-                      edge_ids=False, agg_edge_weight=False):
+                      edge_ids=False, agg_edge_weight=False, edge_features=False):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
         run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in, and
-        only in the weighted_distinct, the shared_draws, the edge_ids and the agg_edge_weight state it was recorded in."""
+        only in the weighted_distinct, the shared_draws, the edge_ids and the agg_edge_weight state, and at the edge-feature width, it was
+        recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -718,13 +793,14 @@ class Engine:
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
         self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct, shared_draws=shared_draws,
-                        edge_ids=edge_ids, agg_edge_weight=agg_edge_weight)
+                        edge_ids=edge_ids, agg_edge_weight=agg_edge_weight, edge_features=edge_features)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
                        stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw,
-                       weighted_distinct=weighted_distinct, shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight)
+                       weighted_distinct=weighted_distinct, shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight,
+                       edge_features=edge_features)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -747,8 +823,10 @@ class Engine:
             self.L.d_stream_sync(stream)
             check()
 
-    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None, edge_ids=None):
-        """edge_ids: whether the pipe's edge ids are read (`edge_ids`, and `edge_w` where the batch ran over retained weights) -- None: as
+    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None, edge_ids=None, edge_features=None):
+        """edge_features: whether the pipe's gathered edge rows are read (`edge_feat` float32 [n_edges, dim]) -- None: as run_batch /
+        capture_batch on this engine left it; True: at the width of the engine's table.
+        edge_ids: whether the pipe's edge ids are read (`edge_ids`, and `edge_w` where the batch ran over retained weights) -- None: as
         run_batch / capture_batch on this engine left it.
         aggregated: how to read the pipe's feature buffer -- None: as run_batch / capture_batch on this engine left it; True / False
         for a caller that drove the launchers itself.  normalised: likewise, whether the pipe's block out-degrees are read (`out_deg`)."""
@@ -773,6 +851,14 @@ class Engine:
             res["edge_ids"] = read_dev(eid, np.int64, n_edges)
             if ew:
                 res["edge_w"] = read_dev(ew, np.float32, n_edges)
+        dim = self._efeat.get((dev, pipe), 0) if edge_features is None else (self.edge_feature_dim if edge_features else 0)
+        if dim:
+            self.L.GPUMemoryPool_SetCurrentPipe(self.pools[dev], pipe)
+            ef = self.L.GPUMemoryPool_GetEdgeFeatureBuffer(self.pools[dev])
+            check()
+            if not ef:
+                raise RuntimeError("result(): the pipe's last batch had no edge rows gathered (GPUMemoryPool_GetEdgeFeatureBuffer is null)")
+            res["edge_feat"] = read_dev(ef, np.float32, n_edges * dim).reshape(n_edges, dim)
         if with_features and o["feat"] is not None and aggregated:
             # aggregated hand-off: rows [0, n_in) are features, rows [n_in, n_in + N) the last hop's neighbour sums per input slot
             n_in, runs = layout.first_block_dst(nc, H), layout.hop_inputs(nc, ec, H)

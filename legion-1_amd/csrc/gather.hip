@@ -150,6 +150,65 @@ __global__ __launch_bounds__(kBlock) void k_gather(GatherKArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// S5, edge features (no counterpart in the reference): edge_feat[e, :] = X[edge_ids[e], :]
+// ------------------------------------------------------------------------------------------------
+// The counterpart of k_gather for the graph's per-edge table (GPUGraphStorage_SetEdgeFeatures): float32 [E, dim], dense, in CSR order, row
+// edge_ids[e] of it for every COO edge e of one hop (hop == 0: of the batch).  It reads the batch's PIPE only -- edge_ids as k_edge_ids left
+// them, and ec -- and the table; never cand, cols, the tile prefixes, hop_state or the position table, which belong to the next batch's
+// sampler while this runs on the gather stream.  The edge range comes from ec on the device, clamped to the buffers' capacity; the grid is
+// persistent, sized from the hop's static bound.
+// Another regime than k_gather: rows of 4-256 bytes (C = 1..16 chunks), 64-bit ids into a table of up to 1.6 G rows -- the source row is
+// table + id * dim in 64-bit arithmetic throughout, only the flat work space (edge, chunk) is 32-bit-divided -- and the chain is id -> row,
+// two dependent trips: U independent id loads go out, then U row loads, then U stores.  An id outside [0, E) cannot occur in a correct batch;
+// if one does it forms no address and the row is stored as zeros (the pool's poison rule).  Every edge of the range is stored and nothing
+// else.  Non-temporal loads and stores as in k_gather: a row is read for this edge and written once for a reader in another process.
+struct EdgeGatherKArgs {
+    EdgeGatherArgs g;
+    FastDiv div_c;   // / chunks-per-row
+};
+
+template <typename VT, int U>
+__global__ __launch_bounds__(kBlock) void k_gather_edges(EdgeGatherKArgs a)
+{
+    constexpr int VEC = sizeof(VT) / 4;
+    const EdgeGatherArgs& g = a.g;
+    const int32_t lo = g.hop > 0 ? legion_hop_edges_begin(g.ec, g.hop) : 0;
+    const int32_t hi = g.hop > 0 ? legion_hop_edges_end(g.ec, g.hop) : legion_batch_edges(g.ec, g.hops);
+    const int32_t e0 = max(lo, 0), e1 = min(hi, g.ids_cap);   // never past edge_ids / out, whatever the counters hold
+    const int32_t C = g.dim / VEC;
+    const int64_t total = e1 > e0 ? (int64_t)(e1 - e0) * C : 0;   // < 2^31: ids_cap * C is checked by the launcher
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t q0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q0 < total; q0 += stride * U) {
+        int64_t id[U], dsti[U];
+        uint32_t ch[U];
+        VT val[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int64_t q = q0 + u * stride;
+            id[u] = -1; dsti[u] = -1; ch[u] = 0;
+            if (q < total) {
+                const uint32_t r = fdiv((uint32_t)q, a.div_c);
+                ch[u] = (uint32_t)q - r * (uint32_t)C;
+                const int64_t e = (int64_t)e0 + r;
+                dsti[u] = e * C + ch[u];
+                id[u] = g.edge_ids[e];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            val[u] = VT(0.0f);
+            if (id[u] >= 0 && id[u] < g.E) {
+                const VT* src = reinterpret_cast<const VT*>(g.table + id[u] * (int64_t)g.dim) + ch[u];
+                val[u] = __builtin_nontemporal_load(src);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (dsti[u] >= 0) __builtin_nontemporal_store(val[u], reinterpret_cast<VT*>(g.out) + dsti[u]);
+    }
+}
+
 // (cached gather, same box, papers100M shape, 25 % of the rows cached: lookup pass k_row_ptrs + k_gather 416-423 us; k_gather_lookup<U> with U = 1: 455,
 // U = 2: 412-414, U = 4: 418 (profiles/r04_cached_gather.md) -- the probes themselves (1.94 M random 4-byte reads of a 444 MB map) bound it: U = 2 is built)
 // FindFeat inside the gather, ONE probe per row and wave: the first lane a wave gives to a row resolves
@@ -646,6 +705,27 @@ void launch_gather(hipStream_t s, const GatherArgs& g, int32_t rows_bound)
     if (fused) { if (vec4) k_gather_lookup<v4f, 2><<<grid, kBlock, 0, s>>>(a); else k_gather_lookup<float, 2><<<grid, kBlock, 0, s>>>(a); }
     else if (vec4) k_gather<v4f, 1, 2><<<grid, kBlock, 0, s>>>(a);
     else k_gather<float, 1, 2><<<grid, kBlock, 0, s>>>(a);
+    HIP_CHECK_LAST();
+}
+
+// The grid rule of k_gather_edges (tests/test_gpu_edge_features.py restates it to size its several-trips case): one workgroup per
+// kBlock * kEdgeGatherU (edge, chunk) items of the hop's static bound, at most kEdgeGatherBlocksPerCu per compute unit -- 8 workgroups of 256
+// threads are what a CU holds, so the grid is resident at once and every lane loops over the rest.
+constexpr int kEdgeGatherU = 2, kEdgeGatherBlocksPerCu = 8;
+void launch_gather_edges(hipStream_t s, const EdgeGatherArgs& g, int32_t edges_bound)
+{
+    if (g.dim <= 0 || edges_bound <= 0) return;
+    EdgeGatherKArgs a;
+    a.g = g;
+    // ids, counters and the output are the pipe's own, on this GPU; the table is the graph's copy on this physical device
+    LEGION_AUDIT_LAUNCH(s, "k_gather_edges", LEGION_AW(g.out), LEGION_AL(g.edge_ids), LEGION_AL(g.ec), LEGION_AR(g.table));
+    const bool vec4 = rows_are_vec4(g.dim, g.table, g.out);
+    const int C = vec4 ? g.dim / 4 : g.dim;
+    if ((int64_t)g.ids_cap * C >= (1ll << 31)) { LEGION_ARG_ERROR("k_gather_edges: edges * chunks per row reaches 2^31 work items"); return; }
+    a.div_c = FastDiv((uint32_t)C);
+    const int grid = grid_for((int64_t)std::min(edges_bound, g.ids_cap) * C, kBlock * kEdgeGatherU, kEdgeGatherBlocksPerCu);
+    if (vec4) k_gather_edges<v4f, kEdgeGatherU><<<grid, kBlock, 0, s>>>(a);
+    else k_gather_edges<float, kEdgeGatherU><<<grid, kBlock, 0, s>>>(a);
     HIP_CHECK_LAST();
 }
 

@@ -35,6 +35,8 @@ void GPUGraphStorage_Build(GPUGraphStorage* g, const LegionBuildInfo* info)
     g->d_frag_tab.assign(P, nullptr);
     g->alias.assign(P, nullptr);
     g->weights.assign(P, nullptr);
+    g->edge_feat.assign(P, nullptr);
+    g->edge_feat_dim = 0;
     // chunk geometry of the fragments: powers of two that fit shard_chunk_bytes()
     g->row_shift = chunk_shift(sizeof(int64_t), 4);
     g->edge_shift = chunk_shift(sizeof(int32_t), 4);
@@ -252,11 +254,63 @@ int GPUGraphStorage_CopyAliasRows(const GPUGraphStorage* g, int32_t dev_id, int6
     return 0;
 }
 
+// ---- edge features: a float32 [E, dim] table in CSR order (INTEGRATION.md "Edge features") ----
+// Row e lies beside indices[e].  One device copy per physical device by the rule of the retained weights (device_leaders / free_replicas);
+// x == NULL drops the table; a failed replacement keeps the earlier one, as SetEdgeWeights does.
+int GPUGraphStorage_SetEdgeFeatures(GPUGraphStorage* g, const float* x, int32_t dim, int32_t location)
+{
+    if (!g || g->edge_feat.empty()) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeFeatures: null graph, or GPUGraphStorage_Build was not called"); return -1; }
+    if (x && location != LEGION_LOC_HOST_PINNED && location != LEGION_LOC_DEVICE && location != LEGION_LOC_HOST_PAGEABLE) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeFeatures: location must be a LEGION_LOC_* value"); return -1; }
+    if (x && dim < 1) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeFeatures: dim must be at least 1 (float32 [E, dim], dense)"); return -1; }
+    int64_t bytes = 0;
+    if (x && (__builtin_mul_overflow(g->edge_num, (int64_t)dim, &bytes) || __builtin_mul_overflow(bytes, (int64_t)sizeof(float), &bytes))) { LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeFeatures: the table's size, E * dim * 4 bytes, overflows"); return -1; }
+    const int P = g->partition_count;
+    std::vector<float*> fresh(P, nullptr);
+    if (x && g->edge_num > 0) {
+        const std::vector<int> leader = device_leaders(P);
+        for (int p = 0; p < P; p++) {
+            if (leader[p] < 0) continue;
+            if (leader[p] != p) fresh[p] = fresh[leader[p]];
+            else {
+                DeviceGuard guard(p);
+                HIP_CHECK(hipMalloc(&fresh[p], (size_t)bytes));
+                if (fresh[p]) HIP_CHECK(hipMemcpy(fresh[p], x, (size_t)bytes, hipMemcpyDefault));
+                if (!fresh[p] || error_pending()) {   // the earlier table stays
+                    if (!error_pending()) LEGION_ARG_ERROR("GPUGraphStorage_SetEdgeFeatures: allocating the table failed");
+                    free_replicas(fresh);
+                    return -1;
+                }
+            }
+            LEGION_AUDIT_SHARE(fresh[p], p);
+        }
+    }
+    // gathers that read the earlier table may still be in flight
+    for (int p = 0; p < P; p++)
+        if (g->edge_feat[p] && !is_remote_device(p)) { DeviceGuard guard(p); HIP_CHECK(hipDeviceSynchronize()); }
+    free_replicas(g->edge_feat);
+    g->edge_feat = fresh;
+    g->edge_feat_dim = x && g->edge_num > 0 ? dim : 0;
+    return error_pending() ? -1 : 0;
+}
+int32_t GPUGraphStorage_GetEdgeFeatureDim(const GPUGraphStorage* g) { return g ? g->edge_feat_dim : 0; }
+int GPUGraphStorage_CopyEdgeFeatureRows(const GPUGraphStorage* g, int32_t dev_id, int64_t e0, int64_t n, float* out)
+{
+    if (!g || dev_id < 0 || dev_id >= (int32_t)g->edge_feat.size() || !g->edge_feat[dev_id]) { LEGION_ARG_ERROR("GPUGraphStorage_CopyEdgeFeatureRows: this logical GPU holds no edge-feature table (GPUGraphStorage_SetEdgeFeatures)"); return -1; }
+    if (e0 < 0 || n < 0 || e0 > g->edge_num - n) { LEGION_ARG_ERROR("GPUGraphStorage_CopyEdgeFeatureRows: rows outside [0, edge count)"); return -1; }
+    if (n == 0) return 0;
+    if (!out) { LEGION_ARG_ERROR("GPUGraphStorage_CopyEdgeFeatureRows: null output"); return -1; }
+    DeviceGuard guard(dev_id);
+    HIP_CHECK(hipMemcpy(out, g->edge_feat[dev_id] + e0 * g->edge_feat_dim, (size_t)n * g->edge_feat_dim * sizeof(float), hipMemcpyDeviceToHost));
+    return error_pending() ? -1 : 0;
+}
+
 void GPUGraphStorage_Finalize(GPUGraphStorage* g)
 {
     if (!g) return;
     free_replicas(g->alias);
     free_replicas(g->weights);
+    free_replicas(g->edge_feat);
+    g->edge_feat_dim = 0;
     free_replicas(g->replica_indptr);
     free_replicas(g->replica_indices);
     for (size_t i = 0; i < g->frag.size(); i++) {

@@ -158,7 +158,10 @@ struct ServeModes {
     bool agg_edge_weight = false;   // $LEGION_AGG_EDGE_WEIGHT=1 / GPUMemoryPool_SetAggEdgeWeight, only with agg_last_hop and edge_ids and
                                  // without agg_norm: the sums scale every row by its draw's edge weight, edge_w of the edge-id mode ("Edge-weighted sums").  A flag
                                  // on top of the aggregated mode: remembered while that mode is off, as the norm is
-    bool operator==(const ServeModes& o) const { return edge_weights == o.edge_weights && agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
+    int32_t edge_feat_dim = 0;   // GPUMemoryPool_SetEdgeFeatures, only with edge_ids: 0 = off, dim > 0 = get_edge_feature_kernel gathers edge_feat[e, :] = X[edge_ids[e], :]
+                                 // from the graph's float32 [E, dim] table (GPUGraphStorage_SetEdgeFeatures) into a per-pipe buffer ("Edge features").  No variable,
+                                 // no mode word: the pool's and the Engine's only (open: the served hand-off)
+    bool operator==(const ServeModes& o) const { return edge_feat_dim == o.edge_feat_dim && edge_weights == o.edge_weights && agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
 };
 // The draw rule of a sampler hop: what `sampling` and the flags `weighted_distinct` and `shared_draws` say together.  draw_rule_of is the one
 // place that reads the three; the launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
@@ -446,6 +449,21 @@ struct GatherArgs {
     bool row_ptr_ready;                       // row_ptr was filled by the caller (exchange plan): skip the lookup pass
 };
 void launch_gather(hipStream_t s, const GatherArgs& a, int32_t rows_bound);
+// Edge features (gather.hip "S5, edge features"): out[e, :] = table[edge_ids[e], :] for the COO edges e of hop `hop` of the pipe's batch
+// (hop 0: all of them, [0, legion_batch_edges)), the range read from ec on the device and clamped to ids_cap; an id outside [0, E) stores zeros.
+struct EdgeGatherArgs {
+    const float* table;       // the graph's float32 [E, dim], dense, on this GPU
+    int64_t E;
+    int32_t dim;
+    const int64_t* edge_ids;  // the pipe's, as k_edge_ids left them
+    const int32_t* ec;        // the pipe's edge counters
+    int32_t hop, hops;        // 1..hops, or 0 = every hop
+    float* out;               // the pipe's edge_feat, float32 [ids_cap, dim]
+    int32_t ids_cap;          // rows of edge_ids and of out
+};
+// chunks a row of `dim` floats is gathered in (16-byte chunks where dim % 4 == 0, else floats): what the 32-bit flat work space is counted in
+constexpr int32_t edge_gather_chunks(int32_t dim) { return dim % 4 == 0 ? dim / 4 : dim; }
+void launch_gather_edges(hipStream_t s, const EdgeGatherArgs& a, int32_t edges_bound);
 // Aggregated last hop (gather.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
 // slots, from the draws in cand[slot * f + j], into rows [legion_first_block_dst(nc, hops), + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
 // wdraw (normalised sums): the weight of every draw by slot, as launch_agg_norm_weights left it; null = plain sums.
@@ -558,18 +576,22 @@ struct GPUMemoryPool {
         int32_t sampled_hop = 0;      // hops of the current batch that GPU_Random_Sampling has queued (0 behind batch_generator_kernel)
         bool sampled_presc = false;   // ... as pre-sampling hops
         uint32_t levels_gathered = 0; // bit l: get_feature_kernel gathered level l of the current batch
+        int32_t edge_id_hop = 0;      // hops 1..edge_id_hop of the current batch left their edge ids (k_edge_ids is queued behind each of them)
+        bool edge_feat_gathered = false;   // get_edge_feature_kernel(_all) gathered edge rows of the current batch (-> Pipe::edge_feat_filled)
     } progress;
     // Everything that exists once per pipe.  own[]: the device buffers the POOL owns per pipe, one row of pool_pipe_buffers() each (below) --
     // allocated when a mode that wants them is set, kept until the scratch is released, null before.  cand_pipe: the aggregated last hop parks
     // its draws in the PIPE's buffer, because k_gather_sum reads them on the gather stream while hop 1 of the next batch already overwrites
     // `cand` on the sampler stream.  The normalised sums rank them through agg_out_deg / agg_wdraw / agg_chunk_cnt; the edge-weighted sums use
-    // the last two in the same way and no degrees.  edge_ids / edge_w: the batch's, read back by callers.
-    enum PipeBuf { kCandPipe, kAggOutDeg, kAggWdraw, kAggChunkCnt, kEdgeIds, kEdgeW, kPipeBufs };
+    // the last two in the same way and no degrees.  edge_ids / edge_w: the batch's, read back by callers.  edge_feat: float32 [num_ids,
+    // modes.edge_feat_dim], the batch's gathered edge rows (GPUMemoryPool_SetEdgeFeatures), read back by callers.
+    enum PipeBuf { kCandPipe, kAggOutDeg, kAggWdraw, kAggChunkCnt, kEdgeIds, kEdgeW, kEdgeFeat, kPipeBufs };
     struct Pipe {
         float* float_features = nullptr;   // the seven buffers the caller registered (IPC buffers)
         int32_t *labels = nullptr, *node_counter = nullptr, *edge_counter = nullptr, *sampled_ids = nullptr, *agg_src_off = nullptr, *agg_dst_off = nullptr;
         void* own[kPipeBufs] = {};
         bool edge_w_filled = false;        // the pipe's last batch ran over retained weights (GetEdgeWeightBuffer is null otherwise)
+        bool edge_feat_filled = false;     // the pipe's last batch had its edge rows gathered (GetEdgeFeatureBuffer is null otherwise)
         template <typename T> T* buf(PipeBuf b) const { return (T*)own[b]; }
     };
     std::vector<Pipe> pipes;               // pipeline_depth of them from the constructor on, never resized
@@ -592,6 +614,8 @@ struct GPUMemoryPool {
     // Edge ids (modes.edge_ids, GPUMemoryPool_SetEdgeIds): max_slots words, one buffer (written by k_sample, read by k_edge_ids of the same
     // hop); allocated when the mode is switched on, kept until the scratch is released
     int32_t* cols = nullptr;
+    int32_t edge_feat_alloc_dim = 0;  // the row width the pipes' edge_feat buffers are allocated for (0: none); another dim reallocates them
+    uint32_t edge_feat_gen = 0;       // ... and counts every such (re)allocation and release: a batch graph that writes them replays only under the count it recorded
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
     int32_t aux_ready_hop = 0, aux_ready_count = 0; // the launch before prepared aux2[hop & 1] for this fan-out
     int32_t* tile_edge = nullptr;
@@ -616,7 +640,8 @@ namespace legion {
 // its modes).  Refused as GPUMemoryPool_SetAggNorm: an unknown norm, and a norm on a pool that does not aggregate the last hop -- unless the
 // pool holds that norm already (it stays set while the aggregated mode is off).  Refused in who's name, whichever setter comes second: the
 // edge-weighted sums (agg_edge_weight) without the aggregated mode -- unless the pool holds the flag already --, without edge ids, or together
-// with a norm.  Refused as GPUMemoryPool_SetLpDraw: a negative triple count,
+// with a norm; and the edge features (edge_feat_dim) without edge ids, at a negative width, or at a width whose per-pipe buffer overflows or
+// whose flat work space (num_ids * edge_gather_chunks) reaches 2^31.  Refused as GPUMemoryPool_SetLpDraw: a negative triple count,
 // and a positive one on a pool without a graph (lp_graph).  Allocates the aggregated modes' per-pipe buffers when the
 // pool owns scratch (call it under the scratch's device); another seed invalidates the shuffled copy, another seeded state the graph cursor.
 bool pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const char* who);
@@ -645,6 +670,10 @@ struct GPUGraphStorage {
     // way; empty / null = not retained (the copy is freed after the build, as it always was)
     std::vector<float*> weights;
     bool retain_weights = false;
+    // Edge features (GPUGraphStorage_SetEdgeFeatures): float32 [E, edge_feat_dim], dense, row e beside indices[e], device memory, one copy per
+    // physical device by the rule of `weights`; empty / null = no table (edge_feat_dim == 0)
+    std::vector<float*> edge_feat;
+    int32_t edge_feat_dim = 0;
     int32_t csr_location = LEGION_LOC_HOST_PINNED;
     bool owns_csr = false;
     // CSR fragment of one logical GPU (device memory on that GPU's physical device).  Both arrays are chunk lists

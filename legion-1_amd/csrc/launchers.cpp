@@ -141,6 +141,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     }
     p->device_id = dev_id;
     p->progress = {};
+    p->pipe().edge_feat_filled = false;   // a new batch on this pipe: its edge rows are not gathered yet
     SeedArgs a;
     a.batch_ids = pipe->sampled_ids; a.labels = pipe->labels; a.batch_size = batch_size;
     a.all_ids = all_ids; a.all_labels = all_labels; a.total_cap = total_cap;
@@ -228,6 +229,7 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     launch_sample_hop((hipStream_t)strm_hdl, csr, b, count, op_id, p->hops, (int32_t)slots, is_presc != 0, draw, eo);
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->progress.sampled_hop = hop; p->progress.sampled_presc = is_presc != 0;
+    if (eo && p->progress.edge_id_hop == hop - 1) p->progress.edge_id_hop = hop;
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint
     p->bound_nodes += (int32_t)slots;
 }
@@ -402,6 +404,45 @@ void get_feature_kernel_all(void* strm_hdl, GPUCache* cache, GPUNodeStorage* nod
     if (!pipe || !in_memory) return;
     if (use_peer_exchange(cache, memorypool, dev_id)) { legion_peer_exchange_gather(strm_hdl, cache, noder, memorypool, dev_id); return; }
     gather_common(strm_hdl, cache, noder, memorypool, *pipe, dev_id, -1, LEGION_NC_TOTAL, memorypool->num_ids); // every row of the batch
+}
+
+// ---- edge features (no counterpart in the reference; INTEGRATION.md "Edge features") ----
+// edge_feat[e, :] = X[edge_ids[e], :] for the COO edges of hop `hop` of the current pipe's batch (hop 0: of every hop), X the graph's table on
+// this GPU.  Everything read is the batch's pipe's or the graph's, so the call may follow the hop on the gather stream.  Refused by name: a pool
+// that is not in the mode, a graph without a table on this GPU or with another row width, a batch that left no edge ids for the hop.
+static void edge_feature_gather(void* strm_hdl, GPUGraphStorage* graph, GPUMemoryPool* p, int32_t dev_id, int hop, const char* who)
+{
+    const std::string name(who);
+    Pipe* pipe = graph ? pool_ready(p, who) : nullptr;
+    if (!pipe) { if (!graph) LEGION_ARG_ERROR((name + ": null graph").c_str()); return; }
+    const int32_t dim = p->modes.edge_feat_dim;
+    if (dim <= 0) { LEGION_ARG_ERROR((name + ": the pool does not gather edge features (GPUMemoryPool_SetEdgeFeatures)").c_str()); return; }
+    const float* table = dev_id >= 0 && dev_id < (int32_t)graph->edge_feat.size() ? graph->edge_feat[dev_id] : nullptr;
+    if (!table) { LEGION_ARG_ERROR((name + ": the graph holds no edge-feature table on this GPU (GPUGraphStorage_SetEdgeFeatures)").c_str()); return; }
+    if (graph->edge_feat_dim != dim) { LEGION_ARG_ERROR((name + ": the graph's edge-feature table has rows of " + std::to_string(graph->edge_feat_dim) + " floats, the pool gathers rows of " + std::to_string(dim) + " (GPUMemoryPool_SetEdgeFeatures)").c_str()); return; }
+    const int last = hop > 0 ? hop : p->hops;   // the last hop whose ids are read
+    if (p->progress.sampled_presc || p->progress.edge_id_hop < last) { LEGION_ARG_ERROR((name + ": the current pipe's batch left no edge ids for this hop: a pre-sampling batch, a batch sampled with edge ids off, or a hop whose GPU_Random_Sampling has not been called").c_str()); return; }
+    if (!pipe_holds(*pipe, {Pool::kEdgeIds, Pool::kEdgeFeat}, (name + ": edge features without the pool's per-pipe buffers (the mode was set before GPUMemoryPool_AllocateScratch failed?)").c_str(), p->edge_feat_alloc_dim == dim)) return;
+    EdgeGatherArgs a;
+    a.table = table; a.E = graph->edge_num; a.dim = dim;
+    a.edge_ids = pipe->buf<int64_t>(Pool::kEdgeIds); a.ec = pipe->edge_counter; a.hop = hop; a.hops = p->hops;
+    a.out = pipe->buf<float>(Pool::kEdgeFeat); a.ids_cap = p->num_ids;
+    // the static bound of the range: the hop's slots, or every hop's (num_ids less the seeds)
+    const int32_t bound = hop > 0 ? p->level_bound[hop] : p->num_ids - p->level_bound[0];
+    launch_gather_edges((hipStream_t)strm_hdl, a, bound);
+    if (!p->capturing) pipe->edge_feat_filled = true;   // a recording gathers nothing yet: its replay sets the flag (LegionBatchGraph_Launch)
+    p->progress.edge_feat_gathered = true;
+}
+// op_id: the hop's sampling op (2, 4, .., 2 * hops), behind that hop's GPU_Random_Sampling
+void get_edge_feature_kernel(void* strm_hdl, GPUGraphStorage* graph, GPUMemoryPool* memorypool, int32_t dev_id, int32_t op_id)
+{
+    if (memorypool && memorypool->owns_scratch && (op_id < 2 || (op_id & 1) || op_id / 2 > memorypool->hops)) { LEGION_ARG_ERROR("get_edge_feature_kernel: op_id must be 2,4,..,2*hops"); return; }
+    edge_feature_gather(strm_hdl, graph, memorypool, dev_id, op_id / 2, "get_edge_feature_kernel");
+}
+// every edge of the batch in one launch, behind the last hop's GPU_Random_Sampling: the bytes of the per-hop calls
+void get_edge_feature_kernel_all(void* strm_hdl, GPUGraphStorage* graph, GPUMemoryPool* memorypool, int32_t dev_id)
+{
+    edge_feature_gather(strm_hdl, graph, memorypool, dev_id, 0, "get_edge_feature_kernel_all");
 }
 
 // ---- owner-computes exchange variant of the gather (SURVEY 5 option b), one process per GPU ---------------------------------

@@ -30,6 +30,10 @@ GPUMemoryPool::GPUMemoryPool(int32_t depth) : pipeline_depth(depth > 0 ? depth :
 // "Has been in the mode", once: the mode is on, or cols is there -- the one allocation every switch on makes on a pool that owns scratch and
 // only release_scratch takes back.  (A pool without a device allocates nothing, so it lists the buffers exactly while the mode is on.)
 static bool lists_edge_ids(const GPUMemoryPool* p) { return p->modes.edge_ids || p->cols; }
+// The buffer of the edge-feature mode (GPUMemoryPool_SetEdgeFeatures) by the same rule: edge_feat (batch, per pipe), float32 [num_ids, dim], an
+// output no launch reads, joins the list behind edge_w once the pool has been in the mode -- the mode is on, or the pipes hold the buffer
+// (edge_feat_alloc_dim: the width they were allocated for, which only release_scratch forgets) -- at the width it is held at.
+static int32_t listed_edge_feat_dim(const GPUMemoryPool* p) { return p->modes.edge_feat_dim > 0 ? p->modes.edge_feat_dim : p->edge_feat_alloc_dim; }
 std::vector<ScratchBuffer> legion::pool_scratch(GPUMemoryPool* p)
 {
     const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots, tiles = (size_t)p->max_tiles + 1;
@@ -67,12 +71,19 @@ std::array<PipeBuffer, GPUMemoryPool::kPipeBufs> legion::pool_pipe_buffers(const
              {Pool::kAggChunkCnt, (size_t)kMaxChunks * sizeof(int32_t), wdraw, true, "agg_chunk_cnt", LEGION_SCRATCH_COUNT, I, batch},
              // an edge id is one 8-byte word no kernel reads back: any bytes are safe in it, a pair of counts is what the poison's kinds offer
              {Pool::kEdgeIds, ids * sizeof(int64_t), eid, eid_listed, "edge_ids", LEGION_SCRATCH_COUNT_PAIR, sizeof(int64_t), batch},
-             {Pool::kEdgeW, ids * sizeof(float), eid, eid_listed, "edge_w", LEGION_SCRATCH_FLOAT, sizeof(float), batch}}};
+             {Pool::kEdgeW, ids * sizeof(float), eid, eid_listed, "edge_w", LEGION_SCRATCH_FLOAT, sizeof(float), batch},
+             {Pool::kEdgeFeat, ids * (size_t)listed_edge_feat_dim(p) * sizeof(float), p->modes.edge_feat_dim > 0, listed_edge_feat_dim(p) > 0, "edge_feat", LEGION_SCRATCH_FLOAT, sizeof(float), batch}}};
 }
 // on the current device: what the pool's modes want and is missing is allocated, what is there stays
 static void alloc_mode_buffers(GPUMemoryPool* p)
 {
     if (!p->owns_scratch) return;
+    if (p->modes.edge_feat_dim > 0 && p->edge_feat_alloc_dim != p->modes.edge_feat_dim) {   // another row width: the pipes' buffers are reallocated below
+        if (p->edge_feat_alloc_dim) HIP_CHECK(hipDeviceSynchronize());                      // a gather into the old ones may still be in flight
+        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[GPUMemoryPool::kEdgeFeat]); pipe.edge_feat_filled = false; }
+        p->edge_feat_alloc_dim = p->modes.edge_feat_dim;
+        p->edge_feat_gen++;
+    }
     for (const PipeBuffer& b : pool_pipe_buffers(p))
         for (GPUMemoryPool::Pipe& pipe : p->pipes)
             if (b.wanted && !pipe.own[b.which]) HIP_CHECK(hipMalloc(&pipe.own[b.which], b.bytes));
@@ -84,7 +95,9 @@ static void release_scratch(GPUMemoryPool* p)
 {
     for (const ScratchBuffer& b : pool_scratch(p)) free_and_null(*b.slot);
     for (const PipeBuffer& b : pool_pipe_buffers(p))   // every row, listed or not: with cols null again the pool lists the edge-id rows only while the mode is on
-        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[b.which]); pipe.edge_w_filled = false; }
+        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[b.which]); pipe.edge_w_filled = pipe.edge_feat_filled = false; }
+    p->edge_feat_alloc_dim = 0;
+    p->edge_feat_gen++;
 }
 static void release_ctl(GPUMemoryPool* p) { free_and_null(p->ctl); }
 static void release_rows_seen(GPUMemoryPool* p)
@@ -115,6 +128,14 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
     if (wanted.agg_edge_weight && !wanted.agg_last_hop && !p->modes.agg_edge_weight) { LEGION_ARG_ERROR((name + ": edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) on a pool that does not aggregate the last hop (GPUMemoryPool_SetAggLastHop first): only neighbour sums are scaled").c_str()); return false; }
     if (wanted.agg_edge_weight && !wanted.edge_ids) { LEGION_ARG_ERROR((name + ": edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) need edge ids (GPUMemoryPool_SetEdgeIds first, and not off while the flag is on): the weight of a draw is the edge_w that mode hands over").c_str()); return false; }
     if (wanted.agg_edge_weight && wanted.agg_norm) { LEGION_ARG_ERROR((name + ": edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) together with a norm (GPUMemoryPool_SetAggNorm): GraphConv(norm='both', edge_weight=) rounds twice per product and has no kernel in this build").c_str()); return false; }
+    // edge features are gathered by the ids the edge-id mode leaves: refused in the name of whichever setter comes second
+    if (wanted.edge_feat_dim < 0) { LEGION_ARG_ERROR((name + ": negative edge-feature width (0 = off, dim > 0 = float32 [edges, dim] per batch)").c_str()); return false; }
+    if (wanted.edge_feat_dim > 0 && !wanted.edge_ids) { LEGION_ARG_ERROR((name + ": edge features (GPUMemoryPool_SetEdgeFeatures) need edge ids (GPUMemoryPool_SetEdgeIds first, and not off while the mode is on): a row is gathered by the id that mode hands over").c_str()); return false; }
+    if (wanted.edge_feat_dim > 0) {
+        int64_t bytes = 0;
+        if (__builtin_mul_overflow((int64_t)p->num_ids * (int64_t)sizeof(float), (int64_t)wanted.edge_feat_dim, &bytes)) { LEGION_ARG_ERROR((name + ": edge features (GPUMemoryPool_SetEdgeFeatures): the size of the per-pipe buffer, NumIds * dim * 4 bytes, overflows").c_str()); return false; }
+        if ((int64_t)p->num_ids * edge_gather_chunks(wanted.edge_feat_dim) >= (1ll << 31)) { LEGION_ARG_ERROR((name + ": edge features (GPUMemoryPool_SetEdgeFeatures): NumIds * chunks per row reaches 2^31 work items (a row is gathered in 16-byte chunks where dim % 4 == 0, else float by float)").c_str()); return false; }
+    }
     if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
     if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k
@@ -205,6 +226,16 @@ float* GPUMemoryPool_GetEdgeWeightBuffer(const GPUMemoryPool* p)
 {
     if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeWeightBuffer: null pool"); return nullptr; }
     return p->pipe().edge_w_filled ? p->pipe().buf<float>(GPUMemoryPool::kEdgeW) : nullptr;
+}
+// edge features ("Edge features"): dim > 0 = behind get_edge_feature_kernel(_all) the pipe holds edge_feat[e, :] = X[edge_ids[e], :], X the graph's
+// table (GPUGraphStorage_SetEdgeFeatures); 0 = off.  Only with edge ids.  Allocates edge_feat (num_ids * dim floats per pipe); another dim reallocates it
+void GPUMemoryPool_SetEdgeFeatures(GPUMemoryPool* p, int32_t dim) { ServeModes m = modes_of(p); m.edge_feat_dim = dim; pool_apply_modes(p, m, "GPUMemoryPool_SetEdgeFeatures"); }
+int32_t GPUMemoryPool_GetEdgeFeatures(const GPUMemoryPool* p) { return p ? p->modes.edge_feat_dim : 0; }
+// the current pipe's buffer, float32 [legion_batch_edges(ec, H), dim] in the order of the COO; null unless the pipe's last batch was gathered
+float* GPUMemoryPool_GetEdgeFeatureBuffer(const GPUMemoryPool* p)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeFeatureBuffer: null pool"); return nullptr; }
+    return p->pipe().edge_feat_filled ? p->pipe().buf<float>(GPUMemoryPool::kEdgeFeat) : nullptr;
 }
 void GPUMemoryPool_SetSampleSeed(GPUMemoryPool* p, int on, uint32_t seed)
 {

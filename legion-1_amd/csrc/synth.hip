@@ -78,6 +78,22 @@ __global__ void k_synth_edge_weights(float* out, int64_t e0, int64_t n)
     }
 }
 
+// edge feature (e, c): the top 24 bits of a 32-bit mix of the entry's position and the column -- an integer in [0, 2^24), exact in float32;
+// another row and another column both give another value (synth.py edge_features() is the NumPy statement)
+constexpr uint32_t kEdgeFeatTag = 0x45464541u;   // "EFEA"
+__host__ __device__ inline uint32_t synth_edge_feature(uint64_t e, uint32_t c)
+{
+    return mix32(mix32((uint32_t)e ^ mix32((uint32_t)(e >> 32) ^ kEdgeFeatTag)) + c * kGolden) >> 8;
+}
+__global__ void k_synth_edge_features(float* out, int64_t e0, int64_t n, int32_t dim)
+{
+    const int64_t total = n * dim;
+    for (int64_t i = threadIdx.x + (int64_t)blockDim.x * blockIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / dim;
+        out[i] = (float)synth_edge_feature((uint64_t)(e0 + r), (uint32_t)(i - r * dim));
+    }
+}
+
 // out[k] = (i*M2 + C2) % V for i = i0 + phase + k*stride  (stride/phase: the tid % G split of a
 // permutation-ordered seed list cannot be written in closed form, so the split is done by the
 // caller; stride = 1, phase = 0 yields the plain list)
@@ -236,6 +252,15 @@ void legion_synth_edge_weights(void* stream, float* out, int64_t e0, int64_t n)
     if (!out || e0 < 0) { LEGION_ARG_ERROR("legion_synth_edge_weights: bad arguments"); return; }
     LEGION_AUDIT_LAUNCH((hipStream_t)stream, "k_synth_edge_weights", LEGION_AW(out));
     k_synth_edge_weights<<<big_grid(n), 256, 0, (hipStream_t)stream>>>(out, e0, n);
+    HIP_CHECK_LAST();
+}
+void legion_synth_edge_features(void* stream, float* out, int64_t e0, int64_t n, int32_t dim)
+{
+    if (n <= 0) return;
+    int64_t total = 0;
+    if (!out || e0 < 0 || dim < 1 || __builtin_mul_overflow(n, (int64_t)dim, &total)) { LEGION_ARG_ERROR("legion_synth_edge_features: bad arguments"); return; }
+    LEGION_AUDIT_LAUNCH((hipStream_t)stream, "k_synth_edge_features", LEGION_AW(out));
+    k_synth_edge_features<<<big_grid(total), 256, 0, (hipStream_t)stream>>>(out, e0, n, dim);
     HIP_CHECK_LAST();
 }
 void legion_synth_labels(void* stream, int32_t* out, int32_t v0, int32_t n, int32_t classes)

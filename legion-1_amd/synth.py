@@ -209,6 +209,35 @@ def edge_weights(E: int, e0: int = 0) -> np.ndarray:
     return np.where(((h & _U64(15)) != 0) & ((hb & _U64(15)) != 0), w, _U64(0)).astype(np.float32)
 
 
+def mix32(z):
+    """csrc/internal.h mix32 on a uint32 array (wrapping arithmetic)."""
+    z = np.asarray(z, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint32(16))) * np.uint32(0x7FEB352D)
+        z = (z ^ (z >> np.uint32(15))) * np.uint32(0x846CA68B)
+        return z ^ (z >> np.uint32(16))
+
+
+EDGE_FEAT_TAG, GOLDEN32 = 0x45464541, 0x9E3779B9
+
+
+def edge_features(e0: int, n: int, dim: int) -> np.ndarray:
+    """float32[n, dim]: rows [e0, e0 + n) of the synthetic per-edge table (legion_synth_edge_features): element (e, c) is the top 24 bits of a
+    32-bit mix of the CSR entry's position and the column -- an integer in [0, 2^24), exact in float32, another one for another row and for
+    another column."""
+    return edge_features_at(np.arange(e0, e0 + n, dtype=np.uint64), dim)
+
+
+def edge_features_at(e, dim: int) -> np.ndarray:
+    """float32[len(e), dim]: the rows of edge_features() at the CSR positions e, in that order."""
+    e = np.asarray(e, dtype=np.uint64).reshape(-1, 1)
+    c = np.arange(dim, dtype=np.uint32).reshape(1, -1)
+    lo, hi = (e & _U64(0xFFFFFFFF)).astype(np.uint32), (e >> _U64(32)).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        row = mix32(lo ^ mix32(hi ^ np.uint32(EDGE_FEAT_TAG)))
+        return (mix32(row + c * np.uint32(GOLDEN32)) >> np.uint32(8)).astype(np.float32)
+
+
 def seed_ids(spec: SynthSpec, i0: int, i1: int) -> np.ndarray:
     i = np.arange(i0, i1, dtype=np.uint64)
     with np.errstate(over="ignore"):
