@@ -13,6 +13,10 @@ Every other shape of the suite outside the BASELINE-shape tests (the reference's
 batch 0's hop 2 has about 20 x CUs tiles (T = 6, two to three tiles per k_write workgroup, five to six per k_sample workgroup) and the
 short last batch's about 6.7 x CUs (T = 2, one tile per k_write workgroup): regime() is that arithmetic, B follows the device's CU count.
 
+The aggregated last hop's slot -> edge prefix (k_draw_weights, k_draw_edge_weights: csrc/gather.hip) runs over its own chunks of the same
+slots: weight_chunks() is that arithmetic -- ten or eleven steps of 256 slots per workgroup in batch 0, four in the short batch, whose last
+chunks are empty; every other shape of the suite has chunks of one step.
+
 Every statement is eidref.run_batch (the alias rule, which hands no edge ids over: weightedref.run_batch); nothing here restates a rule."""
 import numpy as np
 
@@ -108,6 +112,33 @@ def assert_regimes(slots0, slots1, cus):
     assert tiles > 16 * cus and T >= 3 and n_chunks <= MAX_CHUNKS and per_write >= 2, (tiles, T, n_chunks, per_write)
     tiles, T, n_chunks, per_write = regime(slots1, cus, bound)
     assert 4 * cus < tiles <= 8 * cus and T == 2 and n_chunks <= MAX_CHUNKS and per_write == 1, (tiles, T, n_chunks, per_write)
+
+
+BLOCK = 256                                         # kBlock (csrc/internal.h): the slots a workgroup of the slot -> edge passes takes per step
+WEIGHT_WG_PER_CU = 8                                # grid_for's default (csrc/launch.h): launch_agg_norm_weights' and launch_agg_edge_weights' grid
+
+
+def weight_chunks(slots, bound, cus):
+    """(chunk_len, non_empty_chunks, grid) of the slot -> edge prefix of an aggregated last hop of `slots` slots whose static bound is `bound`
+    slots, as launch_agg_edge_weights / launch_agg_norm_weights (the grid: one workgroup per 256 slots of the bound, at most 8 per compute
+    unit and kMaxChunks) and agg_norm_chunk_len (the slots over the grid, rounded up to 256) derive them (csrc/gather.hip).  A workgroup takes
+    chunk_len / 256 steps of its loop; the chunks from non_empty_chunks on have lo == hi == slots."""
+    up = lambda a, b: -(-int(a) // int(b))
+    assert 0 < slots <= bound
+    grid = min(MAX_CHUNKS, up(bound, BLOCK), WEIGHT_WG_PER_CU * cus)
+    chunk_len = up(up(slots, grid), BLOCK) * BLOCK
+    return chunk_len, up(slots, chunk_len), grid
+
+
+def assert_weight_regimes(slots0, slots1, cus):
+    """what the edge-weighted case of this shape exists for: in both batches a workgroup of k_draw_edge_weights takes at least two steps (the
+    carry of the rank from one step to the next, the barrier behind a step), and the short batch leaves whole chunks empty"""
+    bound = slots_bound(2, cus)
+    for slots in (slots0, slots1):
+        chunk_len, filled, grid = weight_chunks(slots, bound, cus)
+        assert chunk_len >= 2 * BLOCK and 1 < filled <= grid, (slots, chunk_len, filled, grid)
+    chunk_len, filled, grid = weight_chunks(slots1, bound, cus)
+    assert filled < grid, (slots1, chunk_len, filled, grid)
 
 
 def statement(g, rule, counter, alias=None, ties=None, cus=CUS):

@@ -109,3 +109,19 @@ def test_the_statement_reaches_the_later_tiles(batches, rule):
     # the new nodes of hop 2, in the order of their first slots, are the batch's ids behind hop 1's
     won = new & (first == slot)
     assert np.array_equal(ids[won], res["ids"][int(res["nc"][7]):])
+
+
+def test_the_edge_weighted_prefix_takes_several_steps_per_chunk(batches):
+    """k_draw_edge_weights at 256 compute units (tests/test_gpu_deep_tiles.py::test_edge_weighted_last_hop_over_five_million_slots): the grid is
+    min(kMaxChunks, ceil(5 248 000 / 256), 8 x 256) = 2048 workgroups, so batch 0's 5.2 million slots make chunks of 2560 or 2816 slots -- ten or
+    eleven steps of the kernel's loop -- and the short batch's 1.7 million chunks of 1024, four steps, with the last chunks empty.  Every
+    shape of tests/test_gpu_agg_edge_weight.py has chunks of exactly 256 slots: one step."""
+    assert X.weight_chunks(1280, 1280, X.CUS) == (256, 5, 5) and X.weight_chunks(4097 * 64, 4097 * 64, X.CUS) == (256, 1025, 1025)
+    bound = X.slots_bound(2)
+    assert bound == 20500 * 256 and X.weight_chunks(bound, bound, X.CUS) == (2816, 1864, 2048)
+    s0, s1 = (X.hop2_slots(batches[("distinct", it)][0]) for it in X.COUNTERS)
+    X.assert_weight_regimes(s0, s1, X.CUS)
+    len0, filled0, grid0 = X.weight_chunks(s0, bound, X.CUS)
+    len1, filled1, grid1 = X.weight_chunks(s1, bound, X.CUS)
+    assert grid0 == grid1 == 2048 and len0 in (2560, 2816) and len1 == 1024 and filled1 < 2048
+    assert len0 * (filled0 - 1) < s0 <= len0 * filled0 and len1 * (filled1 - 1) < s1 <= len1 * filled1

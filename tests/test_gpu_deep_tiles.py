@@ -12,6 +12,9 @@ last batch about 6.7 x CUs.  What a failure of a case here points at, beyond wha
                              0 only, from tile 8 x CUs on: the reload; throughout: the chunk prefix.
   k_edge_ids                 its own copy of the chunk prefix and of the tile loop: edge_ids / edge_w wrong where src_off is right.
   k_draw_weights             the slot -> edge prefix of the aggregated last hop over the same chunks, from cand_pipe.
+  k_draw_edge_weights        its own copy of that prefix for the edge-weighted sums: chunks of ten or eleven steps of 256 slots (four in the
+                             short batch, whose last chunks are empty), where every other shape of the suite has chunks of one step.  A wrong
+                             nbr_sum from a chunk's second step on (slot % chunk_len >= 256): the rank carried from step to step.
 
 deepcases.regime() gives the tile, chunk (tile // T) and workgroup stride (4 x CUs for k_sample and k_mark, 8 x CUs for k_write and
 k_edge_ids) of a differing index: slot = index of the hop's draw, tile = slot // 1024.  Every comparison is array_equal, weights by bit
@@ -22,8 +25,10 @@ import pytest
 import deepcases as X
 import eidref as R
 import scratchpoison as P
+from aggcases import assert_sum_bits
 from conftest import KEYS_NO_FEATURES, assert_batch_equal
 from distinctcases import expected_sums
+from edgeaggref import expected_nbr_sum_edge
 from eidref import assert_edge_ids, bits
 from harness import K, make_engine  # noqa: F401  (K: the module-scoped library fixture)
 
@@ -180,3 +185,29 @@ def test_aggregated_last_hop_over_five_million_slots(K, engines):
     assert np.array_equal(on["out_deg"], d) and np.array_equal(off["out_deg"], d)
     assert np.array_equal(bits(on["features"]), bits(want["features"][:n_in]))
     assert np.array_equal(bits(on["nbr_sum"]), bits(S))
+
+
+def test_edge_weighted_last_hop_over_five_million_slots(K, engines):
+    """k_draw_edge_weights<count> and k_draw_edge_weights behind a T >= 3 hop: the distinct rule's batch 0 and its short last batch handed over
+    as neighbour sums scaled by each draw's edge weight.  The grid is min(kMaxChunks, ceil(bound / 256), 8 x CUs) workgroups and a chunk the
+    slots over the grid rounded up to 256 (deepcases.weight_chunks, from the device's own counters and CU count): here every workgroup takes
+    several steps of its loop, carrying the rank of its slots from one step to the next, and the short batch leaves the last chunks empty --
+    tests/test_gpu_agg_edge_weight.py's shapes have chunks of exactly one step.  The batch and its ids equal the statement (tests/eidref.py),
+    the sums have the bits of tests/edgeaggref.py's."""
+    eng = engines.whole()
+    slots = []
+    for it in X.COUNTERS:
+        want = engines.statement("distinct", it)
+        eng.run_batch(0, it, agg_last_hop=True, edge_ids=True, agg_edge_weight=True, **R.ENGINE_ARGS["distinct"])
+        assert K.lib().GPUMemoryPool_GetAggEdgeWeight(eng.pools[0]) == 1
+        got = eng.result(0)
+        assert_edge_ids(want, got)
+        n_in, N, _, S = expected_nbr_sum_edge(want, engines.g["indptr"], engines.g["indices"], X.FAN)
+        assert N * X.FAN[1] == X.hop2_slots(got) and got["features"].shape == (n_in, X.F) and got["nbr_sum"].shape == S.shape
+        assert np.array_equal(bits(got["features"]), bits(want["features"][:n_in]))
+        assert not np.isnan(S).any() and (want["edge_w"] == 0).any()
+        assert_sum_bits("edge-weighted, batch %d" % it, got["nbr_sum"], S)
+        slots.append(X.hop2_slots(got))
+    X.assert_weight_regimes(slots[0], slots[1], engines.cus)
+    print("weight_chunks at %d CUs: %s, %s" % (engines.cus, X.weight_chunks(slots[0], X.slots_bound(2, engines.cus), engines.cus),
+                                               X.weight_chunks(slots[1], X.slots_bound(2, engines.cus), engines.cus)))

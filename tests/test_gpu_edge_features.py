@@ -1,8 +1,8 @@
 """The edge-feature mode on the GPU (GPUMemoryPool_SetEdgeFeatures: k_gather_edges behind get_edge_feature_kernel / _all, INTEGRATION.md "Edge
 features") against the NumPy statement of tests/efref.py, edge_feat[e, :] = X[edge_ids[e], :]: every row width at which the kernel takes
 another path, both launchers, the clique's fragments, a grid that loops, a poisoned output buffer, two pipes, a table indexed beyond 2^31
-floats, recorded graphs and the refusals.  Every comparison is by bit pattern.  Graph and shapes: tests/drawrulecases.py (multi-edges,
-zero-degree rows, holes).  Run with `pytest -m gpu`."""
+floats, recorded graphs, the gather on a second stream beside the next batch's sampler, and the refusals.  Every comparison is by bit
+pattern.  Graph and shapes: tests/drawrulecases.py (multi-edges, zero-degree rows, holes).  Run with `pytest -m gpu`."""
 import ctypes as C
 
 import numpy as np
@@ -268,6 +268,67 @@ def test_recorded_graph_and_its_refusals(K, engines):
     finally:
         L.legion_clear_error()
         eng.close()
+
+
+# ---- beside the next batch's sampler ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", (3, 20))
+def test_edge_rows_gathered_beside_the_next_batchs_sampler(K, engines, g, dim):
+    """k_gather_edges reads only the batch's pipe and the table, so it can run beside the next batch's sampler.  Depth 2, the schedule of
+    tests/test_gpu_agg_edge_weight.py::test_overlapped_two_stream_schedule_and_the_graphs_refusals: batch i + 1 is sampled (a recorded
+    LegionBatchGraph per pipe) on one stream while get_edge_feature_kernel_all of batch i runs on the other, behind an event.  The sampler of
+    batch i + 1 overwrites the pool's draw buffer, columns and slot states and sets the pool's per-batch host state meanwhile.  So that the
+    rows read back are the second stream's, the pipe's buffer is filled with NaN words on that stream in front of its gather (the recorded
+    batch gathers once itself).  dim 3: the scalar kernel; dim 20: the 16-byte one."""
+    import eidref
+    L = K.lib()
+    eng, X = engines.make(dim, pipeline_depth=2), engines.table(dim)
+    B, fan = D.SHAPES["narrow"]
+    seeds = D.seed_list("narrow")
+    s_samp, s_gath = L.d_stream_create(), L.d_stream_create()
+    try:
+        L.GPUCache_SetPreSc(eng.cache, 0)
+        pool = eng.pools[0]
+        ev_sampled, ev_gathered = [L.d_event_create(), L.d_event_create()], [L.d_event_create(), L.d_event_create()]
+        used = [False, False]
+        graphs = [eng.capture_batch(0, gather=False, pipe=q, stream=s_samp, sample="distinct", edge_ids=True, edge_features=True) for q in (0, 1)]
+        assert L.GPUMemoryPool_GetEdgeFeatures(pool) == dim and L.GPUMemoryPool_GetEdgeIds(pool) == 1
+        bufs = [feat_buffer(K, eng, q) for q in (0, 1)]
+        assert bufs[0][0] != bufs[1][0]
+        want = {it: eidref.run_batch(g, "distinct", seeds, g["labels"][seeds], B, it, fan) for it in D.COUNTERS}
+
+        def enqueue(i, counter):
+            q = i % 2
+            L.GPUMemoryPool_SetCurrentPipe(pool, q)
+            L.GPUMemoryPool_SetCurrentMode(pool, K.TRAINMODE)
+            if used[q]:
+                L.d_stream_wait_event(s_samp, ev_gathered[q])
+            eng.run_graph(graphs[q], counter, sync=False)
+            L.d_event_record(ev_sampled[q], s_samp)
+            L.d_stream_wait_event(s_gath, ev_sampled[q])
+            L.d_memset_async(bufs[q][0], 0xFF, bufs[q][1], s_gath)
+            L.get_edge_feature_kernel_all(s_gath, eng.graph, pool, 0)
+            L.d_event_record(ev_gathered[q], s_gath)
+            used[q] = True
+
+        counters = [0, 1, 1, 0, 1, 0]
+        enqueue(0, counters[0])
+        for i, it in enumerate(counters):
+            if i + 1 < len(counters):
+                enqueue(i + 1, counters[i + 1])          # batch i + 1 is sampled while batch i's edge rows are still being gathered
+            L.d_stream_sync(s_samp)
+            L.d_stream_sync(s_gath)
+            K.check()
+            got = eng.result(0, pipe=i % 2, with_features=False, edge_ids=True, edge_features=True)
+            eidref.assert_edge_ids(want[it], got, weights=False)
+            assert_edge_feat(X, got)
+            n = len(got["edge_ids"]) * dim
+            rest = K.read_dev(bufs[i % 2][0], np.uint32, bufs[i % 2][1] // 4)[n:]
+            assert len(rest) and (rest == 0xFFFFFFFF).all()              # ... and behind the batch's rows the second stream's fill is untouched
+    finally:
+        L.legion_clear_error()
+        eng.close()
+        for s in (s_samp, s_gath):
+            L.d_stream_destroy(s)
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------
