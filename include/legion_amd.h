@@ -838,7 +838,9 @@ void legion_copy_f4(void* stream, void* dst, const void* src, int64_t bytes);
 void legion_sum_words(void* stream, const void* src, int64_t bytes, uint64_t* acc);
 /* the same copy with an explicit variant (profiles/copy_sweep.py): 256-thread workgroups, `unroll` 16-byte chunks in
  * flight per lane (1, 2, 4, 8), nt bit 0 = non-temporal stores, bit 1 = non-temporal loads, contig = block-strided;
- * grid <= 0: one iteration per lane.  Returns 0, or -1 for an unknown variant. */
+ * grid <= 0: one iteration per lane.  Returns 0, or -1 for an unknown variant (a sticky error; nothing is launched).
+ * dst and src are 16-byte aligned and are not checked.  Whole 16-byte chunks are copied: n = bytes / 16 of them, so with
+ * bytes % 16 != 0 the trailing bytes % 16 bytes of dst are left as they are, and bytes < 16 (bytes <= 0 included) copies nothing. */
 int legion_copy_f4_cfg(void* stream, void* dst, const void* src, int64_t bytes, int32_t grid, int32_t unroll, int32_t nt, int32_t contig);
 
 /* ---- self-description for tests ------------------------------------------------------------ */

@@ -352,11 +352,17 @@ void legion_synth_seed_ids(void* stream, int32_t* out, int64_t i0, int64_t n, in
     k_synth_seed_ids<<<big_grid(n), 256, 0, (hipStream_t)stream>>>(out, i0, n, (uint32_t)V, M2, C2, stride, phase);
     HIP_CHECK_LAST();
 }
-// variant: unroll in {1,2,4,8}, nt in 0..3, contig 0/1; grid <= 0: one iteration per lane
+// variant: unroll in {1,2,4,8}, nt in 0..3, contig 0/1; grid <= 0: one iteration per lane; whole 16-byte chunks only (the
+// trailing bytes % 16 bytes of dst are not written: the header's contract)
 int legion_copy_f4_cfg(void* stream, void* dst, const void* src, int64_t bytes, int32_t grid, int32_t unroll, int32_t nt, int32_t contig)
 {
     const int64_t n = bytes / 16;
     if (n <= 0) return 0;
+    // refused before the grid is derived from it: unroll = 0 would divide by zero below
+    if ((unroll != 1 && unroll != 2 && unroll != 4 && unroll != 8) || nt < 0 || nt > 3 || (contig != 0 && contig != 1)) {
+        LEGION_ARG_ERROR("legion_copy_f4_cfg: no such variant");
+        return -1;
+    }
     if (grid <= 0) grid = (int32_t)std::min<int64_t>((n + 256ll * unroll - 1) / (256ll * unroll), 0x7FFFFFFF);
     hipStream_t s = (hipStream_t)stream;
     copy_v4f* d = (copy_v4f*)dst;
