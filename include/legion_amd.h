@@ -577,6 +577,29 @@ int32_t GPUMemoryPool_GetRound(const GPUMemoryPool* p);
  * another lp_draw state; a new round or seed needs no new recording. */
 void GPUMemoryPool_SetLpDraw(GPUMemoryPool* p, int32_t triples_per_batch, GPUGraphStorage* graph);
 int32_t GPUMemoryPool_GetLpDraw(const GPUMemoryPool* p);
+/* Target-edge exclusion (extension; INTEGRATION.md "Target-edge exclusion").  With GPUMemoryPool_SetLpExclude(pool, k), k > 0, a TRAINING batch
+ * of B = 3 k seeds has the target pairs {ids[i], ids[k + i]}, i < k, both ids >= 0 -- read from the batch's own ids, so verbatim lists and
+ * drawn thirds (GPUMemoryPool_SetLpDraw) work alike -- and every COO edge e < legion_batch_edges(ec, H) is marked: edge_keep[e] = 0 where
+ * {ids[dst_off[e]], ids[src_off[e]]} equals a target pair as an unordered pair (both directions, every multi-edge; a pair {s, s} matches
+ * self-loops of s only), 1 otherwise.  lp_excluded[h], 1 <= h <= H, counts the zeros among hop h's edges, lp_excluded[0] is their sum, the
+ * other words of int32[8] are 0.  A batch of another mode, or one whose level-0 size on the device is not 3 k, has every edge kept and all
+ * counts 0.  The edges are marked, not removed, and nothing else of the batch moves; k = 0 is today's behaviour, bit for bit.  The table of the
+ * pairs is built by one launch behind the seed kernel, the marks by one launch behind the last hop's GPU_Random_Sampling, on its stream; a
+ * pre-sampling batch hands nothing over.  Call the setter under the device the pool's scratch lives on: it allocates lp_pairs (uint64 [cap],
+ * cap the smallest power of two >= max(4 k, 64)), edge_keep (NumIds bytes) and lp_excluded per pipe, and a k of another cap reallocates lp_pairs.
+ * Sticky argument errors, by name, in the name of whichever setter comes second: a null pool, k < 0, a switch while the pool is being captured,
+ * the mode together with drawn thirds of another k, the mode together with the aggregated last hop (the sums would contain the excluded
+ * draws); in batch_generator_kernel a training batch under the mode with batch_size != 3 k or on a list whose length is not a multiple of
+ * 3 k.  LegionBatchGraph_Launch refuses a graph recorded in another lp_exclude state.
+ * GPUMemoryPool_GetEdgeKeepBuffer / GetLpExcludedBuffer: the current pipe's buffers (uint8 [legion_batch_edges], int32[8]); null unless the
+ * pipe's last batch ran the marking launch.  legion_lp_pair_slot(lo, hi, cap): the first slot the pair (lo <= hi) is looked for in a table
+ * of cap slots (a power of two), mix32(lo ^ mix32(hi)) & (cap - 1); host code, for tests.
+ * Not served: no LEGION_* variable and no IPC hand-off carry the mode yet. */
+void GPUMemoryPool_SetLpExclude(GPUMemoryPool* p, int32_t triples_per_batch);
+int32_t GPUMemoryPool_GetLpExclude(const GPUMemoryPool* p);
+uint8_t* GPUMemoryPool_GetEdgeKeepBuffer(const GPUMemoryPool* p);
+int32_t* GPUMemoryPool_GetLpExcludedBuffer(const GPUMemoryPool* p);
+uint32_t legion_lp_pair_slot(uint32_t lo, uint32_t hi, uint32_t cap);
 /* Owner-computes exchange variant of the feature gather (SURVEY 5 option b; the reference reads peer caches in-kernel over
  * NVLink, Kernels.cu:662-702 -- this is the collective formulation for one process per GPU, the all-to-all itself is RCCL /
  * hipMemcpyPeer in the caller: legion-1_amd/exchange.py).  plan (requester): rows of the batch cached on another clique member are

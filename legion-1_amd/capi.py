@@ -236,6 +236,11 @@ _SIGS = {
     "GPUMemoryPool_BeginRound": (C.c_int, [vp, vp, vp, i32, i32]),
     "GPUMemoryPool_SetLpDraw": (None, [vp, i32, vp]),
     "GPUMemoryPool_GetLpDraw": (i32, [vp]),
+    "GPUMemoryPool_SetLpExclude": (None, [vp, i32]),
+    "GPUMemoryPool_GetLpExclude": (i32, [vp]),
+    "GPUMemoryPool_GetEdgeKeepBuffer": (vp, [vp]),
+    "GPUMemoryPool_GetLpExcludedBuffer": (vp, [vp]),
+    "legion_lp_pair_slot": (u32, [u32, u32, u32]),
     "GPUMemoryPool_GetRound": (i32, [vp]),
     "legion_exchange_plan": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "legion_exchange_local": (C.c_int, [vp, vp, vp, vp, i32]),
@@ -557,6 +562,7 @@ class Engine:
         self._seed_state = {}   # dev -> (seed or None, round) the pool was last put into (run_batch / capture_batch / run_graph)
         self._norm = {}     # (dev, pipe) -> ... with normalised sums (run_batch(agg_norm="both"))
         self._eid = {}      # (dev, pipe) -> the pipe's last batch left its edge ids (run_batch(edge_ids=True))
+        self._lpx = {}      # (dev, pipe) -> the pipe's last batch had its target edges marked (run_batch(lp_exclude=k))
         self._efeat = {}    # (dev, pipe) -> the row width the pipe's last batch had its edge rows gathered at (run_batch(edge_features=True)), 0: not
         check()
 
@@ -634,8 +640,13 @@ class Engine:
     def run_batch(self, dev=0, counter=0, mode=TRAINMODE, is_presc=False, gather=True, plan=True, pipe=0,
                   batch_size=None, per_level=True, stream=None, sync=True, agg_last_hop=False, agg_norm=None, sample="replace",
                   seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False, agg_edge_weight=False,
-                  edge_features=False):
-        """edge_features (GPUMemoryPool_SetEdgeFeatures, only with edge_ids=True on an Engine with an edge-feature table): the batch additionally
+                  edge_features=False, lp_exclude=0):
+        """lp_exclude: 0, or k > 0 (GPUMemoryPool_SetLpExclude): a training batch of 3 k seeds [src | pos | neg] additionally leaves edge_keep[e] = 0
+        for every COO edge that joins a target pair {ids[i], ids[k + i]}, either direction, and 1 for every other, with the zeros per hop in
+        lp_excluded (INTEGRATION.md "Target-edge exclusion"); result() then returns `edge_keep` uint8 [n_edges] and `lp_excluded` int32[8].  A
+        batch of another mode keeps every edge; a pre-sampling batch marks nothing.  Refused by the library together with agg_last_hop and with an
+        lp_draw of another k.  Set on every call like `lp_draw`.
+        edge_features (GPUMemoryPool_SetEdgeFeatures, only with edge_ids=True on an Engine with an edge-feature table): the batch additionally
         leaves edge_feat[e, :] = X[edge_ids[e], :] in the pipe's buffer -- gathered per hop (get_edge_feature_kernel) where the node rows are
         gathered per level, else in one launch behind the last hop (get_edge_feature_kernel_all); result() then returns `edge_feat` float32
         [n_edges, dim].  A pre-sampling batch gathers nothing.  Set on every call like `edge_ids`.
@@ -671,7 +682,8 @@ class Engine:
         L, pool = self.L, self.pools[dev]
         # a pre-sampling batch aggregates nothing; gather=False: the sampler side of an aggregated batch (the last hop's draws kept per pipe)
         agg, norm = self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, is_presc=is_presc, lp_draw=lp_draw, weighted_distinct=weighted_distinct,
-                                     shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight, edge_features=edge_features)
+                                     shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight, edge_features=edge_features, lp_exclude=lp_exclude)
+        self._lpx[(dev, pipe)] = bool(lp_exclude) and not is_presc
         efeat = bool(edge_features) and not is_presc
         ef_per_hop = efeat and gather and per_level
         self._eid[(dev, pipe)] = bool(edge_ids) and not is_presc
@@ -705,7 +717,7 @@ class Engine:
             check()
 
     def _set_modes(self, dev, agg, norm, sample, seed, round, stream, is_presc=False, lp_draw=0, weighted_distinct=False, shared_draws=False, edge_ids=False,
-                   agg_edge_weight=False, edge_features=False):
+                   agg_edge_weight=False, edge_features=False, lp_exclude=0):
         """The pool's serving modes := the arguments of run_batch / capture_batch, validated; the library is only called for what differs
         (inside a capture nothing does: capture_batch set everything before Begin).  Returns (aggregated, normalised) as set."""
         if norm not in (None, "both"):
@@ -738,6 +750,11 @@ class Engine:
         rule = (("replace", "distinct", "weighted").index(sample), int(bool(weighted_distinct)))
         # the edge-weighted sums sit on top of the aggregated mode and of edge ids, and exclude a norm: off in front of everything they depend on, on behind it
         ew = int(bool(agg_edge_weight) and agg)
+        # target-edge exclusion is refused together with the aggregated last hop and with drawn thirds of another k: off (or at its new k) in front of both
+        # (a pre-sampling batch marks nothing)
+        lpx = 0 if is_presc else int(lp_exclude)
+        if L.GPUMemoryPool_GetLpExclude(pool) != lpx and (agg or lpx == 0 or (L.GPUMemoryPool_GetLpDraw(pool) not in (0, lpx))):
+            L.GPUMemoryPool_SetLpExclude(pool, 0)
         eid_off = L.GPUMemoryPool_GetEdgeIds(pool) and (not edge_ids or rule != (L.GPUMemoryPool_GetSampling(pool), L.GPUMemoryPool_GetWeightedDistinct(pool)))
         if L.GPUMemoryPool_GetAggEdgeWeight(pool) and (not ew or eid_off):
             L.GPUMemoryPool_SetAggEdgeWeight(pool, 0)
@@ -760,6 +777,9 @@ class Engine:
             L.GPUMemoryPool_SetEdgeFeatures(pool, ef)
             check()
         self._set_seed(dev, seed, round, stream, lp_draw)
+        if L.GPUMemoryPool_GetLpExclude(pool) != lpx:   # allocates on the first switch on, reallocates the pair table at another capacity
+            L.GPUMemoryPool_SetLpExclude(pool, lpx)
+            check()
         return agg, bool(norm)
 
     def _set_seed(self, dev, seed, round, stream, lp_draw=0):
@@ -779,12 +799,12 @@ class Engine:
     # ---- the same batch recorded once as a hipGraph (one launch per batch) ---------------------------------------
     def capture_batch(self, dev=0, mode=TRAINMODE, gather=True, plan=True, pipe=0, batch_size=None, per_level=True,
                       stream=None, agg_last_hop=False, agg_norm=None, sample="replace", seed=None, round=0, lp_draw=0, weighted_distinct=False, shared_draws=False,
-                      edge_ids=False, agg_edge_weight=False, edge_features=False):
+                      edge_ids=False, agg_edge_weight=False, edge_features=False, lp_exclude=0):
         """Record run_batch(dev, <any counter>, mode, ...) on `stream`; returns the graph handle for run_graph().  A graph recorded with a
         seed replays only while the pool is seeded (and the other way round); the seed's value and the round may change between replays:
         run_graph(..., seed=, round=).  lp_draw: as run_batch; a graph replays only in the lp_draw state it was recorded in, and
-        only in the weighted_distinct, the shared_draws, the edge_ids and the agg_edge_weight state, and at the edge-feature width, it was
-        recorded in."""
+        only in the weighted_distinct, the shared_draws, the edge_ids, the agg_edge_weight and the lp_exclude state, and at the edge-feature
+        width, it was recorded in."""
         L = self.L
         L.SetGPUDevice(dev)
         if stream is None:
@@ -793,14 +813,14 @@ class Engine:
             stream = self.streams[dev]
         # a recording keeps its modes, and setting them allocates (the aggregated modes' buffers, the shuffled copy): not between Begin and End
         self._set_modes(dev, agg_last_hop, agg_norm, sample, seed, round, stream, lp_draw=lp_draw, weighted_distinct=weighted_distinct, shared_draws=shared_draws,
-                        edge_ids=edge_ids, agg_edge_weight=agg_edge_weight, edge_features=edge_features)
+                        edge_ids=edge_ids, agg_edge_weight=agg_edge_weight, edge_features=edge_features, lp_exclude=lp_exclude)
         if L.GPUMemoryPool_BeginBatchCapture(self.pools[dev], stream) != 0:
             check()
             raise RuntimeError("BeginBatchCapture failed")
         self.run_batch(dev, 0, mode=mode, gather=gather, plan=plan, pipe=pipe, batch_size=batch_size, per_level=per_level,
                        stream=stream, sync=False, agg_last_hop=agg_last_hop, agg_norm=agg_norm, sample=sample, seed=seed, round=round, lp_draw=lp_draw,
                        weighted_distinct=weighted_distinct, shared_draws=shared_draws, edge_ids=edge_ids, agg_edge_weight=agg_edge_weight,
-                       edge_features=edge_features)
+                       edge_features=edge_features, lp_exclude=lp_exclude)
         g = L.GPUMemoryPool_EndBatchCapture(self.pools[dev], stream)
         check()
         if not g:
@@ -823,8 +843,10 @@ class Engine:
             self.L.d_stream_sync(stream)
             check()
 
-    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None, edge_ids=None, edge_features=None):
-        """edge_features: whether the pipe's gathered edge rows are read (`edge_feat` float32 [n_edges, dim]) -- None: as run_batch /
+    def result(self, dev=0, pipe=0, with_features=True, aggregated=None, normalised=None, edge_ids=None, edge_features=None, lp_exclude=None):
+        """lp_exclude: whether the pipe's edge marks are read (`edge_keep` uint8 [n_edges], `lp_excluded` int32[8]) -- None: as run_batch /
+        capture_batch on this engine left it.
+        edge_features: whether the pipe's gathered edge rows are read (`edge_feat` float32 [n_edges, dim]) -- None: as run_batch /
         capture_batch on this engine left it; True: at the width of the engine's table.
         edge_ids: whether the pipe's edge ids are read (`edge_ids`, and `edge_w` where the batch ran over retained weights) -- None: as
         run_batch / capture_batch on this engine left it.
@@ -851,6 +873,14 @@ class Engine:
             res["edge_ids"] = read_dev(eid, np.int64, n_edges)
             if ew:
                 res["edge_w"] = read_dev(ew, np.float32, n_edges)
+        if self._lpx.get((dev, pipe), False) if lp_exclude is None else lp_exclude:
+            self.L.GPUMemoryPool_SetCurrentPipe(self.pools[dev], pipe)
+            keep, cnt = self.L.GPUMemoryPool_GetEdgeKeepBuffer(self.pools[dev]), self.L.GPUMemoryPool_GetLpExcludedBuffer(self.pools[dev])
+            check()
+            if not keep or not cnt:
+                raise RuntimeError("result(): the pipe's last batch did not run the marking launch (GPUMemoryPool_GetEdgeKeepBuffer is null)")
+            res["edge_keep"] = read_dev(keep, np.uint8, n_edges)
+            res["lp_excluded"] = read_dev(cnt, np.int32, 8)
         dim = self._efeat.get((dev, pipe), 0) if edge_features is None else (self.edge_feature_dim if edge_features else 0)
         if dim:
             self.L.GPUMemoryPool_SetCurrentPipe(self.pools[dev], pipe)

@@ -32,11 +32,15 @@ struct LegionBatchGraph {
     // with them, or sums plainly.
     // and for edge_feat_dim: a captured get_edge_feature_kernel holds that row width and the pipe's edge_feat buffer of that width, which
     // another width reallocates (writes_edge_feat: the recording gathered edge rows, under the pool's allocation count edge_feat_gen; pipe: the one it ran on).
+    // and for lp_exclude: a captured batch holds k_lp_pairs and k_lp_edge_keep with that k and the pipe's pair table of that capacity, which a k
+    // of another capacity reallocates (uses_lp: the recording built or read the table, under the pool's allocation count lp_gen), or neither launch.
     ServeModes modes;
     const int32_t* shuf_ids = nullptr;
     int32_t pipe = 0;
     bool writes_edge_feat = false;
     uint32_t edge_feat_gen = 0;
+    bool uses_lp = false;
+    uint32_t lp_gen = 0;
 };
 // The replay rule, one row per mode field a recording is bound to (the comment above says why), compared in this order: the field's state, and
 // the refusal when the recording had it on / had it off.  A field without a row (sampling, agg_last_hop, agg_norm, seed) is not compared.
@@ -48,7 +52,8 @@ constexpr ReplayRule kReplayRules[] = {
     {[](const ServeModes& m) -> int32_t { return m.shared_draws; }, "LegionBatchGraph_Launch: the graph was recorded with shared-key sampling (GPUMemoryPool_SetSharedDraws) and the pool has the flag off now: its k_sample is that mode's instantiation -- record it again", "LegionBatchGraph_Launch: the graph was recorded without shared-key sampling and the pool has the flag on now (GPUMemoryPool_SetSharedDraws): its k_sample is another instantiation -- record it again"},
     {[](const ServeModes& m) -> int32_t { return m.edge_ids; }, "LegionBatchGraph_Launch: the graph was recorded with edge ids (GPUMemoryPool_SetEdgeIds) and the pool has the mode off now: its hops park their columns and launch k_edge_ids -- record it again", "LegionBatchGraph_Launch: the graph was recorded without edge ids and the pool has the mode on now (GPUMemoryPool_SetEdgeIds): its hops leave no edge ids behind -- record it again"},
     {[](const ServeModes& m) -> int32_t { return m.agg_edge_weight; }, "LegionBatchGraph_Launch: the graph was recorded with edge-weighted sums (GPUMemoryPool_SetAggEdgeWeight) and the pool has the flag off now: its last hop is summed by k_draw_edge_weights and the weighted k_gather_sum -- record it again", "LegionBatchGraph_Launch: the graph was recorded without edge-weighted sums and the pool has the flag on now (GPUMemoryPool_SetAggEdgeWeight): its last hop is summed unweighted -- record it again"},
-    {[](const ServeModes& m) -> int32_t { return m.edge_feat_dim; }, "LegionBatchGraph_Launch: the graph was recorded gathering edge features (GPUMemoryPool_SetEdgeFeatures) and the pool is at another row width, or has the mode off, now: its k_gather_edges holds that width and that buffer -- record it again", "LegionBatchGraph_Launch: the graph was recorded without edge features and the pool gathers them now (GPUMemoryPool_SetEdgeFeatures): it leaves no edge rows behind -- record it again"}};
+    {[](const ServeModes& m) -> int32_t { return m.edge_feat_dim; }, "LegionBatchGraph_Launch: the graph was recorded gathering edge features (GPUMemoryPool_SetEdgeFeatures) and the pool is at another row width, or has the mode off, now: its k_gather_edges holds that width and that buffer -- record it again", "LegionBatchGraph_Launch: the graph was recorded without edge features and the pool gathers them now (GPUMemoryPool_SetEdgeFeatures): it leaves no edge rows behind -- record it again"},
+    {[](const ServeModes& m) -> int32_t { return m.lp_exclude; }, "LegionBatchGraph_Launch: the graph was recorded with target-edge exclusion (GPUMemoryPool_SetLpExclude) and the pool is in another lp_exclude state now: its k_lp_pairs and k_lp_edge_keep hold that k and that pair table -- record it again", "LegionBatchGraph_Launch: the graph was recorded without target-edge exclusion and the pool marks target edges now (GPUMemoryPool_SetLpExclude): it leaves no edge_keep behind -- record it again"}};
 
 extern "C" {
 
@@ -74,6 +79,7 @@ LegionBatchGraph* GPUMemoryPool_EndBatchCapture(GPUMemoryPool* p, void* stream)
     g->progress = p->progress;
     g->modes = p->modes; g->shuf_ids = p->seed_reads_shuffle ? p->shuf_ids : nullptr;
     g->pipe = p->current_pipe; g->writes_edge_feat = p->progress.edge_feat_gathered; g->edge_feat_gen = p->edge_feat_gen;
+    g->uses_lp = p->progress.lp_pairs_built || p->progress.lp_marked; g->lp_gen = p->lp_gen;
     HIP_CHECK(hipStreamEndCapture((hipStream_t)stream, &g->graph));
     if (g->graph) HIP_CHECK(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
     if (!g->exec || error_pending()) {
@@ -100,6 +106,10 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
         LEGION_ARG_ERROR("LegionBatchGraph_Launch: the graph writes an edge-feature buffer the pool has reallocated since (GPUMemoryPool_SetEdgeFeatures with another row width in between): record it again");
         return -1;
     }
+    if (g->uses_lp && g->lp_gen != p->lp_gen) {
+        LEGION_ARG_ERROR("LegionBatchGraph_Launch: the graph uses a pair table of target-edge exclusion the pool has reallocated since (GPUMemoryPool_SetLpExclude with a k of another table capacity in between): record it again");
+        return -1;
+    }
     hipStream_t s = (hipStream_t)stream;
     if (++p->batch_serial >= kSerialLimit) { // epoch space exhausted: wipe once and start over (as batch_generator_kernel)
         HIP_CHECK(hipMemsetAsync(p->pos_map, 0xFF, (size_t)p->V * sizeof(pos_t), s));
@@ -111,6 +121,7 @@ int LegionBatchGraph_Launch(LegionBatchGraph* g, void* stream, int32_t counter)
     // the batch now in flight is the recorded one: what the launchers behind it (get_feature_kernel_agg) decide from
     p->progress = g->progress;
     p->pipes[g->pipe].edge_feat_filled = g->progress.edge_feat_gathered;
+    p->pipes[g->pipe].lp_marked = g->progress.lp_marked;
     p->ctl_synced = true;     // k_advance left (counter + 1, next epoch) in ctl
     p->ctl_counter = counter + 1;
     return error_pending() ? -1 : 0;

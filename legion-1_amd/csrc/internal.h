@@ -161,7 +161,11 @@ struct ServeModes {
     int32_t edge_feat_dim = 0;   // GPUMemoryPool_SetEdgeFeatures, only with edge_ids: 0 = off, dim > 0 = get_edge_feature_kernel gathers edge_feat[e, :] = X[edge_ids[e], :]
                                  // from the graph's float32 [E, dim] table (GPUGraphStorage_SetEdgeFeatures) into a per-pipe buffer ("Edge features").  No variable,
                                  // no mode word: the pool's and the Engine's only (open: the served hand-off)
-    bool operator==(const ServeModes& o) const { return edge_feat_dim == o.edge_feat_dim && edge_weights == o.edge_weights && agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
+    int32_t lp_exclude = 0;      // GPUMemoryPool_SetLpExclude: 0 = off, k > 0 = a training batch of 3 k seeds has its target pairs {ids[i], ids[k + i]} looked up among
+                                 // the batch's COO edges: edge_keep[e] = 0 where edge e joins a target pair, either direction ("Target-edge exclusion").  The edges are
+                                 // marked, not removed.  Refused together with agg_last_hop and, at another k, with lp_draw.  No variable, no mode word: the pool's and
+                                 // the Engine's only (open: the served hand-off)
+    bool operator==(const ServeModes& o) const { return lp_exclude == o.lp_exclude && edge_feat_dim == o.edge_feat_dim && edge_weights == o.edge_weights && agg_last_hop == o.agg_last_hop && agg_norm == o.agg_norm && sampling == o.sampling && seeded == o.seeded && seed == o.seed && lp_draw == o.lp_draw && weighted_distinct == o.weighted_distinct && shared_draws == o.shared_draws && edge_ids == o.edge_ids && agg_edge_weight == o.agg_edge_weight; }
 };
 // The draw rule of a sampler hop: what `sampling` and the flags `weighted_distinct` and `shared_draws` say together.  draw_rule_of is the one
 // place that reads the three; the launchers, the fan-out checks and the k_sample dispatch go by the rule and its facts below.
@@ -464,6 +468,26 @@ struct EdgeGatherArgs {
 // chunks a row of `dim` floats is gathered in (16-byte chunks where dim % 4 == 0, else floats): what the 32-bit flat work space is counted in
 constexpr int32_t edge_gather_chunks(int32_t dim) { return dim % 4 == 0 ? dim / 4 : dim; }
 void launch_gather_edges(hipStream_t s, const EdgeGatherArgs& a, int32_t edges_bound);
+// Target-edge exclusion (lp_exclude.hip, lp_exclude.h): the pair table of a batch's k target pairs, behind k_seed, and the marking pass over
+// every COO edge of the batch, behind the last hop.  Everything here but the counters' layout belongs to the batch's pipe.
+struct LpPairsArgs {
+    const int32_t* ids;       // the pipe's sampled_ids: [0, 2 k) are the src and pos thirds, as k_seed left them
+    const int32_t* nc;        // the pipe's node counters: the level-0 size is read on the device
+    uint64_t* pairs;          // uint64[cap], the pipe's lp_pairs
+    int32_t* excluded;        // int32[kLpExcludedWords], the pipe's lp_excluded: zeroed here
+    int32_t k, cap;
+};
+void launch_lp_pairs(hipStream_t s, const LpPairsArgs& a);
+struct LpKeepArgs {
+    const int32_t *ids, *src_off, *dst_off, *nc, *ec;   // the pipe's batch
+    const uint64_t* pairs;    // as k_lp_pairs left it; not read when !active
+    uint8_t* keep;            // uint8[ids_cap], the pipe's edge_keep
+    int32_t* excluded;        // the pipe's lp_excluded
+    int32_t k, cap, hops, ids_cap;
+    bool active;              // k_lp_pairs ran for this batch (a training batch); false: every edge is kept and the counts are zeroed here
+};
+constexpr int kLpExcludedWords = 8;
+void launch_lp_edge_keep(hipStream_t s, const LpKeepArgs& a, int32_t edges_bound);
 // Aggregated last hop (gather.hip "S5, aggregated last hop"): the neighbour sums of the last hop's runs_bound (static bound) input
 // slots, from the draws in cand[slot * f + j], into rows [legion_first_block_dst(nc, hops), + runs) of a.dst.  a.sampled_ids / a.row_ptr are not read.
 // wdraw (normalised sums): the weight of every draw by slot, as launch_agg_norm_weights left it; null = plain sums.
@@ -578,20 +602,25 @@ struct GPUMemoryPool {
         uint32_t levels_gathered = 0; // bit l: get_feature_kernel gathered level l of the current batch
         int32_t edge_id_hop = 0;      // hops 1..edge_id_hop of the current batch left their edge ids (k_edge_ids is queued behind each of them)
         bool edge_feat_gathered = false;   // get_edge_feature_kernel(_all) gathered edge rows of the current batch (-> Pipe::edge_feat_filled)
+        bool lp_pairs_built = false;  // k_lp_pairs is queued behind the current batch's k_seed: a training batch under modes.lp_exclude
+        bool lp_marked = false;       // k_lp_edge_keep is queued behind the current batch's last hop (-> Pipe::lp_marked)
     } progress;
     // Everything that exists once per pipe.  own[]: the device buffers the POOL owns per pipe, one row of pool_pipe_buffers() each (below) --
     // allocated when a mode that wants them is set, kept until the scratch is released, null before.  cand_pipe: the aggregated last hop parks
     // its draws in the PIPE's buffer, because k_gather_sum reads them on the gather stream while hop 1 of the next batch already overwrites
     // `cand` on the sampler stream.  The normalised sums rank them through agg_out_deg / agg_wdraw / agg_chunk_cnt; the edge-weighted sums use
     // the last two in the same way and no degrees.  edge_ids / edge_w: the batch's, read back by callers.  edge_feat: float32 [num_ids,
-    // modes.edge_feat_dim], the batch's gathered edge rows (GPUMemoryPool_SetEdgeFeatures), read back by callers.
-    enum PipeBuf { kCandPipe, kAggOutDeg, kAggWdraw, kAggChunkCnt, kEdgeIds, kEdgeW, kEdgeFeat, kPipeBufs };
+    // modes.edge_feat_dim], the batch's gathered edge rows (GPUMemoryPool_SetEdgeFeatures), read back by callers.  lp_pairs / edge_keep /
+    // lp_excluded: the target pairs' table, the keep byte of every COO edge and the counts of the zeros (GPUMemoryPool_SetLpExclude); the last
+    // two are read back by callers.
+    enum PipeBuf { kCandPipe, kAggOutDeg, kAggWdraw, kAggChunkCnt, kEdgeIds, kEdgeW, kEdgeFeat, kLpPairs, kEdgeKeep, kLpExcluded, kPipeBufs };
     struct Pipe {
         float* float_features = nullptr;   // the seven buffers the caller registered (IPC buffers)
         int32_t *labels = nullptr, *node_counter = nullptr, *edge_counter = nullptr, *sampled_ids = nullptr, *agg_src_off = nullptr, *agg_dst_off = nullptr;
         void* own[kPipeBufs] = {};
         bool edge_w_filled = false;        // the pipe's last batch ran over retained weights (GetEdgeWeightBuffer is null otherwise)
         bool edge_feat_filled = false;     // the pipe's last batch had its edge rows gathered (GetEdgeFeatureBuffer is null otherwise)
+        bool lp_marked = false;            // the pipe's last batch ran the marking launch (GetEdgeKeepBuffer / GetLpExcludedBuffer are null otherwise)
         template <typename T> T* buf(PipeBuf b) const { return (T*)own[b]; }
     };
     std::vector<Pipe> pipes;               // pipeline_depth of them from the constructor on, never resized
@@ -616,6 +645,10 @@ struct GPUMemoryPool {
     int32_t* cols = nullptr;
     int32_t edge_feat_alloc_dim = 0;  // the row width the pipes' edge_feat buffers are allocated for (0: none); another dim reallocates them
     uint32_t edge_feat_gen = 0;       // ... and counts every such (re)allocation and release: a batch graph that writes them replays only under the count it recorded
+    // Target-edge exclusion (modes.lp_exclude, GPUMemoryPool_SetLpExclude): the table capacity the pipes' lp_pairs are allocated for (0: none;
+    // a k of another capacity reallocates them), and the count of such (re)allocations and releases, by the rule of edge_feat_gen
+    int32_t lp_alloc_cap = 0;
+    uint32_t lp_gen = 0;
     int32_t* aux2[2] = {nullptr, nullptr}; // slot states, one buffer per hop parity (hop h uses aux2[h & 1])
     int32_t aux_ready_hop = 0, aux_ready_count = 0; // the launch before prepared aux2[hop & 1] for this fan-out
     int32_t* tile_edge = nullptr;

@@ -7,6 +7,8 @@
 #include <cstring>
 #include <iostream>
 
+#include "lp_exclude.h"
+
 #include "audit_hooks.h"
 
 using namespace legion;
@@ -129,6 +131,13 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
         csr_tables_of(lp_args.csr, graph, cache, dev_id, cache && !cache->is_presc);   // pre-sampling batches: the whole CSR, like their hops
         lp = &lp_args;
     }
+    // Target-edge exclusion: a training batch is 3 k seeds whose first two thirds are the target pairs; k_lp_pairs behind k_seed builds their table
+    const int32_t lpx = mode == LEGION_TRAINMODE ? p->modes.lp_exclude : 0;
+    if (lpx > 0) {
+        if (batch_size != 3 * lpx) { LEGION_ARG_ERROR("batch_generator_kernel: target-edge exclusion (GPUMemoryPool_SetLpExclude): the batch size must be three times the pool's triples per batch"); return; }
+        if (total_cap % (3 * lpx) != 0) { LEGION_ARG_ERROR("batch_generator_kernel: target-edge exclusion (GPUMemoryPool_SetLpExclude): the training list's length is not a multiple of the batch of 3 k ([src | pos | neg] thirds, padded)"); return; }
+        if (!pipe_holds(*pipe, {Pool::kLpPairs, Pool::kEdgeKeep, Pool::kLpExcluded}, "batch_generator_kernel: target-edge exclusion (GPUMemoryPool_SetLpExclude) without the pool's per-pipe buffers (the mode was set before GPUMemoryPool_AllocateScratch failed?)", p->lp_alloc_cap == lp_pair_cap(lpx) && 3 * lpx <= p->batch_size)) return;
+    }
     if (p->device_id != dev_id && audit::on()) {   // the pool starts serving this GPU: its scratch and its output buffers must live there
         for (const ScratchBuffer& b : pool_scratch(p)) if (*b.slot) LEGION_AUDIT_OWNER(*b.slot, dev_id, "batch_generator_kernel: scratch of the memory pool");
         for (const PipeBuffer& b : pool_pipe_buffers(p))
@@ -142,6 +151,7 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     p->device_id = dev_id;
     p->progress = {};
     p->pipe().edge_feat_filled = false;   // a new batch on this pipe: its edge rows are not gathered yet
+    p->pipe().lp_marked = false;          // ... and its edges are not marked yet
     SeedArgs a;
     a.batch_ids = pipe->sampled_ids; a.labels = pipe->labels; a.batch_size = batch_size;
     a.all_ids = all_ids; a.all_labels = all_labels; a.total_cap = total_cap;
@@ -165,6 +175,13 @@ void batch_generator_kernel(void* strm_hdl, GPUNodeStorage* noder, GPUCache* cac
     }
     if (a.size > p->batch_size) { LEGION_ARG_ERROR("batch_generator_kernel: batch larger than the pool was sized for"); return; }
     launch_seed(s, a, p->capturing);
+    if (lpx > 0) {   // reads ids[0, 2 k) and the level-0 size as k_seed left them on this stream: a recorded batch has no per-batch arguments
+        LpPairsArgs t;
+        t.ids = pipe->sampled_ids; t.nc = pipe->node_counter; t.pairs = pipe->buf<uint64_t>(Pool::kLpPairs); t.excluded = pipe->buf<int32_t>(Pool::kLpExcluded);
+        t.k = lpx; t.cap = p->lp_alloc_cap;
+        launch_lp_pairs(s, t);
+        p->progress.lp_pairs_built = true;
+    }
     p->aux_ready_hop = 1; p->aux_ready_count = p->fanout[0]; // k_seed prepared the slot states of hop 1
     p->bound_n = a.size > 0 ? a.size : 0;
     p->bound_nodes = p->bound_n;
@@ -230,6 +247,19 @@ void GPU_Random_Sampling(void* strm_hdl, GPUGraphStorage* graph, GPUCache* cache
     p->aux_ready_hop = hop + 1; p->aux_ready_count = b.next_count; // k_write prepared the next hop's slot states
     p->progress.sampled_hop = hop; p->progress.sampled_presc = is_presc != 0;
     if (eo && p->progress.edge_id_hop == hop - 1) p->progress.edge_id_hop = hop;
+    // Target-edge exclusion (GPUMemoryPool_SetLpExclude): behind the last hop, on this stream and in front of the level's event, one launch marks
+    // every edge of the batch from the pipe's own buffers.  A batch without a pair table (not a training batch) keeps every edge; a
+    // pre-sampling batch hands nothing over.
+    if (p->modes.lp_exclude > 0 && hop == p->hops && !is_presc) {
+        if (!pipe_holds(*pipe, {Pool::kLpPairs, Pool::kEdgeKeep, Pool::kLpExcluded}, "GPU_Random_Sampling: target-edge exclusion (GPUMemoryPool_SetLpExclude) without the pool's per-pipe buffers (the mode was set before GPUMemoryPool_AllocateScratch failed?)", p->lp_alloc_cap == lp_pair_cap(p->modes.lp_exclude))) return;
+        LpKeepArgs m;
+        m.ids = pipe->sampled_ids; m.src_off = pipe->agg_src_off; m.dst_off = pipe->agg_dst_off; m.nc = pipe->node_counter; m.ec = pipe->edge_counter;
+        m.pairs = pipe->buf<uint64_t>(Pool::kLpPairs); m.keep = pipe->buf<uint8_t>(Pool::kEdgeKeep); m.excluded = pipe->buf<int32_t>(Pool::kLpExcluded);
+        m.k = p->modes.lp_exclude; m.cap = p->lp_alloc_cap; m.hops = p->hops; m.ids_cap = p->num_ids; m.active = p->progress.lp_pairs_built;
+        launch_lp_edge_keep((hipStream_t)strm_hdl, m, p->num_ids);
+        if (!p->capturing) pipe->lp_marked = true;   // a recording marks nothing yet: its replay sets the flag (LegionBatchGraph_Launch)
+        p->progress.lp_marked = true;
+    }
     p->bound_n = (int32_t)slots;          // next hop expands every sampled edge endpoint
     p->bound_nodes += (int32_t)slots;
 }

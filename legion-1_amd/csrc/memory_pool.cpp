@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "device_mem.h"
+#include "lp_exclude.h"
 
 using namespace legion;
 
@@ -34,6 +35,11 @@ static bool lists_edge_ids(const GPUMemoryPool* p) { return p->modes.edge_ids ||
 // output no launch reads, joins the list behind edge_w once the pool has been in the mode -- the mode is on, or the pipes hold the buffer
 // (edge_feat_alloc_dim: the width they were allocated for, which only release_scratch forgets) -- at the width it is held at.
 static int32_t listed_edge_feat_dim(const GPUMemoryPool* p) { return p->modes.edge_feat_dim > 0 ? p->modes.edge_feat_dim : p->edge_feat_alloc_dim; }
+// The buffers of target-edge exclusion (GPUMemoryPool_SetLpExclude) by the same rule again: lp_pairs (batch, per pipe), uint64[cap], written by
+// k_lp_pairs behind k_seed and read by k_lp_edge_keep behind the last hop; edge_keep (uint8[num_ids]) and lp_excluded (int32[8]), outputs no
+// launch reads.  They join the list behind edge_feat once the pool has been in the mode -- the mode is on, or the pipes hold the table
+// (lp_alloc_cap: the capacity it was allocated for, which only release_scratch forgets) -- at the capacity it is held at.
+static int32_t listed_lp_cap(const GPUMemoryPool* p) { return p->modes.lp_exclude > 0 ? lp_pair_cap(p->modes.lp_exclude) : p->lp_alloc_cap; }
 std::vector<ScratchBuffer> legion::pool_scratch(GPUMemoryPool* p)
 {
     const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots, tiles = (size_t)p->max_tiles + 1;
@@ -64,6 +70,7 @@ std::array<PipeBuffer, GPUMemoryPool::kPipeBufs> legion::pool_pipe_buffers(const
     const bool agg = p->modes.agg_last_hop, norm = agg && p->modes.agg_norm, eid = p->modes.edge_ids, eid_listed = lists_edge_ids(p);
     const bool wdraw = norm || (agg && p->modes.agg_edge_weight);   // the edge-weighted sums rank their draws the same way, without the degrees
     const size_t ids = (size_t)p->num_ids, slots = (size_t)p->max_slots;
+    const bool lpx = p->modes.lp_exclude > 0, lpx_listed = listed_lp_cap(p) > 0;
     constexpr int32_t I = sizeof(int32_t), batch = LEGION_SCRATCH_BATCH;
     return {{{Pool::kCandPipe, slots * sizeof(int32_t), agg, true, "cand_pipe", LEGION_SCRATCH_ID, I, batch},
              {Pool::kAggOutDeg, ids * sizeof(int32_t), norm, true, "agg_out_deg", LEGION_SCRATCH_COUNT, I, batch},
@@ -72,7 +79,11 @@ std::array<PipeBuffer, GPUMemoryPool::kPipeBufs> legion::pool_pipe_buffers(const
              // an edge id is one 8-byte word no kernel reads back: any bytes are safe in it, a pair of counts is what the poison's kinds offer
              {Pool::kEdgeIds, ids * sizeof(int64_t), eid, eid_listed, "edge_ids", LEGION_SCRATCH_COUNT_PAIR, sizeof(int64_t), batch},
              {Pool::kEdgeW, ids * sizeof(float), eid, eid_listed, "edge_w", LEGION_SCRATCH_FLOAT, sizeof(float), batch},
-             {Pool::kEdgeFeat, ids * (size_t)listed_edge_feat_dim(p) * sizeof(float), p->modes.edge_feat_dim > 0, listed_edge_feat_dim(p) > 0, "edge_feat", LEGION_SCRATCH_FLOAT, sizeof(float), batch}}};
+             {Pool::kEdgeFeat, ids * (size_t)listed_edge_feat_dim(p) * sizeof(float), p->modes.edge_feat_dim > 0, listed_edge_feat_dim(p) > 0, "edge_feat", LEGION_SCRATCH_FLOAT, sizeof(float), batch},
+             // a table slot is one 8-byte word k_lp_pairs overwrites before anything reads it, a keep byte and a count are outputs: any bytes are safe in all three
+             {Pool::kLpPairs, (size_t)listed_lp_cap(p) * sizeof(uint64_t), lpx, lpx_listed, "lp_pairs", LEGION_SCRATCH_COUNT_PAIR, sizeof(uint64_t), batch},
+             {Pool::kEdgeKeep, ids, lpx, lpx_listed, "edge_keep", LEGION_SCRATCH_ID, 1, batch},
+             {Pool::kLpExcluded, (size_t)kLpExcludedWords * sizeof(int32_t), lpx, lpx_listed, "lp_excluded", LEGION_SCRATCH_COUNT, I, batch}}};
 }
 // on the current device: what the pool's modes want and is missing is allocated, what is there stays
 static void alloc_mode_buffers(GPUMemoryPool* p)
@@ -83,6 +94,12 @@ static void alloc_mode_buffers(GPUMemoryPool* p)
         for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[GPUMemoryPool::kEdgeFeat]); pipe.edge_feat_filled = false; }
         p->edge_feat_alloc_dim = p->modes.edge_feat_dim;
         p->edge_feat_gen++;
+    }
+    if (p->modes.lp_exclude > 0 && p->lp_alloc_cap != lp_pair_cap(p->modes.lp_exclude)) {   // another table capacity: the pipes' tables are reallocated below
+        if (p->lp_alloc_cap) HIP_CHECK(hipDeviceSynchronize());                             // a marking pass over the old ones may still be in flight
+        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[GPUMemoryPool::kLpPairs]); pipe.lp_marked = false; }
+        p->lp_alloc_cap = lp_pair_cap(p->modes.lp_exclude);
+        p->lp_gen++;
     }
     for (const PipeBuffer& b : pool_pipe_buffers(p))
         for (GPUMemoryPool::Pipe& pipe : p->pipes)
@@ -95,9 +112,11 @@ static void release_scratch(GPUMemoryPool* p)
 {
     for (const ScratchBuffer& b : pool_scratch(p)) free_and_null(*b.slot);
     for (const PipeBuffer& b : pool_pipe_buffers(p))   // every row, listed or not: with cols null again the pool lists the edge-id rows only while the mode is on
-        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[b.which]); pipe.edge_w_filled = pipe.edge_feat_filled = false; }
+        for (GPUMemoryPool::Pipe& pipe : p->pipes) { free_and_null(pipe.own[b.which]); pipe.edge_w_filled = pipe.edge_feat_filled = pipe.lp_marked = false; }
     p->edge_feat_alloc_dim = 0;
     p->edge_feat_gen++;
+    p->lp_alloc_cap = 0;
+    p->lp_gen++;
 }
 static void release_ctl(GPUMemoryPool* p) { free_and_null(p->ctl); }
 static void release_rows_seen(GPUMemoryPool* p)
@@ -136,6 +155,12 @@ bool legion::pool_apply_modes(GPUMemoryPool* p, const ServeModes& wanted, const 
         if (__builtin_mul_overflow((int64_t)p->num_ids * (int64_t)sizeof(float), (int64_t)wanted.edge_feat_dim, &bytes)) { LEGION_ARG_ERROR((name + ": edge features (GPUMemoryPool_SetEdgeFeatures): the size of the per-pipe buffer, NumIds * dim * 4 bytes, overflows").c_str()); return false; }
         if ((int64_t)p->num_ids * edge_gather_chunks(wanted.edge_feat_dim) >= (1ll << 31)) { LEGION_ARG_ERROR((name + ": edge features (GPUMemoryPool_SetEdgeFeatures): NumIds * chunks per row reaches 2^31 work items (a row is gathered in 16-byte chunks where dim % 4 == 0, else float by float)").c_str()); return false; }
     }
+    // target-edge exclusion reads the batch's own src and pos thirds: refused in the name of whichever setter comes second
+    if (wanted.lp_exclude < 0) { LEGION_ARG_ERROR((name + ": negative triples per batch for target-edge exclusion (GPUMemoryPool_SetLpExclude: 0 = off, k > 0 = batches of 3 k)").c_str()); return false; }
+    if (wanted.lp_exclude > kLpMaxTriples) { LEGION_ARG_ERROR((name + ": target-edge exclusion (GPUMemoryPool_SetLpExclude): more than 2^28 triples per batch exceed the pair table's 32-bit slots").c_str()); return false; }
+    if (wanted.lp_exclude > 0 && wanted.lp_draw > 0 && wanted.lp_exclude != wanted.lp_draw) { LEGION_ARG_ERROR((name + ": target-edge exclusion (GPUMemoryPool_SetLpExclude) and drawn link-prediction thirds (GPUMemoryPool_SetLpDraw) with different triples per batch: both describe the same batch of 3 k seeds").c_str()); return false; }
+    // the neighbour sums would contain the excluded draws (open: a zero weight per excluded draw)
+    if (wanted.lp_exclude > 0 && wanted.agg_last_hop) { LEGION_ARG_ERROR((name + ": target-edge exclusion (GPUMemoryPool_SetLpExclude) together with the aggregated last hop (GPUMemoryPool_SetAggLastHop): the neighbour sums would contain the excluded draws").c_str()); return false; }
     if (wanted.lp_draw > 0 && !p->lp_graph) { LEGION_ARG_ERROR("GPUMemoryPool_SetLpDraw: null graph: the positives are neighbours read from it"); return false; }
     if (wanted.seed != p->modes.seed) p->shuf_valid = false;   // the copy holds another seed's permutation (off and on again under one seed keeps it)
     if (wanted.lp_draw != p->modes.lp_draw) p->shuf_valid = false;   // ... or was shuffled by seeds, not by triples of this k
@@ -252,6 +277,24 @@ void GPUMemoryPool_SetLpDraw(GPUMemoryPool* p, int32_t triples_per_batch, GPUGra
     if (!pool_apply_modes(p, m, "GPUMemoryPool_SetLpDraw") && p && !p->capturing) p->lp_graph = before;
 }
 int32_t GPUMemoryPool_GetLpDraw(const GPUMemoryPool* p) { return p ? p->modes.lp_draw : 0; }
+// target-edge exclusion ("Target-edge exclusion"): k > 0 = a training batch of 3 k seeds leaves edge_keep[e] = 0 for every COO edge that joins a
+// target pair {ids[i], ids[k + i]}, 1 for every other, and the zeros per hop in lp_excluded; 0 = off.  Allocates lp_pairs (uint64[cap]), edge_keep
+// (num_ids bytes) and lp_excluded (int32[8]) per pipe on the first switch on; a k of another table capacity reallocates lp_pairs
+void GPUMemoryPool_SetLpExclude(GPUMemoryPool* p, int32_t triples_per_batch) { ServeModes m = modes_of(p); m.lp_exclude = triples_per_batch; pool_apply_modes(p, m, "GPUMemoryPool_SetLpExclude"); }
+int32_t GPUMemoryPool_GetLpExclude(const GPUMemoryPool* p) { return p ? p->modes.lp_exclude : 0; }
+// the current pipe's buffers, uint8 [legion_batch_edges(ec, H)] in the order of the COO and int32[8]; null unless the pipe's last batch ran the marking launch
+uint8_t* GPUMemoryPool_GetEdgeKeepBuffer(const GPUMemoryPool* p)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetEdgeKeepBuffer: null pool"); return nullptr; }
+    return p->pipe().lp_marked ? p->pipe().buf<uint8_t>(GPUMemoryPool::kEdgeKeep) : nullptr;
+}
+int32_t* GPUMemoryPool_GetLpExcludedBuffer(const GPUMemoryPool* p)
+{
+    if (!p) { LEGION_ARG_ERROR("GPUMemoryPool_GetLpExcludedBuffer: null pool"); return nullptr; }
+    return p->pipe().lp_marked ? p->pipe().buf<int32_t>(GPUMemoryPool::kLpExcluded) : nullptr;
+}
+// the first slot the pair (lo <= hi) is looked for in a table of cap slots (a power of two): the kernels' function (lp_exclude.h), for a test to pin
+uint32_t legion_lp_pair_slot(uint32_t lo, uint32_t hi, uint32_t cap) { return lp_pair_slot(lo, hi, cap); }
 int GPUMemoryPool_GetAggLastHop(const GPUMemoryPool* p) { return p && p->modes.agg_last_hop ? 1 : 0; }
 int GPUMemoryPool_GetAggNorm(const GPUMemoryPool* p) { return p ? p->modes.agg_norm : 0; }
 int GPUMemoryPool_GetSampleDistinct(const GPUMemoryPool* p) { return p && p->modes.sampling == kSamplingDistinct ? 1 : 0; }
